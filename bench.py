@@ -9,10 +9,13 @@ tau/L-up/L-down when the wavenumber axis is sharded over GPUs). The line table i
 region; everything that depends on the atmosphere is inside it.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with these extra objects:
+Prints ONE JSON line on rank 0. A plain run sets up, warms up, times the steps and prints the headline (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, the configuration and the device) and nothing else. --full adds these
+objects, each measured outside the timed steps:
   roofline     -- dominant kernel (the Voigt line-sum): algorithmic bytes / measured launch time vs 8 TB/s, PLUS the
                   roofline that actually binds it (`valu`: vector-instruction issue floor from the committed PMC
                   counts), and the other kernels' times, including the TUD kernel on an optically thin column
@@ -22,8 +25,14 @@ Prints ONE JSON line on rank 0 (contract in the task statement), with these extr
                   tile boundaries (dist.tile_aligned_bounds), so the spectra -- and these sums -- are IDENTICAL for every N
   sharding     -- (N > 1) per-rank shard lengths and line counts, per-rank kernel time of one step (min / max / all ranks:
                   the balance across ranks), `collective_ms` = one un-overlapped all-gather, `bytes_gathered`
+
+--dump-outputs DIR writes what the last timed step computed -- tau, L-up and L-down, float32, as a caller of the path
+receives them (N > 1: the all-gathered spectra) -- to DIR/tau.npy, DIR/Lu.npy, DIR/Ld.npy, each at the same DUMP_SAMPLES
+wavenumbers (grid indices: dump_indices(), seeded, ascending; 48 MB in all). The inputs are seeded, so equal arguments
+give equal inputs and two builds can be compared output for output.
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -42,6 +51,7 @@ CYC_VALU, CYC_TRANS = 2.0, 8.0  # issue cycles per wave64 VALU instruction / per
 N_WAVENUMBERS = 5500000
 N_LINES = 100000
 N_LAYERS = 32
+DUMP_SAMPLES, DUMP_SEED = 4000000, 20261016  # --dump-outputs: 3 x 4 M float32 = 48 MB (the full 3 x 5.5 M would be 66 MB)
 POOL_MAX = 16          # pool size of the CPU baseline. A one-GPU box lists 256 usable CPUs but its share is 16: measured on
                        # it (gpurun_out/r3/bench_1.json), 64 workers give 6.4e6 points/s in 1417 CPU-seconds -- each worker
                        # four times slower than the single-core leg -- against 6.8e6 with 16 workers
@@ -105,6 +115,11 @@ def _cpu_warm(_):
     return 0
 
 
+def dump_indices():
+    """Grid indices (ascending) of the wavenumbers that --dump-outputs writes."""
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(N_WAVENUMBERS, DUMP_SAMPLES, replace=False))
+
+
 def _latest_profile(suffix):
     d = os.path.join(ROOT, "profiles")
     cand = sorted(f for f in os.listdir(d) if f.endswith(suffix)) if os.path.isdir(d) else []
@@ -119,20 +134,28 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what lies outside the headline: CPU baseline, per-kernel rooflines, checksum, "
+                         "(N > 1) the balance across ranks and the collective")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help=f"write tau / Lu / Ld of the last timed step as DIR/<name>.npy (float32, at a fixed seeded sample of "
+                         f"{DUMP_SAMPLES} of the {N_WAVENUMBERS} wavenumbers)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--pipelines", type=int, default=3,
                     help="independent pipelines (stream + records + OD buffer each) the atmospheres of the timed loop alternate over "
                          "(C3 on one GPU: 1.97 / 1.90 / 1.90 ms per step with 1 / 2 / 3; a rank's eighth of the grid: 0.30 / 0.27 / 0.25)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo = rehearsal of the N>1 path on a box with fewer GPUs than ranks (ranks share devices, gather staged through the host); never a measurement")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}"
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline()  # before the GPU is initialised: its workers are child processes
 
     import torch
@@ -170,7 +193,6 @@ def main():
     lines = engine.LineTable(table)
     T, Z = atm["Ts"], atm["Zs"]
     dev = torch.device("cuda", local)
-    OD = torch.empty((N_LAYERS, n_loc), dtype=torch.float32, device=dev)
     # N > 1: the TUD kernel writes straight into the packed [3][per] block that is all-gathered; two blocks so the
     # RCCL all-gather of step k overlaps the kernels of step k+1 (separate stream, async_op). The timed region ends
     # with every gather complete (drain + barrier + synchronize): throughput of a pipelined stream of atmospheres, the
@@ -253,15 +275,59 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
 
-    # ---- checksum of the final spectra (N > 1: the all-gathered block, as every rank holds it) ----------------
-    # formed the same way for every N -- one contiguous [3][nX] block -- so equal spectra give equal sums; `bits` adds the
-    # float32 bit patterns as integers (exact, order-independent): equal iff the spectra are bit-identical
-    if world > 1:
-        g3 = gathered[last["b"]].view(world, 3, per)
-        g = torch.cat([g3[r, :, :int(offs[r + 1] - offs[r])] for r in range(world)], dim=1).contiguous()
-    else:
-        g = torch.stack([last["out"][0][0], last["out"][1][0], last["out"][2]]).contiguous()
-    assert g.shape == (3, N_WAVENUMBERS) and g.dtype == torch.float32
+    # ---- the spectra of the last timed step (N > 1: the all-gathered block, as every rank holds it) ----------------
+    # formed the same way for every N -- one contiguous [3][nX] block -- so equal spectra give equal dumps and checksums
+    if args.full or args.dump_outputs:
+        if world > 1:
+            g3 = gathered[last["b"]].view(world, 3, per)
+            g = torch.cat([g3[r, :, :int(offs[r + 1] - offs[r])] for r in range(world)], dim=1).contiguous()
+        else:
+            g = torch.stack([last["out"][0][0], last["out"][1][0], last["out"][2]]).contiguous()
+        assert g.shape == (3, N_WAVENUMBERS) and g.dtype == torch.float32
+    if args.dump_outputs and rank == 0:
+        sample = g[:, torch.from_numpy(dump_indices()).to(dev)].cpu().numpy()
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for c, key in enumerate(("tau", "Lu", "Ld")):
+            np.save(os.path.join(args.dump_outputs, f"{key}.npy"), sample[c])
+
+    out = None
+    if rank == 0:
+        name = ""
+        try:
+            buf = C.create_string_buffer(128)
+            ncu = C.c_int(0)
+            lib.rtx_device_info(buf, 128, C.byref(ncu))
+            name = buf.value.decode()
+        except Exception:
+            pass
+        out = {
+            "metric": "wavenumber*layer points/s (32-layer TUD, 500-6000 cm^-1 @ 0.001 cm^-1)",
+            "value": float(N_WAVENUMBERS) * N_LAYERS * args.steps / dt, "unit": "wavenumber*layer points/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": "C3: 32-layer TUD (tau,Lu,Ld) StandardAtmosphere rows 1-32, 500-6000 cm^-1 @ 0.001 cm^-1",
+                       "n_wavenumbers": N_WAVENUMBERS, "n_layers": N_LAYERS, "n_lines": N_LINES, "n_angles": 30,
+                       "line_table": "synthetic HITRAN-format H2O+CO2, seed 20261005",
+                       "parallelism": f"wavenumber-sharded x{world}" + (" + 1 RCCL all-gather" if world > 1 else ""),
+                       "pipelines_per_gpu": NP},
+            "device": name,
+        }
+
+    def finish():
+        if out is not None:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        lines.close()
+
+    if not args.full:
+        finish()
+        return
+
+    # ---- --full from here on: everything below is measured outside the timed steps ------------------------------
+    # checksum: `bits` adds the float32 bit patterns as integers (exact, order-independent): equal iff the spectra are
+    # bit-identical
     sums = [float(g[c].double().sum()) for c in range(3)]
     bits = [int(g[c].view(torch.int32).to(torch.int64).sum().item()) for c in range(3)]
 
@@ -321,7 +387,7 @@ def main():
     # back to back per sample -- a synchronise per launch would put the launch latency inside the brackets)
     NB = 4
     t_voigt, t_tud = [], []
-    import ctypes as C
+    OD = torch.empty((N_LAYERS, n_loc), dtype=torch.float32, device=dev)
     plan = lines.plan(N_LAYERS, n_loc) if n_loc > 0 else None
     for _ in range(min(max(args.steps, 3), 5)):
         if n_loc == 0:
@@ -376,7 +442,6 @@ def main():
         ms_tud_thin = float(np.median(tt_))
 
     if rank == 0:
-        pts = float(N_WAVENUMBERS) * N_LAYERS
         # algorithmic bytes of one line-sum launch (SURVEY 8d stage A): 4 B OD write per point
         # + one 48 B fp32 line record per (line, layer)
         alg_bytes = 4.0 * n_loc * N_LAYERS + 48.0 * lines.n * N_LAYERS
@@ -397,25 +462,7 @@ def main():
                         "model": f"{CYC_VALU:g} cycles per wave64 VALU instruction, {CYC_TRANS:g} per transcendental, "
                                  f"{N_SIMD} SIMDs at {CLOCK_HZ / 1e9:g} GHz",
                         "source": vsrc, "counted_on_ms_per_launch": vj.get("ms_per_launch")}
-        name = ""
-        try:
-            buf = C.create_string_buffer(128)
-            ncu = C.c_int(0)
-            lib.rtx_device_info(buf, 128, C.byref(ncu))
-            name = buf.value.decode()
-        except Exception:
-            pass
-        out = {
-            "metric": "wavenumber*layer points/s (32-layer TUD, 500-6000 cm^-1 @ 0.001 cm^-1)",
-            "value": pts * args.steps / dt, "unit": "wavenumber*layer points/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": "C3: 32-layer TUD (tau,Lu,Ld) StandardAtmosphere rows 1-32, 500-6000 cm^-1 @ 0.001 cm^-1",
-                       "n_wavenumbers": N_WAVENUMBERS, "n_layers": N_LAYERS, "n_lines": N_LINES, "n_angles": 30,
-                       "line_table": "synthetic HITRAN-format H2O+CO2, seed 20261005",
-                       "parallelism": f"wavenumber-sharded x{world}" + (" + 1 RCCL all-gather" if world > 1 else ""),
-                       "pipelines_per_gpu": NP},
+        out.update({
             "roofline": {"kernel": "voigt_nodal_kernel",
                          # the kernel moves 1.1x its algorithmic bytes and is nowhere near HBM speed: what binds it is
                          # vector-instruction issue (SURVEY 8d stage A). `bound` names the roofline that achieved / peak /
@@ -436,16 +483,12 @@ def main():
             "checksum": {"tau_sum": sums[0], "Lu_sum": sums[1], "Ld_sum": sums[2], "tau_bits": bits[0], "Lu_bits": bits[1],
                          "Ld_bits": bits[2], "note": "identical for every --gpus N (tile-aligned shards): *_bits is the exact integer sum "
                                                      "of the float32 bit patterns"},
-            "device": name,
-        }
+        })
         if cpu is not None:
             out["cpu_baseline"] = cpu
         if sharding is not None:
             out["sharding"] = sharding
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
-    lines.close()
+    finish()
 
 
 if __name__ == "__main__":

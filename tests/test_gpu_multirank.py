@@ -96,10 +96,10 @@ def test_two_ranks_band_sharded_cube_end_to_end(tmp_path):
 def test_bench_two_ranks_gloo_rehearsal(tmp_path):
     """bench.py's world > 1 branch (packed [3][per] blocks written by rtx_tud, double-buffered gather, barriers,
     max-over-ranks timing) executed end to end: `torch.distributed.run --nproc-per-node 2 bench.py --gpus 2
-    --backend gloo`. A rehearsal on one shared GPU, never a measurement; the JSON line must be well-formed."""
+    --backend gloo --full`. A rehearsal on one shared GPU, never a measurement; the JSON line must be well-formed."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--backend", "gloo", "--no-cpu-baseline"]
+           "--backend", "gloo", "--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "n2")]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -114,13 +114,16 @@ def test_bench_two_ranks_gloo_rehearsal(tmp_path):
     assert sh["collective_ms"] > 0 and sh["bytes_gathered"] == 2 * 3 * max(sh["points_per_rank"]) * 4
     assert 0 < sh["kernel_ms"]["min"] <= sh["kernel_ms"]["max"] and len(sh["kernel_ms"]["per_rank"]) == 2
     # the same workload on ONE rank: identical spectra, bit for bit (integer sums of the float32 bit patterns)
-    cmd1 = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"]
+    cmd1 = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline",
+            "--dump-outputs", str(tmp_path / "n1")]
     env1 = {k: v for k, v in env.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     res1 = subprocess.run(cmd1, env=env1, capture_output=True, text=True, timeout=600)
     assert res1.returncode == 0, res1.stderr[-2000:]
     out1 = json.loads([ln for ln in res1.stdout.splitlines() if ln.startswith("{")][-1])
     for key in ("tau_bits", "Lu_bits", "Ld_bits", "tau_sum", "Lu_sum", "Ld_sum"):
         assert out["checksum"][key] == out1["checksum"][key], (key, out["checksum"][key], out1["checksum"][key])
+    for key in ("tau", "Lu", "Ld"):  # --dump-outputs of the all-gathered block: the single-rank arrays, bit for bit
+        assert np.array_equal(np.load(tmp_path / "n2" / f"{key}.npy"), np.load(tmp_path / "n1" / f"{key}.npy")), key
     rec = os.environ.get("RADTXFR_REHEARSAL_RECORD")
     if rec:
         with open(rec, "w") as f:
