@@ -123,6 +123,17 @@ int rtx_line_prep_profile(rtx_prep* prep, const rtx_lines* lines, const rtx_grid
                           double dil_self, double omega_wing, double omega_wing_hw,
                           double intensity_threshold, double scale, int profile, void* stream);
 
+/* The prologue on an explicit axis X_h[nx] instead of a uniform grid (the reference sorts whatever OmegaGrid it is given
+ * and bisects it, misc/hapi.py:10979-10983, 11133-11134): host fp64, non-decreasing, finite; 0 <= nx <= the max_points of
+ * rtx_prep_create. X_h is copied into a device buffer owned by the prep object (grow-only: a longer axis than before
+ * allocates, hence synchronises), so the caller may free it on return. Same per-line physics as rtx_line_prep_profile;
+ * windows are bisect_right(X, nu -+ W) on the axis itself. profile RTX_PROFILE_VOIGT / _LORENTZ / _DOPPLER;
+ * RTX_PROFILE_SDVOIGT is refused. No tile of an axis is ever cut (rtx_prep_split_bound does not apply). */
+int rtx_line_prep_axis(rtx_prep* prep, const rtx_lines* lines, const double* X_h, int64_t nx, int n_layers,
+                       const double* T_h, const double* p_atm_h, const double* qratio_h, const double* weight_h,
+                       const double* mass_h, double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
+                       double intensity_threshold, double scale, int profile, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Voigt line-sum. Replaces the per-line PROFILE_VOIGT + scatter-add loop, misc/hapi.py:11050,
  * 11135-11138 (PROFILE_VOIGT :10131 -> pcqsdhc PART1 :9900-9915 -> hum1_wei :9833-9844) with a
@@ -134,6 +145,10 @@ int rtx_line_prep_profile(rtx_prep* prep, const rtx_lines* lines, const rtx_grid
 int rtx_voigt_tile_points(void);
 int rtx_voigt_sum(const rtx_prep* prep, const rtx_grid* grid, int n_layers, float* out_f32,
                   double* out_f64, int64_t ld, void* stream);
+/* The line-sum on the axis of the last rtx_line_prep_axis (an error if the last prologue was a grid one, and
+ * rtx_voigt_sum after an axis prologue is one too): out_*[n_layers][ld], ld >= nx, as for rtx_voigt_sum. Point by point
+ * (no Chebyshev-node far wings), deterministic: repeated calls give identical bits. */
+int rtx_voigt_sum_axis(const rtx_prep* prep, int n_layers, float* out_f32, double* out_f64, int64_t ld, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Planck radiance. Replaces planckian(), radiative_transfer.py:792-848.

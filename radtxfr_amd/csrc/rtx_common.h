@@ -92,6 +92,9 @@ struct __attribute__((aligned(16))) LineRec {
   int hi;
   int zw;     // half-width, in grid points, of the band around i0 that can hold |x|+y<15 (0: none)
 };
+// On an explicit axis (rtx_line_prep_axis / voigt_axis_kernel) the grid-relative fields take axis meanings: a = (float)cte,
+// c = 0 (unused: x is formed per tile from the fp64 record, rtx_voigt_axis.hip), lo / hi = the window as axis indices
+// (bisect_right), and [i0, zw) = the axis indices that can hold |x|+y<15 (empty when zw <= i0).
 // fp64 companion (32 B), read only where the Weideman region is entered.
 struct __attribute__((aligned(16))) LineRec64 {
   double sg0;  // nu0 + Shift0
@@ -169,4 +172,9 @@ struct rtx_prep {
   long long split_off, split_n;
   int split_layers;
   const void* split_lines;  // the table the bound was made for
+  // explicit axis (rtx_line_prep_axis): device copy of the axis, grow-only; `axis` tells which prologue ran last
+  double* X;
+  long long x_cap;
+  long long nx;
+  int axis;
 };

@@ -160,6 +160,7 @@ extern "C" int rtx_prep_free(rtx_prep* P) {
   if (P->recsd) (void)hipFree(P->recsd);
   if (P->items) (void)hipFree(P->items);
   if (P->part_ws) (void)hipFree(P->part_ws);
+  if (P->X) (void)hipFree(P->X);
   delete P;
   return 0;
 }
@@ -238,6 +239,8 @@ struct PrepArgs {
   double dil_air, dil_self, omega_wing, omega_wing_hw, thresh, scale;
   int profile;  // RTX_PROFILE_VOIGT / _LORENTZ / _DOPPLER
   GridDev g;
+  const double* X;  // explicit axis (line_prep_axis_kernel): device copy, X[nx]
+  long long nx;
   LineRec* rec;
   LineRec64* rec64;
   int* ic;
@@ -279,6 +282,101 @@ __device__ __forceinline__ int sat_local(long long v, long long n) {
   return (int)(v < -M ? -M : (v > n + M ? n + M : v));
 }
 
+// ---- per-line physics, shared by the grid prologue (line_prep_kernel) and the axis prologue (line_prep_axis_kernel) ----
+struct LinePhys {
+  double GammaD, Gamma0, Shift0, W;
+};
+// GammaD, Gamma0 / Shift0 over the diluent mix and the window half-width OmegaWingF of line l in a layer at (T, p).
+__device__ __forceinline__ LinePhys line_phys(const PrepArgs& a, long long l, double T, double p, double mass, double nu) {
+  LinePhys r;
+  // GammaD, misc/hapi.py:11085-11087
+  const double m = mass * H_CMASSMOL * 1000.0;
+  double GammaD = sqrt(2.0 * H_CBOLTS * T * log(2.0) / m / (H_CC * H_CC)) * nu;
+  if (a.profile == RTX_PROFILE_DOPPLER)  // absorptionCoefficient_Doppler's own SI constants, misc/hapi.py:11534-11538
+    GammaD = (1.1774100225 / 2.99792458e8) * sqrt(1.3806503e-23 / 1.66053873e-27) * sqrt(T) * nu / sqrt(mass);
+  // Gamma0 / Shift0 over the diluent mix, misc/hapi.py:11090-11128
+  double Gamma0 = 0.0, Shift0 = 0.0;
+  const double tr = H_TREF / T;
+  // (Tref/T)^n as exp(n log(Tref/T)): the logarithm is the same for every line of the layer; |n log(Tref/T)| < 1, so the
+  // result is within 2 ulp of pow's (whose extended-precision logarithm is 200 fp64 instructions of this kernel's ~1000)
+  const double ltr = log(tr);
+  if (a.dil_air != 0.0) {
+#if RTX_PREP_ABLATE & 1  /* timing experiments only */
+    Gamma0 += a.dil_air * (a.gamma_air[l] * p / 1.0 * (tr * a.n_air[l]));
+#else
+    Gamma0 += a.dil_air * (a.gamma_air[l] * p / 1.0 * exp(a.n_air[l] * ltr));
+#endif
+    const double dp = a.deltap_air ? a.deltap_air[l] : 0.0;
+    Shift0 += a.dil_air * ((a.delta_air[l] + dp * (T - H_TREF)) * p / 1.0);
+  }
+  if (a.dil_self != 0.0) {
+    double ns = a.n_self ? a.n_self[l] : a.n_air[l];
+    if (a.n_self && ns == 0.0) ns = a.n_air[l];
+    Gamma0 += a.dil_self * (a.gamma_self[l] * p / 1.0 * exp(ns * ltr));
+    const double ds = a.delta_self ? a.delta_self[l] : 0.0;
+    const double dps = a.deltap_self ? a.deltap_self[l] : 0.0;
+    Shift0 += a.dil_self * ((ds + dps * (T - H_TREF)) * p / 1.0);
+  }
+  if (a.profile == RTX_PROFILE_DOPPLER) {  // no pressure broadening; Shift0 = delta_air * p (misc/hapi.py:11543), set by the host through dil_air = 1 / 0 (LineShift)
+    Gamma0 = 0.0;
+    Shift0 = a.dil_air * a.delta_air[l] * p;
+  }
+  // OmegaWingF and the window: Voigt misc/hapi.py:11131-11134, Lorentz :11364, Doppler :11540
+  r.W = a.profile == RTX_PROFILE_LORENTZ   ? fmax(a.omega_wing, a.omega_wing_hw * Gamma0)
+        : a.profile == RTX_PROFILE_DOPPLER ? fmax(a.omega_wing, a.omega_wing_hw * GammaD)
+                                           : fmax(a.omega_wing, fmax(a.omega_wing_hw * Gamma0, a.omega_wing_hw * GammaD));
+  r.GammaD = GammaD; r.Gamma0 = Gamma0; r.Shift0 = Shift0;
+  return r;
+}
+
+// S(T): EnvironmentDependency_Intensity, misc/hapi.py:10169-10175 (SigmaTref/SigmaT = qratio)
+__device__ __forceinline__ double line_strength(const PrepArgs& a, long long l, double T, double nu, double qratio) {
+  const double el = a.elower[l];
+#if RTX_PREP_ABLATE & 2
+  const double ch = (-H_C2 * el / T) * (1.0 - (-H_C2 * nu / T));
+  const double zn = (-H_C2 * el / H_TREF) * (1.0 - (-H_C2 * nu / H_TREF));
+#else
+  const double ch = exp(-H_C2 * el / T) * (1.0 - exp(-H_C2 * nu / T));
+  const double zn = a.zn[l];  // exp(-H_C2 * el / H_TREF) * (1.0 - exp(-H_C2 * nu / H_TREF)), from table creation (lines_zn_kernel)
+#endif
+  return a.sw[l] * qratio * ch / zn;
+}
+
+// profile parameters: pcqsdhc PART1, misc/hapi.py:9900-9915 -- every field of the two records that does not depend on the
+// spectral axis (r.a, r.c, r.i0, r.lo, r.hi, r.zw are the caller's).
+// Lorentz (PROFILE_LORENTZ, misc/hapi.py:10150): with x = (nu - sg0)/Gamma0 the profile is (1/(pi Gamma0)) / (x^2 + 1)
+// = (x^2 K + K) / ((x^2 + 2) x^2 + 1), i.e. the line-sum's far-wing rational with b1 = 2, b0 = 1, Ay = Ay0 = K:
+// the same kernels evaluate it everywhere (no band: y is set to 15), poles at |nu - sg0| = Gamma0 as for Voigt.
+// Doppler (PROFILE_DOPPLER, :10160) is the Voigt profile at y = 0: Re w(x) = exp(-x^2); the band |x| < 15 goes
+// through the fp64 Weideman pass, beyond it the reference's exp(-225) = 1e-98 is dropped.
+__device__ __forceinline__ void line_profile(int profile, const LinePhys& ph, double w, double S, bool dropped, double scale,
+                                             double sg0, LineRec& r, LineRec64& r64) {
+  const bool lor = profile == RTX_PROFILE_LORENTZ;
+  const double cte = lor ? 1.0 / ph.Gamma0 : sqrt(log(2.0)) / ph.GammaD;
+  const double y = lor ? 15.0 : ph.Gamma0 * cte;
+  const double A = dropped ? 0.0 : (lor ? w * S * cte / M_PI * scale : w * S * cte / sqrt(M_PI) * scale);
+  const double yh = y * y + 0.5;
+  r.b1 = lor ? 2.0f : (float)(2.0 * (y * y) - 1.0);
+  r.b0 = lor ? 1.0f : (float)(yh * yh);
+  r.Ay = lor ? (float)A : (float)(A * y * 0.56418958354775628);
+  r.Ay0 = lor ? (float)A : (float)(A * y * 0.56418958354775628 * yh);
+  r.y = (float)y;
+  r.A = (float)A;
+  r64.sg0 = sg0; r64.cte = cte; r64.y = y; r64.A = A;
+}
+
+// maximum of the 256 threads' v -> one atomicMax per block
+__device__ __forceinline__ void block_max_hw(int v, int* dst) {
+  for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_down(v, off));
+  __shared__ int s_hw[4];
+  if ((threadIdx.x & 63) == 0) s_hw[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int m = max(max(s_hw[0], s_hw[1]), max(s_hw[2], s_hw[3]));
+    if (m > 0) atomicMax(dst, m);
+  }
+}
+
 template <bool ENV_ARGS>
 __global__ __launch_bounds__(256) void line_prep_kernel(PrepArgs a) {
   const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -296,42 +394,8 @@ __global__ __launch_bounds__(256) void line_prep_kernel(PrepArgs a) {
     const double nu = a.nu[l];
     const int sp = a.species[l];
     const double w = ew[(size_t)sp * a.n_layers + k];
-    // GammaD, misc/hapi.py:11085-11087
-    const double m = em[sp] * H_CMASSMOL * 1000.0;
-    double GammaD = sqrt(2.0 * H_CBOLTS * T * log(2.0) / m / (H_CC * H_CC)) * nu;
-    if (a.profile == RTX_PROFILE_DOPPLER)  // absorptionCoefficient_Doppler's own SI constants, misc/hapi.py:11534-11538
-      GammaD = (1.1774100225 / 2.99792458e8) * sqrt(1.3806503e-23 / 1.66053873e-27) * sqrt(T) * nu / sqrt(em[sp]);
-    // Gamma0 / Shift0 over the diluent mix, misc/hapi.py:11090-11128
-    double Gamma0 = 0.0, Shift0 = 0.0;
-    const double tr = H_TREF / T;
-    // (Tref/T)^n as exp(n log(Tref/T)): the logarithm is the same for every line of the layer; |n log(Tref/T)| < 1, so the
-    // result is within 2 ulp of pow's (whose extended-precision logarithm is 200 fp64 instructions of this kernel's ~1000)
-    const double ltr = log(tr);
-    if (a.dil_air != 0.0) {
-#if RTX_PREP_ABLATE & 1  /* timing experiments only */
-      Gamma0 += a.dil_air * (a.gamma_air[l] * p / 1.0 * (tr * a.n_air[l]));
-#else
-      Gamma0 += a.dil_air * (a.gamma_air[l] * p / 1.0 * exp(a.n_air[l] * ltr));
-#endif
-      const double dp = a.deltap_air ? a.deltap_air[l] : 0.0;
-      Shift0 += a.dil_air * ((a.delta_air[l] + dp * (T - H_TREF)) * p / 1.0);
-    }
-    if (a.dil_self != 0.0) {
-      double ns = a.n_self ? a.n_self[l] : a.n_air[l];
-      if (a.n_self && ns == 0.0) ns = a.n_air[l];
-      Gamma0 += a.dil_self * (a.gamma_self[l] * p / 1.0 * exp(ns * ltr));
-      const double ds = a.delta_self ? a.delta_self[l] : 0.0;
-      const double dps = a.deltap_self ? a.deltap_self[l] : 0.0;
-      Shift0 += a.dil_self * ((ds + dps * (T - H_TREF)) * p / 1.0);
-    }
-    if (a.profile == RTX_PROFILE_DOPPLER) {  // no pressure broadening; Shift0 = delta_air * p (misc/hapi.py:11543), set by the host through dil_air = 1 / 0 (LineShift)
-      Gamma0 = 0.0;
-      Shift0 = a.dil_air * a.delta_air[l] * p;
-    }
-    // OmegaWingF and the window: Voigt misc/hapi.py:11131-11134, Lorentz :11364, Doppler :11540
-    const double W = a.profile == RTX_PROFILE_LORENTZ   ? fmax(a.omega_wing, a.omega_wing_hw * Gamma0)
-                     : a.profile == RTX_PROFILE_DOPPLER ? fmax(a.omega_wing, a.omega_wing_hw * GammaD)
-                                                        : fmax(a.omega_wing, fmax(a.omega_wing_hw * Gamma0, a.omega_wing_hw * GammaD));
+    const LinePhys ph = line_phys(a, l, T, p, em[sp], nu);
+    const double GammaD = ph.GammaD, Gamma0 = ph.Gamma0, Shift0 = ph.Shift0, W = ph.W;
     long long glo = grid_bisect_right(g, nu - W);
     long long ghi = grid_bisect_right(g, nu + W);
     int lo = clamp_local(glo, g), hi = clamp_local(ghi, g);
@@ -369,44 +433,21 @@ __global__ __launch_bounds__(256) void line_prep_kernel(PrepArgs a) {
         my_hw = hw > 1.0e9 ? 1000000000 : (int)hw;
       }
     } else {
-    // S(T): EnvironmentDependency_Intensity, misc/hapi.py:10169-10175 (SigmaTref/SigmaT = qratio)
-    const double el = a.elower[l];
-#if RTX_PREP_ABLATE & 2
-    const double ch = (-H_C2 * el / T) * (1.0 - (-H_C2 * nu / T));
-    const double zn = (-H_C2 * el / H_TREF) * (1.0 - (-H_C2 * nu / H_TREF));
-#else
-    const double ch = exp(-H_C2 * el / T) * (1.0 - exp(-H_C2 * nu / T));
-    const double zn = a.zn[l];  // exp(-H_C2 * el / H_TREF) * (1.0 - exp(-H_C2 * nu / H_TREF)), from table creation (lines_zn_kernel)
-#endif
-    const double S = a.sw[l] * eq[(size_t)sp * a.n_layers + k] * ch / zn;
+    const double S = line_strength(a, l, T, nu, eq[(size_t)sp * a.n_layers + k]);
     const bool dropped = pre_dropped || (S < a.thresh);
     if (dropped || hi <= lo) { lo = 0; hi = 0; }
-    // profile parameters: pcqsdhc PART1, misc/hapi.py:9900-9915
-    // Lorentz (PROFILE_LORENTZ, misc/hapi.py:10150): with x = (nu - sg0)/Gamma0 the profile is (1/(pi Gamma0)) / (x^2 + 1)
-    // = (x^2 K + K) / ((x^2 + 2) x^2 + 1), i.e. the line-sum's far-wing rational with b1 = 2, b0 = 1, Ay = Ay0 = K:
-    // the same kernels evaluate it everywhere (no band: y is set to 15), poles at |nu - sg0| = Gamma0 as for Voigt.
-    // Doppler (PROFILE_DOPPLER, :10160) is the Voigt profile at y = 0: Re w(x) = exp(-x^2); the band |x| < 15 goes
-    // through the fp64 Weideman pass, beyond it the reference's exp(-225) = 1e-98 is dropped.
-    const bool lor = a.profile == RTX_PROFILE_LORENTZ;
-    const double cte = lor ? 1.0 / Gamma0 : sqrt(log(2.0)) / GammaD;
-    const double y = lor ? 15.0 : Gamma0 * cte;
-    const double A = dropped ? 0.0 : (lor ? w * S * cte / M_PI * a.scale : w * S * cte / sqrt(M_PI) * a.scale);
+    LineRec r;
+    LineRec64 r64;
+    line_profile(a.profile, ph, w, S, dropped, a.scale, sg0, r, r64);
+    const double cte = r64.cte, y = r64.y;
     // nearest grid index to the shifted centre (global), then the residual in fp64
     long long gi0 = llrint((sg0 - g.xmin) / g.step);
     if (gi0 < -M) gi0 = -M;
     if (gi0 > M) gi0 = M;
     const double frac_x = (grid_x(g, gi0) - sg0) * cte;  // x at gi0, |.| <= a/2 when inside the grid
     const double ax = g.step * cte;
-    LineRec r;
     r.a = (float)ax;
     r.c = (float)frac_x;
-    const double yh = y * y + 0.5;
-    r.b1 = lor ? 2.0f : (float)(2.0 * (y * y) - 1.0);
-    r.b0 = lor ? 1.0f : (float)(yh * yh);
-    r.Ay = lor ? (float)A : (float)(A * y * 0.56418958354775628);
-    r.Ay0 = lor ? (float)A : (float)(A * y * 0.56418958354775628 * yh);
-    r.y = (float)y;
-    r.A = (float)A;
     r.i0 = sat_local(gi0 - g.offset, g.n);
     r.lo = lo;
     r.hi = hi;
@@ -418,8 +459,6 @@ __global__ __launch_bounds__(256) void line_prep_kernel(PrepArgs a) {
     }
     r.zw = zw;
     if (zw > 0 && r.y < 1.0f) a.smally[k] = 1;  // benign race: every writer stores 1
-    LineRec64 r64;
-    r64.sg0 = sg0; r64.cte = cte; r64.y = y; r64.A = A;
     const size_t o = (size_t)k * (size_t)a.n_lines + (size_t)l;
 #if !(RTX_PREP_ABLATE & 8)
     a.rec[o] = r;
@@ -448,15 +487,78 @@ __global__ __launch_bounds__(256) void line_prep_kernel(PrepArgs a) {
     }
     }  // !skip
   }
-  // block max -> one atomic per block
-  for (int off = 32; off > 0; off >>= 1) my_hw = max(my_hw, __shfl_down(my_hw, off));
-  __shared__ int s_hw[4];
-  if ((threadIdx.x & 63) == 0) s_hw[threadIdx.x >> 6] = my_hw;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int v = max(max(s_hw[0], s_hw[1]), max(s_hw[2], s_hw[3]));
-    if (v > 0) atomicMax(&a.maxhw[k], v);
+  block_max_hw(my_hw, &a.maxhw[k]);
+}
+
+// ---- the prologue on an explicit axis (rtx_line_prep_axis) --------------------------------------------------------------
+// bisect.bisect_right (RIGHT) / bisect_left of v on the device copy of the axis, with Python's comparisons: the number of
+// points <= v / < v.
+template <bool RIGHT>
+__device__ long long axis_bisect(const double* __restrict__ X, long long nx, double v) {
+  long long lo = 0, hi = nx;
+  while (lo < hi) {
+    const long long mid = (lo + hi) >> 1;
+    if (RIGHT ? v < X[mid] : !(X[mid] < v)) hi = mid;
+    else lo = mid + 1;
   }
+  return lo;
+}
+
+// One thread per (line, layer), as line_prep_kernel, with the same physics (line_phys, line_strength, line_profile). The
+// window is bisect_right(X, nu -+ W) on the axis itself, so every line's support is the reference's point for point
+// (misc/hapi.py:11133-11134). The candidate ranges of tile_ranges_kernel come from index-space inputs: ic[l] =
+// bisect_right(X, nu_l) (non-decreasing: the table is sorted by nu) and maxhw[k] = max over live lines of
+// max(ic - lo, hi - ic) + 1 points, so the bracket [ia - maxhw, ib - 1 + maxhw] of centre indices still holds every line
+// whose window meets tile [ia, ib). Records: LineRec's axis meanings (rtx_common.h); [i0, zw) = the indices within
+// (15 - y + 0.01)/cte of the shifted centre -- the points that can satisfy hum1_wei's |x|+y<15 (misc/hapi.py:9840), with a
+// margin of 0.01 in x far above the fp32 error of the line-sum's x.
+template <bool ENV_ARGS>
+__global__ __launch_bounds__(256) void line_prep_axis_kernel(PrepArgs a) {
+  const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int k = blockIdx.y;
+  int my_hw = 0;
+  const double* eT = ENV_ARGS ? a.env + (size_t)a.T : a.T;
+  const double* ep = ENV_ARGS ? a.env + (size_t)a.p : a.p;
+  const double* eq = ENV_ARGS ? a.env + (size_t)a.qratio : a.qratio;
+  const double* ew = ENV_ARGS ? a.env + (size_t)a.weight : a.weight;
+  const double* em = ENV_ARGS ? a.env + (size_t)a.mass : a.mass;
+  if (l < a.n_lines) {
+    const double T = eT[k], p = ep[k];
+    const double nu = a.nu[l];
+    const int sp = a.species[l];
+    const double w = ew[(size_t)sp * a.n_layers + k];
+    const LinePhys ph = line_phys(a, l, T, p, em[sp], nu);
+    const double S = line_strength(a, l, T, nu, eq[(size_t)sp * a.n_layers + k]);
+    const bool dropped = !(w != 0.0) || !(ph.GammaD > 0.0) || (a.profile == RTX_PROFILE_LORENTZ && !(ph.Gamma0 > 0.0)) ||
+                         (S < a.thresh);
+    long long lo = axis_bisect<true>(a.X, a.nx, nu - ph.W), hi = axis_bisect<true>(a.X, a.nx, nu + ph.W);
+    if (dropped || hi <= lo) { lo = 0; hi = 0; }
+    const long long ic = axis_bisect<true>(a.X, a.nx, nu);
+    if (k == 0) a.ic[l] = (int)ic;
+    const double sg0 = nu + ph.Shift0;
+    LineRec r;
+    LineRec64 r64;
+    line_profile(a.profile, ph, w, S, dropped, a.scale, sg0, r, r64);
+    r.a = (float)r64.cte;
+    r.c = 0.f;
+    long long zlo = 0, zhi = 0;
+    if (r64.y < 15.0 && hi > lo) {
+      const double wz = (15.0 - r64.y + 0.01) / r64.cte;
+      zlo = axis_bisect<false>(a.X, a.nx, sg0 - wz);
+      zhi = axis_bisect<true>(a.X, a.nx, sg0 + wz);
+      zlo = zlo < lo ? lo : zlo;
+      zhi = zhi > hi ? hi : zhi;
+      if (zhi < zlo) zhi = zlo;
+    }
+    r.i0 = (int)zlo; r.zw = (int)zhi;
+    r.lo = (int)lo; r.hi = (int)hi;
+    const size_t o = (size_t)k * (size_t)a.n_lines + (size_t)l;
+    a.rec[o] = r;
+    a.rec64[o] = r64;
+    a.win[o] = make_int2((int)lo, (int)hi);
+    if (hi > lo) my_hw = (int)(ic - lo > hi - ic ? ic - lo : hi - ic) + 1;
+  }
+  block_max_hw(my_hw, &a.maxhw[k]);
 }
 
 // ---- hot tiles: host-side bound on the extra parts (rtx_common.h) ------------------------------------------------------
@@ -522,28 +624,23 @@ static int rtx_split_bound(rtx_prep* P, const rtx_lines* L, const rtx_grid* g, i
 
 extern "C" int64_t rtx_prep_split_bound(const rtx_prep* P) { return P ? P->split_bound : -1; }
 
-extern "C" int rtx_line_prep_profile(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid, int n_layers, const double* T_h,
-                             const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
-                             double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
-                             double intensity_threshold, double scale, int profile, void* stream) {
-  if (!P || !L) RTX_FAIL("prep/lines is NULL");
-  if (profile < RTX_PROFILE_VOIGT || profile > RTX_PROFILE_SDVOIGT) RTX_FAIL("profile=%d", profile);
-  if (profile == RTX_PROFILE_SDVOIGT && !P->recsd) {
-    const size_t nrec = (size_t)(P->n_lines > 0 ? P->n_lines : 1) * (size_t)P->max_layers;
-    RTX_HIP(hipMalloc((void**)&P->recsd, nrec * sizeof(LineRecSD)));
-  }
-  if (rtx_check_grid(grid)) return 1;
+// Checks and per-layer tables common to both prologues: validates the call, packs T | p | qratio | weight | mass into the
+// kernel arguments (or copies them into the prep object when they do not fit), clears maxhw / smally / n_items and fills
+// every field of `a` that does not depend on the spectral axis.
+static int prep_begin(rtx_prep* P, const rtx_lines* L, int n_layers, const double* T_h, const double* p_atm_h,
+                      const double* qratio_h, const double* weight_h, const double* mass_h, double dil_air, double dil_self,
+                      double omega_wing, double omega_wing_hw, double intensity_threshold, double scale, int profile,
+                      hipStream_t st, PrepArgs& a, bool& env_args) {
   if (P->n_lines != L->n) RTX_FAIL("prep object was created for %lld lines, table has %lld", P->n_lines, L->n);
   if (n_layers < 1 || n_layers > P->max_layers) RTX_FAIL("n_layers=%d outside [1,%d]", n_layers, P->max_layers);
   if (!T_h || !p_atm_h || !qratio_h || !weight_h || !mass_h) RTX_FAIL("a per-layer input is NULL");
   if (!(scale > 0.0)) RTX_FAIL("scale must be > 0");
   for (int k = 0; k < n_layers; ++k)
     if (!(T_h[k] > 0.0) || !(p_atm_h[k] >= 0.0)) RTX_FAIL("layer %d: T=%g p=%g not physical", k, T_h[k], p_atm_h[k]);
-  hipStream_t st = (hipStream_t)stream;
   const int ns = L->n_species;
   const size_t nT = (size_t)n_layers, nQ = (size_t)ns * n_layers;
   if (2 * nT + 2 * nQ + ns > P->env_cap) RTX_FAIL("environment tables exceed prep capacity");
-  const bool env_args = 2 * nT + 2 * nQ + ns <= RTX_ENV_MAX;
+  env_args = 2 * nT + 2 * nQ + ns <= RTX_ENV_MAX;
   double* d = P->env;
   if (!env_args) {
     // pageable-source async copies are staged by the runtime before returning: caller may reuse its arrays
@@ -554,11 +651,6 @@ extern "C" int rtx_line_prep_profile(rtx_prep* P, const rtx_lines* L, const rtx_
     RTX_HIP(hipMemcpyAsync(d + 2 * nT + 2 * nQ, mass_h, ns * sizeof(double), hipMemcpyHostToDevice, st));
   }
   RTX_HIP(hipMemsetAsync(P->maxhw, 0, (2 * (size_t)P->max_layers + 1) * sizeof(int), st));  // maxhw, smally and n_items
-  if (rtx_split_bound(P, L, grid, n_layers, T_h, p_atm_h, mass_h, dil_air, dil_self, omega_wing, omega_wing_hw, profile)) return 1;
-  P->n_layers = n_layers;
-  P->scale = scale;
-  if (L->n == 0) return 0;
-  PrepArgs a;
   a.nu = L->nu; a.sw = L->sw; a.elower = L->elower; a.gamma_air = L->gamma_air; a.gamma_self = L->gamma_self;
   a.n_air = L->n_air; a.n_self = L->n_self; a.delta_air = L->delta_air; a.deltap_air = L->deltap_air;
   a.delta_self = L->delta_self; a.species = L->species;
@@ -577,11 +669,77 @@ extern "C" int rtx_line_prep_profile(rtx_prep* P, const rtx_lines* L, const rtx_
   }
   a.dil_air = dil_air; a.dil_self = dil_self; a.omega_wing = omega_wing; a.omega_wing_hw = omega_wing_hw;
   a.thresh = intensity_threshold; a.scale = scale; a.profile = profile;
-  a.g = to_dev(grid);
+  a.X = nullptr; a.nx = 0;
   a.rec = P->rec; a.rec64 = P->rec64; a.ic = P->ic; a.win = P->win; a.maxhw = P->maxhw; a.smally = P->smally;
+  return 0;
+}
+
+extern "C" int rtx_line_prep_profile(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid, int n_layers, const double* T_h,
+                             const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
+                             double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
+                             double intensity_threshold, double scale, int profile, void* stream) {
+  if (!P || !L) RTX_FAIL("prep/lines is NULL");
+  if (profile < RTX_PROFILE_VOIGT || profile > RTX_PROFILE_SDVOIGT) RTX_FAIL("profile=%d", profile);
+  if (profile == RTX_PROFILE_SDVOIGT && !P->recsd) {
+    const size_t nrec = (size_t)(P->n_lines > 0 ? P->n_lines : 1) * (size_t)P->max_layers;
+    RTX_HIP(hipMalloc((void**)&P->recsd, nrec * sizeof(LineRecSD)));
+  }
+  if (rtx_check_grid(grid)) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  PrepArgs a;
+  bool env_args = false;
+  if (prep_begin(P, L, n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, dil_air, dil_self, omega_wing, omega_wing_hw,
+                 intensity_threshold, scale, profile, st, a, env_args))
+    return 1;
+  if (rtx_split_bound(P, L, grid, n_layers, T_h, p_atm_h, mass_h, dil_air, dil_self, omega_wing, omega_wing_hw, profile)) return 1;
+  P->n_layers = n_layers;
+  P->scale = scale;
+  P->axis = 0;
+  if (L->n == 0) return 0;
+  a.g = to_dev(grid);
   dim3 grd((unsigned)((L->n + 255) / 256), (unsigned)n_layers);
   if (env_args) hipLaunchKernelGGL(line_prep_kernel<true>, grd, dim3(256), 0, st, a);
   else hipLaunchKernelGGL(line_prep_kernel<false>, grd, dim3(256), 0, st, a);
+  RTX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int rtx_line_prep_axis(rtx_prep* P, const rtx_lines* L, const double* X_h, int64_t nx, int n_layers, const double* T_h,
+                                  const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
+                                  double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
+                                  double intensity_threshold, double scale, int profile, void* stream) {
+  if (!P || !L) RTX_FAIL("prep/lines is NULL");
+  if (profile < RTX_PROFILE_VOIGT || profile > RTX_PROFILE_DOPPLER)
+    RTX_FAIL("rtx_line_prep_axis: profile=%d (Voigt, Lorentz or Doppler; the speed-dependent sum needs a uniform grid)", profile);
+  const long long cap = P->max_tiles * (long long)rtx_voigt_tile_points();
+  if (nx < 0 || nx > cap) RTX_FAIL("axis of %lld points outside the prep capacity [0, %lld]", (long long)nx, cap);
+  if (nx > 0 && !X_h) RTX_FAIL("axis is NULL");
+  for (int64_t i = 0; i < nx; ++i) {
+    if (!isfinite(X_h[i])) RTX_FAIL("axis point %lld is not finite", (long long)i);
+    if (i > 0 && X_h[i] < X_h[i - 1]) RTX_FAIL("axis must be non-decreasing (point %lld)", (long long)i);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  PrepArgs a;
+  bool env_args = false;
+  if (prep_begin(P, L, n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, dil_air, dil_self, omega_wing, omega_wing_hw,
+                 intensity_threshold, scale, profile, st, a, env_args))
+    return 1;
+  if (nx > P->x_cap) {  // grow-only: allocates, hence synchronises
+    if (P->X) { RTX_HIP(hipFree(P->X)); P->X = nullptr; }
+    P->x_cap = 0;
+    RTX_HIP(hipMalloc((void**)&P->X, (size_t)nx * sizeof(double)));
+    P->x_cap = nx;
+  }
+  if (nx > 0) RTX_HIP(hipMemcpyAsync(P->X, X_h, (size_t)nx * sizeof(double), hipMemcpyHostToDevice, st));  // staged before returning
+  P->n_layers = n_layers;
+  P->scale = scale;
+  P->axis = 1;
+  P->nx = nx;
+  if (L->n == 0 || nx == 0) return 0;
+  a.X = P->X; a.nx = nx;
+  dim3 grd((unsigned)((L->n + 255) / 256), (unsigned)n_layers);
+  if (env_args) hipLaunchKernelGGL(line_prep_axis_kernel<true>, grd, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(line_prep_axis_kernel<false>, grd, dim3(256), 0, st, a);
   RTX_LAUNCH_CHECK();
   return 0;
 }

@@ -567,6 +567,7 @@ static int sd_tables(SdTab* out) {
 extern "C" int rtx_sdvoigt_sum(const rtx_prep* P, const rtx_grid* grid, int n_layers, float* out_f32, double* out_f64, int64_t ld,
                                void* stream) {
   if (!P) RTX_FAIL("prep is NULL");
+  if (P->axis) RTX_FAIL("the last prologue was rtx_line_prep_axis: the speed-dependent sum needs a uniform grid");
   if (rtx_check_grid(grid)) return 1;
   if (!P->recsd) RTX_FAIL("rtx_line_prep_profile(..., RTX_PROFILE_SDVOIGT, ...) has not been run on this prep object");
   if (n_layers < 1 || n_layers > P->n_layers) RTX_FAIL("n_layers=%d, the prologue was run for %d", n_layers, P->n_layers);

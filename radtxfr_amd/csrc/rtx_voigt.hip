@@ -153,6 +153,15 @@ static void launch_tile_ranges(const rtx_prep* P, const rtx_grid* grid, int n_la
   hipLaunchKernelGGL(tile_ranges_kernel, dim3((n_tiles * RNG_G + 255) / 256, n_layers), dim3(256), 0, st, ra);
 }
 
+// The axis line-sum (rtx_voigt_axis.hip) takes the same canonical ranges from index-space inputs (rtx_line_prep_axis); its
+// tiles are never cut.
+void rtx_launch_tile_ranges_n(const rtx_prep* P, long long n, int n_layers, int n_tiles, int tile, hipStream_t st) {
+  rtx_grid g;
+  memset(&g, 0, sizeof(g));
+  g.n = n;  // the one field launch_tile_ranges reads
+  launch_tile_ranges(P, &g, n_layers, n_tiles, tile, st, 0);
+}
+
 // RADTXFR_VOIGT_KERNEL=scatter selects the point-by-point cross-check kernel instead of the default nodal one.
 static int voigt_kernel_choice() {  // 0 nodal, 1 scatter
   static int cached = -1;
@@ -166,6 +175,7 @@ static int voigt_kernel_choice() {  // 0 nodal, 1 scatter
 extern "C" int rtx_voigt_sum(const rtx_prep* P, const rtx_grid* grid, int n_layers, float* out_f32, double* out_f64,
                              int64_t ld, void* stream) {
   if (!P) RTX_FAIL("prep is NULL");
+  if (P->axis) RTX_FAIL("the last prologue was rtx_line_prep_axis: sum with rtx_voigt_sum_axis");
   if (rtx_check_grid(grid)) return 1;
   if (n_layers < 1 || n_layers != P->n_layers) RTX_FAIL("n_layers=%d does not match the last rtx_line_prep (%d)", n_layers, P->n_layers);
   if (!out_f32 && !out_f64) RTX_FAIL("both outputs are NULL");

@@ -277,6 +277,23 @@ def species_factors(species, T_layers, partitionFunction=None, weight=None):
 _TIPS_PLANS = {}
 
 
+def _prologue_inputs(lines, T, p_atm, weight, partitionFunction, qratio, mass):
+    """Host inputs of a prologue (rtx_line_prep_profile / rtx_line_prep_axis): n_layers and the (array, pointer) pairs of
+    T, p, qratio[nS][nL], weight[nS][nL] and mass[nS]; the arrays stay alive as long as the caller holds the tuple."""
+    T = np.atleast_1d(np.asarray(T, dtype=np.float64))
+    p_atm = np.atleast_1d(np.asarray(p_atm, dtype=np.float64))
+    nL = T.size
+    if qratio is None:
+        qratio, mass = species_factors(lines.species, T, partitionFunction, weight=weight)
+    return nL, (_h(T), _h(p_atm), _h(qratio), _h(np.broadcast_to(weight, (len(lines.species), nL))), _h(mass))
+
+
+def _check_outputs(nL, ld, out_f32, out_f64):
+    for o, dt in ((out_f32, torch.float32), (out_f64, torch.float64)):
+        if o is not None:
+            assert o.dtype == dt and o.is_cuda and o.is_contiguous() and o.shape == (nL, ld), (o.dtype, o.shape)
+
+
 def voigt_sum(lines, grid, T, p_atm, weight, out_f32=None, out_f64=None, dil_air=1.0, dil_self=0.0, omega_wing=0.0,
               omega_wing_hw=50.0, intensity_threshold=0.0, scale=1.0, partitionFunction=None, qratio=None, mass=None,
               profile=0):
@@ -285,29 +302,46 @@ def voigt_sum(lines, grid, T, p_atm, weight, out_f32=None, out_f64=None, dil_air
     and runs rtx_sdvoigt_sum).
     weight[nS][nL] multiplies S(T) per species and layer. Outputs are [nL][grid.n] device tensors."""
     lib = _lib.load()
-    T = np.atleast_1d(np.asarray(T, dtype=np.float64))
-    p_atm = np.atleast_1d(np.asarray(p_atm, dtype=np.float64))
-    nL = T.size
-    if qratio is None:
-        qratio, mass = species_factors(lines.species, T, partitionFunction, weight=weight)
+    nL, env = _prologue_inputs(lines, T, p_atm, weight, partitionFunction, qratio, mass)
     plan = lines.plan(nL, grid.n)
-    T_h, T_p = _h(T)
-    p_h, p_p = _h(p_atm)
-    q_h, q_p = _h(qratio)
-    w_h, w_p = _h(np.broadcast_to(weight, (len(lines.species), nL)))
-    m_h, m_p = _h(mass)
     st = _stream_ptr()
-    _lib.check(lib.rtx_line_prep_profile(plan._h, lines._h, grid.byref(), nL, T_p, p_p, q_p, w_p, m_p, float(dil_air),
+    _lib.check(lib.rtx_line_prep_profile(plan._h, lines._h, grid.byref(), nL, *(e[1] for e in env), float(dil_air),
                                          float(dil_self), float(omega_wing), float(omega_wing_hw),
                                          float(intensity_threshold), float(scale), int(profile), st))
     ld = grid.n
-    for o, dt in ((out_f32, torch.float32), (out_f64, torch.float64)):
-        if o is not None:
-            assert o.dtype == dt and o.is_cuda and o.is_contiguous() and o.shape == (nL, ld), (o.dtype, o.shape)
+    _check_outputs(nL, ld, out_f32, out_f64)
     if int(profile) == 3:  # speed-dependent Voigt: its own fp64 line-sum
         _lib.check(lib.rtx_sdvoigt_sum(plan._h, grid.byref(), nL, _ptr(out_f32), _ptr(out_f64), ld, st))
     else:
         _lib.check(lib.rtx_voigt_sum(plan._h, grid.byref(), nL, _ptr(out_f32), _ptr(out_f64), ld, st))
+    return out_f32, out_f64
+
+
+def voigt_sum_axis(lines, X, T, p_atm, weight, out_f32=None, out_f64=None, dil_air=1.0, dil_self=0.0, omega_wing=0.0,
+                   omega_wing_hw=50.0, intensity_threshold=0.0, scale=1.0, partitionFunction=None, qratio=None, mass=None,
+                   profile=0):
+    """voigt_sum on an explicit axis X (host, finite, non-decreasing; need not be uniform) instead of a Grid:
+    rtx_line_prep_axis + rtx_voigt_sum_axis. Windows are bisect_right on X itself, as the reference's (misc/hapi.py:
+    11133-11134). profile 0 Voigt, 1 Lorentz, 2 Doppler (the speed-dependent sum needs a uniform grid).
+    Outputs are [nL][X.size] device tensors."""
+    lib = _lib.load()
+    X = np.ascontiguousarray(np.asarray(X, dtype=np.float64).ravel())
+    if not np.all(np.isfinite(X)):
+        raise ValueError("voigt_sum_axis: the axis has non-finite points")
+    if X.size > 1 and np.any(X[1:] < X[:-1]):
+        raise ValueError("voigt_sum_axis: the axis must be non-decreasing (np.sort it)")
+    if int(profile) not in (0, 1, 2):
+        raise NotImplementedError("voigt_sum_axis: profile %d; an explicit axis takes Voigt (0), Lorentz (1) or Doppler (2)"
+                                  % int(profile))
+    nL, env = _prologue_inputs(lines, T, p_atm, weight, partitionFunction, qratio, mass)
+    nx = X.size
+    plan = lines.plan(nL, max(nx, 1))
+    st = _stream_ptr()
+    _lib.check(lib.rtx_line_prep_axis(plan._h, lines._h, X.ctypes.data_as(C.c_void_p), nx, nL, *(e[1] for e in env),
+                                      float(dil_air), float(dil_self), float(omega_wing), float(omega_wing_hw),
+                                      float(intensity_threshold), float(scale), int(profile), st))
+    _check_outputs(nL, nx, out_f32, out_f64)
+    _lib.check(lib.rtx_voigt_sum_axis(plan._h, nL, _ptr(out_f32), _ptr(out_f64), nx, st))
     return out_f32, out_f64
 
 

@@ -202,9 +202,17 @@ def _absorption_coefficient(profile, Components, SourceTables, partitionFunction
     extra = set(dil) - {"air", "self"}
     if extra:
         raise NotImplementedError("diluents %s are not supported (air, self only)" % sorted(extra))
-    if Omegas.size < 2:
-        raise NotImplementedError("the HIP line-sum needs a grid of at least 2 points")
-    grid = engine.Grid.from_axis(Omegas)
+    # a uniform grid (what Grid.from_axis recognises) takes the grid line-sum; any other sorted grid -- non-uniform,
+    # repeated points, fewer than 2 points -- the explicit-axis one (rtx_line_prep_axis + rtx_voigt_sum_axis)
+    grid = None
+    if Omegas.size >= 2:
+        try:
+            grid = engine.Grid.from_axis(Omegas)
+        except NotImplementedError:
+            grid = None
+    if grid is None and profile == 3 and Omegas.size:
+        raise NotImplementedError("speed-dependent Voigt (non-zero SD_air / SD_self) needs a uniform wavenumber grid: this "
+                                  "OmegaGrid / WavenumberGrid is not an np.linspace")
     # per-species weight = factor / natural * abundance (misc/hapi.py:11136-11137); 0 filters the species out (:11066)
     w = np.zeros((len(tbl.species), 1))
     for s, mi in enumerate(tbl.species):
@@ -213,13 +221,19 @@ def _absorption_coefficient(profile, Components, SourceTables, partitionFunction
     # fold a power of two into the fp32 strengths so HITRAN-unit intensities (~1e-19..1e-30) stay normal
     smax = float(np.max(tbl.cols["sw"])) * float(np.max(w)) if tbl.n and np.max(w) > 0 else 1.0
     scale = 2.0 ** (-math.floor(math.log2(smax))) if smax > 0 and math.isfinite(smax) else 1.0
-    if tbl.n == 0:
+    if tbl.n == 0 or Omegas.size == 0:
         Xsect = np.zeros(Omegas.size)
-    else:
+    elif grid is not None:
         out = torch.empty((1, grid.n), dtype=torch.float64, device=engine.device())
         engine.voigt_sum(tbl, grid, [T], [p], w, out_f64=out, dil_air=dil.get("air", 0.0), dil_self=dil.get("self", 0.0),
                          omega_wing=OmegaWing, omega_wing_hw=OmegaWingHW, intensity_threshold=IntensityThreshold,
                          scale=scale, partitionFunction=partitionFunction, profile=profile)
+        Xsect = out[0].cpu().numpy()
+    else:
+        out = torch.empty((1, Omegas.size), dtype=torch.float64, device=engine.device())
+        engine.voigt_sum_axis(tbl, Omegas, [T], [p], w, out_f64=out, dil_air=dil.get("air", 0.0), dil_self=dil.get("self", 0.0),
+                              omega_wing=OmegaWing, omega_wing_hw=OmegaWingHW, intensity_threshold=IntensityThreshold,
+                              scale=scale, partitionFunction=partitionFunction, profile=profile)
         Xsect = out[0].cpu().numpy()
     if File:
         with open(File, "w") as f:
@@ -237,9 +251,10 @@ def absorptionCoefficient_Voigt(Components=None, SourceTables=None, partitionFun
     """Absorption coefficient with the Voigt profile; same inputs/outputs as misc/hapi.py:10906-11141.
 
     Returns (Omegas, Xsect) as float64 NumPy arrays. The sum over lines runs on the GPU
-    (rtx_line_prep + rtx_voigt_sum); line strengths are carried in fp32 with a power-of-two scale,
-    so Xsect agrees with the reference to ~1e-6 relative, not bit for bit.
-    Not supported (raises): EnvDependences hooks, diluents other than air/self, non-uniform grids.
+    (rtx_line_prep + rtx_voigt_sum on a uniform grid; rtx_line_prep_axis + rtx_voigt_sum_axis on any other sorted
+    OmegaGrid -- non-uniform, repeated points, a single point); line strengths are carried in fp32 with a power-of-two
+    scale, so Xsect agrees with the reference to ~1e-6 relative, not bit for bit.
+    Not supported (raises): EnvDependences hooks, diluents other than air/self.
     """
     return _absorption_coefficient(0, Components, SourceTables, partitionFunction, Environment, OmegaRange, OmegaStep, OmegaWing,
                                    IntensityThreshold, OmegaWingHW, GammaL, HITRAN_units, LineShift, File, Format, OmegaGrid,
@@ -291,7 +306,8 @@ def absorptionCoefficient_SDVoigt(Components=None, SourceTables=None, partitionF
     Tables without speed-dependence columns (the 160-character HITRAN .par format has none) give Gamma2 = 0, for which
     pcqsdhc takes its PART1 branch (:9908-9915), i.e. the Voigt profile: those go through the fp32 Voigt line-sum.
     Tables with non-zero SD_air / SD_self (:10884-10890) go through rtx_sdvoigt_sum: pcqsdhc PART2-4 in fp64, far wings at
-    Chebyshev nodes (the path of the reference's cross-section generator, misc/RT_gen_AbsXS_files.py:90)."""
+    Chebyshev nodes (the path of the reference's cross-section generator, misc/RT_gen_AbsXS_files.py:90); those need a uniform
+    grid (a non-uniform OmegaGrid raises NotImplementedError)."""
     sd = False
     for name in listOfTuples(SourceTables):
         if name is None or name not in LOCAL_TABLE_CACHE:
