@@ -123,6 +123,19 @@ int rtx_line_prep_profile(rtx_prep* prep, const rtx_lines* lines, const rtx_grid
                           double dil_self, double omega_wing, double omega_wing_hw,
                           double intensity_threshold, double scale, int profile, void* stream);
 
+/* The grid prologue with every line's window held at another temperature: T_win_h[n_layers] (host) replaces T_h in
+ * OmegaWingF (misc/hapi.py:11131), hence in the windows bisect(X, nu -+ W) (:11133-11134), the candidate half-widths and
+ * the hot-tile bound; strengths, partition sums, widths and shifts are taken at T_h as in rtx_line_prep_profile. With
+ * T_win_h = T_h the records are those of rtx_line_prep_profile. Used for dOD/dT by central differences at T_h = T -+ h with
+ * T_win_h = T: the derivative of the truncated line-sum with each line's support fixed (no cut-off steps). T_win_h is
+ * copied into a device buffer owned by the prep object (grow-only: the first call allocates, hence synchronises).
+ * profile RTX_PROFILE_VOIGT / _LORENTZ / _DOPPLER. Follow with rtx_voigt_sum. */
+int rtx_line_prep_window(rtx_prep* prep, const rtx_lines* lines, const rtx_grid* grid, int n_layers,
+                         const double* T_h, const double* T_win_h, const double* p_atm_h, const double* qratio_h,
+                         const double* weight_h, const double* mass_h, double dil_air, double dil_self,
+                         double omega_wing, double omega_wing_hw, double intensity_threshold, double scale,
+                         int profile, void* stream);
+
 /* The prologue on an explicit axis X_h[nx] instead of a uniform grid (the reference sorts whatever OmegaGrid it is given
  * and bisects it, misc/hapi.py:10979-10983, 11133-11134): host fp64, non-decreasing, finite; 0 <= nx <= the max_points of
  * rtx_prep_create. X_h is copied into a device buffer owned by the prep object (grow-only: a longer axis than before
@@ -186,6 +199,27 @@ int rtx_tud(const float* OD, int64_t ld, const rtx_grid* grid, int n_layers, con
             int n_alt, const uint8_t* mask_h, int n_mu, const double* mu_h, int n_down,
             int n_angle, int return_od, float* tau, float* Lu, float* Ld, float* Ld_angles,
             int64_t ld_out, void* stream);
+
+/* Jacobian of the rtx_tud outputs with respect to layer temperatures and mixing ratios (one slant factor mu), for the
+ * layers layers_h[n_lay] (host, each in [0,n_layers), in output order):
+ *   J[n_wrt][n_lay][2*n_alt+1][ld_J] float32, rows: tau of each altitude, L-up of each altitude, Ld;
+ *   wrt: n_wrt = (OD_plus != NULL) + n_spec entries; T (when OD_plus is given) at position t_pos in [0, n_spec], the
+ *   n_spec species of K in their order in the other positions (t_pos = 0 without OD_plus).
+ * Inputs: OD[n_layers][ld] of the state; OD_plus / OD_minus[n_layers][ld] at T -+ fd_step (windows at T,
+ * rtx_line_prep_window), or both NULL; K[n_spec][n_layers][ld] the optical depth per unit mixing ratio of each species;
+ * tau[n_alt][ld_tau] the base transmittances rtx_tud wrote (may be NULL with return_od); T_h, mask_h, n_down, n_angle,
+ * return_od as for rtx_tud. With dOD = (OD_plus - OD_minus)/(2 fd_step) for T and dOD = K for a species:
+ *   J = (d row / d OD_l) dOD + [wrt = T] (d row / d T_l at fixed OD),
+ * d/dOD_l of tau: -mu tau [Z_l <= zs] (return_od: mu [Z_l <= zs]); of L-up, l < count: mu t_l Q (B_l - L^(l-1)),
+ * Q = prod_{l<j<count} t_j; of Ld, l < n_down: sum_q (w_q/c_q) t_{l,q} P_{l,q} (B_l - R_{l+1,q}) (P: transmittance below l,
+ * R_{l+1}: downwelling radiance at the top of layer l); the fixed-OD T terms carry (1 - t) dB/dT in place of the
+ * OD factor. Structural zeros (an altitude's L-up above its count, Ld above n_down, a species without lines) are exact.
+ * A layer's rows do not depend on which other layers are requested (bit-identical for any subset or blocking). */
+int rtx_tud_jacobian(const float* OD, const float* OD_plus, const float* OD_minus, int64_t ld, double fd_step,
+                     const float* K, int n_spec, const float* tau, int64_t ld_tau, const rtx_grid* grid,
+                     int n_layers, const double* T_h, int n_alt, const uint8_t* mask_h, double mu, int n_down,
+                     int n_angle, int return_od, const int32_t* layers_h, int n_lay, int t_pos, float* J,
+                     int64_t ld_J, void* stream);
 /* The tabulated G of rtx_tud, for host-side checks (no device involved): rtx_tud_gtable_size() doubles, rows of
  * {interval centre, a0 .. a6}: G(S) = sum a_k (S - centre)^k on the row's interval; intervals: 16 per binade of
  * S + 2^-6 below S = 16 (row = (bits(float(S) + 2^-6) >> 19) - (bits(2^-6) >> 19)), width 1/2 from there to S = 48.

@@ -35,6 +35,7 @@ PROTOTYPES = {
     "rtx_line_prep": (_i32, [_vp, _vp, _gp, _i32, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _vp]),
     "rtx_line_prep_profile": (_i32, [_vp, _vp, _gp, _i32, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _i32, _vp]),
     "rtx_prep_split_bound": (_i64, [_vp]),
+    "rtx_line_prep_window": (_i32, [_vp, _vp, _gp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _i32, _vp]),
     "rtx_line_prep_axis": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _i32, _vp]),
     "rtx_voigt_sum": (_i32, [_vp, _gp, _i32, _vp, _vp, _i64, _vp]),
     "rtx_voigt_sum_axis": (_i32, [_vp, _i32, _vp, _vp, _i64, _vp]),
@@ -44,6 +45,8 @@ PROTOTYPES = {
     "rtx_voigt_tile_points": (_i32, []),
     "rtx_planck": (_i32, [_gp, _vp, _i64, _vp, _i64, _i32, _vp, _vp]),
     "rtx_tud": (_i32, [_vp, _i64, _gp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "rtx_tud_jacobian": (_i32, [_vp, _vp, _vp, _i64, _dbl, _vp, _i32, _vp, _i64, _gp, _i32, _vp, _i32, _vp, _dbl, _i32, _i32,
+                                 _i32, _vp, _i32, _i32, _vp, _i64, _vp]),
     "rtx_tud_gtable_size": (_i32, []),
     "rtx_tud_gtable": (_i32, [_i32, _vp, _vp]),
     "rtx_compute_tud": (_i32, [_vp, _vp, _gp, _i32, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _i32, _vp, _i32, _vp,

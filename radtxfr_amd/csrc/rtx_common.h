@@ -177,4 +177,7 @@ struct rtx_prep {
   long long x_cap;
   long long nx;
   int axis;
+  // window temperatures of rtx_line_prep_window: device copy, grow-only
+  double* twin;
+  int twin_cap;
 };

@@ -161,6 +161,7 @@ extern "C" int rtx_prep_free(rtx_prep* P) {
   if (P->items) (void)hipFree(P->items);
   if (P->part_ws) (void)hipFree(P->part_ws);
   if (P->X) (void)hipFree(P->X);
+  if (P->twin) (void)hipFree(P->twin);
   delete P;
   return 0;
 }
@@ -241,6 +242,7 @@ struct PrepArgs {
   GridDev g;
   const double* X;  // explicit axis (line_prep_axis_kernel): device copy, X[nx]
   long long nx;
+  const double* Twin;  // line_prep_kernel<., true>: per-layer temperature of the windows (device copy, rtx_line_prep_window)
   LineRec* rec;
   LineRec64* rec64;
   int* ic;
@@ -377,7 +379,9 @@ __device__ __forceinline__ void block_max_hw(int v, int* dst) {
   }
 }
 
-template <bool ENV_ARGS>
+// WIN: every window (W, hence lo / hi, maxhw and the skip test) is that of the line at the layer's window temperature
+// a.Twin[k] (rtx_line_prep_window); strengths, widths and shifts stay at T. WIN = false is the reference's prologue.
+template <bool ENV_ARGS, bool WIN>
 __global__ __launch_bounds__(256) void line_prep_kernel(PrepArgs a) {
   const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const int k = blockIdx.y;
@@ -395,7 +399,8 @@ __global__ __launch_bounds__(256) void line_prep_kernel(PrepArgs a) {
     const int sp = a.species[l];
     const double w = ew[(size_t)sp * a.n_layers + k];
     const LinePhys ph = line_phys(a, l, T, p, em[sp], nu);
-    const double GammaD = ph.GammaD, Gamma0 = ph.Gamma0, Shift0 = ph.Shift0, W = ph.W;
+    const double GammaD = ph.GammaD, Gamma0 = ph.Gamma0, Shift0 = ph.Shift0;
+    const double W = WIN ? line_phys(a, l, a.Twin[k], p, em[sp], nu).W : ph.W;
     long long glo = grid_bisect_right(g, nu - W);
     long long ghi = grid_bisect_right(g, nu + W);
     int lo = clamp_local(glo, g), hi = clamp_local(ghi, g);
@@ -669,7 +674,7 @@ static int prep_begin(rtx_prep* P, const rtx_lines* L, int n_layers, const doubl
   }
   a.dil_air = dil_air; a.dil_self = dil_self; a.omega_wing = omega_wing; a.omega_wing_hw = omega_wing_hw;
   a.thresh = intensity_threshold; a.scale = scale; a.profile = profile;
-  a.X = nullptr; a.nx = 0;
+  a.X = nullptr; a.nx = 0; a.Twin = nullptr;
   a.rec = P->rec; a.rec64 = P->rec64; a.ic = P->ic; a.win = P->win; a.maxhw = P->maxhw; a.smally = P->smally;
   return 0;
 }
@@ -698,8 +703,8 @@ extern "C" int rtx_line_prep_profile(rtx_prep* P, const rtx_lines* L, const rtx_
   if (L->n == 0) return 0;
   a.g = to_dev(grid);
   dim3 grd((unsigned)((L->n + 255) / 256), (unsigned)n_layers);
-  if (env_args) hipLaunchKernelGGL(line_prep_kernel<true>, grd, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(line_prep_kernel<false>, grd, dim3(256), 0, st, a);
+  if (env_args) hipLaunchKernelGGL((line_prep_kernel<true, false>), grd, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((line_prep_kernel<false, false>), grd, dim3(256), 0, st, a);
   RTX_LAUNCH_CHECK();
   return 0;
 }
@@ -750,4 +755,46 @@ extern "C" int rtx_line_prep(rtx_prep* P, const rtx_lines* L, const rtx_grid* gr
                              double intensity_threshold, double scale, void* stream) {
   return rtx_line_prep_profile(P, L, grid, n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, dil_air, dil_self, omega_wing,
                                omega_wing_hw, intensity_threshold, scale, RTX_PROFILE_VOIGT, stream);
+}
+
+// The grid prologue with the windows held at other temperatures: the derivative of the truncated line-sum with every
+// line's support fixed (rtx_tud_jacobian's dOD/dT). Everything but the windows is taken at T_h; OmegaWingF, hence
+// the windows, the candidate half-widths and the hot-tile bound, at T_win_h. T_win_h is copied into a device buffer owned by
+// the prep object (grow-only). With T_win_h == T_h the records are those of rtx_line_prep_profile.
+extern "C" int rtx_line_prep_window(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid, int n_layers, const double* T_h,
+                                    const double* T_win_h, const double* p_atm_h, const double* qratio_h, const double* weight_h,
+                                    const double* mass_h, double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
+                                    double intensity_threshold, double scale, int profile, void* stream) {
+  if (!P || !L) RTX_FAIL("prep/lines is NULL");
+  if (profile < RTX_PROFILE_VOIGT || profile > RTX_PROFILE_DOPPLER)
+    RTX_FAIL("rtx_line_prep_window: profile=%d (Voigt, Lorentz or Doppler)", profile);
+  if (rtx_check_grid(grid)) return 1;
+  if (!T_win_h) RTX_FAIL("T_win_h is NULL");
+  for (int k = 0; k < n_layers; ++k)
+    if (!(T_win_h[k] > 0.0)) RTX_FAIL("layer %d: window temperature %g not physical", k, T_win_h[k]);
+  hipStream_t st = (hipStream_t)stream;
+  PrepArgs a;
+  bool env_args = false;
+  if (prep_begin(P, L, n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, dil_air, dil_self, omega_wing, omega_wing_hw,
+                 intensity_threshold, scale, profile, st, a, env_args))
+    return 1;
+  if (n_layers > P->twin_cap) {  // grow-only: allocates, hence synchronises
+    if (P->twin) { RTX_HIP(hipFree(P->twin)); P->twin = nullptr; }
+    P->twin_cap = 0;
+    RTX_HIP(hipMalloc((void**)&P->twin, (size_t)P->max_layers * sizeof(double)));
+    P->twin_cap = P->max_layers;
+  }
+  RTX_HIP(hipMemcpyAsync(P->twin, T_win_h, (size_t)n_layers * sizeof(double), hipMemcpyHostToDevice, st));  // staged before returning
+  if (rtx_split_bound(P, L, grid, n_layers, T_win_h, p_atm_h, mass_h, dil_air, dil_self, omega_wing, omega_wing_hw, profile)) return 1;
+  P->n_layers = n_layers;
+  P->scale = scale;
+  P->axis = 0;
+  if (L->n == 0) return 0;
+  a.g = to_dev(grid);
+  a.Twin = P->twin;
+  dim3 grd((unsigned)((L->n + 255) / 256), (unsigned)n_layers);
+  if (env_args) hipLaunchKernelGGL((line_prep_kernel<true, true>), grd, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((line_prep_kernel<false, true>), grd, dim3(256), 0, st, a);
+  RTX_LAUNCH_CHECK();
+  return 0;
 }

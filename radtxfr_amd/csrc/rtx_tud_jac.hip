@@ -1,0 +1,302 @@
+// Jacobian of the TUD outputs (tau, L-up per sensor altitude, Ld) with respect to layer temperatures and mixing ratios:
+// the chain rule through the recurrences of rtx_tud, closed form.
+//
+// rtx_tud_jacobian : J[wrt][layer][row][nu], row = tau of each altitude, L-up of each altitude, Ld (2 n_alt + 1 rows);
+//                    wrt = T (when asked, at t_pos) and one entry per species. The caller supplies, per layer, what the
+//                    layer's optical depth does: (OD+ - OD-) / 2h for T, the line-sum at 1 ppmv for a species.
+//
+// Mapping (CDNA4): lane <-> wavenumber as in rtx_tud; a run-time loop over the layers; every J row is a dword store per
+// lane, contiguous along the wavenumber axis (256 B per wave and store), non-temporal (nothing reads J back soon).
+// The requested layers are taken TUDJ_CH at a time; for each such chunk the lane
+//   (a) sweeps the column bottom-up once: fp64 prefix sums S_j = sum_{i<j} OD_i, D_l = B_l - L^(l-1) (L: the upwelling
+//       recurrence) and the sums S_cnt(a) at each altitude's layer count;
+//   (b) runs the downwelling stream recurrences top-down, TUDJ_QG streams at a time, from n_down - 1 to the chunk's
+//       lowest layer, carrying E_{l,q} = B_l - R_{l+1,q} (R_{l+1,q}: the radiance arriving at the top of layer l);
+//   (c) stores the chunk's rows.
+// Every product of transmittances is exp(-(S_b - S_a) c) of an fp64 difference of prefix sums (no division of cumulative
+// products, which underflow in opaque columns). The two differences a layer's sensitivity carries, B_l - L^(l-1) and
+// B_l - R_{l+1}, are recurrences of their own driven by fp64 differences of neighbouring layers' B: no radiance is
+// subtracted from a Planck value (that cancels where temperature barely changes with height, e.g. an isothermal
+// stratosphere), and no "everything above l" sum appears. A layer's value depends only on
+// the layer, never on which chunk or launch it is computed in: results are bit-identical for any subset of layers and
+// any blocking of them.
+#include <math.h>
+#include <string.h>
+
+#include "rtx_common.h"
+
+#define RT_C2 1.43877736830e-02  // radiative_transfer.py:72
+#define RT_C1 1.19104295315e-16  // radiative_transfer.py:71
+#define LOG2E 1.4426950408889634
+#define LN2 0.6931471805599453
+
+#define TUDJ_MAX_LAYERS 128
+#define TUDJ_MAX_ALT 16
+#define TUDJ_MAX_ANGLES 96
+#define TUDJ_MAX_SPEC 16
+#ifndef TUDJ_CH
+#define TUDJ_CH 8  // requested layers per chunk (registers: fp64 S_l, S_l+1 and four floats each)
+#endif
+#ifndef TUDJ_QG
+#define TUDJ_QG 8  // downwelling streams advanced together
+#endif
+
+struct TudJacArgs {
+  const float* OD;       // [n_layers][ld]
+  const float* ODp;      // [n_layers][ld] at T + h (windows at T), or NULL
+  const float* ODm;      // [n_layers][ld] at T - h
+  const float* K;        // [n_spec][n_layers][ld] OD per ppmv
+  const float* tau;      // [n_alt][ld_tau] base transmittances (unused with return_od)
+  float* J;              // [n_wrt][n_lay][2 n_alt + 1][ld_J]
+  long long ld, ld_tau, ld_J;
+  GridDev g;
+  int n_layers, n_alt, n_down, n_str, return_od, with_T, n_spec, n_lay, t_pos;
+  float mu, inv_2h;
+  double mu_d;
+  double c2l2e_over_T[TUDJ_MAX_LAYERS];  // 100 c2 log2(e) / T_k, as rtx_tud forms it
+  int lay[TUDJ_MAX_LAYERS];              // requested layers, in output order
+  unsigned int lbits[TUDJ_MAX_LAYERS];    // layer l: bit a = [Z_l <= zs_a] (tau mask), bit 16 + a = [l < count_a]
+  int count[TUDJ_MAX_ALT];
+  double str_ic[TUDJ_MAX_ANGLES];        // 1 / cos(theta_q) of the evaluated streams
+  float str_w[TUDJ_MAX_ANGLES];          // omega_q = cos sin / sum(cos sin)
+  float str_wc[TUDJ_MAX_ANGLES];         // omega_q / cos(theta_q)
+};
+
+// e^-y for y >= 0 given in fp64: the argument rounded once to fp32, then v_exp_f32 (|y| up to ~87 matters)
+__device__ __forceinline__ float exp_neg(double y) { return __builtin_amdgcn_exp2f((float)(-y * LOG2E)); }
+
+// 1 - e^-y, accurate to ~1e-7 relative also for a thin layer (the form of rtx_tud.hip's em_thin)
+__device__ __forceinline__ float one_minus_exp_neg(float y) {
+  const float z = -y * (float)LOG2E;  // log2 of the transmittance
+  if (z > -0.0625f) {
+    const float q = fmaf(fmaf(fmaf(9.6181291076e-3f, z, 5.5504108665e-2f), z, 2.4022650696e-1f), z, 6.9314718056e-1f);
+    return -z * q;
+  }
+  return 1.0f - __builtin_amdgcn_exp2f(z);
+}
+
+// B(nu, T_k) as rtx_tud evaluates it and its analytic temperature derivative: with u = c2 nu / T (t = u log2 e, the fp64
+// exponent planck_f32 forms), dB/dT = B (u / T) e^u / (e^u - 1) = B (u / T) (1 + B / c1x3).
+__device__ __forceinline__ void planck_dT(double c1x3, double x, double ct, float& B, float& dB) {
+  B = planck_f32(c1x3, x, ct);
+  // u / T = (t ln2) / T and 1/T = ct / (100 c2 log2 e)
+  const double uT = x * ct * ct * (LN2 / (100.0 * RT_C2 * LOG2E));
+  dB = B * (float)uT * (1.0f + B / (float)c1x3);
+}
+
+// B in fp64: only differences of neighbouring layers' B are formed from it (the recurrences below)
+__device__ __forceinline__ double planck_f64(double c1x3, double x, double ct) { return c1x3 / expm1(x * ct * LN2); }
+
+__global__ __launch_bounds__(256) void tud_jac_kernel(TudJacArgs a) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.g.n) return;  // no cross-lane work: dead lanes leave
+  const int nL = a.n_layers;
+  const float* __restrict__ od = a.OD + i;
+  const double x = grid_x(a.g, a.g.offset + i);
+  const double x100 = x * 100.0;
+  const double c1x3 = RT_C1 * (x100 * x100 * x100) * 1e4;
+  const int nrow = 2 * a.n_alt + 1;
+  const int n_wrt = a.with_T + a.n_spec;
+
+  for (int k0 = 0; k0 < a.n_lay; k0 += TUDJ_CH) {
+    const int nk = min(TUDJ_CH, a.n_lay - k0);
+    int lmax = -1, lmin_d = nL;
+    for (int k = 0; k < nk; ++k) {
+      const int l = a.lay[k0 + k];
+      lmax = max(lmax, l);
+      if (l < a.n_down) lmin_d = min(lmin_d, l);
+    }
+    // ---- (a) bottom-up: prefix sums, D_l = B_l - L^(l-1), S at each altitude's count. D is carried by its own
+    //      recurrence D_{j+1} = t_j D_j + (B_{j+1} - B_j), D_0 = B_0, with the B differences in fp64: forming B_l - L^(l-1)
+    //      from the radiance recurrence cancels where neighbouring layers have (nearly) the same temperature ----
+    double S0[TUDJ_CH], S1[TUDJ_CH];
+    float Dl[TUDJ_CH], odl[TUDJ_CH];
+#pragma unroll
+    for (int k = 0; k < TUDJ_CH; ++k) { S0[k] = S1[k] = 0.0; Dl[k] = odl[k] = 0.f; }
+    double Scnt[TUDJ_MAX_ALT];
+#pragma unroll
+    for (int q = 0; q < TUDJ_MAX_ALT; ++q) Scnt[q] = 0.0;
+    double S = 0.0;
+    double Bc = planck_f64(c1x3, x, a.c2l2e_over_T[0]);
+    float D = (float)Bc;
+    for (int j = 0; j < nL; ++j) {
+#pragma unroll
+      for (int q = 0; q < TUDJ_MAX_ALT; ++q)
+        if (q < a.n_alt && a.count[q] == j) Scnt[q] = S;
+      const float o = od[(size_t)j * a.ld];
+#pragma unroll
+      for (int k = 0; k < TUDJ_CH; ++k)
+        if (k < nk && a.lay[k0 + k] == j) { S0[k] = S; Dl[k] = D; odl[k] = o; }
+      if (j < lmax) {  // D_{j+1} is needed up to D_lmax
+        const double Bn = planck_f64(c1x3, x, a.c2l2e_over_T[j + 1]);
+        D = fmaf(__builtin_amdgcn_exp2f(-(o * a.mu) * (float)LOG2E), D, (float)(Bn - Bc));
+        Bc = Bn;
+      }
+      S += (double)o;
+#pragma unroll
+      for (int k = 0; k < TUDJ_CH; ++k)
+        if (k < nk && a.lay[k0 + k] == j) S1[k] = S;
+    }
+#pragma unroll
+    for (int q = 0; q < TUDJ_MAX_ALT; ++q)
+      if (q < a.n_alt && a.count[q] == nL) Scnt[q] = S;
+
+    // ---- (b) downwelling: g = sum_q (w_q/c_q) e^{-S_{l+1}/c_q} E_{l,q},  E_{l,q} = B_l - R_{l+1,q},
+    //                       h = sum_q w_q (1 - t_{l,q}) e^{-S_l/c_q} dB_l.
+    //      E by its own recurrence, top-down: E_{n_down-1} = B_{n_down-1}, E_{j-1} = t_{j,q} E_j + (B_{j-1} - B_j) ----
+    float gLd[TUDJ_CH], hLd[TUDJ_CH];
+#pragma unroll
+    for (int k = 0; k < TUDJ_CH; ++k) { gLd[k] = 0.f; hLd[k] = 0.f; }
+    if (lmin_d < a.n_down) {
+      for (int q0 = 0; q0 < a.n_str; q0 += TUDJ_QG) {
+        double Bt = planck_f64(c1x3, x, a.c2l2e_over_T[a.n_down - 1]);
+        float E[TUDJ_QG];
+#pragma unroll
+        for (int q = 0; q < TUDJ_QG; ++q) E[q] = (float)Bt;
+        for (int j = a.n_down - 1; j >= lmin_d; --j) {
+          const float o = od[(size_t)j * a.ld];
+#pragma unroll
+          for (int k = 0; k < TUDJ_CH; ++k) {
+            if (k < nk && a.lay[k0 + k] == j) {  // wave-uniform
+              float B, dB;
+              planck_dT(c1x3, x, a.c2l2e_over_T[j], B, dB);
+              float g = gLd[k], h = hLd[k];
+#pragma unroll
+              for (int q = 0; q < TUDJ_QG; ++q) {
+                if (q0 + q < a.n_str) {
+                  const double ic = a.str_ic[q0 + q];
+                  g += a.str_wc[q0 + q] * exp_neg(S1[k] * ic) * E[q];
+                  h += a.str_w[q0 + q] * one_minus_exp_neg(o * (float)ic) * exp_neg(S0[k] * ic) * dB;
+                }
+              }
+              gLd[k] = g;
+              hLd[k] = h;
+            }
+          }
+          if (j > lmin_d) {
+            const double Bn = planck_f64(c1x3, x, a.c2l2e_over_T[j - 1]);
+            const float dBn = (float)(Bn - Bt);
+#pragma unroll
+            for (int q = 0; q < TUDJ_QG; ++q)
+              E[q] = fmaf(__builtin_amdgcn_exp2f(-(o * (float)a.str_ic[q0 + q]) * (float)LOG2E), E[q], dBn);
+            Bt = Bn;
+          }
+        }
+      }
+    }
+
+    // ---- (c) rows of the chunk: the row factors g = d row / d OD_l and h = d row / d T_l at fixed OD (register arrays
+    //      indexed by unrolled constants only), then J = g dOD/dx (+ h for T), one wrt at a time ----
+    const size_t wstride = (size_t)a.n_lay * nrow * a.ld_J;
+#pragma unroll
+    for (int k = 0; k < TUDJ_CH; ++k) {
+      if (k < nk) {
+        const int l = a.lay[k0 + k];
+        float B, dB;
+        planck_dT(c1x3, x, a.c2l2e_over_T[l], B, dB);
+        const float em_l = one_minus_exp_neg(odl[k] * a.mu);
+        const float t_l = __builtin_amdgcn_exp2f(-(odl[k] * a.mu) * (float)LOG2E);  // not 1 - em_l: t is tiny where thick
+        float gT[TUDJ_MAX_ALT], gU[TUDJ_MAX_ALT], hU[TUDJ_MAX_ALT];
+        const unsigned lb = a.lbits[l];  // one scalar word per layer instead of 2 x n_alt table reads
+#pragma unroll
+        for (int ia = 0; ia < TUDJ_MAX_ALT; ++ia) {
+          gT[ia] = gU[ia] = hU[ia] = 0.f;
+          if (ia < a.n_alt) {
+            // tau: -mu tau [Z_l <= zs]; returnOD: mu [Z_l <= zs]
+            if ((lb >> ia) & 1u) gT[ia] = a.return_od ? a.mu : -a.mu * a.tau[(size_t)ia * a.ld_tau + i];
+            // L-up: mu t_l Q D_l (D_l = B_l - L^(l-1)) and (1 - t_l) Q dB_l, Q = prod_{l<j<count} t_j; zero above the count
+            if ((lb >> (16 + ia)) & 1u) {
+              const float Q = exp_neg(a.mu_d * (Scnt[ia] - S1[k]));
+              gU[ia] = a.mu * t_l * Q * Dl[k];
+              hU[ia] = em_l * Q * dB;
+            }
+          }
+        }
+        const bool down = l < a.n_down;
+        const float gD = down ? gLd[k] : 0.f, hD = down ? hLd[k] : 0.f;
+        float* const out0 = a.J + (size_t)(k0 + k) * nrow * a.ld_J + i;
+        for (int w = 0; w < n_wrt; ++w) {
+          const bool isT = a.with_T && w == 0;
+          // output slot: T at t_pos, the species in their order around it
+          const int slot = !a.with_T ? w : isT ? a.t_pos : (w - 1 < a.t_pos ? w - 1 : w);
+          float* const out = out0 + (size_t)slot * wstride;
+          const size_t e = (size_t)l * a.ld + i;
+          const float d = isT ? (a.ODp[e] - a.ODm[e]) * a.inv_2h : a.K[(size_t)(w - a.with_T) * nL * a.ld + e];
+#pragma unroll
+          for (int ia = 0; ia < TUDJ_MAX_ALT; ++ia)
+            if (ia < a.n_alt) __builtin_nontemporal_store(gT[ia] * d, out + (size_t)ia * a.ld_J);
+#pragma unroll
+          for (int ia = 0; ia < TUDJ_MAX_ALT; ++ia)
+            if (ia < a.n_alt)
+              __builtin_nontemporal_store(isT ? fmaf(gU[ia], d, hU[ia]) : gU[ia] * d, out + (size_t)(a.n_alt + ia) * a.ld_J);
+          __builtin_nontemporal_store(isT ? fmaf(gD, d, hD) : gD * d, out + (size_t)(2 * a.n_alt) * a.ld_J);
+        }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------
+extern "C" int rtx_tud_jacobian(const float* OD, const float* OD_plus, const float* OD_minus, int64_t ld, double fd_step,
+                                const float* K, int n_spec, const float* tau, int64_t ld_tau, const rtx_grid* grid, int n_layers,
+                                const double* T_h, int n_alt, const uint8_t* mask_h, double mu, int n_down, int n_angle,
+                                int return_od, const int32_t* layers_h, int n_lay, int t_pos, float* J, int64_t ld_J,
+                                void* stream) {
+  if (rtx_check_grid(grid)) return 1;
+  const int with_T = OD_plus != nullptr;
+  if (!OD || !T_h || !mask_h || !layers_h || !J) RTX_FAIL("a required pointer is NULL");
+  if ((OD_plus == nullptr) != (OD_minus == nullptr)) RTX_FAIL("OD_plus and OD_minus are given together or not at all");
+  if (with_T && !(fd_step > 0.0)) RTX_FAIL("fd_step=%g must be > 0", fd_step);
+  if (n_spec < 0 || n_spec > TUDJ_MAX_SPEC) RTX_FAIL("n_spec=%d outside [0,%d]", n_spec, TUDJ_MAX_SPEC);
+  if (n_spec > 0 && !K) RTX_FAIL("K is NULL");
+  if (with_T + n_spec < 1) RTX_FAIL("nothing to differentiate (no OD_plus and n_spec = 0)");
+  if (!return_od && !tau) RTX_FAIL("tau is NULL (needed unless return_od)");
+  if (n_layers < 1 || n_layers > TUDJ_MAX_LAYERS) RTX_FAIL("n_layers=%d outside [1,%d]", n_layers, TUDJ_MAX_LAYERS);
+  if (n_alt < 1 || n_alt > TUDJ_MAX_ALT) RTX_FAIL("n_alt=%d outside [1,%d]", n_alt, TUDJ_MAX_ALT);
+  if (n_angle < 1 || n_angle > TUDJ_MAX_ANGLES) RTX_FAIL("n_angle=%d outside [1,%d]", n_angle, TUDJ_MAX_ANGLES);
+  if (n_down < 0 || n_down > n_layers) RTX_FAIL("n_down=%d outside [0,%d]", n_down, n_layers);
+  if (n_lay < 1 || n_lay > TUDJ_MAX_LAYERS) RTX_FAIL("n_lay=%d outside [1,%d]", n_lay, TUDJ_MAX_LAYERS);
+  if (!(mu >= 1.0) || !isfinite(mu)) RTX_FAIL("mu=%g must be finite and >= 1", mu);
+  if (t_pos < 0 || (with_T ? t_pos > n_spec : t_pos != 0)) RTX_FAIL("t_pos=%d outside [0,%d]", t_pos, with_T ? n_spec : 0);
+  if (ld < grid->n || ld_J < grid->n || (!return_od && ld_tau < grid->n)) RTX_FAIL("leading dimension smaller than the shard");
+  TudJacArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int k = 0; k < n_lay; ++k) {
+    if (layers_h[k] < 0 || layers_h[k] >= n_layers) RTX_FAIL("layer index %d outside [0,%d)", layers_h[k], n_layers);
+    a.lay[k] = layers_h[k];
+  }
+  for (int k = 0; k < n_layers; ++k) {
+    if (!(T_h[k] > 0.0)) RTX_FAIL("layer %d temperature %g", k, T_h[k]);
+    a.c2l2e_over_T[k] = 100.0 * RT_C2 * LOG2E / T_h[k];
+  }
+  for (int ia = 0; ia < n_alt; ++ia) {
+    int c = 0;
+    for (int k = 0; k < n_layers; ++k)
+      if (mask_h[(size_t)ia * n_layers + k]) { a.lbits[k] |= 1u << ia; ++c; }
+    a.count[ia] = c;
+    for (int k = 0; k < c; ++k) a.lbits[k] |= 1u << (16 + ia);
+  }
+  // angles = linspace(0, pi/2, nA, endpoint=False) (:368), weights cos*sin / sum (:387-388); theta = 0 has weight 0
+  const double dth = (M_PI / 2.0) / (double)n_angle;
+  double wsum = 0.0;
+  for (int q = 0; q < n_angle; ++q) wsum += cos(q * dth) * sin(q * dth);
+  int ns = 0;
+  for (int q = 1; q < n_angle; ++q) {
+    const double th = (double)q * dth, c = cos(th), w = c * sin(th) / wsum;
+    a.str_ic[ns] = 1.0 / c;
+    a.str_w[ns] = (float)w;
+    a.str_wc[ns] = (float)(w / c);
+    ++ns;
+  }
+  a.n_str = ns;
+  a.OD = OD; a.ODp = OD_plus; a.ODm = OD_minus; a.K = K; a.tau = tau; a.J = J;
+  a.ld = ld; a.ld_tau = ld_tau; a.ld_J = ld_J; a.g = to_dev(grid);
+  a.n_layers = n_layers; a.n_alt = n_alt; a.n_down = n_down; a.return_od = return_od;
+  a.with_T = with_T; a.n_spec = n_spec; a.n_lay = n_lay; a.t_pos = t_pos;
+  a.mu = (float)mu; a.mu_d = mu; a.inv_2h = with_T ? (float)(0.5 / fd_step) : 0.f;
+  if (grid->n == 0) return 0;
+  const long long blocks = (grid->n + 255) / 256;
+  hipLaunchKernelGGL(tud_jac_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  RTX_LAUNCH_CHECK();
+  return 0;
+}

@@ -815,3 +815,143 @@ def reduce_resolution_cached(Y, x0, h, n, dX, N=4, window="hanning"):
             _REDUCE_PLANS.clear()
         plan = _REDUCE_PLANS[key] = _reduce_plan(x0, h, n, dX, N, window, None, Y.device)
     return _reduce_apply(Y, x0, h, n, plan, checked=False)
+
+
+# ---- TUD Jacobian (rtx_line_prep_window + rtx_voigt_sum for dOD/dx, rtx_tud_jacobian) -------------------------------
+JAC_BLOCK_BYTES = 2 << 30  # J block per rtx_tud_jacobian launch (float32 [n_wrt][layers][rows][n])
+# rtx_tud_jacobian's limits (include/radtxfr_hip.h), checked here before any device work
+JAC_MAX_LAYERS, JAC_MAX_ALT, JAC_MAX_ANGLES, JAC_MAX_SPEC = 128, 16, 96, 16
+
+
+def jacobian_limits(n_layers, n_alt, n_angle, n_spec):
+    """Raise ValueError where rtx_tud_jacobian would refuse the shape (host-only check)."""
+    if not 1 <= int(n_layers) <= JAC_MAX_LAYERS:
+        raise ValueError("Jacobian: %d layers, supported 1..%d" % (n_layers, JAC_MAX_LAYERS))
+    if not 1 <= int(n_alt) <= JAC_MAX_ALT:
+        raise ValueError("Jacobian: %d sensor altitudes, supported 1..%d" % (n_alt, JAC_MAX_ALT))
+    if not 1 <= int(n_angle) <= JAC_MAX_ANGLES:
+        raise ValueError("Jacobian: N_angle=%d, supported 1..%d" % (n_angle, JAC_MAX_ANGLES))
+    if int(n_spec) > JAC_MAX_SPEC:
+        raise ValueError("Jacobian: %d species in wrt, supported up to %d" % (n_spec, JAC_MAX_SPEC))
+
+
+def voigt_sum_window(lines, grid, T, T_win, p_atm, weight, out_f32, qratio=None, mass=None, partitionFunction=None):
+    """voigt_sum with every line's window taken at the layer temperatures T_win instead of T (rtx_line_prep_window +
+    rtx_voigt_sum): strengths, partition sums and widths at T, supports at T_win. Output [nL][grid.n] float32."""
+    lib = _lib.load()
+    nL, env = _prologue_inputs(lines, T, p_atm, weight, partitionFunction, qratio, mass)
+    T_win, T_win_p = _h(np.atleast_1d(T_win))
+    assert T_win.size == nL
+    plan = lines.plan(nL, grid.n)
+    st = _stream_ptr()
+    T_e, p_e, q_e, w_e, m_e = (e[1] for e in env)
+    _lib.check(lib.rtx_line_prep_window(plan._h, lines._h, grid.byref(), nL, T_e, T_win_p, p_e, q_e, w_e, m_e, 1.0, 0.0,
+                                        0.0, 50.0, 0.0, 1.0, 0, st))
+    _check_outputs(nL, grid.n, out_f32, None)
+    _lib.check(lib.rtx_voigt_sum(plan._h, grid.byref(), nL, _ptr(out_f32), None, grid.n, st))
+    return out_f32
+
+
+def jacobian_species_columns(MF_ID, wrt):
+    """Column of MFs_VAL each species entry of `wrt` differentiates (its first occurrence in MF_ID, as layer_weights_od maps
+    a line's molecule to a column). Raises ValueError for an id not in MF_ID."""
+    ids = [int(v) for v in np.asarray(MF_ID).ravel()]
+    cols = []
+    for w in wrt:
+        if isinstance(w, str):
+            continue
+        if int(w) not in ids:
+            raise ValueError("wrt: molecule id %r is not in MFs_ID %r" % (w, ids))
+        cols.append(ids.index(int(w)))
+    return cols
+
+
+def tud_jacobian(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=False,
+                 wrt=("T",), layers=None, fd_step_T=0.5, block_bytes=JAC_BLOCK_BYTES, on_block=None, mark=None):
+    """compute_TUD's outputs and their Jacobian with respect to layer temperatures and mixing ratios, on the device.
+
+    wrt: "T" and/or molecule ids of MF_ID (T, when present, is computed first whatever its position: J's wrt axis follows
+    `wrt`). layers: layer indices (default all), in output order. Returns (tau, Lu, Ld, OD, J): float32 device tensors,
+    tau / Lu [nAlt][n], Ld [n], OD [nL][n] bit-identical to TudRunner / compute_TUD, J [n_wrt][n_layers][2 nAlt + 1][n]
+    (rows: tau per altitude, L-up per altitude, Ld). With on_block(k0, k1, J_block) J is not kept: each block of layers
+    (at most block_bytes of float32) is handed to the callback as soon as it is written, and None is returned for J.
+    mark(name): called after each stage is enqueued ("base", "T", "species", "jacobian"), for timing.
+
+    dOD/dT is the central difference of two line-sums at T -+ fd_step_T with every line's window at T (voigt_sum_window);
+    dOD/dMF of a species is the line-sum of that species alone at 1 ppmv (OD is linear in each mixing ratio)."""
+    lib = _lib.load()
+    T = np.ascontiguousarray(np.atleast_1d(np.asarray(T, dtype=np.float64)))
+    Z = np.atleast_1d(np.asarray(Z, dtype=np.float64))
+    nL = T.size
+    P_pa = np.atleast_1d(np.asarray(P_pa, dtype=np.float64))
+    PL_km = np.atleast_1d(np.asarray(PL_km, dtype=np.float64))
+    MF_VAL = np.asarray(MF_VAL, dtype=np.float64).reshape(nL, -1)
+    wrt = tuple(wrt)
+    if len(set(wrt)) != len(wrt) or any(isinstance(w_, str) and w_ != "T" for w_ in wrt):
+        raise ValueError("wrt: distinct entries, each \"T\" or a molecule id of MFs_ID (got %r)" % (wrt,))
+    with_T = "T" in wrt
+    spec_cols = jacobian_species_columns(MF_ID, wrt)
+    layers = np.arange(nL, dtype=np.int32) if layers is None else np.ascontiguousarray(np.asarray(layers, dtype=np.int32).ravel())
+    if layers.size == 0 or layers.min() < 0 or layers.max() >= nL:
+        raise ValueError("layers: indices must lie in [0, %d)" % nL)
+    if with_T and not (fd_step_T > 0.0):
+        raise ValueError("fd_step_T must be > 0")
+    th = np.asarray(theta_r, dtype=np.float64).ravel()
+    if th.size != 1:
+        raise NotImplementedError("tud_jacobian: one slant path (theta_r) per call")
+    jacobian_limits(nL, np.array([Altitudes]).size, N_angle, len(spec_cols))
+    mu = float(1.0 / np.cos(th[0]))
+    dev = device()
+    # base state: exactly what compute_TUD runs
+    run = TudRunner(lines, grid, Z, n_layers=nL, Altitudes=Altitudes, theta_r=theta_r, N_angle=N_angle, returnOD=returnOD)
+    tau, Lu, Ld = run.run(T, P_pa, PL_km, MF_VAL, MF_ID)
+    OD = run.OD
+    if mark:
+        mark("base")
+    n = grid.n
+    ODp = ODm = None
+    if with_T:
+        ODp = torch.empty((nL, n), dtype=torch.float32, device=dev)
+        ODm = torch.empty_like(ODp)
+        for sgn, out in ((1.0, ODp), (-1.0, ODm)):
+            Ts = T + sgn * float(fd_step_T)
+            w, p_atm = layer_weights_od(lines.species, Ts, P_pa, PL_km, MF_VAL, MF_ID)
+            voigt_sum_window(lines, grid, Ts, T, p_atm, w, out)
+    if mark:
+        mark("T")
+    K = None
+    if spec_cols:
+        K = torch.empty((len(spec_cols), nL, n), dtype=torch.float32, device=dev)
+        for s, c in enumerate(spec_cols):
+            unit = np.zeros_like(MF_VAL)
+            unit[:, c] = 1.0
+            w, p_atm = layer_weights_od(lines.species, T, P_pa, PL_km, unit, MF_ID)
+            voigt_sum(lines, grid, T, p_atm, w, out_f32=K[s])
+    if mark:
+        mark("species")
+    # J's wrt axis follows `wrt`: the kernel writes T's rows at t_pos and the species (K's order = their order in wrt) around it
+    n_wrt = int(with_T) + len(spec_cols)
+    t_pos = wrt.index("T") if with_T else 0
+    nA = run.shape[0]
+    nrow = 2 * nA + 1
+    per_layer = n_wrt * nrow * n * 4
+    nb = int(max(1, min(layers.size, int(block_bytes) // max(per_layer, 1))))
+    J = None if on_block is not None else torch.empty((n_wrt, layers.size, nrow, n), dtype=torch.float32, device=dev)
+    T_h, T_p = _h(T)
+    mask = run.mask
+    st = _stream_ptr()
+    for k0 in range(0, layers.size, nb):
+        k1 = min(k0 + nb, layers.size)
+        blk = torch.empty((n_wrt, k1 - k0, nrow, n), dtype=torch.float32, device=dev)
+        lay = np.ascontiguousarray(layers[k0:k1])
+        _lib.check(lib.rtx_tud_jacobian(
+            _ptr(OD), _ptr(ODp), _ptr(ODm), OD.stride(0), float(fd_step_T), _ptr(K), len(spec_cols), _ptr(tau), tau.stride(0),
+            grid.byref(), nL, T_p, nA, mask.ctypes.data_as(C.c_void_p), mu, run.n_down, int(N_angle), int(bool(returnOD)),
+            lay.ctypes.data_as(C.c_void_p), lay.size, t_pos, _ptr(blk), n, st))
+        if mark:
+            mark("jacobian")
+        if on_block is not None:
+            on_block(k0, k1, blk)
+        else:
+            J[:, k0:k1] = blk
+    return tau, Lu, Ld, OD, J

@@ -508,6 +508,129 @@ def compute_TUD_batch(Xmin, Xmax, atmospheres, opts=options, reduce=None, device
     return results
 
 
+JACOBIAN_HOST_LIMIT = 4 << 30  # bytes of full-resolution float64 results compute_TUD_jacobian returns without reduce=
+
+
+def _jacobian_args(Xmin, Xmax, o, wrt, layers, reduce, fd_step_T):
+    """compute_TUD_jacobian's argument checks, all on the host (no device is touched): (wrt, layers, nX)."""
+    if np.asarray(o["theta_r"]).size != 1:
+        raise NotImplementedError("compute_TUD_jacobian: one slant path (a single theta_r) per call")
+    if o["save"]:
+        raise ValueError("compute_TUD_jacobian: save=True is a compute_TUD option (the per-stream dump) and is not offered here")
+    if isinstance(wrt, (str, int, np.integer)):
+        wrt = (wrt,)
+    wrt = tuple(w if isinstance(w, str) else int(w) for w in wrt)
+    if not wrt:
+        raise ValueError("compute_TUD_jacobian: wrt is empty")
+    ids = [int(v) for v in np.asarray(o["MFs_ID"]).ravel()]
+    for w in wrt:
+        if isinstance(w, str):
+            if w != "T":
+                raise ValueError("compute_TUD_jacobian: wrt entry %r: \"T\" or a molecule id of MFs_ID %r" % (w, ids))
+        elif w not in ids:
+            raise ValueError("compute_TUD_jacobian: wrt molecule id %d is not in MFs_ID %r" % (w, ids))
+    if len(set(wrt)) != len(wrt):
+        raise ValueError("compute_TUD_jacobian: wrt %r names an entry twice" % (wrt,))
+    nL = np.asarray(o["Ts"]).size
+    lay = np.arange(nL) if layers is None else np.asarray(layers).ravel()
+    if lay.size == 0 or not np.issubdtype(lay.dtype, np.integer):
+        raise ValueError("compute_TUD_jacobian: layers must be a non-empty sequence of layer indices")
+    if lay.min() < 0 or lay.max() >= nL:
+        raise ValueError("compute_TUD_jacobian: layer index outside [0, %d)" % nL)
+    if "T" in wrt and not (float(fd_step_T) > 0.0):
+        raise ValueError("compute_TUD_jacobian: fd_step_T=%r must be > 0" % (fd_step_T,))
+    nX = int(np.ceil((Xmax - Xmin) / o["DVOUT"]))  # make_spectral_axis's count
+    nZ = np.array([o["Altitudes"]]).size
+    engine.jacobian_limits(nL, nZ, int(o["N_angle"]), sum(1 for w in wrt if not isinstance(w, str)))
+    if reduce is None:
+        nbytes = 8 * nX * ((2 * nZ + 1) * (1 + len(wrt) * lay.size))
+        if nbytes > JACOBIAN_HOST_LIMIT:
+            raise ValueError("compute_TUD_jacobian: the full-resolution result would take %.1f GiB of host memory (limit %.0f GiB): "
+                             "pass reduce=dict(dX=...) or fewer layers= / wrt=" % (nbytes / 2.0 ** 30, JACOBIAN_HOST_LIMIT / 2.0 ** 30))
+    elif "dX" not in reduce:
+        raise ValueError("compute_TUD_jacobian: reduce needs dX")
+    return wrt, np.ascontiguousarray(lay, dtype=np.int32), nX
+
+
+def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, reduce=None, fd_step_T=0.5, **kwargs):
+    """compute_TUD and the derivatives of its outputs with respect to layer temperatures and mixing ratios in one call:
+    what the reference's caller builds from 1 + 3 x 66 perturbed atmospheres (Generate_LWIR_TUD.py:55-71, JacIn, one
+    layer and one quantity at a time, relStep 0.001) -- here closed-form chain rule through the TUD recurrences.
+
+    kwargs as compute_TUD (DVOUT, Zs, Ts, Ps, PLs, MFs_VAL, MFs_ID, Altitudes, theta_r, N_angle, returnOD, line_table); one
+    theta_r; save is not offered. wrt: "T" and / or molecule ids of MFs_ID. layers: layer indices (default all), in
+    output order. Returns (X, tau, Lu, Ld, J):
+      X, tau, Lu, Ld  bit-identical to compute_TUD with the same kwargs (reduced as compute_TUD_batch(reduce=) reduces them
+                      when `reduce` is given, X then the reduced axis);
+      J               {wrt entry: (dtau, dLu, dLd)}, each float64 with the shape compute_TUD gives that output plus a
+                      trailing axis over `layers`, in units per K ("T") and per ppmv (a molecule id, the unit of MFs_VAL).
+    Definition: for layer l and x in {T_l, MF_s,l}, d/dx of the same outputs compute_TUD returns -- the tau slot (tau, or
+    sum(OD) mu under returnOD), L-up per sensor altitude and Ld, with every quirk of the reference's TUD body (the
+    Z <= zs mask for tau, the first count(mask) layers for L-up, the last altitude's count for Ld, weight 0 at theta = 0).
+    OD_l is linear in MF_s,l: dOD_l/dMF_s,l is the line-sum of species s alone at 1 ppmv (exact; MF = 0 is fine).
+    dOD_l/dT_l is the central difference of line-sums at T -+ fd_step_T [K] with every line's window held at the base T:
+    the derivative of the truncated line-sum with each line's support fixed (the reference's cut-off OmegaWingHW x width
+    moves with T; a finite difference of it carries those steps). Everything else is analytic.
+    reduce = dict(dX=..., N=4, window="hanning"): reduceResolution of the base outputs and of every J row on the device
+    (engine.reduce_resolution_cached). Without it, full-resolution results above 4 GiB are refused (ValueError): pass
+    reduce= or fewer layers=. Arguments are checked before any device work."""
+    o = dict(opts)
+    o.update(kwargs)
+    wrt, lay, _ = _jacobian_args(Xmin, Xmax, o, wrt, layers, reduce, fd_step_T)
+    Z = np.asarray(o["Zs"], dtype=np.float64)
+    T = np.asarray(o["Ts"], dtype=np.float64)
+    X_ = _cached_axis(Xmin, Xmax, o["DVOUT"])
+    grid = engine.Grid(Xmin, Xmax, X_.size)
+    tbl = _resolve_table(o.get("line_table"))
+    Z_s = np.array([o["Altitudes"]]).ravel()
+    nZ = Z_s.size
+    nrow = 2 * nZ + 1
+    n_lay = lay.size
+    red = None
+    if reduce is not None:
+        red = dict(dX=float(reduce["dX"]), N=reduce.get("N", 4), window=reduce.get("window", "hanning"))
+    x0 = float(X_[0])
+    host = {}  # wrt entry -> float64 [nX_out][nrow][n_lay]
+
+    def on_block(k0, k1, blk):
+        rows = blk.view(-1, grid.n)
+        if red is not None:
+            _, out = engine.reduce_resolution_cached(rows, x0, grid.step, grid.n, red["dX"], N=red["N"], window=red["window"])
+        else:
+            out = rows
+        out = out.view(len(wrt), k1 - k0, nrow, -1)
+        for w_i, w in enumerate(wrt):
+            h = out[w_i].permute(2, 1, 0).to(torch.float64).cpu().numpy()  # [n_out][nrow][k1-k0]
+            if w not in host:
+                host[w] = np.empty((h.shape[0], nrow, n_lay))
+            host[w][:, :, k0:k1] = h
+
+    tau, Lu, Ld, _, _ = engine.tud_jacobian(tbl, grid, Z, T, o["Ps"], o["PLs"], o["MFs_VAL"], o["MFs_ID"], Altitudes=Z_s,
+                                             theta_r=np.asarray(o["theta_r"], dtype=np.float64), N_angle=int(o["N_angle"]),
+                                             returnOD=bool(o["returnOD"]), wrt=wrt, layers=lay, fd_step_T=float(fd_step_T),
+                                             on_block=on_block)
+    if red is not None:
+        rows = torch.cat([tau, Lu, Ld[None, :]])
+        X_out, r = engine.reduce_resolution_cached(rows, x0, grid.step, grid.n, red["dX"], N=red["N"], window=red["window"])
+        r = r.cpu().numpy()
+        tau_, Lu_ = _tud_shapes(r[:nZ], r[nZ:2 * nZ], nZ, 1)
+        Ld_ = r[2 * nZ]
+    else:
+        (tau_h, Lu_h, Ld_h), done = _rows_to_host_f64([tau, Lu, Ld[None, :]])
+        done.synchronize()
+        tau_, Lu_ = _tud_shapes(tau_h, Lu_h, nZ, 1)
+        Ld_ = Ld_h[0]
+        X_out = X_
+    J = {}
+    for w in wrt:
+        h = host[w]
+        if nZ == 1:
+            J[w] = (np.ascontiguousarray(h[:, 0, :]), np.ascontiguousarray(h[:, 1, :]), np.ascontiguousarray(h[:, 2, :]))
+        else:
+            J[w] = (np.ascontiguousarray(h[:, :nZ, :]), np.ascontiguousarray(h[:, nZ:2 * nZ, :]), np.ascontiguousarray(h[:, 2 * nZ, :]))
+    return X_out, tau_, Lu_, Ld_, J
+
+
 def compute_LWIR_apparent_radiance(X, emis, Ts, tau, La, Ld, dT=None, return_Ls=False):
     r"""L = tau [emis B(Ts + dT) + (1 - emis) Ld] + La for every combination, signature of :1017-1069.
 
