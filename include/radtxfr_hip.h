@@ -214,6 +214,7 @@ int rtx_tud(const float* OD, int64_t ld, const rtx_grid* grid, int n_layers, con
  * Q = prod_{l<j<count} t_j; of Ld, l < n_down: sum_q (w_q/c_q) t_{l,q} P_{l,q} (B_l - R_{l+1,q}) (P: transmittance below l,
  * R_{l+1}: downwelling radiance at the top of layer l); the fixed-OD T terms carry (1 - t) dB/dT in place of the
  * OD factor. Structural zeros (an altitude's L-up above its count, Ld above n_down, a species without lines) are exact.
+ * With n_angle = 1 no stream has weight: rtx_tud's Ld is 0/0 and every Ld row of J is NaN, as its derivative is.
  * A layer's rows do not depend on which other layers are requested (bit-identical for any subset or blocking). */
 int rtx_tud_jacobian(const float* OD, const float* OD_plus, const float* OD_minus, int64_t ld, double fd_step,
                      const float* K, int n_spec, const float* tau, int64_t ld_tau, const rtx_grid* grid,

@@ -542,6 +542,93 @@ def compute_TUD(tbl, Xmin, Xmax, DVOUT, Zs, Ts, Ps, PLs, MFs_VAL, MFs_ID, Altitu
     return X, tau, Lu, Ld
 
 
+# ---- TUD Jacobian (the definitions rtx_line_prep_window and rtx_tud_jacobian implement) --------------------------------
+def od_fixed_window(tbl, X, T, T_win, P_pa, PL_km, MF_VAL, MF_ID):
+    """layer_od with absorptionCoefficient_Voigt's loop restated: every line's window from the base temperature T_win,
+    everything else at T (the definition rtx_line_prep_window implements)."""
+    p = float(P_pa) / 101325.0
+    t = _tables()
+    X = np.asarray(X, dtype=np.float64)
+    glist = X.tolist()
+    od = np.zeros(X.size)
+    M = np.asarray(tbl["molec_id"]).astype(int)
+    for m, ppmv in zip(np.asarray(MF_ID).tolist(), np.asarray(MF_VAL).tolist()):
+        keep = M == m
+        if not keep.any():
+            continue
+        sub = {k: np.asarray(v)[keep] for k, v in tbl.items()}
+        P = line_params(sub, T, p)
+        Pw = line_params(sub, T_win, p)
+        nu = np.asarray(sub["nu"], dtype=np.float64)
+        xs = np.zeros(X.size)
+        for r in range(nu.size):
+            W = max(0.0, 50.0 * Pw["Gamma0"][r], 50.0 * Pw["GammaD"][r])
+            lo, hi = _bisect.bisect(glist, nu[r] - W), _bisect.bisect(glist, nu[r] + W)
+            if hi <= lo:
+                continue
+            ls = PROFILE_VOIGT(nu[r] + P["Shift0"][r], P["GammaD"][r], P["Gamma0"][r], X[lo:hi])[0]
+            mi = (int(P["M"][r]), int(P["I"][r]))
+            xs[lo:hi] += volumeConcentration(p, T) * P["S"][r] * ls * (t["abun"][mi] / t["abun"][mi])
+        od += xs * (ppmv * 1e-6) * PL_km * 1e5
+    return od
+
+
+def planck_dT(X, T):
+    """B(nu, T) [nX][nL] of planckian and dB/dT analytic: dB/dT = B (u/T) e^u/(e^u - 1), u = c2 nu / T."""
+    B = planckian(X, T)
+    u = C2 * (np.asarray(X)[:, None] * 100.0) / np.asarray(T)[None, :]
+    return B, B * (u / np.asarray(T)[None, :]) * (-1.0 / np.expm1(-u))
+
+
+def jacobian_from_od(X, OD, T, Z, Altitudes, theta_r=0.0, N_angle=30, returnOD=False, layers=None):
+    """g[row][nX][layer] = d row / d OD_l and h[row][nX][layer] = d row / d T_l at fixed OD, rows = tau per altitude,
+    L-up per altitude, Ld: the closed forms rtx_tud_jacobian evaluates, with prefix sums for every transmittance product.
+    With N_angle = 1 tud_from_od's Ld is 0/0 (theta = 0 carries weight 0), so are its derivatives: the Ld rows are NaN."""
+    OD = np.asarray(OD, dtype=np.float64)  # [nX][nL]
+    nX, nL = OD.shape
+    layers = np.arange(nL) if layers is None else np.asarray(layers)
+    Z_s = np.array([Altitudes]).ravel()
+    nZ = Z_s.size
+    mu = 1.0 / np.cos(theta_r)
+    B, dB = planck_dT(X, T)
+    S = np.concatenate([np.zeros((nX, 1)), np.cumsum(OD, axis=1)], axis=1)  # S[:, j] = sum_{i<j} OD_i
+    t = np.exp(-mu * OD)
+    Lr = np.zeros((nX, nL + 1))  # Lr[:, l] = L^(l-1)
+    for k in range(nL):
+        Lr[:, k + 1] = t[:, k] * Lr[:, k] + (1 - t[:, k]) * B[:, k]
+    masks = [Z <= zs for zs in Z_s]
+    n_down = int(masks[-1].sum())
+    g = np.zeros((2 * nZ + 1, nX, layers.size))
+    h = np.zeros_like(g)
+    for a, m in enumerate(masks):
+        cnt = int(m.sum())
+        tau_a = np.exp(-mu * np.sum(OD[:, m], axis=1))
+        for c, l in enumerate(layers):
+            if m[l]:
+                g[a, :, c] = mu if returnOD else -mu * tau_a
+            if l < cnt:
+                Q = np.exp(-mu * (S[:, cnt] - S[:, l + 1]))
+                g[nZ + a, :, c] = mu * t[:, l] * Q * (B[:, l] - Lr[:, l])
+                h[nZ + a, :, c] = (1 - t[:, l]) * Q * dB[:, l]
+    if int(N_angle) == 1:
+        g[2 * nZ] = h[2 * nZ] = np.nan
+        return g, h
+    angles = np.linspace(0, np.pi / 2.0, N_angle, endpoint=False)
+    w = np.cos(angles) * np.sin(angles)
+    w = w / w.sum()
+    for q in range(1, N_angle):
+        cq = np.cos(angles[q])
+        tq = np.exp(-OD / cq)
+        R = np.zeros((nX, nL + 1))  # R[:, l] = radiance arriving at the top of layer l - 1 from above (R_l)
+        for k in range(n_down - 1, -1, -1):
+            R[:, k] = tq[:, k] * R[:, k + 1] + (1 - tq[:, k]) * B[:, k]
+        for c, l in enumerate(layers):
+            if l < n_down:
+                g[2 * nZ, :, c] += (w[q] / cq) * np.exp(-S[:, l + 1] / cq) * (B[:, l] - R[:, l + 1])
+                h[2 * nZ, :, c] += w[q] * (1 - tq[:, l]) * np.exp(-S[:, l] / cq) * dB[:, l]
+    return g, h
+
+
 # ---- post-processing of TUD products (SURVEY 8f row 2) ----------------------------------------
 def smooth(x, window_len=11, window="hanning"):
     """radiative_transfer.py:1266-1324: reflect-pad by window_len-1 samples, convolve with the normalised

@@ -212,8 +212,9 @@ __global__ __launch_bounds__(256) void tud_jac_kernel(TudJacArgs a) {
             }
           }
         }
+        // N_angle = 1: no stream has weight, compute_TUD's Ld is 0/0 (NaN), and so is its derivative in every layer
         const bool down = l < a.n_down;
-        const float gD = down ? gLd[k] : 0.f, hD = down ? hLd[k] : 0.f;
+        const float gD = a.n_str == 0 ? NAN : down ? gLd[k] : 0.f, hD = a.n_str == 0 ? NAN : down ? hLd[k] : 0.f;
         float* const out0 = a.J + (size_t)(k0 + k) * nrow * a.ld_J + i;
         for (int w = 0; w < n_wrt; ++w) {
           const bool isT = a.with_T && w == 0;

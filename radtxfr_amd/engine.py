@@ -879,7 +879,6 @@ def tud_jacobian(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes=(500,)
 
     dOD/dT is the central difference of two line-sums at T -+ fd_step_T with every line's window at T (voigt_sum_window);
     dOD/dMF of a species is the line-sum of that species alone at 1 ppmv (OD is linear in each mixing ratio)."""
-    lib = _lib.load()
     T = np.ascontiguousarray(np.atleast_1d(np.asarray(T, dtype=np.float64)))
     Z = np.atleast_1d(np.asarray(Z, dtype=np.float64))
     nL = T.size
@@ -900,7 +899,6 @@ def tud_jacobian(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes=(500,)
     if th.size != 1:
         raise NotImplementedError("tud_jacobian: one slant path (theta_r) per call")
     jacobian_limits(nL, np.array([Altitudes]).size, N_angle, len(spec_cols))
-    mu = float(1.0 / np.cos(th[0]))
     dev = device()
     # base state: exactly what compute_TUD runs
     run = TudRunner(lines, grid, Z, n_layers=nL, Altitudes=Altitudes, theta_r=theta_r, N_angle=N_angle, returnOD=returnOD)
@@ -930,28 +928,67 @@ def tud_jacobian(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes=(500,)
     if mark:
         mark("species")
     # J's wrt axis follows `wrt`: the kernel writes T's rows at t_pos and the species (K's order = their order in wrt) around it
-    n_wrt = int(with_T) + len(spec_cols)
     t_pos = wrt.index("T") if with_T else 0
-    nA = run.shape[0]
+    J = tud_jacobian_from_od(OD, ODp, ODm, fd_step_T, K, tau, grid, T, Z, Altitudes=Altitudes, theta_r=theta_r,
+                             N_angle=N_angle, returnOD=returnOD, layers=layers, t_pos=t_pos, block_bytes=block_bytes,
+                             on_block=on_block, mark=mark)
+    return tau, Lu, Ld, OD, J
+
+
+def tud_jacobian_from_od(OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z, Altitudes=(500,), theta_r=0.0, N_angle=30,
+                         returnOD=False, layers=None, t_pos=0, block_bytes=JAC_BLOCK_BYTES, on_block=None, mark=None):
+    """rtx_tud_jacobian on given float32 device columns: OD [nL][>=n] (the base state), OD_plus / OD_minus at T -+ fd_step_T
+    (or both None: no T rows), K [n_spec][nL][.] OD per ppmv (or None), all with OD's row stride; tau [nAlt][>=n] the base
+    transmittances (None allowed with returnOD). Altitude masks and n_down are formed as TudRunner forms them. Returns J
+    [n_wrt][n_layers][2 nAlt + 1][n], T's rows at t_pos and the species in K's order around them, or None with on_block
+    (see tud_jacobian)."""
+    lib = _lib.load()
+    T = np.ascontiguousarray(np.atleast_1d(np.asarray(T, dtype=np.float64)))
+    Z = np.atleast_1d(np.asarray(Z, dtype=np.float64))
+    nL = T.size
+    layers = np.arange(nL, dtype=np.int32) if layers is None else np.ascontiguousarray(np.asarray(layers, dtype=np.int32).ravel())
+    Z_s = np.array([Altitudes], dtype=np.float64).ravel()
+    mask = np.ascontiguousarray(np.stack([(Z <= zs) for zs in Z_s]).astype(np.uint8))
+    n_down = int(mask[-1].sum())  # quirk 3: the LAST altitude's layer count (:353, :370)
+    th = np.asarray(theta_r, dtype=np.float64).ravel()
+    if th.size != 1:
+        raise NotImplementedError("tud_jacobian: one slant path (theta_r) per call")
+    mu = float(1.0 / np.cos(th[0]))
+    with_T = OD_plus is not None
+    n_spec = 0 if K is None else int(K.shape[0])
+    n = grid.n
+    ld = OD.stride(0)
+    assert OD.dtype == torch.float32 and OD.is_cuda and OD.dim() == 2 and OD.shape[0] == nL and OD.shape[1] >= n
+    assert OD.stride(1) == 1
+    for t in (OD_plus, OD_minus):
+        assert t is None or (t.dtype == torch.float32 and t.shape == OD.shape and t.stride() == OD.stride())
+    if K is not None:
+        assert K.dtype == torch.float32 and K.dim() == 3 and K.shape[1] == nL and K.shape[2] >= n
+        assert K.stride(2) == 1 and K.stride(1) == ld and K.stride(0) == nL * ld
+    if tau is not None:
+        assert tau.dtype == torch.float32 and tau.dim() == 2 and tau.shape[0] == Z_s.size and tau.shape[1] >= n
+        assert tau.stride(1) == 1
+    n_wrt = int(with_T) + n_spec
+    nA = Z_s.size
     nrow = 2 * nA + 1
     per_layer = n_wrt * nrow * n * 4
     nb = int(max(1, min(layers.size, int(block_bytes) // max(per_layer, 1))))
+    dev = OD.device
     J = None if on_block is not None else torch.empty((n_wrt, layers.size, nrow, n), dtype=torch.float32, device=dev)
     T_h, T_p = _h(T)
-    mask = run.mask
     st = _stream_ptr()
     for k0 in range(0, layers.size, nb):
         k1 = min(k0 + nb, layers.size)
         blk = torch.empty((n_wrt, k1 - k0, nrow, n), dtype=torch.float32, device=dev)
         lay = np.ascontiguousarray(layers[k0:k1])
         _lib.check(lib.rtx_tud_jacobian(
-            _ptr(OD), _ptr(ODp), _ptr(ODm), OD.stride(0), float(fd_step_T), _ptr(K), len(spec_cols), _ptr(tau), tau.stride(0),
-            grid.byref(), nL, T_p, nA, mask.ctypes.data_as(C.c_void_p), mu, run.n_down, int(N_angle), int(bool(returnOD)),
-            lay.ctypes.data_as(C.c_void_p), lay.size, t_pos, _ptr(blk), n, st))
+            _ptr(OD), _ptr(OD_plus), _ptr(OD_minus), ld, float(fd_step_T), _ptr(K), n_spec, _ptr(tau),
+            tau.stride(0) if tau is not None else 0, grid.byref(), nL, T_p, nA, mask.ctypes.data_as(C.c_void_p), mu, n_down, int(N_angle),
+            int(bool(returnOD)), lay.ctypes.data_as(C.c_void_p), lay.size, t_pos, _ptr(blk), n, st))
         if mark:
             mark("jacobian")
         if on_block is not None:
             on_block(k0, k1, blk)
         else:
             J[:, k0:k1] = blk
-    return tau, Lu, Ld, OD, J
+    return J

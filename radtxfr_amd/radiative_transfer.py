@@ -567,6 +567,7 @@ def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, redu
     Definition: for layer l and x in {T_l, MF_s,l}, d/dx of the same outputs compute_TUD returns -- the tau slot (tau, or
     sum(OD) mu under returnOD), L-up per sensor altitude and Ld, with every quirk of the reference's TUD body (the
     Z <= zs mask for tau, the first count(mask) layers for L-up, the last altitude's count for Ld, weight 0 at theta = 0).
+    With N_angle = 1 that Ld is 0/0 (NaN), and so is every dLd.
     OD_l is linear in MF_s,l: dOD_l/dMF_s,l is the line-sum of species s alone at 1 ppmv (exact; MF = 0 is fine).
     dOD_l/dT_l is the central difference of line-sums at T -+ fd_step_T [K] with every line's window held at the base T:
     the derivative of the truncated line-sum with each line's support fixed (the reference's cut-off OmegaWingHW x width

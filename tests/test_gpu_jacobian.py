@@ -1,14 +1,14 @@
 """rt.compute_TUD_jacobian on the GPU (rtx_line_prep_window + rtx_voigt_sum for dOD/dx, rtx_tud_jacobian): against fp64
 finite differences of the oracle, bit-level invariances, exact structural zeros, the device reduce, and the caller's
 configuration (Generate_LWIR_TUD.py: 199 JacIn atmospheres) at full size."""
-import bisect
-
 import numpy as np
 import pytest
 
 from conftest import rel_err
 from oracle import cpu_ref as ref
 from radtxfr_amd import synthetic
+
+_od_fixed_window = ref.od_fixed_window  # every line's window at the base temperature (rtx_line_prep_window)
 
 pytestmark = pytest.mark.gpu
 
@@ -52,35 +52,6 @@ def case(rt):
 def _rows(X, OD, T, Z, returnOD):
     tau, Lu, Ld = ref.tud_from_od(X, OD, T, Z, Altitudes=ALTS, theta_r=0.0, N_angle=30, returnOD=returnOD)
     return tau.T, Lu.T, Ld  # [9][nX], [9][nX], [nX]
-
-
-def _od_fixed_window(tbl, X, T, T_win, P_pa, PL_km, MF_VAL, MF_ID):
-    """cpu_ref.layer_od with cpu_ref.absorptionCoefficient_Voigt's loop restated: every line's window from the base
-    temperature T_win, everything else at T (the definition rtx_line_prep_window implements)."""
-    p = float(P_pa) / 101325.0
-    t = ref._tables()
-    glist = X.tolist()
-    od = np.zeros(X.size)
-    M = np.asarray(tbl["molec_id"]).astype(int)
-    for m, ppmv in zip(np.asarray(MF_ID).tolist(), np.asarray(MF_VAL).tolist()):
-        keep = M == m
-        if not keep.any():
-            continue
-        sub = {k: np.asarray(v)[keep] for k, v in tbl.items()}
-        P = ref.line_params(sub, T, p)
-        Pw = ref.line_params(sub, T_win, p)
-        nu = np.asarray(sub["nu"], dtype=np.float64)
-        xs = np.zeros(X.size)
-        for r in range(nu.size):
-            W = max(0.0, 50.0 * Pw["Gamma0"][r], 50.0 * Pw["GammaD"][r])
-            lo, hi = bisect.bisect(glist, nu[r] - W), bisect.bisect(glist, nu[r] + W)
-            if hi <= lo:
-                continue
-            ls = ref.PROFILE_VOIGT(nu[r] + P["Shift0"][r], P["GammaD"][r], P["Gamma0"][r], X[lo:hi])[0]
-            mi = (int(P["M"][r]), int(P["I"][r]))
-            xs[lo:hi] += ref.volumeConcentration(p, T) * P["S"][r] * ls * (t["abun"][mi] / t["abun"][mi])
-        od += xs * (ppmv * 1e-6) * PL_km * 1e5
-    return od
 
 
 def _cmp(got, fd, base, step, tol, what, floor_abs=0.0, eps_rel=1e2 * np.finfo(np.float64).eps):

@@ -51,60 +51,11 @@ def test_full_resolution_host_result_is_bounded():
 
 
 # ------------------------------------------------------------------ the formulas, restated in NumPy (fp64)
-def _planck_dT(X, T):
-    """B(nu, T) [nX][nL] of the oracle and dB/dT analytic: dB/dT = B (u/T) e^u/(e^u - 1), u = c2 nu / T."""
-    B = cpu_ref.planckian(X, T)
-    u = cpu_ref.C2 * (np.asarray(X)[:, None] * 100.0) / np.asarray(T)[None, :]
-    return B, B * (u / np.asarray(T)[None, :]) * (-1.0 / np.expm1(-u))
+jacobian_from_od = cpu_ref.jacobian_from_od  # the closed forms rtx_tud_jacobian evaluates
 
 
-def jacobian_from_od(X, OD, T, Z, Altitudes, theta_r=0.0, N_angle=30, returnOD=False, layers=None):
-    """g[row][nX][layer] = d row / d OD_l and h[row][nX][layer] = d row / d T_l at fixed OD, rows = tau per altitude,
-    L-up per altitude, Ld: the closed forms rtx_tud_jacobian evaluates, with prefix sums for every transmittance product."""
-    OD = np.asarray(OD, dtype=np.float64)  # [nX][nL]
-    nX, nL = OD.shape
-    layers = np.arange(nL) if layers is None else np.asarray(layers)
-    Z_s = np.array([Altitudes]).ravel()
-    nZ = Z_s.size
-    mu = 1.0 / np.cos(theta_r)
-    B, dB = _planck_dT(X, T)
-    S = np.concatenate([np.zeros((nX, 1)), np.cumsum(OD, axis=1)], axis=1)  # S[:, j] = sum_{i<j} OD_i
-    t = np.exp(-mu * OD)
-    Lr = np.zeros((nX, nL + 1))  # Lr[:, l] = L^(l-1)
-    for k in range(nL):
-        Lr[:, k + 1] = t[:, k] * Lr[:, k] + (1 - t[:, k]) * B[:, k]
-    masks = [Z <= zs for zs in Z_s]
-    n_down = int(masks[-1].sum())
-    g = np.zeros((2 * nZ + 1, nX, layers.size))
-    h = np.zeros_like(g)
-    for a, m in enumerate(masks):
-        cnt = int(m.sum())
-        tau_a = np.exp(-mu * np.sum(OD[:, m], axis=1))
-        for c, l in enumerate(layers):
-            if m[l]:
-                g[a, :, c] = mu if returnOD else -mu * tau_a
-            if l < cnt:
-                Q = np.exp(-mu * (S[:, cnt] - S[:, l + 1]))
-                g[nZ + a, :, c] = mu * t[:, l] * Q * (B[:, l] - Lr[:, l])
-                h[nZ + a, :, c] = (1 - t[:, l]) * Q * dB[:, l]
-    angles = np.linspace(0, np.pi / 2.0, N_angle, endpoint=False)
-    w = np.cos(angles) * np.sin(angles)
-    w = w / w.sum()
-    for q in range(1, N_angle):
-        cq = np.cos(angles[q])
-        tq = np.exp(-OD / cq)
-        R = np.zeros((nX, nL + 1))  # R[:, l] = radiance arriving at the top of layer l - 1 from above (R_l)
-        for k in range(n_down - 1, -1, -1):
-            R[:, k] = tq[:, k] * R[:, k + 1] + (1 - tq[:, k]) * B[:, k]
-        for c, l in enumerate(layers):
-            if l < n_down:
-                g[2 * nZ, :, c] += (w[q] / cq) * np.exp(-S[:, l + 1] / cq) * (B[:, l] - R[:, l + 1])
-                h[2 * nZ, :, c] += w[q] * (1 - tq[:, l]) * np.exp(-S[:, l] / cq) * dB[:, l]
-    return g, h
-
-
-def _rows(X, OD, T, Z, alts, returnOD):
-    tau, Lu, Ld = cpu_ref.tud_from_od(X, OD, T, Z, Altitudes=alts, theta_r=0.0, N_angle=30, returnOD=returnOD)
+def _rows(X, OD, T, Z, alts, returnOD, theta_r=0.0, N_angle=30):
+    tau, Lu, Ld = cpu_ref.tud_from_od(X, OD, T, Z, Altitudes=alts, theta_r=theta_r, N_angle=N_angle, returnOD=returnOD)
     return np.concatenate([tau.reshape(X.size, -1).T, Lu.reshape(X.size, -1).T, Ld[None, :]])
 
 
@@ -113,25 +64,41 @@ def _richardson(d, e):
     return (4.0 * d(0.5 * e) - d(e)) / 3.0
 
 
-@pytest.mark.parametrize("returnOD", [False, True])
-def test_sensitivity_formulas_match_oracle_finite_differences(returnOD):
+def _column():
     rng = np.random.default_rng(7)
     nX, nL = 6, 12
     X = np.linspace(700.0, 1400.0, nX)
     # thin, moderate and opaque layers; a non-monotonic height so that a tau mask is not a prefix
     OD = np.exp(rng.uniform(np.log(1e-4), np.log(3.0), (nX, nL)))
     T = np.linspace(290.0, 215.0, nL) + rng.uniform(-3, 3, nL)
+    T[6:10] = 221.5  # an isothermal run: B_l - B_l+1 = 0 exactly, where the differences the kernel carries would cancel
     Z = np.arange(nL, dtype=np.float64)
     Z[3], Z[4] = Z[4], Z[3]
-    alts = np.array([3.5, 6.0, 11.0])
-    layers = np.array([0, 1, 3, 4, 7, 11])
-    g, h = jacobian_from_od(X, OD, T, Z, alts, returnOD=returnOD, layers=layers)
+    return X, OD, T, Z
+
+
+# altitude sets: the last one at the top of the column (n_down = nL); the last one inside it (n_down = 7) with one below
+# the surface (count 0) before it; the last one below the surface (n_down = 0: no downwelling at all)
+ALT_SETS = {"top": np.array([3.5, 6.0, 11.0]), "inside": np.array([11.0, -1.0, 6.0]), "below": np.array([3.5, -0.5])}
+
+
+@pytest.mark.parametrize("alts", list(ALT_SETS))
+@pytest.mark.parametrize("N_angle", [2, 9, 30])
+@pytest.mark.parametrize("theta_r", [0.0, 0.7])
+@pytest.mark.parametrize("returnOD", [False, True])
+def test_sensitivity_formulas_match_oracle_finite_differences(returnOD, theta_r, N_angle, alts):
+    X, OD, T, Z = _column()
+    alts = ALT_SETS[alts]
+    nZ = alts.size
+    layers = np.array([0, 1, 3, 4, 7, 8, 11])
+    g, h = jacobian_from_od(X, OD, T, Z, alts, theta_r=theta_r, N_angle=N_angle, returnOD=returnOD, layers=layers)
+    rows = lambda O, T_: _rows(X, O, T_, Z, alts, returnOD, theta_r, N_angle)
     for c, l in enumerate(layers):
         def d_od(e):
             Op, Om = OD.copy(), OD.copy()
             Op[:, l] += e
             Om[:, l] -= e
-            return (_rows(X, Op, T, Z, alts, returnOD) - _rows(X, Om, T, Z, alts, returnOD)) / (2 * e)
+            return (rows(Op, T) - rows(Om, T)) / (2 * e)
 
         # at fixed OD the rows are linear in B_l: their change over a wide temperature step divided by B's change is
         # d row / d B_l up to rounding alone; times dB/dT from a (Richardson) difference of the oracle's planckian
@@ -139,12 +106,43 @@ def test_sensitivity_formulas_match_oracle_finite_differences(returnOD):
         Tp[l] += 20.0
         Tm[l] -= 20.0
         dB = cpu_ref.planckian(X, Tp[l]) - cpu_ref.planckian(X, Tm[l])
-        d_row_dB = (_rows(X, OD, Tp, Z, alts, returnOD) - _rows(X, OD, Tm, Z, alts, returnOD)) / dB[None, :]
+        d_row_dB = (rows(OD, Tp) - rows(OD, Tm)) / dB[None, :]
         dBdT = _richardson(lambda e: (cpu_ref.planckian(X, T[l] + e) - cpu_ref.planckian(X, T[l] - e)) / (2 * e), 0.2)
         fdT = d_row_dB * dBdT[None, :]
         fd = _richardson(d_od, 2e-3)  # steps large enough that rounding stays below 1e-8 of the smallest row
         for r in range(fd.shape[0]):
             assert rel_err(g[r, :, c], fd[r]) <= 1e-8, ("OD", l, r)
             assert rel_err(h[r, :, c], fdT[r]) <= 1e-8, ("T", l, r)
-    # structural zeros: L-up of the lowest altitude (count 4) above its count, Ld above the last altitude's count
-    assert np.all(g[3, :, 4:] == 0) and np.all(h[3, :, 4:] == 0)
+    # structural zeros: tau outside an altitude's mask, L-up at or above its count, Ld at or above the last one's count
+    counts = [int((Z <= zs).sum()) for zs in alts]
+    for c, l in enumerate(layers):
+        for a, zs in enumerate(alts):
+            if not Z[l] <= zs:
+                assert np.all(g[a, :, c] == 0) and np.all(h[a, :, c] == 0)
+            if l >= counts[a]:
+                assert np.all(g[nZ + a, :, c] == 0) and np.all(h[nZ + a, :, c] == 0)
+        if l >= counts[-1]:
+            assert np.all(g[2 * nZ, :, c] == 0) and np.all(h[2 * nZ, :, c] == 0)
+    if nZ == 3 and counts[0] == 4:  # L-up of the lowest altitude (count 4) above its count
+        assert np.all(g[3, :, 4:] == 0) and np.all(h[3, :, 4:] == 0)
+
+
+@pytest.mark.parametrize("theta_r", [0.0, 0.7])
+def test_single_angle_downwelling_derivatives_are_nan(theta_r):
+    """N_angle = 1: the oracle's Ld is 0/0 (theta = 0 carries weight 0), and so is any difference of it: the closed form's
+    Ld rows are NaN too, every other row is unaffected."""
+    X, OD, T, Z = _column()
+    alts = ALT_SETS["inside"]
+    nZ = alts.size
+    layers = np.array([0, 5, 11])
+    with np.errstate(invalid="ignore"):
+        g, h = jacobian_from_od(X, OD, T, Z, alts, theta_r=theta_r, N_angle=1, layers=layers)
+        g30, h30 = jacobian_from_od(X, OD, T, Z, alts, theta_r=theta_r, N_angle=30, layers=layers)
+        for l in layers:
+            Op, Om = OD.copy(), OD.copy()
+            Op[:, l] += 1e-3
+            Om[:, l] -= 1e-3
+            fd = (_rows(X, Op, T, Z, alts, False, theta_r, 1) - _rows(X, Om, T, Z, alts, False, theta_r, 1)) / 2e-3
+            assert np.isnan(fd[2 * nZ]).all() and not np.isnan(fd[:2 * nZ]).any()
+    assert np.isnan(g[2 * nZ]).all() and np.isnan(h[2 * nZ]).all()
+    assert np.array_equal(g[:2 * nZ], g30[:2 * nZ]) and np.array_equal(h[:2 * nZ], h30[:2 * nZ])
