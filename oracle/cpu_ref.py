@@ -629,6 +629,194 @@ def jacobian_from_od(X, OD, T, Z, Altitudes, theta_r=0.0, N_angle=30, returnOD=F
     return g, h
 
 
+# ---- the nodal line-sum's classification (rtx_voigt_scatter.hip: row_geom, nodal_tile) -------------------------------
+# Restated so that host tests can show which path a configuration reaches. Not an oracle of values: the line-sum's
+# results are checked against absorptionCoefficient_Voigt; this only says which code evaluates which (line, tile).
+LS_ROWS, LS_NEAR, LS_TILE_DIST, LS_NW = 16, 2, 512, 2  # RTX_SC_ROWS, RTX_SC_NEAR, RTX_SC_TILE_DIST, SC_NW
+LS_EDGE_CAP, LS_ENT_CAP, LS_SPLIT_MIN, LS_SPLIT_PART = 32, 16, 768, 256  # SC_EDGE_CAP, SC_ENT_CAP, RTX_SPLIT_*
+
+
+def _row_bits(lo, hi, rows=LS_ROWS):
+    r = np.arange(rows)[None, :]
+    return (r >= np.asarray(lo)[:, None]) & (r < np.asarray(hi)[:, None])
+
+
+def row_masks(i0, lo, hi, zw, ia, nt, rows=LS_ROWS, near=LS_NEAR):
+    """row_geom and the row masks of voigt_nodal_kernel for lines (local i0, window [lo, hi), band half-width zw; int
+    arrays) in the tile [ia, ia + nt): bool [lines][rows] masks reach, inside (m_in), near, band, far, pp, edge, bd, and
+    the per-line r_lo, r_hi, part_l, part_r, rc (centre row, floor)."""
+    i0, lo, hi, zw = (np.asarray(v, dtype=np.int64) for v in (i0, lo, hi, zw))
+    dlo, dhi = lo - ia, hi - ia
+    lo_t, hi_t = np.maximum(dlo, 0), np.minimum(dhi, nt)
+    r_lo, r_hi = lo_t >> 6, (hi_t + 63) >> 6
+    c0 = (lo_t + 63) >> 6
+    c1 = np.where(dhi < nt, hi_t >> 6, r_hi)  # a ragged last row of the grid is not an edge
+    zl, zh = i0 - np.maximum(zw, 0) - ia, i0 + np.maximum(zw, 0) - ia
+    has_z = (zw > 0) & (zh >= 0) & (zl < 64 * rows)
+    z0 = np.where(has_z, np.where(zl > 0, zl >> 6, 0), rows)
+    z1 = np.where(has_z, np.minimum(zh >> 6, rows - 1), -1)
+    rc = (i0 - ia) >> 6
+    n0, n1 = np.minimum(rc - near, zl >> 6), np.maximum(rc + near, zh >> 6)
+    reach = ((hi > ia) & (lo < ia + nt))[:, None]
+    m = {"reach": reach & _row_bits(r_lo, r_hi, rows), "inside": reach & _row_bits(c0, c1, rows),
+         "near": _row_bits(np.maximum(n0, 0), np.minimum(n1, rows - 1) + 1, rows), "band": _row_bits(z0, z1 + 1, rows)}
+    m["far"] = m["inside"] & ~m["near"]
+    m["pp"] = m["inside"] & m["near"] & ~m["band"]
+    m["edge"] = m["reach"] & ~m["inside"] & ~m["band"]
+    m["bd"] = m["reach"] & m["band"]
+    m.update(r_lo=r_lo, r_hi=r_hi, part_l=c0 != r_lo, part_r=c1 != r_hi, rc=rc)
+    return m
+
+
+def linesum_records(tbl, grid, T, p, omega_wing=0.0, omega_wing_hw=50.0, Diluent=None):
+    """line_prep_kernel's geometry for one layer, per line of `tbl` in ascending-nu (stable) order -- the order of the
+    device table: local i0 (nearest index to the shifted centre, clamped), window [lo, hi) (local, bisect_right of
+    nu -+ W on the global axis, clamped to the shard; empty = 0, 0), zw, fp32 y, cte, sg0, the global gi0 before the
+    local clamp and whether W came from OmegaWing. grid = (xmin, xmax, n_total, offset, n)."""
+    xmin, xmax, n_total, offset, n = grid
+    step = (xmax - xmin) / (n_total - 1)
+    order = np.argsort(np.asarray(tbl["nu"], dtype=np.float64), kind="stable")
+    sub = {k: np.asarray(v)[order] for k, v in tbl.items()}
+    P = line_params(sub, T, p, Diluent=Diluent)
+    nu = np.asarray(sub["nu"], dtype=np.float64)
+    Whw = omega_wing_hw * np.maximum(P["Gamma0"], P["GammaD"])
+    W = np.maximum(omega_wing, Whw)
+
+    def gx(ig):
+        return np.where(ig == n_total - 1, xmax, ig.astype(np.float64) * step + xmin)
+
+    def bisect_right(v):
+        t = (v - xmin) / step
+        k = np.where(~(t > -1.0), 0, np.where(t >= n_total, n_total, np.floor(np.clip(t, -2.0, n_total)) + 1)).astype(np.int64)
+        k = np.clip(k, 0, n_total)
+        for _ in range(4):
+            k = np.where((k < n_total) & (gx(np.minimum(k, n_total - 1)) <= v), k + 1, k)
+            k = np.where((k > 0) & (gx(np.maximum(k - 1, 0)) > v), k - 1, k)
+        return k
+
+    lo = np.clip(bisect_right(nu - W) - offset, 0, n)
+    hi = np.clip(bisect_right(nu + W) - offset, 0, n)
+    live = hi > lo
+    lo, hi = np.where(live, lo, 0), np.where(live, hi, 0)
+    sg0 = nu + P["Shift0"]
+    cte = np.sqrt(np.log(2.0)) / P["GammaD"]
+    y = P["Gamma0"] * cte
+    gi0 = np.clip(np.rint((sg0 - xmin) / step), -1e9, 1e9).astype(np.int64)
+    i0 = np.clip(gi0 - offset, -100000000, n + 100000000)
+    zw = np.where((y < 15.0) & live, np.minimum(np.ceil((15.0 - y) / (step * cte)) + 2.0, 4e7), 0).astype(np.int64)
+    return {"i0": i0, "lo": lo, "hi": hi, "zw": zw, "y": y.astype(np.float32), "cte": cte, "sg0": sg0, "gi0": gi0,
+            "W_omega": omega_wing > Whw, "nu": nu, "step": step}
+
+
+def _band_row_labels(R, l, r, ia, grid, smally):
+    """The band_row branch a (line, row) takes: lanes' x in fp64 (the kernel's fp32 x differs by ~1e-7 of |x|)."""
+    xmin, xmax, n_total, offset, n = grid
+    i = offset + ia + 64 * r + np.arange(64)
+    X = np.where(i == n_total - 1, xmax, i * R["step"] + xmin)
+    x = (X - R["sg0"][l]) * R["cte"][l]
+    y = float(R["y"][l])
+    out = set()
+    if smally and y < 1.0:
+        if np.all(np.abs(x) >= 5.5):
+            out.add("band_outer")  # asymK_re<12> in fp32
+        else:
+            return {"band_w64"}  # fp64 Weideman on every lane
+    if np.any(np.abs(np.abs(x) + y - 15.0) < 2e-3):
+        out.add("band_recheck")  # the |x| + y < 15 switch repeated in fp64
+    if y >= 1.0:
+        wz = np.abs(x) + y < 15.0
+        if y >= 6.0:
+            out.add("band_asym6")
+        elif not np.any(wz & (x * x + y * y < 64.0)):
+            out.add("band_series")  # 1 <= y < 6, every Weideman lane at |z| >= 8
+        else:
+            out.add("band_wei32")
+    return out
+
+
+def linesum_census(tbl, grid, T, p, omega_wing=0.0, omega_wing_hw=50.0, Diluent=None):
+    """Which paths of rtx_voigt_sum's nodal kernel a call reaches: a Counter of labels over every layer, (line, tile or
+    hot-tile part) and wave round. T, p: per-layer sequences. Candidates are the canonical range of each tile (first to
+    last line whose window meets it, tile_ranges_kernel), cut into parts of LS_SPLIT_PART when longer than LS_SPLIT_MIN;
+    candidate c of a part goes to wave c % LS_NW, round c // (64 LS_NW)."""
+    from collections import Counter
+    xmin, xmax, n_total, offset, n = grid
+    tile = 64 * LS_ROWS
+    full_rows = (1 << LS_ROWS) - 1
+    C = Counter()
+    for T_k, p_k in zip(np.atleast_1d(T), np.atleast_1d(p)):
+        R = linesum_records(tbl, grid, float(T_k), float(p_k), omega_wing, omega_wing_hw, Diluent)
+        i0, lo, hi, zw = R["i0"], R["lo"], R["hi"], R["zw"]
+        smally = bool(np.any((zw > 0) & (R["y"] < 1.0)))
+        C["smally_layer" if smally else "plain_layer"] += 1
+        live = hi > lo
+        C["W_omega"] += int(np.sum(live & R["W_omega"]))
+        C["W_hw"] += int(np.sum(live & ~R["W_omega"]))
+        C["i0_clamped"] += int(np.sum(live & (i0 != R["gi0"] - offset)))
+        C["centre_left"] += int(np.sum(live & (i0 < 0)))
+        C["centre_right"] += int(np.sum(live & (i0 >= n)))
+        C["covers_grid"] += int(np.sum(live & (lo == 0) & (hi == n) & (i0 > 0) & (i0 < n - 1)))
+        C["narrow"] += int(np.sum(live & (hi - lo < 64) & (lo > 0) & (hi < n)))
+        for ia in range(0, n, tile):
+            nt = min(tile, n - ia)
+            reach = live & (hi > ia) & (lo < ia + nt)
+            if not reach.any():
+                continue
+            idx = np.nonzero(reach)[0]
+            first, last = int(idx[0]), int(idx[-1]) + 1
+            cnt = last - first
+            parts = [(first, min(first + LS_SPLIT_PART, last))] if cnt > LS_SPLIT_MIN else [(first, last)]
+            if cnt > LS_SPLIT_MIN:
+                C["hot_smally" if smally else "hot_plain"] += 1
+                for q in range(1, (cnt - 1) // LS_SPLIT_PART + 1):
+                    parts.append((first + q * LS_SPLIT_PART, min(first + (q + 1) * LS_SPLIT_PART, last)))
+            for a, b in parts:
+                sl = np.arange(a, b)
+                if b - a > 64 * LS_NW:
+                    C["rounds"] += 1
+                m = row_masks(i0[sl], lo[sl], hi[sl], zw[sl], ia, nt)
+                bitsum = lambda M: (M.astype(np.int64) << np.arange(LS_ROWS)).sum(1)
+                far, pp, ed, bd = bitsum(m["far"]), bitsum(m["pp"]), bitsum(m["edge"]), bitsum(m["bd"])
+                is_t = (far == full_rows) & ((ia - i0[sl] >= LS_TILE_DIST) | (i0[sl] - (ia + tile - 1) >= LS_TILE_DIST))
+                full = (far == full_rows) & ~is_t
+                part = (far != 0) & (far != full_rows)
+                single = (pp == 0) & (bd == 0) & (ed != 0) & ((ed & (ed - 1)) == 0)
+                re = np.where(single, np.log2(np.maximum(ed, 1)).astype(np.int64), 0)
+                left, right = m["part_l"] & (re == m["r_lo"]), m["part_r"] & (re == m["r_hi"] - 1)
+                edge_only = single & (left != right)
+                entry = ~edge_only & ((pp | ed | bd) != 0)
+                for name, sel in (("tile", is_t), ("full", full), ("partial", part), ("edge_only", edge_only),
+                                  ("entry", entry), ("near", pp != 0), ("band", bd != 0)):
+                    C[name] += int(sel.sum())
+                    if name in ("tile", "full", "partial", "edge_only", "entry"):
+                        c = np.arange(b - a)
+                        key = (c % LS_NW) + LS_NW * (c // (64 * LS_NW))
+                        per = np.bincount(key[sel], minlength=1)
+                        if name == "edge_only" and per.max() > LS_EDGE_CAP:
+                            C["edge_overflow"] += 1  # a wave round emits more than the list holds: drained mid-round
+                        if name == "entry" and per.max() > LS_ENT_CAP:
+                            C["entry_overflow"] += 1
+                        if name in ("tile", "full", "partial") and np.any((per > 8) & (per % 8 != 0)):
+                            C[name + "_ragged"] += 1  # several groups of 8 members in a round, the last one ragged
+                for d in (511, 512, 513):
+                    C["tile_left_%d" % d] += int(np.sum(is_t & (ia - i0[sl] == d)))
+                    C["tile_right_%d" % d] += int(np.sum(is_t & (i0[sl] - (ia + tile - 1) == d)))
+                    C["full_left_%d" % d] += int(np.sum(full & (ia - i0[sl] == d)))
+                    C["full_right_%d" % d] += int(np.sum(full & (i0[sl] - (ia + tile - 1) == d)))
+                inside = (i0[sl] >= ia) & (i0[sl] < ia + nt) & (pp != 0)
+                for rc in (0, LS_ROWS // 2, LS_ROWS - 1):
+                    C["centre_row_%d" % rc] += int(np.sum(inside & (m["rc"] == rc)))
+                C["one_row"] += int(np.sum((m["r_hi"] - m["r_lo"] == 1) & m["part_l"] & m["part_r"] & (m["reach"].any(1))))
+                dlo, dhi = lo[sl] - ia, hi[sl] - ia
+                C["lo_aligned"] += int(np.sum((dlo > 0) & (dlo < nt) & (dlo % 64 == 0)))
+                C["hi_aligned"] += int(np.sum((dhi > 0) & (dhi < nt) & (dhi % 64 == 0)))
+                for j in np.nonzero(bd != 0)[0]:
+                    for r in np.nonzero(m["bd"][j])[0]:
+                        for lab in _band_row_labels(R, a + j, int(r), ia, grid, smally):
+                            C[lab] += 1
+    return C
+
+
 # ---- post-processing of TUD products (SURVEY 8f row 2) ----------------------------------------
 def smooth(x, window_len=11, window="hanning"):
     """radiative_transfer.py:1266-1324: reflect-pad by window_len-1 samples, convolve with the normalised

@@ -278,7 +278,8 @@ __device__ __forceinline__ int clamp_local(long long ig, const GridDev& g) {
 }
 
 // Local centre index clamped to [-1e8, n+1e8]: with n <= 2e9 and zw <= 4e7 every i - i0, lo - i0 and
-// i0 +- zw the line-sum forms stays inside int32. A centre that far outside cannot reach the shard.
+// i0 +- zw the line-sum forms stays inside int32. A centre that far outside reaches the shard only through a wide
+// OmegaWing; its record's c is then taken at the clamped index (line_prep_kernel), so its far wing stays exact.
 __device__ __forceinline__ int sat_local(long long v, long long n) {
   const long long M = 100000000LL;
   return (int)(v < -M ? -M : (v > n + M ? n + M : v));
@@ -449,11 +450,13 @@ __global__ __launch_bounds__(256) void line_prep_kernel(PrepArgs a) {
     long long gi0 = llrint((sg0 - g.xmin) / g.step);
     if (gi0 < -M) gi0 = -M;
     if (gi0 > M) gi0 = M;
-    const double frac_x = (grid_x(g, gi0) - sg0) * cte;  // x at gi0, |.| <= a/2 when inside the grid
+    r.i0 = sat_local(gi0 - g.offset, g.n);
+    // x at the record's centre index: gi0 (|.| <= a/2 when inside the grid) unless the local clamp moved it -- a centre
+    // over 1e8 points outside the shard whose window still reaches in (OmegaWing) -- so that x = u a + c is the line's own
+    const double frac_x = (grid_x(g, g.offset + (long long)r.i0) - sg0) * cte;
     const double ax = g.step * cte;
     r.a = (float)ax;
     r.c = (float)frac_x;
-    r.i0 = sat_local(gi0 - g.offset, g.n);
     r.lo = lo;
     r.hi = hi;
     // half-width (grid points) of the band that can satisfy |x|+y<15 (hum1_wei switch, misc/hapi.py:9840)

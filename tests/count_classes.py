@@ -2,7 +2,8 @@
 """CPU-side census of the line-sum's work on the C3 workload, with the nodal kernel's geometry (16-row tiles, near zone
 +- 2 rows): per tile and layer, how many candidate lines, how many reach the tile, how many are row-level members (full:
 every row of the tile a far row; partial), how many rows go point by point (near zone / window edge / Weideman band).
-Pure NumPy on the oracle's line parameters; no GPU.   python tests/count_classes.py"""
+Pure NumPy on the oracle's line parameters and its restatement of the kernel's row masks (cpu_ref.row_masks);
+no GPU.   python tests/count_classes.py"""
 import os
 import sys
 
@@ -37,19 +38,8 @@ for k in (0, 8, 16, 24, 31):
         ia, ib = t * TILE, min((t + 1) * TILE, N)
         c["cand"] += int(((ic >= ia - maxhw) & (ic <= ib - 1 + maxhw)).sum())
         idx = np.nonzero((hi > ia) & (lo < ib))[0]
-        rows = np.arange(ROWS)[None, :]
-        lo_t, hi_t = np.maximum(lo[idx] - ia, 0)[:, None], np.minimum(hi[idx] - ia, ib - ia)[:, None]
-        reach = (rows * 64 < hi_t) & (rows * 64 + 64 > lo_t)
-        inside = (rows * 64 >= lo_t) & (rows * 64 + 64 <= hi_t)
-        rc = ((i0[idx] - ia) >> 6)[:, None]
-        zl, zh = ((i0[idx] - zw[idx] - ia) >> 6)[:, None], ((i0[idx] + zw[idx] - ia) >> 6)[:, None]
-        has_band = (zw[idx] > 0)[:, None]
-        band = has_band & (rows >= zl) & (rows <= zh)
-        near = (rows >= np.minimum(rc - NEAR, zl)) & (rows <= np.maximum(rc + NEAR, zh))
-        far = inside & ~near
-        pp = inside & near & ~band
-        edge = reach & ~inside & ~band
-        bd = reach & band
+        m = cpu_ref.row_masks(i0[idx], lo[idx], hi[idx], zw[idx], ia, ib - ia, rows=ROWS, near=NEAR)
+        far, pp, edge, bd = m["far"], m["pp"], m["edge"], m["bd"]
         ent = (pp | edge | bd).any(1)
         c["reach"] += idx.size
         c["full"] += int(far.all(1).sum())

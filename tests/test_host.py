@@ -600,3 +600,27 @@ def test_sdvoigt_regime_zones_and_node_error_bounds():
     assert cheb_err(32, 1024, 256.0, 0.05) <= 1e-10   # coarse grid: the regime boundary lies inside 256 points
     assert cheb_err(12, 64, 420.0, step) <= 1e-10
     assert cheb_err(12, 64, 129.0, 0.05) <= 1e-10     # three rows from the centre row at the least: >= 129 points to the centre
+
+
+def test_linesum_case_census():
+    """tests/linesum_cases.py (the configurations of tests/test_gpu_linesum_paths.py) reaches, case by case, the paths of
+    the nodal line-sum it names: cpu_ref.linesum_census restates row_geom, the tile / row-level member, edge-only and
+    entry classification, the wave rounds, the list capacities, the hot-tile split and the band-row branches. A case
+    shifted off its class fails here, on a CPU. The restatement's constants are the kernel's."""
+    import linesum_cases as LC
+    from oracle import cpu_ref
+    src = open(os.path.join(ROOT, "radtxfr_amd", "csrc", "rtx_voigt_scatter.hip")).read()
+    src += open(os.path.join(ROOT, "radtxfr_amd", "csrc", "rtx_common.h")).read()
+    define = lambda name: int(re.search(r"#define %s (\d+)" % name, src).group(1))
+    assert (define("RTX_SC_ROWS"), define("RTX_SC_NEAR"), define("RTX_SC_TILE_DIST"), define("SC_NW")) == \
+        (cpu_ref.LS_ROWS, cpu_ref.LS_NEAR, cpu_ref.LS_TILE_DIST, cpu_ref.LS_NW)
+    assert (define("SC_EDGE_CAP"), define("RTX_SPLIT_MIN"), define("RTX_SPLIT_PART")) == \
+        (cpu_ref.LS_EDGE_CAP, cpu_ref.LS_SPLIT_MIN, cpu_ref.LS_SPLIT_PART)
+    assert "#define SC_ENT_CAP (SC_EDGE_LIST ? %d :" % cpu_ref.LS_ENT_CAP in src
+    for branch in ("__ballot(fabsf(x) < 5.5f)", "q.y >= 6.0f", "fmaf(x, x, q.y * q.y) < 64.0f", "fabsf(s32 - 15.0f) < 2e-3f"):
+        assert branch in src, branch
+    for name, c in LC.CASES.items():
+        C = cpu_ref.linesum_census(c["tbl"], c["grid"], c["T"], c["p"], c["ow"], c["hw"])
+        missing = [e for e in c["expect"] if not e.startswith("!") and C[e] <= 0]
+        present = [e[1:] for e in c["expect"] if e.startswith("!") and C[e[1:]] > 0]
+        assert not missing and not present, (name, missing, present)
