@@ -69,6 +69,16 @@ int rtx_lines_set_sd(rtx_lines* lines, const double* sd_air_h, const double* sd_
 /* Optional deltap_self column: temperature dependence of the self-induced pressure shift,
  * Shift0 += abun_self * (delta_self + deltap_self*(T - Tref)) * p (misc/hapi.py:11120-11128). NULL = 0. */
 int rtx_lines_set_deltap_self(rtx_lines* lines, const double* deltap_self_h);
+/* Extra broadener column sets: the gamma_<sp>, n_<sp>, delta_<sp>, deltap_<sp> and SD_<sp> columns the reference reads for
+ * any Diluent key other than air and self (misc/hapi.py:11090-11128; SD :10860-10890). Set j (0 <= j < n_extra) is column
+ * set 2 + j of rtx_line_prep_mix (0 = air, 1 = self keep the columns of rtx_lines_create / _set_sd / _set_deltap_self).
+ * Each argument is an array of n_extra host pointers, entry j the column of set j in the row order given to
+ * rtx_lines_create (n_lines doubles), or NULL; a whole argument may be NULL. The reference's fallbacks: an absent gamma,
+ * delta, deltap or SD column is 0, an absent n column is n_air (:11103-11110; a foreign n of 0 stays 0 -- only self falls
+ * back where its n is 0). Replaces the previous set; n_extra = 0 drops it. Allocates device memory and synchronises. */
+#define RTX_MAX_BROADENERS 64
+int rtx_lines_set_broadeners(rtx_lines* lines, int n_extra, const double* const* gamma_h, const double* const* n_h,
+                             const double* const* delta_h, const double* const* deltap_h, const double* const* sd_h);
 
 /* ------------------------------------------------------------------------------------------
  * Per-(line, layer) prologue, fp64. Replaces the per-line environment block of
@@ -146,6 +156,33 @@ int rtx_line_prep_axis(rtx_prep* prep, const rtx_lines* lines, const double* X_h
                        const double* T_h, const double* p_atm_h, const double* qratio_h, const double* weight_h,
                        const double* mass_h, double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
                        double intensity_threshold, double scale, int profile, void* stream);
+
+/* The prologue with per-layer diluent mixes: Diluent of misc/hapi.py:11025-11032 as fractions per (diluent, species,
+ * layer) over any column sets instead of two call-wide scalars. Arguments as rtx_line_prep_profile / rtx_line_prep_axis with
+ * dil_air, dil_self replaced by
+ *   n_dil              0 <= n_dil <= RTX_MAX_DILUENTS diluents
+ *   dil_h[n_dil]       column set of each: 0 air, 1 self, 2 + j extra set j of rtx_lines_set_broadeners
+ *   frac_h[n_dil][n_species][n_layers]   fractions (host; not validated, as the reference's range check never fires)
+ * Per (line, layer), summed over the diluents in the caller's order (misc/hapi.py:11090-11128, 10884-10890):
+ *   Gamma0 += f * gamma * p * (Tref/T)^n,  Shift0 += f * (delta + deltap * (T - Tref)) * p,
+ *   Gamma2 += f * SD * p * gamma  (RTX_PROFILE_SDVOIGT; the un-scaled gamma column of each set).
+ * A diluent may repeat (the reference sums keys that differ only in case: "AIR" and "air" are two entries of set 0). A zero
+ * fraction contributes nothing. S(T), GammaD, windows, records and the hot-tile bound (which takes the largest
+ * sum_d |f_d| gamma_max_d over species and layers with each set's n range) are those of the scalar prologues; with
+ * {air: dil_air, self: dil_self} the records are theirs bit for bit. The fractions are copied into a device buffer owned by
+ * the prep object (grow-only: the first call allocates, hence synchronises).
+ * rtx_line_prep_mix: profile RTX_PROFILE_VOIGT / _LORENTZ / _SDVOIGT (Doppler takes no diluent, misc/hapi.py:11510-11513);
+ * follow with rtx_voigt_sum, or rtx_sdvoigt_sum for SDVOIGT. rtx_line_prep_axis_mix: RTX_PROFILE_VOIGT / _LORENTZ; follow
+ * with rtx_voigt_sum_axis. */
+#define RTX_MAX_DILUENTS 8
+int rtx_line_prep_mix(rtx_prep* prep, const rtx_lines* lines, const rtx_grid* grid, int n_layers, const double* T_h,
+                      const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
+                      int n_dil, const int32_t* dil_h, const double* frac_h, double omega_wing, double omega_wing_hw,
+                      double intensity_threshold, double scale, int profile, void* stream);
+int rtx_line_prep_axis_mix(rtx_prep* prep, const rtx_lines* lines, const double* X_h, int64_t nx, int n_layers,
+                           const double* T_h, const double* p_atm_h, const double* qratio_h, const double* weight_h,
+                           const double* mass_h, int n_dil, const int32_t* dil_h, const double* frac_h, double omega_wing,
+                           double omega_wing_hw, double intensity_threshold, double scale, int profile, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Voigt line-sum. Replaces the per-line PROFILE_VOIGT + scatter-add loop, misc/hapi.py:11050,

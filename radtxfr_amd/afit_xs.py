@@ -53,15 +53,18 @@ def AFIT_XS_read(File):
 
 
 def cross_section_grid(SourceTables, T, P_atm, X, WavenumberWingHW=50.0, WavenumberWing=0.0, IntensityThreshold=0.0,
-                       GammaL="gamma_air", Components=None):
+                       GammaL="gamma_air", Components=None, Diluent=None):
     """HITRAN-unit Voigt cross sections [cm^2/molecule] of one table for every (T, p) pair of the grids: the body of the
     reference's double loop (RT_gen_AbsXS_files.py:88-90: absorptionCoefficient_SDVoigt, i.e. the Voigt line-sum for tables
-    without speed-dependence columns and rtx_sdvoigt_sum for tables with them) as one batched launch per 128 states. X must be uniform. Returns xs[nT][nP][nX] float64 (host)."""
+    without speed-dependence columns and rtx_sdvoigt_sum for tables with them) as one batched launch per 128 states. X must be uniform. Returns xs[nT][nP][nX] float64 (host).
+    Diluent: {broadener: fraction} as absorptionCoefficient_SDVoigt takes it (any keys, misc/hapi.py:10860-10890); None keeps
+    GammaL (gamma_air: air, gamma_self: self)."""
     T = np.atleast_1d(np.asarray(T, dtype=np.float64))
     P = np.atleast_1d(np.asarray(P_atm, dtype=np.float64))
     X = np.asarray(X, dtype=np.float64)
     engine.require_gpu()
-    tbl = _hapi._device_table(_hapi.listOfTuples(SourceTables))
+    names = _hapi.listOfTuples(SourceTables)
+    tbl = _hapi._device_table(names, [k.lower() for k in Diluent] if Diluent else ())
     grid = engine.Grid.from_axis(X)
     comps = [p for p in tbl.species if p != (0, 0)] if Components is None else [(int(c[0]), int(c[1])) + tuple(c[2:3]) for c in Components]
     w = np.zeros(len(tbl.species))
@@ -74,6 +77,8 @@ def cross_section_grid(SourceTables, T, P_atm, X, WavenumberWingHW=50.0, Wavenum
     smax = float(np.max(tbl.cols["sw"])) * float(np.max(w)) if tbl.n and np.max(w) > 0 else 1.0
     scale = 2.0 ** (-np.floor(np.log2(smax))) if smax > 0 and np.isfinite(smax) else 1.0
     dil = {"air": 1.0} if GammaL.lower() == "gamma_air" else {"self": 1.0}
+    mix = {k: float(v) for k, v in Diluent.items()} if Diluent else None
+    has_sd = tbl.has_sd or (mix is not None and tbl.extra_has_sd(mix))
     out = np.empty((len(states), X.size))
     # states per launch: the per-(line, state) records (80-128 B each) and, with the caller's 350-half-width wings, the
     # partial tiles of the line-sum's part list (every tile then has > 256 candidate lines) must fit comfortably
@@ -88,7 +93,7 @@ def cross_section_grid(SourceTables, T, P_atm, X, WavenumberWingHW=50.0, Wavenum
             try:
                 engine.voigt_sum(tbl, grid, Tk, pk, np.tile(w[:, None], (1, len(chunk))), out_f64=dev, dil_air=dil.get("air", 0.0),
                                  dil_self=dil.get("self", 0.0), omega_wing=WavenumberWing, omega_wing_hw=WavenumberWingHW,
-                                 intensity_threshold=IntensityThreshold, scale=scale, profile=3 if tbl.has_sd else 0)
+                                 intensity_threshold=IntensityThreshold, scale=scale, profile=3 if has_sd else 0, diluent=mix)
             except _lib.RtxError as e:
                 if "work list" in str(e) and per > 1:  # too many partial tiles for one launch: fewer states at a time
                     per = max(1, per // 4)
@@ -121,14 +126,15 @@ def cross_section_grid(SourceTables, T, P_atm, X, WavenumberWingHW=50.0, Wavenum
     return out.reshape(T.size, P.size, X.size)
 
 
-def generate_xs_files(SourceTables, ID, T, P_atm, X, descr, WavenumberWingHW=50.0, directory="."):
+def generate_xs_files(SourceTables, ID, T, P_atm, X, descr, WavenumberWingHW=50.0, directory=".", Diluent=None):
     """The reference's generator loop (RT_gen_AbsXS_files.py:86-92) for one molecule table: one AFIT_XS file per (T, p);
-    returns the file names in the reference's order (T outer, p inner). P is written in Pa (101325*p, :91)."""
+    returns the file names in the reference's order (T outer, p inner). P is written in Pa (101325*p, :91). Diluent: as for
+    cross_section_grid (None: air)."""
     import os
 
     T = np.atleast_1d(np.asarray(T, dtype=np.float64))
     P = np.atleast_1d(np.asarray(P_atm, dtype=np.float64))
-    xs = cross_section_grid(SourceTables, T, P, X, WavenumberWingHW=WavenumberWingHW)
+    xs = cross_section_grid(SourceTables, T, P, X, WavenumberWingHW=WavenumberWingHW, Diluent=Diluent)
     names = []
     for it, t in enumerate(T):
         for ip, p in enumerate(P):

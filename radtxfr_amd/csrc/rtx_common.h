@@ -121,6 +121,12 @@ struct rtx_lines {
   // host side, for the bound on candidates per tile (hot-tile split, below): the sorted centres and column extremes
   double* nu_host;
   double ga_max, gs_max, n_lo, n_hi;
+  double na_lo, na_hi, ns_lo, ns_hi;  // n ranges of the air and the self column sets on their own (self after its n_air fallback)
+  // extra broadener column sets (rtx_lines_set_broadeners): [n_extra][n] each, every column filled (absent gamma / delta /
+  // deltap / SD = 0, absent n = n_air), so the mixed prologue reads them without tests
+  int n_extra;
+  double *x_gamma, *x_n, *x_delta, *x_deltap, *x_sd;
+  double *x_gmax, *x_nlo, *x_nhi;  // host, [n_extra]: |gamma| maximum and n range of each set (hot-tile bound)
 };
 
 // ---- hot tiles ---------------------------------------------------------------------------------------
@@ -180,4 +186,7 @@ struct rtx_prep {
   // window temperatures of rtx_line_prep_window: device copy, grow-only
   double* twin;
   int twin_cap;
+  // diluent fractions of rtx_line_prep_mix / _axis_mix: device copy [n_dil][n_species][n_layers], grow-only
+  double* frac;
+  size_t frac_cap;
 };

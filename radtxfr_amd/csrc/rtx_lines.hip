@@ -59,6 +59,10 @@ extern "C" int rtx_lines_free(rtx_lines* L) {
   for (double* q : p)
     if (q) (void)hipFree(q);
   if (L->species) (void)hipFree(L->species);
+  double* x[] = {L->x_gamma, L->x_n, L->x_delta, L->x_deltap, L->x_sd};
+  for (double* q : x)
+    if (q) (void)hipFree(q);
+  free(L->x_gmax); free(L->x_nlo); free(L->x_nhi);
   free(L->nu_host);
   delete L;
   return 0;
@@ -112,6 +116,7 @@ extern "C" int rtx_lines_create(int64_t n, int n_species, const double* nu_h, co
     return 1;
   }
   L->n_lo = 1e300; L->n_hi = -1e300;
+  L->na_lo = L->ns_lo = 1e300; L->na_hi = L->ns_hi = -1e300;
   for (int64_t i = 0; i < n; ++i) {
     L->nu_host[i] = nu_h[i];
     L->ga_max = fmax(L->ga_max, fabs(gamma_air_h[i]));
@@ -119,6 +124,8 @@ extern "C" int rtx_lines_create(int64_t n, int n_species, const double* nu_h, co
     const double na = n_air_h[i], ns = (n_self_h && n_self_h[i] != 0.0) ? n_self_h[i] : na;
     L->n_lo = fmin(L->n_lo, fmin(na, ns));
     L->n_hi = fmax(L->n_hi, fmax(na, ns));
+    L->na_lo = fmin(L->na_lo, na); L->na_hi = fmax(L->na_hi, na);
+    L->ns_lo = fmin(L->ns_lo, ns); L->ns_hi = fmax(L->ns_hi, ns);
   }
   *out = L;
   return 0;
@@ -147,6 +154,51 @@ extern "C" int rtx_lines_set_deltap_self(rtx_lines* L, const double* deltap_self
   return 0;
 }
 
+// Extra broadener column sets (gamma_<sp>, n_<sp>, delta_<sp>, deltap_<sp>, SD_<sp> of misc/hapi.py:11090-11128, 10860-10890):
+// replaces the table's previous set. Every device column is filled, the reference's fallbacks applied here once: an absent
+// gamma / delta / deltap / SD column is 0, an absent n column is n_air (a foreign n of 0 stays 0).
+extern "C" int rtx_lines_set_broadeners(rtx_lines* L, int n_extra, const double* const* gamma_h, const double* const* n_h,
+                                        const double* const* delta_h, const double* const* deltap_h, const double* const* sd_h) {
+  if (!L) RTX_FAIL("lines is NULL");
+  if (n_extra < 0 || n_extra > RTX_MAX_BROADENERS) RTX_FAIL("n_extra=%d outside [0,%d]", n_extra, RTX_MAX_BROADENERS);
+  double** dst[5] = {&L->x_gamma, &L->x_n, &L->x_delta, &L->x_deltap, &L->x_sd};
+  for (double** d : dst)
+    if (*d) { (void)hipFree(*d); *d = nullptr; }
+  free(L->x_gmax); free(L->x_nlo); free(L->x_nhi);
+  L->x_gmax = L->x_nlo = L->x_nhi = nullptr;
+  L->n_extra = 0;
+  if (n_extra == 0) return 0;
+  L->x_gmax = (double*)calloc((size_t)n_extra, sizeof(double));
+  L->x_nlo = (double*)calloc((size_t)n_extra, sizeof(double));
+  L->x_nhi = (double*)calloc((size_t)n_extra, sizeof(double));
+  if (!L->x_gmax || !L->x_nlo || !L->x_nhi) RTX_FAIL("out of host memory");
+  const size_t n = (size_t)L->n, cnt = (size_t)n_extra * (n > 0 ? n : 1);
+  const double* const* src[5] = {gamma_h, n_h, delta_h, deltap_h, sd_h};
+  for (int c = 0; c < 5; ++c) {
+    RTX_HIP(hipMalloc((void**)dst[c], cnt * sizeof(double)));
+    for (int j = 0; j < n_extra && n > 0; ++j) {
+      double* col = *dst[c] + (size_t)j * n;
+      const double* h = src[c] ? src[c][j] : nullptr;
+      if (h) RTX_HIP(hipMemcpy(col, h, n * sizeof(double), hipMemcpyHostToDevice));
+      else if (c == 1) RTX_HIP(hipMemcpy(col, L->n_air, n * sizeof(double), hipMemcpyDeviceToDevice));
+      else RTX_HIP(hipMemset(col, 0, n * sizeof(double)));
+    }
+  }
+  for (int j = 0; j < n_extra; ++j) {
+    const double* g = gamma_h ? gamma_h[j] : nullptr;
+    const double* nn = n_h ? n_h[j] : nullptr;
+    double gm = 0.0, lo = L->na_lo, hi = L->na_hi;
+    if (nn) { lo = 1e300; hi = -1e300; }
+    for (size_t i = 0; i < n; ++i) {
+      if (g) gm = fmax(gm, fabs(g[i]));
+      if (nn) { lo = fmin(lo, nn[i]); hi = fmax(hi, nn[i]); }
+    }
+    L->x_gmax[j] = gm; L->x_nlo[j] = lo; L->x_nhi[j] = hi;
+  }
+  L->n_extra = n_extra;
+  return 0;
+}
+
 // ---- prep object -------------------------------------------------------------------------------------
 extern "C" int rtx_prep_free(rtx_prep* P) {
   if (!P) return 0;
@@ -162,6 +214,7 @@ extern "C" int rtx_prep_free(rtx_prep* P) {
   if (P->part_ws) (void)hipFree(P->part_ws);
   if (P->X) (void)hipFree(P->X);
   if (P->twin) (void)hipFree(P->twin);
+  if (P->frac) (void)hipFree(P->frac);
   delete P;
   return 0;
 }
@@ -210,6 +263,8 @@ extern "C" int rtx_prep_create(const rtx_lines* lines, int max_layers, int64_t m
 #define RTX_PREP_ABLATE 0
 #endif
 #define RTX_ENV_MAX 416  /* doubles of per-layer tables carried in the prologue's kernel arguments (3.3 KB of the 4 KB) */
+#define RTX_MIX_MAX 8    /* diluents per mixed prologue (include/radtxfr_hip.h: RTX_MAX_DILUENTS) */
+static_assert(RTX_MIX_MAX == RTX_MAX_DILUENTS, "kernel-argument diluent slots");
 
 // The reference-temperature half of S(T) (misc/hapi.py:10171-10172) depends on the line alone: formed once per table, by the
 // same expression the prologue used to evaluate per (line, layer) -- two of its four fp64 exponentials and two divisions.
@@ -249,7 +304,14 @@ struct PrepArgs {
   int2* win;
   int* maxhw;
   int* smally;
+  // mixed prologue (MIX = true: rtx_line_prep_mix / _axis_mix): diluent d takes column set dil_idx[d] (0 air, 1 self, 2 + j
+  // extra set j) with fraction frac[(d*n_species + species)*n_layers + layer] (device copy); x_* = the extra sets [n_extra][n]
+  int n_dil;
+  int dil_idx[RTX_MIX_MAX];
+  const double* frac;
+  const double *x_gamma, *x_n, *x_delta, *x_deltap, *x_sd;
 };
+static_assert(sizeof(PrepArgs) <= 4096, "the prologue's kernel arguments must stay within 4 KB");
 
 // The per-layer tables (T, p, qratio, weight, mass: 324 doubles for 4 species x 32 layers) travel in the kernel arguments
 // when they fit: the prologue then needs no host-to-device copy, which was 5 hipMemcpyAsync calls (~10 us of host time
@@ -288,9 +350,42 @@ __device__ __forceinline__ int sat_local(long long v, long long n) {
 // ---- per-line physics, shared by the grid prologue (line_prep_kernel) and the axis prologue (line_prep_axis_kernel) ----
 struct LinePhys {
   double GammaD, Gamma0, Shift0, W;
+  double Gam2;  // MIX only: the speed-dependent width of profile SDVOIGT (misc/hapi.py:10884-10890)
 };
-// GammaD, Gamma0 / Shift0 over the diluent mix and the window half-width OmegaWingF of line l in a layer at (T, p).
-__device__ __forceinline__ LinePhys line_phys(const PrepArgs& a, long long l, double T, double p, double mass, double nu) {
+
+// Column set c of line l for the mixed prologue -- 0 air, 1 self, 2 + j extra set j -- with the reference's fallbacks
+// (misc/hapi.py:11097-11125): an absent delta / deltap is 0, an absent n is n_air, and so is a self n of 0. The extra sets
+// carry theirs already (rtx_lines_set_broadeners).
+struct DilCols {
+  double g, n, d, dp;
+};
+__device__ __forceinline__ DilCols dil_cols(const PrepArgs& a, int c, long long l) {
+  DilCols r;
+  if (c == 0) {
+    r.g = a.gamma_air[l]; r.n = a.n_air[l]; r.d = a.delta_air[l]; r.dp = a.deltap_air ? a.deltap_air[l] : 0.0;
+  } else if (c == 1) {
+    double ns = a.n_self ? a.n_self[l] : a.n_air[l];
+    if (a.n_self && ns == 0.0) ns = a.n_air[l];
+    r.g = a.gamma_self[l]; r.n = ns;
+    r.d = a.delta_self ? a.delta_self[l] : 0.0;
+    r.dp = a.deltap_self ? a.deltap_self[l] : 0.0;
+  } else {
+    const size_t o = (size_t)(c - 2) * (size_t)a.n_lines + (size_t)l;
+    r.g = a.x_gamma[o]; r.n = a.x_n[o]; r.d = a.x_delta[o]; r.dp = a.x_deltap[o];
+  }
+  return r;
+}
+__device__ __forceinline__ double dil_sd(const PrepArgs& a, int c, long long l) {
+  if (c == 0) return a.sd_air ? a.sd_air[l] : 0.0;
+  if (c == 1) return a.sd_self ? a.sd_self[l] : 0.0;
+  return a.x_sd[(size_t)(c - 2) * (size_t)a.n_lines + (size_t)l];
+}
+
+// GammaD, Gamma0 / Shift0 over the diluent mix and the window half-width OmegaWingF of line l (species sp) in layer k at
+// (T, p). MIX = false: the call-wide dil_air / dil_self; MIX = true: the per-(diluent, species, layer) fractions.
+template <bool MIX>
+__device__ __forceinline__ LinePhys line_phys(const PrepArgs& a, long long l, double T, double p, double mass, double nu, int sp,
+                                              int k) {
   LinePhys r;
   // GammaD, misc/hapi.py:11085-11087
   const double m = mass * H_CMASSMOL * 1000.0;
@@ -303,6 +398,20 @@ __device__ __forceinline__ LinePhys line_phys(const PrepArgs& a, long long l, do
   // (Tref/T)^n as exp(n log(Tref/T)): the logarithm is the same for every line of the layer; |n log(Tref/T)| < 1, so the
   // result is within 2 ulp of pow's (whose extended-precision logarithm is 200 fp64 instructions of this kernel's ~1000)
   const double ltr = log(tr);
+  r.Gam2 = 0.0;
+  if (MIX) {
+    // misc/hapi.py:11090-11128 (Gamma2 :10884-10890, from each set's un-scaled gamma) in the caller's diluent order; a zero
+    // fraction is skipped, as the air / self prologue skips a zero dil_air / dil_self
+    for (int d = 0; d < a.n_dil; ++d) {
+      const double f = a.frac[((size_t)d * a.n_species + sp) * a.n_layers + k];
+      if (f == 0.0) continue;
+      const int c = a.dil_idx[d];
+      const DilCols q = dil_cols(a, c, l);
+      Gamma0 += f * (q.g * p / 1.0 * exp(q.n * ltr));
+      Shift0 += f * ((q.d + q.dp * (T - H_TREF)) * p / 1.0);
+      if (a.profile == RTX_PROFILE_SDVOIGT) r.Gam2 += f * (dil_sd(a, c, l) * p) * q.g;
+    }
+  } else {
   if (a.dil_air != 0.0) {
 #if RTX_PREP_ABLATE & 1  /* timing experiments only */
     Gamma0 += a.dil_air * (a.gamma_air[l] * p / 1.0 * (tr * a.n_air[l]));
@@ -320,6 +429,7 @@ __device__ __forceinline__ LinePhys line_phys(const PrepArgs& a, long long l, do
     const double dps = a.deltap_self ? a.deltap_self[l] : 0.0;
     Shift0 += a.dil_self * ((ds + dps * (T - H_TREF)) * p / 1.0);
   }
+  }  // !MIX
   if (a.profile == RTX_PROFILE_DOPPLER) {  // no pressure broadening; Shift0 = delta_air * p (misc/hapi.py:11543), set by the host through dil_air = 1 / 0 (LineShift)
     Gamma0 = 0.0;
     Shift0 = a.dil_air * a.delta_air[l] * p;
@@ -382,7 +492,8 @@ __device__ __forceinline__ void block_max_hw(int v, int* dst) {
 
 // WIN: every window (W, hence lo / hi, maxhw and the skip test) is that of the line at the layer's window temperature
 // a.Twin[k] (rtx_line_prep_window); strengths, widths and shifts stay at T. WIN = false is the reference's prologue.
-template <bool ENV_ARGS, bool WIN>
+// MIX: Gamma0 / Shift0 / Gamma2 over the per-(diluent, species, layer) fractions (rtx_line_prep_mix); everything else as MIX = false.
+template <bool ENV_ARGS, bool WIN, bool MIX>
 __global__ __launch_bounds__(256) void line_prep_kernel(PrepArgs a) {
   const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const int k = blockIdx.y;
@@ -399,9 +510,9 @@ __global__ __launch_bounds__(256) void line_prep_kernel(PrepArgs a) {
     const double nu = a.nu[l];
     const int sp = a.species[l];
     const double w = ew[(size_t)sp * a.n_layers + k];
-    const LinePhys ph = line_phys(a, l, T, p, em[sp], nu);
+    const LinePhys ph = line_phys<MIX>(a, l, T, p, em[sp], nu, sp, k);
     const double GammaD = ph.GammaD, Gamma0 = ph.Gamma0, Shift0 = ph.Shift0;
-    const double W = WIN ? line_phys(a, l, a.Twin[k], p, em[sp], nu).W : ph.W;
+    const double W = WIN ? line_phys<MIX>(a, l, a.Twin[k], p, em[sp], nu, sp, k).W : ph.W;
     long long glo = grid_bisect_right(g, nu - W);
     long long ghi = grid_bisect_right(g, nu + W);
     int lo = clamp_local(glo, g), hi = clamp_local(ghi, g);
@@ -478,8 +589,12 @@ __global__ __launch_bounds__(256) void line_prep_kernel(PrepArgs a) {
     if (a.profile == RTX_PROFILE_SDVOIGT) {
       // Gamma2 = sum_species abun * SD_species * p/pref * gamma_species(Tref) (misc/hapi.py:10884-10890); Shift2 = 0
       double Gam2 = 0.0;
-      if (a.dil_air != 0.0 && a.sd_air) Gam2 += a.dil_air * (a.sd_air[l] * p) * a.gamma_air[l];
-      if (a.dil_self != 0.0 && a.sd_self) Gam2 += a.dil_self * (a.sd_self[l] * p) * a.gamma_self[l];
+      if (MIX) {
+        Gam2 = ph.Gam2;
+      } else {
+        if (a.dil_air != 0.0 && a.sd_air) Gam2 += a.dil_air * (a.sd_air[l] * p) * a.gamma_air[l];
+        if (a.dil_self != 0.0 && a.sd_self) Gam2 += a.dil_self * (a.sd_self[l] * p) * a.gamma_self[l];
+      }
       LineRecSD q;
       q.nu = nu; q.cte = cte; q.Gam0 = Gamma0; q.Shift0 = Shift0; q.Gam2 = Gam2; q.WS = dropped ? 0.0 : w * S;
       q.inv_Gam2 = Gam2 != 0.0 ? 1.0 / Gam2 : 0.0;
@@ -520,7 +635,7 @@ __device__ long long axis_bisect(const double* __restrict__ X, long long nx, dou
 // whose window meets tile [ia, ib). Records: LineRec's axis meanings (rtx_common.h); [i0, zw) = the indices within
 // (15 - y + 0.01)/cte of the shifted centre -- the points that can satisfy hum1_wei's |x|+y<15 (misc/hapi.py:9840), with a
 // margin of 0.01 in x far above the fp32 error of the line-sum's x.
-template <bool ENV_ARGS>
+template <bool ENV_ARGS, bool MIX>
 __global__ __launch_bounds__(256) void line_prep_axis_kernel(PrepArgs a) {
   const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const int k = blockIdx.y;
@@ -535,7 +650,7 @@ __global__ __launch_bounds__(256) void line_prep_axis_kernel(PrepArgs a) {
     const double nu = a.nu[l];
     const int sp = a.species[l];
     const double w = ew[(size_t)sp * a.n_layers + k];
-    const LinePhys ph = line_phys(a, l, T, p, em[sp], nu);
+    const LinePhys ph = line_phys<MIX>(a, l, T, p, em[sp], nu, sp, k);
     const double S = line_strength(a, l, T, nu, eq[(size_t)sp * a.n_layers + k]);
     const bool dropped = !(w != 0.0) || !(ph.GammaD > 0.0) || (a.profile == RTX_PROFILE_LORENTZ && !(ph.Gamma0 > 0.0)) ||
                          (S < a.thresh);
@@ -577,16 +692,45 @@ __global__ __launch_bounds__(256) void line_prep_axis_kernel(PrepArgs a) {
 // nothing is read back from the device. The sweep (~0.1 ms for 100 000 lines) is redone only when the grid changes or a call
 // needs a wider window than the cached bound was made for (25 % headroom). A table that cannot have a hot tile (every
 // uniform table of the benchmarks) has bound 0 and never launches the two extra kernels.
-static int rtx_split_bound(rtx_prep* P, const rtx_lines* L, const rtx_grid* g, int n_layers, const double* T_h, const double* p_h,
-                           const double* mass_h, double dil_air, double dil_self, double omega_wing, double omega_wing_hw, int profile) {
-  if (L->n == 0 || g->n == 0) { P->split_bound = 0; return 0; }
-  double g0 = 0.0, t_max = 0.0;
+// Bound on Gamma0 over every line and layer of a call with the call-wide fractions dil_air / dil_self.
+static double gamma0_bound(const rtx_lines* L, int n_layers, const double* T_h, const double* p_h, double dil_air, double dil_self) {
+  double g0 = 0.0;
   for (int k = 0; k < n_layers; ++k) {
     const double tr = H_TREF / T_h[k];
     g0 = fmax(g0, p_h[k] * fmax(pow(tr, L->n_lo), pow(tr, L->n_hi)));
-    t_max = fmax(t_max, T_h[k]);
   }
-  g0 *= fabs(dil_air) * L->ga_max + fabs(dil_self) * L->gs_max;
+  return g0 * (fabs(dil_air) * L->ga_max + fabs(dil_self) * L->gs_max);
+}
+
+// The same with per-(diluent, species, layer) fractions: max over species and layers of p sum_d |f_d| gmax_d (Tref/T)^n_d, with
+// the |gamma| maximum and the n range of every column set used.
+static double gamma0_bound_mix(const rtx_lines* L, int n_layers, const double* T_h, const double* p_h, int n_dil, const int32_t* dil_h,
+                               const double* frac_h) {
+  double g0 = 0.0;
+  const int ns = L->n_species;
+  for (int k = 0; k < n_layers; ++k) {
+    const double tr = H_TREF / T_h[k];
+    for (int s = 0; s < ns; ++s) {
+      double sum = 0.0;
+      for (int d = 0; d < n_dil; ++d) {
+        const int c = dil_h[d];
+        const double gm = c == 0 ? L->ga_max : c == 1 ? L->gs_max : L->x_gmax[c - 2];
+        const double lo = c == 0 ? L->na_lo : c == 1 ? L->ns_lo : L->x_nlo[c - 2];
+        const double hi = c == 0 ? L->na_hi : c == 1 ? L->ns_hi : L->x_nhi[c - 2];
+        sum += fabs(frac_h[((size_t)d * ns + s) * n_layers + k]) * gm * fmax(pow(tr, lo), pow(tr, hi));
+      }
+      g0 = fmax(g0, p_h[k] * sum);
+    }
+  }
+  return g0;
+}
+
+// g0: bound on Gamma0 over the call (gamma0_bound / gamma0_bound_mix)
+static int rtx_split_bound(rtx_prep* P, const rtx_lines* L, const rtx_grid* g, int n_layers, const double* T_h, const double* mass_h,
+                           double g0, double omega_wing, double omega_wing_hw, int profile) {
+  if (L->n == 0 || g->n == 0) { P->split_bound = 0; return 0; }
+  double t_max = 0.0;
+  for (int k = 0; k < n_layers; ++k) t_max = fmax(t_max, T_h[k]);
   double m_min = 1e300;
   for (int s = 0; s < L->n_species; ++s)
     if (mass_h[s] > 0.0) m_min = fmin(m_min, mass_h[s]);
@@ -678,16 +822,50 @@ static int prep_begin(rtx_prep* P, const rtx_lines* L, int n_layers, const doubl
   a.dil_air = dil_air; a.dil_self = dil_self; a.omega_wing = omega_wing; a.omega_wing_hw = omega_wing_hw;
   a.thresh = intensity_threshold; a.scale = scale; a.profile = profile;
   a.X = nullptr; a.nx = 0; a.Twin = nullptr;
+  a.n_dil = 0; a.frac = nullptr;
+  for (int d = 0; d < RTX_MIX_MAX; ++d) a.dil_idx[d] = 0;
+  a.x_gamma = L->x_gamma; a.x_n = L->x_n; a.x_delta = L->x_delta; a.x_deltap = L->x_deltap; a.x_sd = L->x_sd;
   a.rec = P->rec; a.rec64 = P->rec64; a.ic = P->ic; a.win = P->win; a.maxhw = P->maxhw; a.smally = P->smally;
   return 0;
 }
 
-extern "C" int rtx_line_prep_profile(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid, int n_layers, const double* T_h,
-                             const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
-                             double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
-                             double intensity_threshold, double scale, int profile, void* stream) {
+// The diluent mix of rtx_line_prep_mix / _axis_mix: checks it and copies the fractions into the prep object's buffer (grow-only:
+// a larger set than before allocates, hence synchronises). After prep_begin.
+static int mix_begin(rtx_prep* P, const rtx_lines* L, int n_layers, int n_dil, const int32_t* dil_h, const double* frac_h,
+                     hipStream_t st, PrepArgs& a) {
+  if (n_dil < 0 || n_dil > RTX_MIX_MAX) RTX_FAIL("n_dil=%d outside [0,%d]", n_dil, RTX_MIX_MAX);
+  if (n_dil > 0 && (!dil_h || !frac_h)) RTX_FAIL("diluent indices / fractions are NULL");
+  for (int d = 0; d < n_dil; ++d)
+    if (dil_h[d] < 0 || dil_h[d] >= 2 + L->n_extra)
+      RTX_FAIL("diluent %d: column set %d outside [0,%d) (0 air, 1 self, 2.. rtx_lines_set_broadeners)", d, dil_h[d], 2 + L->n_extra);
+  const size_t nf = (size_t)n_dil * (size_t)L->n_species * (size_t)n_layers;
+  if (nf > P->frac_cap) {
+    if (P->frac) { RTX_HIP(hipFree(P->frac)); P->frac = nullptr; }
+    P->frac_cap = 0;
+    const size_t cap = (size_t)RTX_MIX_MAX * (size_t)L->n_species * (size_t)P->max_layers;
+    RTX_HIP(hipMalloc((void**)&P->frac, cap * sizeof(double)));
+    P->frac_cap = cap;
+  }
+  if (nf) RTX_HIP(hipMemcpyAsync(P->frac, frac_h, nf * sizeof(double), hipMemcpyHostToDevice, st));  // staged before returning
+  a.n_dil = n_dil;
+  for (int d = 0; d < n_dil; ++d) a.dil_idx[d] = dil_h[d];
+  a.frac = P->frac;
+  return 0;
+}
+
+// Grid prologue of rtx_line_prep_profile (mix == NULL: dil_air / dil_self) and rtx_line_prep_mix.
+struct MixIn {
+  int n_dil;
+  const int32_t* dil;
+  const double* frac;
+};
+static int line_prep_grid(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid, int n_layers, const double* T_h,
+                          const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
+                          double dil_air, double dil_self, const MixIn* mix, double omega_wing, double omega_wing_hw,
+                          double intensity_threshold, double scale, int profile, void* stream) {
   if (!P || !L) RTX_FAIL("prep/lines is NULL");
   if (profile < RTX_PROFILE_VOIGT || profile > RTX_PROFILE_SDVOIGT) RTX_FAIL("profile=%d", profile);
+  if (mix && profile == RTX_PROFILE_DOPPLER) RTX_FAIL("rtx_line_prep_mix: the Doppler profile takes no diluent");
   if (profile == RTX_PROFILE_SDVOIGT && !P->recsd) {
     const size_t nrec = (size_t)(P->n_lines > 0 ? P->n_lines : 1) * (size_t)P->max_layers;
     RTX_HIP(hipMalloc((void**)&P->recsd, nrec * sizeof(LineRecSD)));
@@ -699,26 +877,52 @@ extern "C" int rtx_line_prep_profile(rtx_prep* P, const rtx_lines* L, const rtx_
   if (prep_begin(P, L, n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, dil_air, dil_self, omega_wing, omega_wing_hw,
                  intensity_threshold, scale, profile, st, a, env_args))
     return 1;
-  if (rtx_split_bound(P, L, grid, n_layers, T_h, p_atm_h, mass_h, dil_air, dil_self, omega_wing, omega_wing_hw, profile)) return 1;
+  if (mix && mix_begin(P, L, n_layers, mix->n_dil, mix->dil, mix->frac, st, a)) return 1;
+  const double g0 = mix ? gamma0_bound_mix(L, n_layers, T_h, p_atm_h, mix->n_dil, mix->dil, mix->frac)
+                        : gamma0_bound(L, n_layers, T_h, p_atm_h, dil_air, dil_self);
+  if (rtx_split_bound(P, L, grid, n_layers, T_h, mass_h, g0, omega_wing, omega_wing_hw, profile)) return 1;
   P->n_layers = n_layers;
   P->scale = scale;
   P->axis = 0;
   if (L->n == 0) return 0;
   a.g = to_dev(grid);
   dim3 grd((unsigned)((L->n + 255) / 256), (unsigned)n_layers);
-  if (env_args) hipLaunchKernelGGL((line_prep_kernel<true, false>), grd, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((line_prep_kernel<false, false>), grd, dim3(256), 0, st, a);
+  if (mix) {
+    if (env_args) hipLaunchKernelGGL((line_prep_kernel<true, false, true>), grd, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((line_prep_kernel<false, false, true>), grd, dim3(256), 0, st, a);
+  } else {
+    if (env_args) hipLaunchKernelGGL((line_prep_kernel<true, false, false>), grd, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((line_prep_kernel<false, false, false>), grd, dim3(256), 0, st, a);
+  }
   RTX_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" int rtx_line_prep_axis(rtx_prep* P, const rtx_lines* L, const double* X_h, int64_t nx, int n_layers, const double* T_h,
-                                  const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
-                                  double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
-                                  double intensity_threshold, double scale, int profile, void* stream) {
+extern "C" int rtx_line_prep_profile(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid, int n_layers, const double* T_h,
+                             const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
+                             double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
+                             double intensity_threshold, double scale, int profile, void* stream) {
+  return line_prep_grid(P, L, grid, n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, dil_air, dil_self, nullptr, omega_wing,
+                        omega_wing_hw, intensity_threshold, scale, profile, stream);
+}
+
+extern "C" int rtx_line_prep_mix(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid, int n_layers, const double* T_h,
+                                 const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
+                                 int n_dil, const int32_t* dil_h, const double* frac_h, double omega_wing, double omega_wing_hw,
+                                 double intensity_threshold, double scale, int profile, void* stream) {
+  const MixIn mix = {n_dil, dil_h, frac_h};
+  return line_prep_grid(P, L, grid, n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, 0.0, 0.0, &mix, omega_wing, omega_wing_hw,
+                        intensity_threshold, scale, profile, stream);
+}
+
+static int line_prep_axis(rtx_prep* P, const rtx_lines* L, const double* X_h, int64_t nx, int n_layers, const double* T_h,
+                          const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
+                          double dil_air, double dil_self, const MixIn* mix, double omega_wing, double omega_wing_hw,
+                          double intensity_threshold, double scale, int profile, void* stream) {
   if (!P || !L) RTX_FAIL("prep/lines is NULL");
   if (profile < RTX_PROFILE_VOIGT || profile > RTX_PROFILE_DOPPLER)
     RTX_FAIL("rtx_line_prep_axis: profile=%d (Voigt, Lorentz or Doppler; the speed-dependent sum needs a uniform grid)", profile);
+  if (mix && profile == RTX_PROFILE_DOPPLER) RTX_FAIL("rtx_line_prep_axis_mix: the Doppler profile takes no diluent");
   const long long cap = P->max_tiles * (long long)rtx_voigt_tile_points();
   if (nx < 0 || nx > cap) RTX_FAIL("axis of %lld points outside the prep capacity [0, %lld]", (long long)nx, cap);
   if (nx > 0 && !X_h) RTX_FAIL("axis is NULL");
@@ -732,6 +936,7 @@ extern "C" int rtx_line_prep_axis(rtx_prep* P, const rtx_lines* L, const double*
   if (prep_begin(P, L, n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, dil_air, dil_self, omega_wing, omega_wing_hw,
                  intensity_threshold, scale, profile, st, a, env_args))
     return 1;
+  if (mix && mix_begin(P, L, n_layers, mix->n_dil, mix->dil, mix->frac, st, a)) return 1;
   if (nx > P->x_cap) {  // grow-only: allocates, hence synchronises
     if (P->X) { RTX_HIP(hipFree(P->X)); P->X = nullptr; }
     P->x_cap = 0;
@@ -746,10 +951,32 @@ extern "C" int rtx_line_prep_axis(rtx_prep* P, const rtx_lines* L, const double*
   if (L->n == 0 || nx == 0) return 0;
   a.X = P->X; a.nx = nx;
   dim3 grd((unsigned)((L->n + 255) / 256), (unsigned)n_layers);
-  if (env_args) hipLaunchKernelGGL(line_prep_axis_kernel<true>, grd, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(line_prep_axis_kernel<false>, grd, dim3(256), 0, st, a);
+  if (mix) {
+    if (env_args) hipLaunchKernelGGL((line_prep_axis_kernel<true, true>), grd, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((line_prep_axis_kernel<false, true>), grd, dim3(256), 0, st, a);
+  } else {
+    if (env_args) hipLaunchKernelGGL((line_prep_axis_kernel<true, false>), grd, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((line_prep_axis_kernel<false, false>), grd, dim3(256), 0, st, a);
+  }
   RTX_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int rtx_line_prep_axis(rtx_prep* P, const rtx_lines* L, const double* X_h, int64_t nx, int n_layers, const double* T_h,
+                                  const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
+                                  double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
+                                  double intensity_threshold, double scale, int profile, void* stream) {
+  return line_prep_axis(P, L, X_h, nx, n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, dil_air, dil_self, nullptr, omega_wing,
+                        omega_wing_hw, intensity_threshold, scale, profile, stream);
+}
+
+extern "C" int rtx_line_prep_axis_mix(rtx_prep* P, const rtx_lines* L, const double* X_h, int64_t nx, int n_layers, const double* T_h,
+                                      const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
+                                      int n_dil, const int32_t* dil_h, const double* frac_h, double omega_wing, double omega_wing_hw,
+                                      double intensity_threshold, double scale, int profile, void* stream) {
+  const MixIn mix = {n_dil, dil_h, frac_h};
+  return line_prep_axis(P, L, X_h, nx, n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, 0.0, 0.0, &mix, omega_wing, omega_wing_hw,
+                        intensity_threshold, scale, profile, stream);
 }
 
 extern "C" int rtx_line_prep(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid, int n_layers, const double* T_h,
@@ -788,7 +1015,9 @@ extern "C" int rtx_line_prep_window(rtx_prep* P, const rtx_lines* L, const rtx_g
     P->twin_cap = P->max_layers;
   }
   RTX_HIP(hipMemcpyAsync(P->twin, T_win_h, (size_t)n_layers * sizeof(double), hipMemcpyHostToDevice, st));  // staged before returning
-  if (rtx_split_bound(P, L, grid, n_layers, T_win_h, p_atm_h, mass_h, dil_air, dil_self, omega_wing, omega_wing_hw, profile)) return 1;
+  if (rtx_split_bound(P, L, grid, n_layers, T_win_h, mass_h, gamma0_bound(L, n_layers, T_win_h, p_atm_h, dil_air, dil_self), omega_wing,
+                      omega_wing_hw, profile))
+    return 1;
   P->n_layers = n_layers;
   P->scale = scale;
   P->axis = 0;
@@ -796,8 +1025,8 @@ extern "C" int rtx_line_prep_window(rtx_prep* P, const rtx_lines* L, const rtx_g
   a.g = to_dev(grid);
   a.Twin = P->twin;
   dim3 grd((unsigned)((L->n + 255) / 256), (unsigned)n_layers);
-  if (env_args) hipLaunchKernelGGL((line_prep_kernel<true, true>), grd, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((line_prep_kernel<false, true>), grd, dim3(256), 0, st, a);
+  if (env_args) hipLaunchKernelGGL((line_prep_kernel<true, true, false>), grd, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((line_prep_kernel<false, true, false>), grd, dim3(256), 0, st, a);
   RTX_LAUNCH_CHECK();
   return 0;
 }

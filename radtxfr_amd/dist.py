@@ -62,6 +62,14 @@ def subset_lines(columns, x_lo, x_hi, reach):
     return {k: np.asarray(v)[m] for k, v in columns.items()}
 
 
+def _no_broadening(fn, broadening):
+    """The sharded drivers broaden by air at the layer pressure only: their work estimates (engine.max_wing_cm,
+    engine.tile_costs) bound windows from gamma_air alone."""
+    if broadening is not None:
+        raise NotImplementedError("%s: broadening=%r is not supported by the sharded drivers; use broadening=None or "
+                                  "radiative_transfer.compute_TUD / compute_TUD_batch" % (fn, broadening))
+
+
 def _all_gather_flat(send, world, group=None):
     """ONE all_gather_into_tensor of equal flat blocks. RCCL ("nccl") gathers device buffers in place over xGMI; the
     gloo backend (CPU tests, and rehearsals of the N > 1 path with several ranks sharing one GPU) has no device
@@ -132,12 +140,13 @@ def tud_shard_plan(line_table, Xmin, Xmax, n_total, Ts, Ps, world, balance=True)
 
 
 def compute_TUD_sharded(Xmin, Xmax, DVOUT, line_table, Zs, Ts, Ps, PLs, MFs_VAL, MFs_ID, Altitudes=(500,), theta_r=0.0,
-                        N_angle=30, group=None, balance=True):
+                        N_angle=30, group=None, balance=True, broadening=None):
     """compute_TUD (radiative_transfer.py:274-392) with the spectral axis sharded over the ranks of
     `group`; every rank returns the full (X, tau, Lu, Ld) as float32 device tensors (X as NumPy fp64).
     One sensor altitude / slant path per call. Shards are tile-aligned (tud_shard_plan): the spectra are
-    bit-identical for every world size, including 1."""
+    bit-identical for every world size, including 1. broadening: None only (NotImplementedError otherwise)."""
     from . import engine
+    _no_broadening("compute_TUD_sharded", broadening)
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     n_total = int(np.ceil((Xmax - Xmin) / DVOUT))
     grid_full = engine.Grid(Xmin, Xmax, n_total)
@@ -175,8 +184,9 @@ class LocalShardedTud:
     One sensor altitude and slant path per object (the packed block carries three rows)."""
 
     def __init__(self, devices, Xmin, Xmax, DVOUT, line_table, Zs, Ts, Ps, Altitudes=(500,), theta_r=0.0, N_angle=30, balance=True,
-                 backend=-1):
+                 backend=-1, broadening=None):
         from . import comm, engine
+        _no_broadening("LocalShardedTud", broadening)
         self.devices = [int(d) for d in devices]
         world = len(self.devices)
         self.n_total = int(np.ceil((Xmax - Xmin) / DVOUT))
@@ -265,7 +275,7 @@ def hsi_cube_sharded(compute_bands, n_bands_total, group=None):
 
 
 def hsi_cube_from_atmosphere(Xmin, Xmax, DVOUT, line_table, Zs, Ts, Ps, PLs, MFs_VAL, MFs_ID, Xk, endmembers, kidx, frac, Tpix,
-                             resFactor=2, Altitudes=(500,), theta_r=0.0, N_angle=30, group=None):
+                             resFactor=2, Altitudes=(500,), theta_r=0.0, N_angle=30, group=None, broadening=None):
     """Config C5 end to end across the ranks of `group` (the reference's single-process model is
     LWIR_HSI_Generator.py:109-179 on a stored TUD): line table + atmosphere -> monochromatic tau, L-up, L-down on the
     MAKO span -> per-pixel at-sensor radiance -> triangle ILS -> cube [n_bands][n_pixels].
@@ -278,8 +288,10 @@ def hsi_cube_from_atmosphere(Xmin, Xmax, DVOUT, line_table, Zs, Ts, Ps, PLs, MFs
     candidate lines, same summation order).
 
     Xk [nk] knot axis, endmembers [nk][nEnd] float32, kidx [nPix][nMix] int32, frac [nPix][nMix] float32, Tpix [nPix]
-    float64: device tensors (sensor.hsi_cube). Returns (X_out [nB] NumPy, cube [nB][nPix] float32 device)."""
+    float64: device tensors (sensor.hsi_cube). Returns (X_out [nB] NumPy, cube [nB][nPix] float32 device).
+    broadening: None only (NotImplementedError otherwise)."""
     from . import _lib, engine, sensor
+    _no_broadening("hsi_cube_from_atmosphere", broadening)
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     n_total = int(np.ceil((Xmax - Xmin) / DVOUT))

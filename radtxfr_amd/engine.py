@@ -115,6 +115,13 @@ class Grid:
 
 _COLS = ("nu", "sw", "elower", "gamma_air", "gamma_self", "n_air", "delta_air")
 _OPT_COLS = ("n_self", "deltap_air", "delta_self")
+# the columns of one broadener <sp> (misc/hapi.py:11090-11128, SD :10860-10890): <field><sp>, sp in lower case
+BROADENER_FIELDS = ("gamma_", "n_", "delta_", "deltap_", "SD_")
+MAX_DILUENTS = 8  # per prologue (include/radtxfr_hip.h: RTX_MAX_DILUENTS)
+
+
+def _is_broadener_column(k):
+    return isinstance(k, str) and any(k.startswith(f) and k[len(f):] not in ("", "air", "self") for f in BROADENER_FIELDS)
 
 
 class LineTable:
@@ -166,11 +173,70 @@ class LineTable:
                 self.cols["deltap_self"] = dps
                 _lib.check(lib.rtx_lines_set_deltap_self(self._h, dps.ctypes.data_as(C.c_void_p)))
         self._plans = {}
+        # extra broadener column sets (rtx_lines_set_broadeners), uploaded on demand by broadener_sets(): the source columns
+        # (caller's row order), the uploaded sets {sp: {field: sorted column}} in set order and their fingerprints
+        self._order = order
+        self._xsrc = {k: v for k, v in columns.items() if _is_broadener_column(k)}
+        self._xcols, self._xsig = {}, {}
+
+    def broadeners_stale(self, sigs):
+        """The broadeners of {sp: fingerprint} whose columns this table does not hold, or holds with another fingerprint."""
+        return [sp for sp, sig in sigs.items() if sp not in self._xcols or self._xsig.get(sp) != sig]
+
+    def broadener_sets(self, names, columns=None, sigs=None):
+        """Column set of each diluent name for rtx_line_prep_mix: 0 air, 1 self, 2 + j the j-th uploaded extra set, None for
+        a broadener without any column (gamma = delta = 0: it contributes nothing). Names are matched in lower case, as the
+        reference builds gamma_<sp> (misc/hapi.py:11092). The columns of a broadener not yet on the device -- or whose
+        fingerprint in `sigs` differs from the uploaded one -- are taken from `columns` (caller's row order; default: the
+        columns given at creation) and the whole extra set is uploaded again; the sets stay on the device between calls."""
+        src = self._xsrc if columns is None else columns
+        names = [str(n).lower() for n in names]
+        changed = False
+        for sp in dict.fromkeys(names):
+            if sp in ("air", "self"):
+                continue
+            sig = None if sigs is None else sigs.get(sp)
+            if sp in self._xcols and (sigs is None or self._xsig.get(sp) == sig):
+                continue
+            cols = {f: src[f + sp] for f in BROADENER_FIELDS if f + sp in src}
+            if cols:
+                self._xcols[sp] = {f: np.ascontiguousarray(np.asarray(v, dtype=np.float64)[:self._order.size][self._order])
+                                   for f, v in cols.items()}
+                self._xsig[sp] = sig
+                changed = True
+            elif sp in self._xcols:
+                del self._xcols[sp]
+                self._xsig.pop(sp, None)
+                changed = True
+        if changed:
+            self._upload_broadeners()
+        order = list(self._xcols)
+        return [0 if sp == "air" else 1 if sp == "self" else (2 + order.index(sp) if sp in self._xcols else None) for sp in names]
+
+    def extra_has_sd(self, names):
+        """True where a speed-dependence column SD_<sp> of an uploaded extra broadener among `names` is non-zero."""
+        return any(np.any(self._xcols[sp]["SD_"] != 0.0) for sp in (str(n).lower() for n in names)
+                   if sp in self._xcols and "SD_" in self._xcols[sp])
+
+    def _upload_broadeners(self):
+        n_x = len(self._xcols)
+        if n_x > 64:
+            raise ValueError("more than 64 extra broadeners on one line table")
+        arr = []
+        for f in BROADENER_FIELDS:
+            a = (C.c_void_p * max(n_x, 1))()
+            for j, cols in enumerate(self._xcols.values()):
+                a[j] = cols[f].ctypes.data if f in cols else None
+            arr.append(a)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().rtx_lines_set_broadeners(self._h, n_x, *arr))
 
     def host_columns(self):
         """The uploaded columns as a host column dict (sorted by nu): what another device's copy is built from."""
         cols = dict(self.cols)
         cols.update(self._sd)
+        for sp, c in self._xcols.items():
+            cols.update({f + sp: v for f, v in c.items()})
         cols["molec_id"], cols["local_iso_id"] = self.molec_id, self.local_iso_id
         return cols
 
@@ -183,7 +249,11 @@ class LineTable:
         if dev not in peers:
             with torch.cuda.device(dev):
                 peers[dev] = LineTable(self.host_columns())
-        return peers[dev]
+        peer = peers[dev]
+        if list(peer._xcols) != list(self._xcols) or peer._xsig != self._xsig:  # extra broadeners uploaded here since
+            peer._xcols, peer._xsig = dict(self._xcols), dict(self._xsig)
+            peer._upload_broadeners()
+        return peer
 
     def plan(self, n_layers, n_points):
         """A prep object big enough for (n_layers, n_points); cached, grown on demand."""
@@ -288,6 +358,26 @@ def _prologue_inputs(lines, T, p_atm, weight, partitionFunction, qratio, mass):
     return nL, (_h(T), _h(p_atm), _h(qratio), _h(np.broadcast_to(weight, (len(lines.species), nL))), _h(mass))
 
 
+def diluent_mix(lines, diluent, nL):
+    """rtx_line_prep_mix's diluent arguments for `diluent` = {name: fraction}, a fraction a scalar or [nS][nL]: (n_dil,
+    (set indices int32, pointer), (fractions [n_dil][nS][nL], pointer)), in the dict's order. Names are case-insensitive and
+    each key is its own diluent, so "AIR" and "air" are both summed (the reference's loop over Diluent, misc/hapi.py:11090).
+    A broadener without any column on the table is left out: its contribution is 0, as the reference's fallbacks make it."""
+    names = list(diluent)
+    sets = lines.broadener_sets(names)
+    nS = len(lines.species)
+    idx, fr = [], []
+    for k, c in zip(names, sets):
+        if c is not None:
+            idx.append(c)
+            fr.append(np.broadcast_to(np.asarray(diluent[k], dtype=np.float64), (nS, nL)))
+    if len(idx) > MAX_DILUENTS:
+        raise ValueError("diluent: %d broadeners with columns, at most %d per call" % (len(idx), MAX_DILUENTS))
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    frac = np.ascontiguousarray(np.stack(fr) if fr else np.zeros((0, nS, nL)), dtype=np.float64)
+    return len(idx), (idx, idx.ctypes.data_as(C.c_void_p)), (frac, frac.ctypes.data_as(C.c_void_p))
+
+
 def _check_outputs(nL, ld, out_f32, out_f64):
     for o, dt in ((out_f32, torch.float32), (out_f64, torch.float64)):
         if o is not None:
@@ -296,18 +386,27 @@ def _check_outputs(nL, ld, out_f32, out_f64):
 
 def voigt_sum(lines, grid, T, p_atm, weight, out_f32=None, out_f64=None, dil_air=1.0, dil_self=0.0, omega_wing=0.0,
               omega_wing_hw=50.0, intensity_threshold=0.0, scale=1.0, partitionFunction=None, qratio=None, mass=None,
-              profile=0):
+              profile=0, diluent=None):
     """Prologue + line-sum for n_layers homogeneous states on `grid` (rtx_line_prep_profile + rtx_voigt_sum);
     profile 0 Voigt, 1 Lorentz, 2 Doppler, 3 speed-dependent Voigt (include/radtxfr_hip.h; 3 needs SD columns in `lines`
     and runs rtx_sdvoigt_sum).
-    weight[nS][nL] multiplies S(T) per species and layer. Outputs are [nL][grid.n] device tensors."""
+    weight[nS][nL] multiplies S(T) per species and layer. Outputs are [nL][grid.n] device tensors.
+    diluent: {broadener: fraction} replacing dil_air / dil_self (rtx_line_prep_mix; profiles 0, 1, 3): a fraction is a
+    scalar or [nS][nL] (per species and layer); names other than air / self use the table's gamma_<sp>, n_<sp>, delta_<sp>,
+    deltap_<sp>, SD_<sp> columns (LineTable.broadener_sets)."""
     lib = _lib.load()
     nL, env = _prologue_inputs(lines, T, p_atm, weight, partitionFunction, qratio, mass)
     plan = lines.plan(nL, grid.n)
     st = _stream_ptr()
-    _lib.check(lib.rtx_line_prep_profile(plan._h, lines._h, grid.byref(), nL, *(e[1] for e in env), float(dil_air),
-                                         float(dil_self), float(omega_wing), float(omega_wing_hw),
-                                         float(intensity_threshold), float(scale), int(profile), st))
+    if diluent is None:
+        _lib.check(lib.rtx_line_prep_profile(plan._h, lines._h, grid.byref(), nL, *(e[1] for e in env), float(dil_air),
+                                             float(dil_self), float(omega_wing), float(omega_wing_hw),
+                                             float(intensity_threshold), float(scale), int(profile), st))
+    else:
+        n_dil, idx, frac = diluent_mix(lines, diluent, nL)
+        _lib.check(lib.rtx_line_prep_mix(plan._h, lines._h, grid.byref(), nL, *(e[1] for e in env), n_dil, idx[1], frac[1],
+                                         float(omega_wing), float(omega_wing_hw), float(intensity_threshold), float(scale),
+                                         int(profile), st))
     ld = grid.n
     _check_outputs(nL, ld, out_f32, out_f64)
     if int(profile) == 3:  # speed-dependent Voigt: its own fp64 line-sum
@@ -319,11 +418,11 @@ def voigt_sum(lines, grid, T, p_atm, weight, out_f32=None, out_f64=None, dil_air
 
 def voigt_sum_axis(lines, X, T, p_atm, weight, out_f32=None, out_f64=None, dil_air=1.0, dil_self=0.0, omega_wing=0.0,
                    omega_wing_hw=50.0, intensity_threshold=0.0, scale=1.0, partitionFunction=None, qratio=None, mass=None,
-                   profile=0):
+                   profile=0, diluent=None):
     """voigt_sum on an explicit axis X (host, finite, non-decreasing; need not be uniform) instead of a Grid:
     rtx_line_prep_axis + rtx_voigt_sum_axis. Windows are bisect_right on X itself, as the reference's (misc/hapi.py:
     11133-11134). profile 0 Voigt, 1 Lorentz, 2 Doppler (the speed-dependent sum needs a uniform grid).
-    Outputs are [nL][X.size] device tensors."""
+    diluent: as for voigt_sum (rtx_line_prep_axis_mix; profiles 0, 1). Outputs are [nL][X.size] device tensors."""
     lib = _lib.load()
     X = np.ascontiguousarray(np.asarray(X, dtype=np.float64).ravel())
     if not np.all(np.isfinite(X)):
@@ -337,9 +436,15 @@ def voigt_sum_axis(lines, X, T, p_atm, weight, out_f32=None, out_f64=None, dil_a
     nx = X.size
     plan = lines.plan(nL, max(nx, 1))
     st = _stream_ptr()
-    _lib.check(lib.rtx_line_prep_axis(plan._h, lines._h, X.ctypes.data_as(C.c_void_p), nx, nL, *(e[1] for e in env),
-                                      float(dil_air), float(dil_self), float(omega_wing), float(omega_wing_hw),
-                                      float(intensity_threshold), float(scale), int(profile), st))
+    if diluent is None:
+        _lib.check(lib.rtx_line_prep_axis(plan._h, lines._h, X.ctypes.data_as(C.c_void_p), nx, nL, *(e[1] for e in env),
+                                          float(dil_air), float(dil_self), float(omega_wing), float(omega_wing_hw),
+                                          float(intensity_threshold), float(scale), int(profile), st))
+    else:
+        n_dil, idx, frac = diluent_mix(lines, diluent, nL)
+        _lib.check(lib.rtx_line_prep_axis_mix(plan._h, lines._h, X.ctypes.data_as(C.c_void_p), nx, nL, *(e[1] for e in env),
+                                              n_dil, idx[1], frac[1], float(omega_wing), float(omega_wing_hw),
+                                              float(intensity_threshold), float(scale), int(profile), st))
     _check_outputs(nL, nx, out_f32, out_f64)
     _lib.check(lib.rtx_voigt_sum_axis(plan._h, nL, _ptr(out_f32), _ptr(out_f64), nx, st))
     return out_f32, out_f64
@@ -373,13 +478,61 @@ def layer_weights_od(species, T, P_pa, PL_km, MF_VAL, MF_ID):
     return w, p_atm
 
 
-def optical_depths(lines, grid, T, P_pa, PL_km, MF_VAL, MF_ID, out=None):
-    """OD[nL][grid.n] float32 on the device (layer-major, wavenumber-contiguous)."""
+# HITRAN molecule ids of the gases of StdAtmos (radiative_transfer.options["MFs_ID"]) by formula: the foreign broadeners
+# broadening= may name (their columns are gamma_<formula>, n_<formula>, ...)
+HITRAN_FORMULA_IDS = {"h2o": 1, "co2": 2, "o3": 3, "n2o": 4, "co": 5, "ch4": 6, "o2": 7, "n2": 22}
+
+
+def broadening_gases(broadening):
+    """The foreign gases of a broadening= option: None for None (air at the layer pressure, the default path), () for
+    "self", the formulas after "self" for a tuple such as ("self", "h2o"). Raises ValueError for anything else."""
+    if broadening is None:
+        return None
+    b = (broadening,) if isinstance(broadening, str) else tuple(broadening)
+    b = tuple(str(g).lower() for g in b)
+    foreign = tuple(g for g in b if g != "self")
+    if b.count("self") != 1 or len(set(foreign)) != len(foreign) or any(g not in HITRAN_FORMULA_IDS for g in foreign):
+        raise ValueError("broadening=%r: None, \"self\", or a tuple of \"self\" and distinct foreign gases among %s"
+                         % (broadening, sorted(HITRAN_FORMULA_IDS)))
+    return foreign
+
+
+def broadening_fractions(species, MF_VAL, MF_ID, foreign=()):
+    """The per-layer diluent mix of broadening= (LBLRTM broadens each absorber by its own partial pressure): {"air": [nS][nL],
+    "self": [nS][nL], gas: [nS][nL] for each foreign gas}. Species s of molecule m has self fraction x_m (MF_VAL * 1e-6 of
+    m's first column in MF_ID, 0 for a molecule not in MF_ID), foreign fraction x_g for every listed gas g != m (0 for a line
+    of g itself: it takes self), and air the remainder 1 - (x_m + sum_g x_g)."""
+    MF_VAL = np.asarray(MF_VAL, dtype=np.float64)
+    ids = [int(v) for v in np.asarray(MF_ID).ravel()]
+    nL = MF_VAL.shape[0]
+    MF_VAL = MF_VAL.reshape(nL, -1)
+
+    def x_of(m):
+        return MF_VAL[:, ids.index(m)] * 1e-6 if m in ids else np.zeros(nL)
+
+    x_self = np.array([x_of(int(m)) for m, _ in species]).reshape(len(species), nL)
+    out = {"air": None, "self": x_self}
+    total = x_self.copy()
+    for g in foreign:
+        gid = HITRAN_FORMULA_IDS[g]
+        f = np.array([np.zeros(nL) if int(m) == gid else x_of(gid) for m, _ in species]).reshape(len(species), nL)
+        out[g] = f
+        total = total + f
+    out["air"] = 1.0 - total
+    return out
+
+
+def optical_depths(lines, grid, T, P_pa, PL_km, MF_VAL, MF_ID, out=None, broadening=None):
+    """OD[nL][grid.n] float32 on the device (layer-major, wavenumber-contiguous).
+    broadening: None (every line broadened by air at the layer pressure), "self" or ("self", gas, ...): each species
+    broadened by the per-layer mix of broadening_fractions (rtx_line_prep_mix)."""
     T = np.atleast_1d(np.asarray(T, dtype=np.float64))
     w, p_atm = layer_weights_od(lines.species, T, np.atleast_1d(P_pa), np.atleast_1d(PL_km), MF_VAL, MF_ID)
+    foreign = broadening_gases(broadening)
+    dil = None if foreign is None else broadening_fractions(lines.species, np.asarray(MF_VAL).reshape(T.size, -1), MF_ID, foreign)
     if out is None:
         out = torch.empty((T.size, grid.n), dtype=torch.float32, device=device())
-    voigt_sum(lines, grid, T, p_atm, w, out_f32=out)
+    voigt_sum(lines, grid, T, p_atm, w, out_f32=out, diluent=dil)
     return out
 
 
@@ -450,12 +603,15 @@ class TudRunner:
     altitude masks, slant factors, device buffers, the ctypes argument objects -- is set up once; run() does the
     per-atmosphere host factors (TIPS ratios, column weights) and ONE call into the library (rtx_compute_tud: prologue +
     line-sum + TUD enqueued back to back). Outputs are float32 device tensors owned by the runner (or `out`), overwritten
-    by the next run(): tau, Lu [nAlt*nMu][n], Ld [n], OD [nL][n]."""
+    by the next run(): tau, Lu [nAlt*nMu][n], Ld [n], OD [nL][n].
+    broadening: None (the fused rtx_compute_tud), "self" or ("self", gas, ...): each species broadened by its per-layer
+    mix (broadening_fractions), run as rtx_line_prep_mix + rtx_voigt_sum + rtx_tud -- the same line-sum and TUD kernels."""
 
     def __init__(self, lines, grid, Z, n_layers=None, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=False, out=None,
-                 OD=None, plan=None):
+                 OD=None, plan=None, broadening=None):
         self.lib = _lib.load()
         self.lines, self.grid = lines, grid
+        self.foreign = broadening_gases(broadening)
         Z = np.atleast_1d(np.asarray(Z, dtype=np.float64))
         self.nL = int(Z.size if n_layers is None else n_layers)
         Z_s = np.array([Altitudes], dtype=np.float64).ravel()
@@ -507,6 +663,22 @@ class TudRunner:
         env[2 * nL + 2 * nS * nL:] = mass
         base = env.ctypes.data
         vp = C.c_void_p
+        if self.foreign is not None:
+            dil = broadening_fractions(lines.species, np.asarray(MF_VAL, dtype=np.float64).reshape(nL, -1), MF_ID, self.foreign)
+            n_dil, idx, frac = diluent_mix(lines, dil, nL)
+            st = _stream_ptr()
+            with trace_range("rtx_line_prep_mix + rtx_voigt_sum + rtx_tud"):
+                _lib.check(self.lib.rtx_line_prep_mix(
+                    self.plan._h, lines._h, self.grid.byref(), nL, vp(base), vp(base + 8 * nL), vp(base + 16 * nL),
+                    vp(base + 8 * (2 * nL + nS * nL)), vp(base + 8 * (2 * nL + 2 * nS * nL)), n_dil, idx[1], frac[1], 0.0, 50.0, 0.0,
+                    1.0, 0, st))
+                _lib.check(self.lib.rtx_voigt_sum(self.plan._h, self.grid.byref(), nL, vp(self.OD.data_ptr()), None,
+                                                  self.OD.stride(0), st))
+                _lib.check(self.lib.rtx_tud(
+                    vp(self.OD.data_ptr()), self.OD.stride(0), self.grid.byref(), nL, vp(base), self.shape[0],
+                    self.mask.ctypes.data_as(vp), self.shape[1], self.mu.ctypes.data_as(vp), self.n_down, self.N_angle, self.returnOD,
+                    self._ptrs[0], self._ptrs[1], self._ptrs[2], None, self._ld_out, st))
+            return self.tau, self.Lu, self.Ld
         with trace_range("rtx_compute_tud"):
             _lib.check(self.lib.rtx_compute_tud(
                 self.plan._h, lines._h, self.grid.byref(), nL, vp(base), vp(base + 8 * nL), vp(base + 16 * nL),
@@ -523,7 +695,8 @@ class TudPipelines:
     pipeline the four kernels of a step run back to back; across pipelines the fp64 prologue and the HBM-bound TUD pass of
     one atmosphere share the chip with the VALU-bound line-sum of the next (C3 on MI355X, bench.py: 1.97 / 1.90 / 1.90 /
     1.91 ms per atmosphere with 1 / 2 / 3 / 4 pipelines; profiles/r3_time_pipeline.txt). Results are the single-runner results bit for bit.
-    outs: optional list of P (tau, Lu, Ld) output triples (e.g. rows of packed blocks that are all-gathered)."""
+    outs: optional list of P (tau, Lu, Ld) output triples (e.g. rows of packed blocks that are all-gathered).
+    kw: TudRunner's keywords (Altitudes, theta_r, N_angle, returnOD, broadening)."""
 
     def __init__(self, lines, grid, Z, n_layers=None, n_pipes=2, outs=None, **kw):
         self.streams = [torch.cuda.Stream() for _ in range(int(n_pipes))]

@@ -77,10 +77,56 @@ def _column_signature(v, nrow):
     return (a.size, d)
 
 
-def _device_table(names):
+def _broadener_signatures(names, species):
+    """{sp: fingerprint of the broadener columns gamma_<sp>, n_<sp>, ... of every table in `names`} (empty tuple: none)."""
+    sigs = {}
+    for sp in species:
+        sig = []
+        for n in names:
+            d, nrow = LOCAL_TABLE_CACHE[n]["data"], LOCAL_TABLE_CACHE[n]["header"]["number_of_rows"]
+            sig.extend((n, f + sp, _column_signature(d[f + sp], nrow)) for f in engine.BROADENER_FIELDS if f + sp in d)
+        sigs[sp] = tuple(sig)
+    return sigs
+
+
+def _broadener_columns(names, species):
+    """The broadener columns of `species` concatenated over the tables, each table's absent ones by the reference's
+    fallbacks (gamma / delta / deltap / SD 0, n = that table's n_air): {<field><sp>: array}."""
+    cols = {}
+    for sp in species:
+        for f in engine.BROADENER_FIELDS:
+            if not any(f + sp in LOCAL_TABLE_CACHE[n]["data"] for n in names):
+                continue
+            parts = []
+            for n in names:
+                d, nrow = LOCAL_TABLE_CACHE[n]["data"], LOCAL_TABLE_CACHE[n]["header"]["number_of_rows"]
+                if f + sp in d:
+                    parts.append(np.asarray(d[f + sp], dtype=np.float64)[:nrow])
+                elif f == "n_":
+                    parts.append(np.asarray(d["n_air"], dtype=np.float64)[:nrow])
+                else:
+                    parts.append(np.zeros(nrow))
+            cols[f + sp] = np.concatenate(parts)
+    return cols
+
+
+def _device_table(names, diluents=()):
     """Device LineTable for one or several cached tables (concatenated). The reference re-reads LOCAL_TABLE_CACHE on
     every call (misc/hapi.py:11044-11125); here the device copy is reused only while a content fingerprint of EVERY
-    uploaded column is unchanged, so in-place edits of a cached table are seen (tests/test_gpu_parity.py)."""
+    uploaded column is unchanged, so in-place edits of a cached table are seen (tests/test_gpu_parity.py).
+    diluents: broadener names (lower case) other than air / self whose columns the call reads: they are fingerprinted too
+    and (re-)uploaded to the table when new or edited (LineTable.broadener_sets)."""
+    tbl = _device_table_base(names)
+    extra = [sp for sp in dict.fromkeys(diluents) if sp not in ("air", "self")]
+    if extra:
+        sigs = _broadener_signatures(names, extra)
+        stale = tbl.broadeners_stale(sigs)
+        if stale:
+            tbl.broadener_sets(stale, columns=_broadener_columns(names, stale), sigs=sigs)
+    return tbl
+
+
+def _device_table_base(names):
     key = tuple(names)
     sig = []
     for n in names:
@@ -198,10 +244,15 @@ def _absorption_coefficient(profile, Components, SourceTables, partitionFunction
             Diluent = {"self": 1.0}
         else:
             raise Exception("Unknown GammaL value: %s" % GammaL)
+    # the reference sums over the Diluent keys in their order, each lower-cased (misc/hapi.py:11090-11092; "AIR" and "air"
+    # are two terms). Air / self alone, each once, keep the call-wide dil_air / dil_self prologue; anything else takes the
+    # per-diluent one (rtx_line_prep_mix), which reads the table's gamma_<sp>, n_<sp>, ... columns of every other key
+    keys = [k.lower() for k in Diluent]
+    mix = None
+    if set(keys) - {"air", "self"} or len(set(keys)) != len(keys):
+        mix = {k: float(v) for k, v in Diluent.items()}
+        tbl = _device_table(SourceTables, keys)
     dil = {k.lower(): float(v) for k, v in Diluent.items()}
-    extra = set(dil) - {"air", "self"}
-    if extra:
-        raise NotImplementedError("diluents %s are not supported (air, self only)" % sorted(extra))
     # a uniform grid (what Grid.from_axis recognises) takes the grid line-sum; any other sorted grid -- non-uniform,
     # repeated points, fewer than 2 points -- the explicit-axis one (rtx_line_prep_axis + rtx_voigt_sum_axis)
     grid = None
@@ -227,13 +278,13 @@ def _absorption_coefficient(profile, Components, SourceTables, partitionFunction
         out = torch.empty((1, grid.n), dtype=torch.float64, device=engine.device())
         engine.voigt_sum(tbl, grid, [T], [p], w, out_f64=out, dil_air=dil.get("air", 0.0), dil_self=dil.get("self", 0.0),
                          omega_wing=OmegaWing, omega_wing_hw=OmegaWingHW, intensity_threshold=IntensityThreshold,
-                         scale=scale, partitionFunction=partitionFunction, profile=profile)
+                         scale=scale, partitionFunction=partitionFunction, profile=profile, diluent=mix)
         Xsect = out[0].cpu().numpy()
     else:
         out = torch.empty((1, Omegas.size), dtype=torch.float64, device=engine.device())
         engine.voigt_sum_axis(tbl, Omegas, [T], [p], w, out_f64=out, dil_air=dil.get("air", 0.0), dil_self=dil.get("self", 0.0),
                               omega_wing=OmegaWing, omega_wing_hw=OmegaWingHW, intensity_threshold=IntensityThreshold,
-                              scale=scale, partitionFunction=partitionFunction, profile=profile)
+                              scale=scale, partitionFunction=partitionFunction, profile=profile, diluent=mix)
         Xsect = out[0].cpu().numpy()
     if File:
         with open(File, "w") as f:
@@ -254,7 +305,9 @@ def absorptionCoefficient_Voigt(Components=None, SourceTables=None, partitionFun
     (rtx_line_prep + rtx_voigt_sum on a uniform grid; rtx_line_prep_axis + rtx_voigt_sum_axis on any other sorted
     OmegaGrid -- non-uniform, repeated points, a single point); line strengths are carried in fp32 with a power-of-two
     scale, so Xsect agrees with the reference to ~1e-6 relative, not bit for bit.
-    Not supported (raises): EnvDependences hooks, diluents other than air/self.
+    Diluent: any keys, as the reference (misc/hapi.py:11090-11128): a key other than air / self reads the table's
+    gamma_<key>, n_<key>, delta_<key>, deltap_<key> columns (absent ones: 0, n_air). Fractions are not validated.
+    Not supported (raises): EnvDependences hooks.
     """
     return _absorption_coefficient(0, Components, SourceTables, partitionFunction, Environment, OmegaRange, OmegaStep, OmegaWing,
                                    IntensityThreshold, OmegaWingHW, GammaL, HITRAN_units, LineShift, File, Format, OmegaGrid,
@@ -305,15 +358,16 @@ def absorptionCoefficient_SDVoigt(Components=None, SourceTables=None, partitionF
 
     Tables without speed-dependence columns (the 160-character HITRAN .par format has none) give Gamma2 = 0, for which
     pcqsdhc takes its PART1 branch (:9908-9915), i.e. the Voigt profile: those go through the fp32 Voigt line-sum.
-    Tables with non-zero SD_air / SD_self (:10884-10890) go through rtx_sdvoigt_sum: pcqsdhc PART2-4 in fp64, far wings at
+    Tables with non-zero SD_air / SD_self (or SD_<key> of another Diluent key) (:10884-10890) go through rtx_sdvoigt_sum: pcqsdhc PART2-4 in fp64, far wings at
     Chebyshev nodes (the path of the reference's cross-section generator, misc/RT_gen_AbsXS_files.py:90); those need a uniform
     grid (a non-uniform OmegaGrid raises NotImplementedError)."""
     sd = False
+    sd_cols = ["SD_air", "SD_self"] + ["SD_" + k.lower() for k in (Diluent or {}) if k.lower() not in ("air", "self")]
     for name in listOfTuples(SourceTables):
         if name is None or name not in LOCAL_TABLE_CACHE:
             continue
         data = LOCAL_TABLE_CACHE[name]["data"]
-        for col in ("SD_air", "SD_self"):
+        for col in sd_cols:
             if col in data and np.any(np.asarray(data[col], dtype=np.float64) != 0.0):
                 sd = True
     return _absorption_coefficient(3 if sd else 0, Components, SourceTables, partitionFunction, Environment, OmegaRange, OmegaStep,

@@ -145,7 +145,7 @@ def BT2L(X_in, T_in, wavelength=False, bad_value=np.nan, spectral_dim=0):
                           "Assumes X given in µm and L given in µF")
 
 
-def _resolve_table(spec):
+def _resolve_table(spec, diluents=()):
     if spec is None:
         raise Exception("compute_OD: set opts['line_table'] to a table in radtxfr_amd.hapi.LOCAL_TABLE_CACHE "
                         "(the reference's LBLRTM binary and AER TAPE3 are git-LFS stubs; there is no built-in line file)")
@@ -154,12 +154,12 @@ def _resolve_table(spec):
     if isinstance(spec, str):
         if spec not in _hapi.LOCAL_TABLE_CACHE:
             raise Exception("%s: no such table. Check tableList() for more info." % spec)
-        return _hapi._device_table([spec])
+        return _hapi._device_table([spec], diluents)
     if isinstance(spec, dict):
         key = "__dict_%d" % id(spec)
         if key not in _hapi.LOCAL_TABLE_CACHE or _hapi.LOCAL_TABLE_CACHE[key].get("_src") is not spec:
             _hapi.LOCAL_TABLE_CACHE[key] = {"header": {"number_of_rows": len(spec["nu"])}, "data": spec, "_src": spec}
-        return _hapi._device_table([key])
+        return _hapi._device_table([key], diluents)
     raise TypeError("opts['line_table'] must be a table name, a column dict or an engine.LineTable")
 
 
@@ -232,7 +232,7 @@ def _tud_shapes(tau2, Lu2, nZ, nMu):
 _SIDE_STREAMS = {}
 
 
-def _compute_tud_chunked(tbl, grid, Z, T, P, PL, MF, ID, Z_s, theta, nA, returnOD, n_chunks):
+def _compute_tud_chunked(tbl, grid, Z, T, P, PL, MF, ID, Z_s, theta, nA, returnOD, n_chunks, broadening=None):
     """compute_TUD's device work in n_chunks tile-aligned wavenumber chunks, each chunk's widening and device-to-host copy
     (side stream) under the next chunk's kernels: a single call is PCIe-bound (132 MB of float64 at C3 size: 2.7 ms against
     1.9 ms of kernels), and chunks cut on line-sum tile boundaries give the unchunked bits. Returns (tau_h, Lu_h, Ld_h,
@@ -266,7 +266,8 @@ def _compute_tud_chunked(tbl, grid, Z, T, P, PL, MF, ID, Z_s, theta, nA, returnO
             continue
         sl = slice(off, off + ln)
         run = engine.TudRunner(tbl, grid.shard(grid.offset + off, ln), Z, n_layers=nL, Altitudes=Z_s, theta_r=theta, N_angle=nA,
-                               returnOD=returnOD, out=(tau[:, sl], Lu[:, sl], Ld[sl]), OD=OD[:, :ln], plan=plan)
+                               returnOD=returnOD, out=(tau[:, sl], Lu[:, sl], Ld[sl]), OD=OD[:, :ln], plan=plan,
+                               broadening=broadening)
         run.run(T, P, PL, MF, ID)
         ready = torch.cuda.Event()
         ready.record()
@@ -291,17 +292,25 @@ def compute_TUD(Xmin, Xmax, opts=options, **kwargs):
     """Monochromatic transmittance, upwelling and downwelling radiance, signature of :274-392.
 
     kwargs honoured (:304-314): DVOUT, Zs, Ts, Ps, PLs, MFs_VAL, MFs_ID, theta_r, N_angle, Altitudes,
-    save, returnOD, plus line_table. Returns (X, tau, Lu, Ld); tau/Lu are (nX,), (nX,nMu), (nX,nZ) or
+    save, returnOD, plus line_table and broadening. Returns (X, tau, Lu, Ld); tau/Lu are (nX,), (nX,nMu), (nX,nZ) or
     (nX,nZ,nMu) by the reference's squeeze rules (:357-365); Ld is (nX,).
     Quirks 3-6 of SURVEY.md section 9 are reproduced (downwelling uses the layer count of the last
     sensor altitude; tau uses the Z<=zs mask, L-up the first count layers; returnOD; theta=0 weight 0).
     X is a cached read-only array (see _cached_axis; copy_axis=True gives the reference's fresh writable one); the
     spectra are fresh float64 arrays -- views of page-locked memory while less than _hostio.PINNED_RESULT_CAP is lent
     out to live results, ordinary pageable arrays beyond that.
+    broadening (keyword only, not in `options`): None, the default, broadens every line by air at the layer pressure.
+    "self" broadens each species by the per-layer mix {air: 1 - x, self: x}, x its molecule's mixing ratio in that layer
+    (MFs_VAL * 1e-6; 0 for a molecule not in MFs_ID) -- LBLRTM, behind the reference's compute_OD, broadens each absorber by
+    its own partial pressure. ("self", "h2o", ...) adds foreign broadeners by HITRAN formula, each at its layer mixing
+    ratio, read from the table's gamma_<formula>, n_<formula>, ... columns; a line of that gas takes self, air the remainder
+    (engine.broadening_fractions).
     """
     trace = [time.perf_counter()] if _TRACE else None
     o = dict(opts)
     o.update(kwargs)
+    broadening = o.get("broadening")
+    foreign = engine.broadening_gases(broadening)
     Z = np.asarray(o["Zs"], dtype=np.float64)
     T = np.asarray(o["Ts"], dtype=np.float64)
     P = np.asarray(o["Ps"], dtype=np.float64)
@@ -316,7 +325,7 @@ def compute_TUD(Xmin, Xmax, opts=options, **kwargs):
     grid = engine.Grid(Xmin, Xmax, X_.size)
     if trace:
         trace.append(time.perf_counter())
-    tbl = _resolve_table(o.get("line_table"))
+    tbl = _resolve_table(o.get("line_table"), foreign or ())
     if trace:
         trace.append(time.perf_counter())
     if o.get("copy_axis"):
@@ -326,7 +335,7 @@ def compute_TUD(Xmin, Xmax, opts=options, **kwargs):
         chunks = 4 if grid.n >= 2000000 else 2 if grid.n >= 500000 else 1
     if chunks > 1 and mu_s.size <= engine.TUD_MAX_MU and not o["save"]:
         got = _compute_tud_chunked(tbl, grid, Z, T, P, PL, MF, ID, Z_s, np.asarray(o["theta_r"], dtype=np.float64), nA,
-                                   bool(o["returnOD"]), int(chunks))
+                                   bool(o["returnOD"]), int(chunks), broadening=broadening)
         if got is not None:
             tau_h, Lu_h, Ld_h, (nZ, nMu) = got
             if trace:
@@ -339,12 +348,12 @@ def compute_TUD(Xmin, Xmax, opts=options, **kwargs):
     if mu_s.size <= engine.TUD_MAX_MU and not o["save"]:
         # the common case: one call into the library (rtx_compute_tud)
         run = engine.TudRunner(tbl, grid, Z, n_layers=T.size, Altitudes=Z_s, theta_r=np.asarray(o["theta_r"], dtype=np.float64),
-                               N_angle=nA, returnOD=bool(o["returnOD"]))
+                               N_angle=nA, returnOD=bool(o["returnOD"]), broadening=broadening)
         tau, Lu, Ld = run.run(T, P, PL, MF, ID)
         nZ, nMu = run.shape
         OD = run.OD
     else:
-        OD = engine.optical_depths(tbl, grid, T, P, PL, MF, ID)  # [nL][nX] float32 on the device
+        OD = engine.optical_depths(tbl, grid, T, P, PL, MF, ID, broadening=broadening)  # [nL][nX] float32 on the device
         res = engine.tud(OD, grid, T, Z, Altitudes=Z_s, theta_r=np.asarray(o["theta_r"], dtype=np.float64), N_angle=nA,
                          returnOD=bool(o["returnOD"]), per_angle=bool(o["save"]))
         tau, Lu, Ld, (nZ, nMu) = res[:4]
@@ -375,7 +384,7 @@ class _TudPipeline:
     outputs: the copy of one is in flight while the other is being computed), each on a compute stream of its own, a
     side stream for the device-to-host copies, a pinned staging ring."""
 
-    def __init__(self, dev, tbl, grid, Z, nL, Z_s, theta_r, N_angle, returnOD):
+    def __init__(self, dev, tbl, grid, Z, nL, Z_s, theta_r, N_angle, returnOD, broadening=None):
         self.dev = int(dev)
         with torch.cuda.device(self.dev):
             self.lines = tbl.on_device(self.dev)
@@ -389,7 +398,7 @@ class _TudPipeline:
             for st, pl in zip(self.computes, self.plans):
                 with torch.cuda.stream(st):
                     self.runs.append(engine.TudRunner(self.lines, grid, Z, n_layers=nL, Altitudes=Z_s, theta_r=theta_r, N_angle=N_angle,
-                                                      returnOD=returnOD, plan=pl))
+                                                      returnOD=returnOD, plan=pl, broadening=broadening))
         self.busy = [None, None]  # copy-done event of each runner's outputs
         self.staging = _hostio.Staging(depth=2)
         self.k = 0
@@ -443,8 +452,8 @@ def compute_TUD_batch(Xmin, Xmax, atmospheres, opts=options, reduce=None, device
     runs on a side stream while the next atmosphere's kernels run on the compute stream.
 
     atmospheres: sequence of dicts with any of Ts, Ps, PLs, MFs_VAL (the per-atmosphere kwargs of the reference's caller);
-    everything else (Zs, MFs_ID, DVOUT, Altitudes, theta_r, N_angle, returnOD, line_table) comes from opts / kwargs and is
-    common to the batch. reduce = dict(dX=..., N=4, window="hanning") applies reduceResolution (:1327-1350) to tau, Lu and
+    everything else (Zs, MFs_ID, DVOUT, Altitudes, theta_r, N_angle, returnOD, line_table, broadening) comes from opts /
+    kwargs and is common to the batch (broadening as for compute_TUD: the mix follows each atmosphere's MFs_VAL). reduce = dict(dX=..., N=4, window="hanning") applies reduceResolution (:1327-1350) to tau, Lu and
     Ld on the device, as the reference's caller does right after each compute_TUD (Generate_LWIR_TUD.py:124-126): only the
     reduced spectra cross PCIe then.
     devices: GPU indices to spread the atmospheres over (the reference's Pool axis without a launcher): atmosphere k goes
@@ -469,6 +478,8 @@ def compute_TUD_batch(Xmin, Xmax, atmospheres, opts=options, reduce=None, device
     mu_s = f(1.0 / np.cos(o["theta_r"]))
     if mu_s.size > engine.TUD_MAX_MU:
         raise ValueError("compute_TUD_batch takes at most %d slant paths" % engine.TUD_MAX_MU)
+    broadening = o.get("broadening")
+    foreign = engine.broadening_gases(broadening)
     engine.require_gpu()
     devs = [torch.cuda.current_device()] if devices is None else [int(d) for d in devices]
     if not devs or any(d < 0 or d >= torch.cuda.device_count() for d in devs):
@@ -476,10 +487,10 @@ def compute_TUD_batch(Xmin, Xmax, atmospheres, opts=options, reduce=None, device
     X_ = _cached_axis(Xmin, Xmax, o["DVOUT"])
     grid = engine.Grid(Xmin, Xmax, X_.size)
     with torch.cuda.device(devs[0]):
-        tbl = _resolve_table(o.get("line_table"))
+        tbl = _resolve_table(o.get("line_table"), foreign or ())
     nL = np.asarray(o["Ts"]).size
     theta = np.asarray(o["theta_r"], dtype=np.float64)
-    pipes = [_TudPipeline(d, tbl, grid, Z, nL, Z_s, theta, int(o["N_angle"]), bool(o["returnOD"])) for d in devs]
+    pipes = [_TudPipeline(d, tbl, grid, Z, nL, Z_s, theta, int(o["N_angle"]), bool(o["returnOD"]), broadening=broadening) for d in devs]
     nZ, nMu = pipes[0].runs[0].shape
     pending = []  # (pipeline, ticket, X of the result) in input order
     results = []
@@ -513,6 +524,9 @@ JACOBIAN_HOST_LIMIT = 4 << 30  # bytes of full-resolution float64 results comput
 
 def _jacobian_args(Xmin, Xmax, o, wrt, layers, reduce, fd_step_T):
     """compute_TUD_jacobian's argument checks, all on the host (no device is touched): (wrt, layers, nX)."""
+    if o.get("broadening") is not None:
+        raise NotImplementedError("compute_TUD_jacobian: broadening=%r is not supported (with self-broadening dOD/dMF is no "
+                                  "longer OD per ppmv); use broadening=None" % (o.get("broadening"),))
     if np.asarray(o["theta_r"]).size != 1:
         raise NotImplementedError("compute_TUD_jacobian: one slant path (a single theta_r) per call")
     if o["save"]:
