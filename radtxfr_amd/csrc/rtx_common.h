@@ -63,11 +63,15 @@ static inline int xcd_slots(int n_tiles) {  // block slots per XCD: grid.x = 8 *
 }
 
 // ---- Planck radiance in fp32 from an fp64 exponent (shared by the TUD and at-sensor kernels) ----------
+#define RT_C1 1.19104295315e-16  // radiative_transfer.py:71
+#define RT_C2 1.43877736830e-02  // radiative_transfer.py:72
+#define LOG2E 1.4426950408889634
+#define LN2 0.6931471805599453
 // B(nu,T) in uW/(cm^2 sr cm^-1):  c1*(100 nu)^3*1e4 / (exp(c2*100 nu/T) - 1)
 __device__ __forceinline__ float planck_f32(double c1x3, double x, double c2l2e_over_T) {
   const double t = x * c2l2e_over_T;  // log2 of the exponential, fp64
   if (t < 1.5) {                      // small arguments (far-IR / microwave): expm1 in fp64
-    return (float)(c1x3 / expm1(t * 0.6931471805599453));
+    return (float)(c1x3 / expm1(t * LN2));
   }
   const double n = rint(t);
   const float f = (float)(t - n);     // |f| <= 1/2, exact difference

@@ -17,9 +17,6 @@
 
 #include "rtx_common.h"
 
-#define RT_C1 1.19104295315e-16
-#define RT_C2 1.43877736830e-02
-
 // ---------------------------------------------------------------------------------------------------
 struct RadArgs {
   const double* X;
@@ -90,7 +87,7 @@ __global__ __launch_bounds__(256) void apparent_radiance_row_kernel(RadArgs a) {
   for (long long ix = (long long)blockIdx.x * 4 + wave; ix < a.nX; ix += (long long)gridDim.x * 4) {
     const double x = a.X[ix];
     const double x100 = x * 100.0;
-    const float B = planck_f32(RT_C1 * (x100 * x100 * x100) * 1e4, x, 100.0 * RT_C2 * 1.4426950408889634 / a.Ts[0]);
+    const float B = planck_f32(RT_C1 * (x100 * x100 * x100) * 1e4, x, 100.0 * RT_C2 * LOG2E / a.Ts[0]);
     const float tau = a.tau[ix], La = a.La[ix], Ld = a.Ld[ix];
     const float4* em = reinterpret_cast<const float4*>(a.emis + ix * a.nE);
     float4* L = reinterpret_cast<float4*>(a.L + ix * a.nE);
@@ -1089,7 +1086,7 @@ extern "C" int rtx_band_moments(int kind, const rtx_grid* grid, const float* tau
   a.centre = centre; a.sigma = sigma; a.node_span = 1.0f;
   for (int q = 0; q < CUBE_QMAX; ++q)
     for (int d = 0; d < CUBE_QMAX; ++d) a.coef[q][d] = 0.f;
-  a.c2l2e_over_T = 100.0 * RT_C2 * 1.4426950408889634 / Ts;
+  a.c2l2e_over_T = 100.0 * RT_C2 * LOG2E / Ts;
   a.N = N_out; a.C = C_out; a.MLd = nullptr; a.MB = M_out; a.jrange = reinterpret_cast<int2*>(jrange_out);
   const dim3 g(nB), blk(64 * BBM_WAVES);
   if (kind == 0) hipLaunchKernelGGL((band_basis_moments_kernel<0, 1, true>), g, blk, 0, (hipStream_t)stream, a);
@@ -1233,7 +1230,7 @@ __global__ __launch_bounds__(256) void pixel_cube_kernel(CubeArgs a) {
   const int n_pl = (int)min((long long)CUBE_PB, a.nPix - p0);  // pixels of this workgroup (>= 1)
   const int nMix = a.nMix;
   {
-    const double kT = 100.0 * RT_C2 * 1.4426950408889634 / a.Tpix[p0 + min((int)threadIdx.x, n_pl - 1)];
+    const double kT = 100.0 * RT_C2 * LOG2E / a.Tpix[p0 + min((int)threadIdx.x, n_pl - 1)];
     s_kT[threadIdx.x] = kT;
     const float hi = (float)kT;
     s_kTf[threadIdx.x] = make_float2(hi, (float)(kT - (double)hi));

@@ -26,11 +26,7 @@
 #include <mutex>
 #include <vector>
 
-#include "rtx_common.h"
-
-#define RT_C1 1.19104295315e-16  // radiative_transfer.py:71
-#define RT_C2 1.43877736830e-02  // radiative_transfer.py:72
-#define LOG2E 1.4426950408889634
+#include "rtx_tud_common.h"
 
 // ---------------------------------------------------------------------------------------------------
 struct PlanckArgs {
@@ -180,34 +176,70 @@ struct TudArgs {
   float mu[TUD_MAX_MU];
   unsigned int mask[TUD_MAX_ALT][TUD_MAX_LAYERS / 32];
   int count[TUD_MAX_ALT];
-  const double* gtab;                  // angle-summed transmission function G (tud_g_kernel): [g_nint][8] doubles
-  int g_nint;
+  const double* gtab;                  // angle-summed transmission function G (tud_g_kernel): [TUDG_NINT][8] doubles
   double g0;                           // G(0) = sum of the quadrature weights
-  int planck_nodes;                    // 1: B_k across a wave's 64 wavenumbers by a parabola through 3 of them (host-checked: error < 1e-10)
 };
 
-// 1 - exp(-OD*sec) = 1 - 2^y (y = OD*c <= 0), accurate to ~1e-7 RELATIVE also when it is tiny.
-// A layer's emissivity (1 - t) is what weights its Planck radiance in L <- t L + (1 - t) B; forming it as 1 - fl(t)
-// from v_exp_f32 loses everything once t is within a few ulp of 1 (an optically thin layer: the LWIR window),
-// and the error of the accumulated radiance then reaches 1e-5..1e-4 of a thin path's radiance. So:
-//   |y| <  1/16 : 1 - 2^y = -y*ln2*(1 + z/2 + z^2/6 + z^3/24), z = y ln2            (truncation 2.9e-8)
-//   |y| >= 1/16 : 1 - v_exp_f32(y)                                                    (relative error <= 1.4e-6)
-// (round 1: degree 5 below 1/8, 7e-9 / 7e-7; one operation more per stream and layer: TUD_THIN_DEG5 / TUD_THIN_Y)
-#ifndef TUD_THIN_Y
-#define TUD_THIN_Y 0.0625f
-#endif
-#ifndef TUD_THIN_DEG5
-#define TUD_THIN_DEG5 0  /* 1: degree-5 emissivity polynomial (use with TUD_THIN_Y 0.125f) */
-#endif
 #define TUD_OPAQUE_Y 26.0f
-__device__ __forceinline__ float em_thin(float y) {  // valid for -1/8 < y <= 0
-#if TUD_THIN_DEG5
-  const float q = fmaf(fmaf(fmaf(fmaf(1.3333558146e-3f, y, 9.6181291076e-3f), y, 5.5504108665e-2f), y, 2.4022650696e-1f), y,
-                       6.9314718056e-1f);  // ln2^5/120, ln2^4/24, ln2^3/6, ln2^2/2, ln2
-#else
-  const float q = fmaf(fmaf(fmaf(9.6181291076e-3f, y, 5.5504108665e-2f), y, 2.4022650696e-1f), y, 6.9314718056e-1f);
-#endif
-  return -y * q;
+
+// ---- building blocks of the TUD kernels -----------------------------------------------------------
+// What every lane sets up first. Per-layer constants without a trip to memory inside the layer loop: lane l keeps
+// 100 c2 log2(e)/T of layers l and l + 64 and the loop fetches layer k's with two v_readlane (the kernel-argument array
+// indexed by the loop counter was a scalar load and its wait -- a few hundred exposed cycles -- in every iteration).
+__device__ __forceinline__ double readlane_f64(double v, int lane) {  // lane is wave-uniform
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+  return __hiloint2double(hi, lo);
+}
+struct TudLane {
+  bool live;
+  long long i;  // dead lanes shadow the last point: ballots stay wave-wide
+  const float* __restrict__ od_col;
+  double x, c1x3;
+  double ct_a, ct_b;  // set by layer_consts(): a kernel calls it AFTER issuing its first OD loads, so that these loads are
+                      // the younger ones and waiting for them (the Planck set-up does at once) leaves no OD load outstanding
+  __device__ __forceinline__ explicit TudLane(const TudArgs& a) {
+    const long long i_raw = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    live = i_raw < a.g.n;
+    i = live ? i_raw : a.g.n - 1;
+    od_col = a.OD + i;
+    x = grid_x(a.g, a.g.offset + i);
+    const double x100 = x * 100.0;
+    c1x3 = RT_C1 * (x100 * x100 * x100) * 1e4;
+  }
+  __device__ __forceinline__ void layer_consts(const TudArgs& a) {
+    const int lane_id = threadIdx.x & 63, nL = a.n_layers;
+    ct_a = a.c2l2e_over_T[lane_id < nL ? lane_id : 0];
+    ct_b = a.c2l2e_over_T[lane_id + 64 < nL ? lane_id + 64 : 0];
+  }
+  __device__ __forceinline__ double c2l2e_of(int k) const { return readlane_f64(k < 64 ? ct_a : ct_b, k & 63); }  // k wave-uniform
+  __device__ __forceinline__ float planck(int k) const { return planck_f32(c1x3, x, c2l2e_of(k)); }
+};
+
+// An altitude's layer mask in four scalar registers.
+struct LayerMask {
+  unsigned w0, w1, w2, w3;
+  __device__ __forceinline__ bool bit(int k) const {
+    const unsigned w = k < 32 ? w0 : k < 64 ? w1 : k < 96 ? w2 : w3;
+    return (w >> (k & 31)) & 1u;
+  }
+};
+__device__ __forceinline__ LayerMask layer_mask(const TudArgs& a, int ia) {
+  return LayerMask{a.mask[ia][0], a.mask[ia][1], a.mask[ia][2], a.mask[ia][3]};
+}
+
+// One layer of the upwelling recurrence t*Lu + (1-t)*B, y = OD*c: thin lanes through the emissivity, thick lanes through
+// the transmittance (the other way round each form cancels: L + e (B - L) with e ~ 1, or t (L - B) + B with t ~ 1).
+__device__ __forceinline__ float up_step(float Lu, float B, float y) {
+  return (y > -TUD_THIN_Y) ? fmaf(em_thin(y), B - Lu, Lu) : fmaf(__builtin_amdgcn_exp2f(y), Lu - B, B);
+}
+
+// How opaque is opaque: what is dropped is at most (transmittance) x (the largest Planck radiance of the column), what
+// is kept is at least of the order of the smallest one, so the transmittance has to be 2^-26 of the RATIO of the two
+// -- at 6000 cm^-1 between 190 K and 310 K that ratio is 4e7, at 700 cm^-1 it is 8.
+__device__ __forceinline__ float opaque_y(const TudArgs& a, const TudLane& l) {
+  const float b_hot = planck_f32(l.c1x3, l.x, a.c2l2e_over_Tmax), b_cold = planck_f32(l.c1x3, l.x, a.c2l2e_over_Tmin);
+  const float r = __builtin_amdgcn_logf(b_hot / b_cold);  // log2
+  return (b_cold > 0.f && r == r && r < 1e30f) ? TUD_OPAQUE_Y + 1.0f + fmaxf(r, 0.f) : 3.0e38f;
 }
 
 // Layer loop outside (run-time trip count: any n_layers, no per-n_layers register blow-up), the slant streams
@@ -217,7 +249,7 @@ __device__ __forceinline__ float em_thin(float y) {  // valid for -1/8 < y <= 0
 //   opaque: every stream has t <= 2^-26:  L <- B            (1 VALU per stream; most of an opaque band)
 //   thick : t = 2^y,             L <- t (L - B) + B          (the fp32 form of :372, 4 VALU per stream)
 //   thin  : e = em_thin(y),      L <- L + e (B - L)
-//   mixed : per lane, the thin form where |y| < 1/8 and the thick form elsewhere
+//   mixed : per lane, the thin form where |y| < TUD_THIN_Y and the thick form elsewhere
 // OD is read once per block of streams, coalesced along the wavenumber axis.
 #ifndef TUD_STAGE
 #define TUD_STAGE 4  // layers fetched ahead per chunk (tud_g_kernel, C3 column / thinned: 4 -> 0.212 / 0.296 ms, 8 -> 0.219 / 0.305, 16 -> 0.246 / 0.331)
@@ -239,39 +271,24 @@ template <int NA, bool COL>
 __global__ __launch_bounds__(256) void tud_kernel(TudArgs a) {
   extern __shared__ float s_od[];  // COL: [n_layers][256]; else [TUD_STAGE][256]
   float (*s_stage)[256] = reinterpret_cast<float (*)[256]>(s_od);
-  const long long i_raw = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool live = i_raw < a.g.n;
-  const long long i = live ? i_raw : a.g.n - 1;  // dead lanes shadow the last point: ballots stay wave-wide
+  TudLane ln(a);
+  const bool live = ln.live;
+  const long long i = ln.i;
   const int nL = a.n_layers;
-  const float* __restrict__ od_col = a.OD + i;
+  const float* __restrict__ od_col = ln.od_col;
   if (COL) {
     float* dst = &s_stage[0][threadIdx.x & ~63u];  // wave-uniform base; the DMA adds lane * 4
     for (int k = 0; k < nL; ++k)
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(od_col + (size_t)k * a.ld),
                                        (__attribute__((address_space(3))) void*)(dst + k * 256), 4, 0, 0);
   }
-  const double x = grid_x(a.g, a.g.offset + i);
-  const double x100 = x * 100.0;
-  const double c1x3 = RT_C1 * (x100 * x100 * x100) * 1e4;
+  const double x = ln.x, c1x3 = ln.c1x3;
   if (COL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the column has landed (this wave's own slots)
+  ln.layer_consts(a);
   auto od_at = [&](int k) -> float { return COL ? s_stage[k][threadIdx.x] : od_col[(size_t)k * a.ld]; };
-  // Per-layer constants without a trip to memory inside the layer loop: lane l keeps 100 c2 log2(e)/T of layers l and
-  // l + 64 and the loop fetches layer k's with two v_readlane (the kernel-argument array indexed by the loop counter was
-  // a scalar load and its wait -- a few hundred exposed cycles -- in every iteration); likewise the first altitude's
-  // layer mask is held in four scalar registers.
-  const int lane_id = threadIdx.x & 63;
-  const double ct_a = a.c2l2e_over_T[lane_id < nL ? lane_id : 0];
-  const double ct_b = COL ? 0.0 : a.c2l2e_over_T[lane_id + 64 < nL ? lane_id + 64 : 0];
-  auto c2l2e_of = [&](int k) -> double {  // k is wave-uniform
-    const double v = (COL || k < 64) ? ct_a : ct_b;
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), k & 63), hi = __builtin_amdgcn_readlane(__double2hiint(v), k & 63);
-    return __hiloint2double(hi, lo);
-  };
-  const unsigned mk0 = a.mask[0][0], mk1 = a.mask[0][1], mk2 = a.mask[0][2], mk3 = a.mask[0][3];
-  auto mask0_bit = [&](int k) -> bool {
-    const unsigned w = k < 32 ? mk0 : k < 64 ? mk1 : k < 96 ? mk2 : mk3;
-    return (w >> (k & 31)) & 1u;
-  };
+  // COL: at most TUD_COL_LAYERS (< 64) layers, so one register of per-layer constants and no choice between two
+  auto planck_of = [&](int k) -> float { return COL ? planck_f32(c1x3, x, readlane_f64(ln.ct_a, k & 63)) : ln.planck(k); };
+  const LayerMask mask0 = layer_mask(a, 0);
 
   // ---- every further (altitude, slant factor) pair: transmittance + upwelling bottom-up (:346-356) ----------
   for (int p = 1; p < a.n_alt * a.n_mu; ++p) {
@@ -283,11 +300,7 @@ __global__ __launch_bounds__(256) void tud_kernel(TudArgs a) {
       const float od = od_at(k);
       if ((a.mask[ia][k >> 5] >> (k & 31)) & 1u) s += od;
       if (k < cnt) {
-        const float B = planck_f32(c1x3, x, c2l2e_of(k));
-        const float y = od * c;
-        // t*Lu + (1-t)*B: thin lanes through the emissivity, thick lanes through the transmittance (the other way
-        // round each form cancels: L + e (B - L) with e ~ 1, or t (L - B) + B with t ~ 1)
-        Lu = (y > -TUD_THIN_Y) ? fmaf(em_thin(y), B - Lu, Lu) : fmaf(__builtin_amdgcn_exp2f(y), Lu - B, B);
+        Lu = up_step(Lu, planck_of(k), od * c);
       }
     }
     if (live) {
@@ -305,15 +318,7 @@ __global__ __launch_bounds__(256) void tud_kernel(TudArgs a) {
   const float c0 = a.mu_c[0];
   float s0 = 0.f, S0 = 0.f, Lu0 = 0.f;
   float acc = 0.f;
-  // How opaque is opaque: what is dropped is at most (transmittance) x (the largest Planck radiance of the column), what
-  // is kept is at least of the order of the smallest one, so the transmittance has to be 2^-26 of the RATIO of the two
-  // -- at 6000 cm^-1 between 190 K and 310 K that ratio is 4e7, at 700 cm^-1 it is 8.
-  float y_opq;
-  {
-    const float b_hot = planck_f32(c1x3, x, a.c2l2e_over_Tmax), b_cold = planck_f32(c1x3, x, a.c2l2e_over_Tmin);
-    const float r = __builtin_amdgcn_logf(b_hot / b_cold);  // log2
-    y_opq = (b_cold > 0.f && r == r && r < 1e30f) ? TUD_OPAQUE_Y + 1.0f + fmaxf(r, 0.f) : 3.0e38f;
-  }
+  const float y_opq = opaque_y(a, ln);
   // Opaque columns. Downwelling at the surface is blind to everything above the lowest slab whose NADIR transmittance
   // is <= 2^-y_opq (what enters it from above reaches the surface attenuated to < 1.5e-8 of the column's own emission, in every stream): find
   // the top of that slab for the whole wave and start the recurrences there. Likewise L-up at the sensor stops
@@ -392,23 +397,21 @@ __global__ __launch_bounds__(256) void tud_kernel(TudArgs a) {
       if (k > k_lo) od_next = COL ? s_stage[k - 1][threadIdx.x] : s_stage[kc - k + 1][threadIdx.x];
       const bool streams = k <= k_start;                    // wave-uniform (k_start < nd)
       const bool up = !(TUD_ABLATE & 4) && a0 == 0 && up_live && k < cnt0;       // wave-uniform
-      if (a0 == 0 && mask0_bit(k)) s0 += od;
+      if (a0 == 0 && mask0.bit(k)) s0 += od;
       if (!streams && !up) continue;
 #if TUD_ABLATE & 2
       const float B = (float)c1x3 * (1e-3f + od);
 #else
-      const float B = planck_f32(c1x3, x, c2l2e_of(k));
+      const float B = planck_of(k);
 #endif
       if (up) {
-        const float y = od * c0;
-        const float e = (y > -TUD_THIN_Y) ? em_thin(y) : 1.0f - __builtin_amdgcn_exp2f(y);
-        Lu0 = fmaf(e * B, __builtin_amdgcn_exp2f(S0 * c0), Lu0);
+        Lu0 = fmaf(emissivity(od * c0) * B, __builtin_amdgcn_exp2f(S0 * c0), Lu0);
         S0 += od;
         if (__ballot(S0 * c0 <= -y_opq) == ~0ull) up_live = false;  // c0 < 0
       }
       if (!streams) continue;
-      const bool thick = od * c_min >= TUD_THIN_Y;  // even the nadir stream has |y| >= 1/8
-      const bool thin = od * c_max < TUD_THIN_Y;    // even the most oblique stream has |y| < 1/8
+      const bool thick = od * c_min >= TUD_THIN_Y;  // even the nadir stream has |y| >= TUD_THIN_Y
+      const bool thin = od * c_max < TUD_THIN_Y;    // even the most oblique stream has |y| < TUD_THIN_Y
       // opaque: even the most transparent (nadir) stream has t <= 2^-26: t (L - B) is below half an ulp of B for
       // |L - B| <= 2 B ... and at most 1.5e-8 |L - B| otherwise -- the layer simply replaces L by B
       const bool opaque = od * c_min >= y_opq;
@@ -440,24 +443,12 @@ __global__ __launch_bounds__(256) void tud_kernel(TudArgs a) {
         // 1 - 2^(OD c) as a polynomial in the stream's c with per-lane coefficients A_k = -q_k OD^k (5 multiplies per
         // layer, shared by all streams): 5 VALU per stream instead of forming y and running em_thin (6)
         const float o2 = od * od;
-        const float A1 = -6.9314718056e-1f * od, A2 = -2.4022650696e-1f * o2, A3 = -5.5504108665e-2f * (o2 * od);
-        const float A4 = -9.6181291076e-3f * (o2 * o2);
-#if TUD_THIN_DEG5
-        const float A5 = -1.3333558146e-3f * (o2 * o2 * od);
-#endif
+        const float A1 = -EM_Q1 * od, A2 = -EM_Q2 * o2, A3 = -EM_Q3 * (o2 * od), A4 = -EM_Q4 * (o2 * o2);
 #pragma unroll
         for (int q0 = 0; q0 < NA; q0 += TUD_ILP) {  // step-major, as above
           float e[TUD_ILP];
-#if TUD_THIN_DEG5
-#pragma unroll
-          for (int i = 0; i < TUD_ILP; ++i) if (q0 + i < NA) e[i] = fmaf(cth[q0 + i], A5, A4);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int i = 0; i < TUD_ILP; ++i) if (q0 + i < NA) e[i] = fmaf(cth[q0 + i], e[i], A3);
-#else
 #pragma unroll
           for (int i = 0; i < TUD_ILP; ++i) if (q0 + i < NA) e[i] = fmaf(cth[q0 + i], A4, A3);
-#endif
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int i = 0; i < TUD_ILP; ++i) if (q0 + i < NA) e[i] = fmaf(cth[q0 + i], e[i], A2);
@@ -479,11 +470,7 @@ __global__ __launch_bounds__(256) void tud_kernel(TudArgs a) {
         // (|c| ascends with the stream index): all lanes thick for the block's most transparent stream -> transmittance
         // form; all lanes thin for its most oblique one -> emissivity polynomial; else both forms and a per-lane select.
         const float o2 = od * od;
-        const float A1 = -6.9314718056e-1f * od, A2 = -2.4022650696e-1f * o2, A3 = -5.5504108665e-2f * (o2 * od);
-        const float A4 = -9.6181291076e-3f * (o2 * o2);
-#if TUD_THIN_DEG5
-        const float A5 = -1.3333558146e-3f * (o2 * o2 * od);
-#endif
+        const float A1 = -EM_Q1 * od, A2 = -EM_Q2 * o2, A3 = -EM_Q3 * (o2 * od), A4 = -EM_Q4 * (o2 * o2);
 #pragma unroll
         for (int q0 = 0; q0 < NA; q0 += 4) {
           // |c| ascends with the stream index (pads repeat the last stream): the block's extremes are its end streams,
@@ -506,16 +493,8 @@ __global__ __launch_bounds__(256) void tud_kernel(TudArgs a) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) if (i < nq) L[q0 + i] = fmaf(w[i], L[q0 + i] - B, B);
           } else if (blk_thin) {
-#if TUD_THIN_DEG5
-#pragma unroll
-            for (int i = 0; i < 4; ++i) if (i < nq) w[i] = fmaf(cth[q0 + i], A5, A4);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) if (i < nq) w[i] = fmaf(cth[q0 + i], w[i], A3);
-#else
 #pragma unroll
             for (int i = 0; i < 4; ++i) if (i < nq) w[i] = fmaf(cth[q0 + i], A4, A3);
-#endif
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int i = 0; i < 4; ++i) if (i < nq) w[i] = fmaf(cth[q0 + i], w[i], A2);
@@ -606,7 +585,7 @@ __device__ __forceinline__ double tudg_eval(const double* __restrict__ s_g, doub
 
 // Planck radiances of a layer across the 64 consecutive wavenumbers of a wave: B(nu, T_k) is so smooth in nu that a parabola
 // through its values at lanes 0, 32 and 63 reproduces it to < 1e-10 on grids this fine (the host checks
-// (4/nu_min + c2/T_min) x 63 steps <= 7e-3 and clears TudArgs.planck_nodes otherwise). The three values of EVERY layer are
+// (4/nu_min + c2/T_min) x 63 steps <= 7e-3 and launches the PN = false instantiations otherwise). The three values of EVERY layer are
 // computed in one go with lane = layer (lane k already holds layer k's 100 c2 log2e / T): 3 Planck evaluations per wave
 // instead of one per layer, and the layer loop rebuilds B_k with two FMAs on coefficients fetched by v_readlane.
 struct PlanckNodes {
@@ -614,8 +593,10 @@ struct PlanckNodes {
   float c0b, c1b, c2b;  // ... of layer k + 64
   float t;
 };
-__device__ __forceinline__ PlanckNodes planck_nodes_setup(const TudArgs& a, double ct_a, double ct_b, int nL) {
+__device__ __forceinline__ PlanckNodes planck_nodes_setup(const TudArgs& a, const TudLane& l) {
   PlanckNodes P;
+  const double ct_a = l.ct_a, ct_b = l.ct_b;
+  const int nL = a.n_layers;
   const long long i0w = (long long)blockIdx.x * blockDim.x + (threadIdx.x & ~63u);  // raw index of lane 0 (may lie past the shard: grid_x extrapolates)
   const float t1 = 32.0f / 63.0f;
   float b[3], bb[3];
@@ -639,52 +620,68 @@ __device__ __forceinline__ PlanckNodes planck_nodes_setup(const TudArgs& a, doub
   P.t = (float)(threadIdx.x & 63) * (1.0f / 63.0f);
   return P;
 }
-__device__ __forceinline__ float planck_nodes_eval(const PlanckNodes& P, int k) {  // k wave-uniform
-  float c0, c1, c2;
-  if (k < 64) {
-    c0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(P.c0), k));
-    c1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(P.c1), k));
-    c2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(P.c2), k));
-  } else {
-    c0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(P.c0b), k - 64));
-    c1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(P.c1b), k - 64));
-    c2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(P.c2b), k - 64));
-  }
+// B of the layer whose coefficients sit in lane `lane` of the first (hi = false) or second register set; both wave-uniform.
+// The unrolled chunks pass a static lane offset and one choice of set per chunk.
+__device__ __forceinline__ float planck_nodes_eval(const PlanckNodes& P, bool hi, int lane) {
+  const float c0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hi ? P.c0b : P.c0), lane));
+  const float c1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hi ? P.c1b : P.c1), lane));
+  const float c2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hi ? P.c2b : P.c2), lane));
   return fmaf(fmaf(c2, P.t, c1), P.t, c0);
 }
+__device__ __forceinline__ float planck_nodes_eval(const PlanckNodes& P, int k) {  // k wave-uniform: a branch, not three selects
+  if (k < 64) return planck_nodes_eval(P, false, k);
+  return planck_nodes_eval(P, true, k - 64);
+}
+
+__device__ __forceinline__ void tudg_load(double* s_g, const TudArgs& a) {  // the G table into LDS; __syncthreads() before use
+  for (int t = threadIdx.x; t < TUDG_NINT * 4; t += 256) reinterpret_cast<double2*>(s_g)[t] = reinterpret_cast<const double2*>(a.gtab)[t];
+}
+
+// The downwelling sum_k B_k [G(S_k) - G(S_k+1)], bottom-up. Downwelling at the surface is blind to everything above the
+// depth where G has dropped to 2^-27 of G(0) times the column's Planck dynamic range at this wavenumber (what is dropped is
+// at most that transmission times the largest Planck radiance, what is kept is of the order of the smallest): once every
+// lane is there the wave stops evaluating G.
+struct TudDown {
+  double S, g_prev, g_floor;
+  float acc;
+  bool live;  // wave-uniform
+  __device__ __forceinline__ TudDown(const double* s_g, const TudArgs& a, const TudLane& l) {
+    S = 0.0;
+    g_prev = tudg_eval(s_g, 0.0);  // (not a.g0: the table's own value, so that an empty column gives exactly 0)
+    acc = 0.f;
+    g_floor = a.g0 * (double)__builtin_amdgcn_exp2f(-fminf(opaque_y(a, l), 120.0f));
+    live = a.n_down > 0;
+  }
+  __device__ __forceinline__ void step(const double* s_g, float od, float B) {
+    S += (double)od;
+    const double g = tudg_eval(s_g, S);
+    acc = fmaf(B, (float)(g_prev - g), acc);
+    g_prev = g;
+    if (__ballot(g > g_floor) == 0ull) live = false;
+  }
+  __device__ __forceinline__ float result(const TudArgs& a) const {  // a NaN optical depth poisons the sum, as in the reference
+    return (S != S) ? __builtin_nanf("") : acc * a.inv_wsum;
+  }
+};
 
 template <bool PN>
 __global__ __launch_bounds__(256) void tud_g_kernel(TudArgs a) {
   __shared__ double s_g[TUDG_NINT * 8];
   __shared__ float s_stage[TUD_STAGE][256];  // each thread's own slots
-  for (int t = threadIdx.x; t < TUDG_NINT * 4; t += 256) reinterpret_cast<double2*>(s_g)[t] = reinterpret_cast<const double2*>(a.gtab)[t];
-  const long long i_raw = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool live = i_raw < a.g.n;
-  const long long i = live ? i_raw : a.g.n - 1;  // dead lanes shadow the last point: ballots stay wave-wide
+  tudg_load(s_g, a);
+  TudLane ln(a);
   const int nL = a.n_layers;
-  const float* __restrict__ od_col = a.OD + i;
+  const float* __restrict__ od_col = ln.od_col;
+  // The staged OD fetch (these loads, the bumped pointers and the hand-over at the top of the chunk loop) is spelled out here
+  // and in tud_g_snap_kernel, not shared: as a struct or as functions taking the arrays it compiled to another chunk loop
+  // (other branch structure and waits, generic loads in one form), and this loop is the one bound by the scalar unit.
   float nxt[TUD_STAGE];
 #pragma unroll
   for (int t = 0; t < TUD_STAGE; ++t) nxt[t] = od_col[(size_t)(t < nL ? t : nL - 1) * a.ld];
-  const double x = grid_x(a.g, a.g.offset + i);
-  const double x100 = x * 100.0;
-  const double c1x3 = RT_C1 * (x100 * x100 * x100) * 1e4;
-  // per-layer constants by v_readlane, the first altitude's mask in scalar registers (as in tud_kernel)
-  const int lane_id = threadIdx.x & 63;
-  const double ct_a = a.c2l2e_over_T[lane_id < nL ? lane_id : 0];
-  const double ct_b = a.c2l2e_over_T[lane_id + 64 < nL ? lane_id + 64 : 0];
-  auto c2l2e_of = [&](int k) -> double {  // k is wave-uniform
-    const double v = k < 64 ? ct_a : ct_b;
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), k & 63), hi = __builtin_amdgcn_readlane(__double2hiint(v), k & 63);
-    return __hiloint2double(hi, lo);
-  };
-  const unsigned mk0 = a.mask[0][0], mk1 = a.mask[0][1], mk2 = a.mask[0][2], mk3 = a.mask[0][3];
-  auto mask0_bit = [&](int k) -> bool {
-    const unsigned w = k < 32 ? mk0 : k < 64 ? mk1 : k < 96 ? mk2 : mk3;
-    return (w >> (k & 31)) & 1u;
-  };
+  ln.layer_consts(a);
+  const LayerMask mask0 = layer_mask(a, 0);
   PlanckNodes PNd;
-  if (PN) PNd = planck_nodes_setup(a, ct_a, ct_b, nL);
+  if (PN) PNd = planck_nodes_setup(a, ln);
   __syncthreads();  // the table is in LDS
 
   // ---- every further (altitude, slant factor) pair: transmittance + upwelling bottom-up (:346-356) ----------
@@ -694,16 +691,12 @@ __global__ __launch_bounds__(256) void tud_g_kernel(TudArgs a) {
     const float c = a.mu_c[im];
     float s = 0.f, Lu = 0.f;
     for (int k = 0; k < nL; ++k) {
-      const float od = od_col[(size_t)k * a.ld];
+      const float od = ln.od_col[(size_t)k * a.ld];
       if ((a.mask[ia][k >> 5] >> (k & 31)) & 1u) s += od;
-      if (k < cnt) {
-        const float B = PN ? planck_nodes_eval(PNd, k) : planck_f32(c1x3, x, c2l2e_of(k));
-        const float y = od * c;
-        Lu = (y > -TUD_THIN_Y) ? fmaf(em_thin(y), B - Lu, Lu) : fmaf(__builtin_amdgcn_exp2f(y), Lu - B, B);
-      }
+      if (k < cnt) Lu = up_step(Lu, PN ? planck_nodes_eval(PNd, k) : ln.planck(k), od * c);
     }
-    if (live) {
-      const size_t o = (size_t)p * (size_t)a.ld_out + (size_t)i;
+    if (ln.live) {
+      const size_t o = (size_t)p * (size_t)a.ld_out + (size_t)ln.i;
       a.tau[o] = a.return_od ? s * a.mu[im] : __builtin_amdgcn_exp2f(s * c);
       a.Lu[o] = Lu;
     }
@@ -712,30 +705,19 @@ __global__ __launch_bounds__(256) void tud_g_kernel(TudArgs a) {
   // ---- the first pair's transmittance and upwelling, and the downwelling, in one bottom-up pass -------------------------
   const int nd = a.n_down, cnt0 = a.count[0];
   const float c0 = a.mu_c[0];
-  float s0 = 0.f, Lu0 = 0.f, acc = 0.f;
-  double S = 0.0, g_prev = tudg_eval(s_g, 0.0);  // (not a.g0: the table's own value, so that an empty column gives exactly 0)
-  // Downwelling at the surface is blind to everything above the depth where G has dropped to 2^-27 of G(0) times the
-  // column's Planck dynamic range at this wavenumber (what is dropped is at most that transmission times the largest
-  // Planck radiance, what is kept is of the order of the smallest): once every lane is there the wave stops evaluating G.
-  double g_floor;
-  {
-    const float b_hot = planck_f32(c1x3, x, a.c2l2e_over_Tmax), b_cold = planck_f32(c1x3, x, a.c2l2e_over_Tmin);
-    const float r = __builtin_amdgcn_logf(b_hot / b_cold);  // log2
-    const float y_opq = (b_cold > 0.f && r == r && r < 1e30f) ? TUD_OPAQUE_Y + 1.0f + fmaxf(r, 0.f) : 3.0e38f;
-    g_floor = a.g0 * (double)__builtin_amdgcn_exp2f(-fminf(y_opq, 120.0f));
-  }
-  bool down_live = nd > 0;  // wave-uniform
+  float s0 = 0.f, Lu0 = 0.f;
+  TudDown down(s_g, a, ln);
   // The layer loop is bound by the CU's one scalar unit, not by HBM or the vector ALUs (round 3: 1.04e8 scalar against
   // 1.19e8 vector instructions per launch, ~45 scalar instructions per layer: 64-bit index products for the prefetch
   // addresses, the 128-bit mask lookup, the up / down flags, the loop control of a run-time inner loop). So: the prefetch
-  // pointers are bumped instead of recomputed, and a chunk of TUD_STAGE layers that all count for the upwelling and the
-  // downwelling (every chunk of the C3 column) runs unrolled with static layer offsets and a chunk-level mask word.
-  const unsigned long long m_lo = (unsigned long long)mk0 | ((unsigned long long)mk1 << 32);
-  const unsigned long long m_hi = (unsigned long long)mk2 | ((unsigned long long)mk3 << 32);
+  // pointers are bumped instead of recomputed, and a chunk of TUD_STAGE layers that all count for the upwelling
+  // and the downwelling (every chunk of the C3 column) runs unrolled with static layer offsets and a chunk-level mask word.
+  const unsigned long long m_lo = (unsigned long long)mask0.w0 | ((unsigned long long)mask0.w1 << 32);
+  const unsigned long long m_hi = (unsigned long long)mask0.w2 | ((unsigned long long)mask0.w3 << 32);
   const size_t bump = (size_t)TUD_STAGE * (size_t)a.ld;
   const float* pf[TUD_STAGE];
 #pragma unroll
-  for (int t = 0; t < TUD_STAGE; ++t) pf[t] = od_col + (size_t)(TUD_STAGE + t) * (size_t)a.ld;  // layer kc + TUD_STAGE + t (dereferenced only if < nL)
+  for (int t = 0; t < TUD_STAGE; ++t) pf[t] = od_col + (size_t)(TUD_STAGE + t) * (size_t)a.ld;
   for (int kc = 0; kc < nL; kc += TUD_STAGE) {
 #pragma unroll
     for (int t = 0; t < TUD_STAGE; ++t) s_stage[t][threadIdx.x] = nxt[t];
@@ -757,100 +739,50 @@ __global__ __launch_bounds__(256) void tud_g_kernel(TudArgs a) {
       for (int t = 0; t < TUD_STAGE; ++t) {
         const float od = s_stage[t][threadIdx.x];
         if ((mchunk >> t) & 1u) s0 += od;
-        const int kk = (kc & 63) + t;
-        const float q0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hi_set ? PNd.c0b : PNd.c0), kk));
-        const float q1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hi_set ? PNd.c1b : PNd.c1), kk));
-        const float q2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hi_set ? PNd.c2b : PNd.c2), kk));
-        const float B = fmaf(fmaf(q2, PNd.t, q1), PNd.t, q0);  // planck_nodes_eval(PNd, kc + t)
-        {
-          const float y = od * c0;
-          Lu0 = (y > -TUD_THIN_Y) ? fmaf(em_thin(y), B - Lu0, Lu0) : fmaf(__builtin_amdgcn_exp2f(y), Lu0 - B, B);
-        }
-        if (down_live) {
-          S += (double)od;
-          const double g = tudg_eval(s_g, S);
-          acc = fmaf(B, (float)(g_prev - g), acc);
-          g_prev = g;
-          if (__ballot(g > g_floor) == 0ull) down_live = false;
-        }
+        const float B = planck_nodes_eval(PNd, hi_set, (kc & 63) + t);
+        Lu0 = up_step(Lu0, B, od * c0);
+        if (down.live) down.step(s_g, od, B);
       }
       continue;
     }
     for (int k = kc; k < k_hi; ++k) {
       const float od = s_stage[k - kc][threadIdx.x];
-      if (mask0_bit(k)) s0 += od;
-      const bool up = k < cnt0, dn = down_live && k < nd;  // wave-uniform
+      if (mask0.bit(k)) s0 += od;
+      const bool up = k < cnt0, dn = down.live && k < nd;  // wave-uniform
       if (!up && !dn) continue;
-      const float B = PN ? planck_nodes_eval(PNd, k) : planck_f32(c1x3, x, c2l2e_of(k));
-      if (up) {
-        const float y = od * c0;
-        Lu0 = (y > -TUD_THIN_Y) ? fmaf(em_thin(y), B - Lu0, Lu0) : fmaf(__builtin_amdgcn_exp2f(y), Lu0 - B, B);
-      }
-      if (dn) {
-        S += (double)od;
-        const double g = tudg_eval(s_g, S);
-        acc = fmaf(B, (float)(g_prev - g), acc);
-        g_prev = g;
-        if (__ballot(g > g_floor) == 0ull) down_live = false;
-      }
+      const float B = PN ? planck_nodes_eval(PNd, k) : ln.planck(k);
+      if (up) Lu0 = up_step(Lu0, B, od * c0);
+      if (dn) down.step(s_g, od, B);
     }
   }
-  if (live) {
-    a.tau[i] = a.return_od ? s0 * a.mu[0] : __builtin_amdgcn_exp2f(s0 * c0);
-    a.Lu[i] = Lu0;
-    a.Ld[i] = (S != S) ? __builtin_nanf("") : acc * a.inv_wsum;  // a NaN optical depth poisons the sum, as in the reference
+  if (ln.live) {
+    a.tau[ln.i] = a.return_od ? s0 * a.mu[0] : __builtin_amdgcn_exp2f(s0 * c0);
+    a.Lu[ln.i] = Lu0;
+    a.Ld[ln.i] = down.result(a);
   }
 }
 
 // PB = (altitude, slant) pairs advanced together in one bottom-up pass: they share the OD loads and the Planck values (the
 // reference's main caller asks for 9 sensor altitudes, Generate_LWIR_TUD.py:81; one pass per pair recomputed B for each).
-// A single pair takes tud_g_kernel above (70 registers, 7 waves per SIMD); several run here in blocks of PB = 8 (109
-// registers), the first block carrying the downwelling.
+// A single pair takes tud_g_kernel above; several run here in blocks of PB = TUDG_PB (84 registers), the first block
+// carrying the downwelling.
 #ifndef TUDG_PB
 #define TUDG_PB 3  // 9 pairs, ms: blocks of 2 -> 1.29, 3 -> 1.01, 4 -> 1.15, 8 -> 1.32 (one pass per pair: 1.41)
-#endif
-#ifndef TUDG_PAIR_BALLOT
-#define TUDG_PAIR_BALLOT 0  // 1: one form only where the whole wave agrees (1.48 against 1.15 at blocks of 4: the branches cost more)
 #endif
 template <int PB>
 __global__ __launch_bounds__(256) void tud_g_pairs_kernel(TudArgs a) {
   __shared__ double s_g[TUDG_NINT * 8];
   __shared__ float s_stage[TUD_STAGE][256];  // each thread's own slots
-  for (int t = threadIdx.x; t < TUDG_NINT * 4; t += 256) reinterpret_cast<double2*>(s_g)[t] = reinterpret_cast<const double2*>(a.gtab)[t];
-  const long long i_raw = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool live = i_raw < a.g.n;
-  const long long i = live ? i_raw : a.g.n - 1;  // dead lanes shadow the last point: ballots stay wave-wide
+  tudg_load(s_g, a);
+  TudLane ln(a);
   const int nL = a.n_layers;
-  const float* __restrict__ od_col = a.OD + i;
-  const double x = grid_x(a.g, a.g.offset + i);
-  const double x100 = x * 100.0;
-  const double c1x3 = RT_C1 * (x100 * x100 * x100) * 1e4;
-  // per-layer constants by v_readlane (as in tud_kernel)
-  const int lane_id = threadIdx.x & 63;
-  const double ct_a = a.c2l2e_over_T[lane_id < nL ? lane_id : 0];
-  const double ct_b = a.c2l2e_over_T[lane_id + 64 < nL ? lane_id + 64 : 0];
-  auto c2l2e_of = [&](int k) -> double {  // k is wave-uniform
-    const double v = k < 64 ? ct_a : ct_b;
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), k & 63), hi = __builtin_amdgcn_readlane(__double2hiint(v), k & 63);
-    return __hiloint2double(hi, lo);
-  };
+  const float* __restrict__ od_col = ln.od_col;
+  ln.layer_consts(a);
   __syncthreads();  // the table is in LDS
 
   const int nd = a.n_down;
   const int npair = a.n_alt * a.n_mu;
-  float acc = 0.f;
-  double S = 0.0, g_prev = tudg_eval(s_g, 0.0);  // (not a.g0: the table's own value, so that an empty column gives exactly 0)
-  // Downwelling at the surface is blind to everything above the depth where G has dropped to 2^-27 of G(0) times the
-  // column's Planck dynamic range at this wavenumber (what is dropped is at most that transmission times the largest
-  // Planck radiance, what is kept is of the order of the smallest): once every lane is there the wave stops evaluating G.
-  double g_floor;
-  {
-    const float b_hot = planck_f32(c1x3, x, a.c2l2e_over_Tmax), b_cold = planck_f32(c1x3, x, a.c2l2e_over_Tmin);
-    const float r = __builtin_amdgcn_logf(b_hot / b_cold);  // log2
-    const float y_opq = (b_cold > 0.f && r == r && r < 1e30f) ? TUD_OPAQUE_Y + 1.0f + fmaxf(r, 0.f) : 3.0e38f;
-    g_floor = a.g0 * (double)__builtin_amdgcn_exp2f(-fminf(y_opq, 120.0f));
-  }
-  bool down_live = nd > 0;  // wave-uniform
+  TudDown down(s_g, a, ln);
 
   // ---- transmittance and upwelling of PB (altitude, slant) pairs bottom-up (:346-356); the first block also carries the
   //      downwelling --------------------------------------------------------------------------------------------------------
@@ -874,6 +806,8 @@ __global__ __launch_bounds__(256) void tud_g_pairs_kernel(TudArgs a) {
 #pragma unroll
     for (int j = 0; j < PB; ++j) { sp[j] = 0.f; Lu[j] = 0.f; }
     const bool first = p0 == 0;
+    // (clamped index products, not the bumped 64-bit prefetch pointers of tud_g_kernel: next to the PB recurrences those take
+    // this kernel to 100 registers, one wave per SIMD fewer)
     float nxt[TUD_STAGE];
 #pragma unroll
     for (int t = 0; t < TUD_STAGE; ++t) nxt[t] = od_col[(size_t)(t < nL ? t : nL - 1) * a.ld];
@@ -886,50 +820,31 @@ __global__ __launch_bounds__(256) void tud_g_pairs_kernel(TudArgs a) {
       for (int k = kc; k < k_hi; ++k) {
         const float od = s_stage[k - kc][threadIdx.x];
 #pragma unroll
-        for (int j = 0; j < PB; ++j) {
-          const unsigned w = k < 32 ? mw[j][0] : k < 64 ? mw[j][1] : k < 96 ? mw[j][2] : mw[j][3];
-          if ((w >> (k & 31)) & 1u) sp[j] += od;
-        }
-        const bool up = k < cnt_max, dn = first && down_live && k < nd;  // wave-uniform
+        for (int j = 0; j < PB; ++j)
+          if (LayerMask{mw[j][0], mw[j][1], mw[j][2], mw[j][3]}.bit(k)) sp[j] += od;
+        const bool up = k < cnt_max, dn = first && down.live && k < nd;  // wave-uniform
         if (!up && !dn) continue;
-        const float B = planck_f32(c1x3, x, c2l2e_of(k));
+        const float B = ln.planck(k);
+        // per lane, the form that does not cancel (up_step). Choosing one form per pair where the whole wave agrees was
+        // slower (1.48 against 1.15 ms at blocks of 4: the branches cost more than the second form)
 #pragma unroll
-        for (int j = 0; j < PB; ++j) {
-          if (k < cntp[j]) {
-            // t Lu + (1-t) B: thin lanes through the emissivity, thick lanes through the transmittance (the other way round
-            // each form cancels); one form only where the whole wave agrees
-            const float y = od * cp[j];
-            const bool thin = y > -TUD_THIN_Y;
-#if TUDG_PAIR_BALLOT
-            const unsigned long long tb = __ballot(thin);
-            if (tb == ~0ull) Lu[j] = fmaf(em_thin(y), B - Lu[j], Lu[j]);
-            else if (tb == 0ull) Lu[j] = fmaf(__builtin_amdgcn_exp2f(y), Lu[j] - B, B);
-            else
-#endif
-            Lu[j] = thin ? fmaf(em_thin(y), B - Lu[j], Lu[j]) : fmaf(__builtin_amdgcn_exp2f(y), Lu[j] - B, B);
-          }
-        }
-        if (dn) {
-          S += (double)od;
-          const double g = tudg_eval(s_g, S);
-          acc = fmaf(B, (float)(g_prev - g), acc);
-          g_prev = g;
-          if (__ballot(g > g_floor) == 0ull) down_live = false;
-        }
+        for (int j = 0; j < PB; ++j)
+          if (k < cntp[j]) Lu[j] = up_step(Lu[j], B, od * cp[j]);
+        if (dn) down.step(s_g, od, B);
       }
     }
-    if (live) {
+    if (ln.live) {
 #pragma unroll
       for (int j = 0; j < PB; ++j) {
         if (p0 + j < npair) {
-          const size_t o = (size_t)(p0 + j) * (size_t)a.ld_out + (size_t)i;
+          const size_t o = (size_t)(p0 + j) * (size_t)a.ld_out + (size_t)ln.i;
           a.tau[o] = a.return_od ? sp[j] * mup[j] : __builtin_amdgcn_exp2f(sp[j] * cp[j]);
           a.Lu[o] = Lu[j];
         }
       }
     }
   }
-  if (live) a.Ld[i] = (S != S) ? __builtin_nanf("") : acc * a.inv_wsum;  // a NaN optical depth poisons the sum, as in the reference
+  if (ln.live) a.Ld[ln.i] = down.result(a);
 }
 
 // Several sensor altitudes and slant paths, the usual case of prefix masks (altitudes on an ascending height grid: the layers
@@ -943,28 +858,16 @@ template <int NMU, bool PN>
 __global__ __launch_bounds__(256) void tud_g_snap_kernel(TudArgs a) {
   __shared__ double s_g[TUDG_NINT * 8];
   __shared__ float s_stage[TUD_STAGE][256];  // each thread's own slots
-  for (int t = threadIdx.x; t < TUDG_NINT * 4; t += 256) reinterpret_cast<double2*>(s_g)[t] = reinterpret_cast<const double2*>(a.gtab)[t];
-  const long long i_raw = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool live = i_raw < a.g.n;
-  const long long i = live ? i_raw : a.g.n - 1;  // dead lanes shadow the last point: ballots stay wave-wide
+  tudg_load(s_g, a);
+  TudLane ln(a);
   const int nL = a.n_layers;
-  const float* __restrict__ od_col = a.OD + i;
+  const float* __restrict__ od_col = ln.od_col;
   float nxt[TUD_STAGE];
 #pragma unroll
   for (int t = 0; t < TUD_STAGE; ++t) nxt[t] = od_col[(size_t)(t < nL ? t : nL - 1) * a.ld];
-  const double x = grid_x(a.g, a.g.offset + i);
-  const double x100 = x * 100.0;
-  const double c1x3 = RT_C1 * (x100 * x100 * x100) * 1e4;
-  const int lane_id = threadIdx.x & 63;
-  const double ct_a = a.c2l2e_over_T[lane_id < nL ? lane_id : 0];
-  const double ct_b = a.c2l2e_over_T[lane_id + 64 < nL ? lane_id + 64 : 0];
-  auto c2l2e_of = [&](int k) -> double {  // k is wave-uniform
-    const double v = k < 64 ? ct_a : ct_b;
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), k & 63), hi = __builtin_amdgcn_readlane(__double2hiint(v), k & 63);
-    return __hiloint2double(hi, lo);
-  };
+  ln.layer_consts(a);
   PlanckNodes PNd;
-  if (PN) PNd = planck_nodes_setup(a, ct_a, ct_b, nL);
+  if (PN) PNd = planck_nodes_setup(a, ln);
   __syncthreads();  // the table is in LDS
 
   const int nd = a.n_down, n_alt = a.n_alt, n_mu = a.n_mu;
@@ -978,24 +881,17 @@ __global__ __launch_bounds__(256) void tud_g_snap_kernel(TudArgs a) {
   float cm[NMU], mum[NMU], Lu[NMU];
 #pragma unroll
   for (int m = 0; m < NMU; ++m) { cm[m] = a.mu_c[m < n_mu ? m : 0]; mum[m] = a.mu[m < n_mu ? m : 0]; Lu[m] = 0.f; }
-  float s_run = 0.f, acc = 0.f;
-  double S = 0.0, g_prev = tudg_eval(s_g, 0.0);
-  double g_floor;
-  {
-    const float b_hot = planck_f32(c1x3, x, a.c2l2e_over_Tmax), b_cold = planck_f32(c1x3, x, a.c2l2e_over_Tmin);
-    const float r = __builtin_amdgcn_logf(b_hot / b_cold);  // log2
-    const float y_opq = (b_cold > 0.f && r == r && r < 1e30f) ? TUD_OPAQUE_Y + 1.0f + fmaxf(r, 0.f) : 3.0e38f;
-    g_floor = a.g0 * (double)__builtin_amdgcn_exp2f(-fminf(y_opq, 120.0f));
-  }
+  float s_run = 0.f;
+  TudDown down(s_g, a, ln);
   // every altitude whose column has c layers gets its outputs now
   auto snapshot = [&](int c) {
     if (c < 128 && !(((c < 64 ? snap_lo : snap_hi) >> (c & 63)) & 1ull)) return;
     for (int ia = 0; ia < n_alt; ++ia) {
-      if (a.count[ia] != c || !live) continue;
+      if (a.count[ia] != c || !ln.live) continue;
 #pragma unroll
       for (int m = 0; m < NMU; ++m) {
         if (m < n_mu) {
-          const size_t o = (size_t)(ia * n_mu + m) * (size_t)a.ld_out + (size_t)i;
+          const size_t o = (size_t)(ia * n_mu + m) * (size_t)a.ld_out + (size_t)ln.i;
           a.tau[o] = a.return_od ? s_run * mum[m] : __builtin_amdgcn_exp2f(s_run * cm[m]);
           a.Lu[o] = Lu[m];
         }
@@ -1003,9 +899,8 @@ __global__ __launch_bounds__(256) void tud_g_snap_kernel(TudArgs a) {
     }
   };
   snapshot(0);
-  bool down_live = nd > 0;  // wave-uniform
-  // as in tud_g_kernel: prefetch pointers bumped, and a chunk whose layers all count for the upwelling and the downwelling
-  // runs unrolled with static offsets (the layer loop is bound by the CU's one scalar unit)
+  // as in tud_g_kernel (staged OD fetch spelled out, see there): a chunk whose layers all count for the upwelling and the downwelling runs unrolled with static
+  // offsets (the layer loop is bound by the CU's one scalar unit)
   const size_t bump = (size_t)TUD_STAGE * (size_t)a.ld;
   const float* pf[TUD_STAGE];
 #pragma unroll
@@ -1029,71 +924,41 @@ __global__ __launch_bounds__(256) void tud_g_snap_kernel(TudArgs a) {
 #pragma unroll
       for (int t = 0; t < TUD_STAGE; ++t) {
         const float od = s_stage[t][threadIdx.x];
-        const int kk = kc + t;
-        const float q0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(PNd.c0), kk));
-        const float q1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(PNd.c1), kk));
-        const float q2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(PNd.c2), kk));
-        const float B = fmaf(fmaf(q2, PNd.t, q1), PNd.t, q0);  // planck_nodes_eval(PNd, kc + t), kc + t < 64
+        const float B = planck_nodes_eval(PNd, false, kc + t);  // kc + t < 64
         s_run += od;
 #pragma unroll
-        for (int m = 0; m < NMU; ++m) {
-          if (NMU == 1 || m < n_mu) {
-            const float y = od * cm[m];
-            Lu[m] = (y > -TUD_THIN_Y) ? fmaf(em_thin(y), B - Lu[m], Lu[m]) : fmaf(__builtin_amdgcn_exp2f(y), Lu[m] - B, B);
-          }
-        }
-        if ((snap_chunk >> t) & 1u) snapshot(kk + 1);
-        if (down_live) {
-          S += (double)od;
-          const double g = tudg_eval(s_g, S);
-          acc = fmaf(B, (float)(g_prev - g), acc);
-          g_prev = g;
-          if (__ballot(g > g_floor) == 0ull) down_live = false;
-        }
+        for (int m = 0; m < NMU; ++m)
+          if (NMU == 1 || m < n_mu) Lu[m] = up_step(Lu[m], B, od * cm[m]);
+        if ((snap_chunk >> t) & 1u) snapshot(kc + t + 1);
+        if (down.live) down.step(s_g, od, B);
       }
       continue;
     }
     for (int k = kc; k < k_hi; ++k) {
       const float od = s_stage[k - kc][threadIdx.x];
-      const bool up = k < cnt_max, dn = down_live && k < nd;  // wave-uniform
+      const bool up = k < cnt_max, dn = down.live && k < nd;  // wave-uniform
       if (!up && !dn) continue;
-      const float B = PN ? planck_nodes_eval(PNd, k) : planck_f32(c1x3, x, c2l2e_of(k));
+      const float B = PN ? planck_nodes_eval(PNd, k) : ln.planck(k);
       if (up) {
         s_run += od;
 #pragma unroll
-        for (int m = 0; m < NMU; ++m) {
-          if (m < n_mu) {
-            const float y = od * cm[m];
-            Lu[m] = (y > -TUD_THIN_Y) ? fmaf(em_thin(y), B - Lu[m], Lu[m]) : fmaf(__builtin_amdgcn_exp2f(y), Lu[m] - B, B);
-          }
-        }
+        for (int m = 0; m < NMU; ++m)
+          if (m < n_mu) Lu[m] = up_step(Lu[m], B, od * cm[m]);
         snapshot(k + 1);
       }
-      if (dn) {
-        S += (double)od;
-        const double g = tudg_eval(s_g, S);
-        acc = fmaf(B, (float)(g_prev - g), acc);
-        g_prev = g;
-        if (__ballot(g > g_floor) == 0ull) down_live = false;
-      }
+      if (dn) down.step(s_g, od, B);
     }
   }
-  if (live) a.Ld[i] = (S != S) ? __builtin_nanf("") : acc * a.inv_wsum;
+  if (ln.live) a.Ld[ln.i] = down.result(a);
 }
 
 // Host side of G: piecewise Chebyshev interpolants of degree TUDG_DEG in fp64, stored as monomials in (S - mid).
 struct GTab { double* dev; double g0; };
 static void tudg_build(int n_angle, std::vector<double>& tab, double& g0_out) {
-  std::vector<double> w, sec;
-  const double dth = (M_PI / 2.0) / (double)n_angle;
-  double g0 = 0.0;
-  for (int ii = 1; ii < n_angle; ++ii) {  // theta = 0 has weight exactly 0
-    const double th = (double)ii * dth;
-    w.push_back(cos(th) * sin(th));
-    sec.push_back(1.0 / cos(th));
-    g0 += w.back();
-  }
-  auto G = [&](double S) { double r = 0.0; for (size_t q = 0; q < w.size(); ++q) r += w[q] * exp(-S * sec[q]); return r; };
+  const TudQuadrature quad = tud_quadrature(n_angle);
+  std::vector<double> sec;
+  for (int ii = 1; ii < n_angle; ++ii) sec.push_back(1.0 / cos(quad.th[ii]));  // theta = 0 has weight exactly 0
+  auto G = [&](double S) { double r = 0.0; for (size_t q = 0; q < sec.size(); ++q) r += quad.w[q + 1] * exp(-S * sec[q]); return r; };
   constexpr int N = TUDG_DEG + 1;
   tab.assign((size_t)TUDG_NINT * 8, 0.0);
   for (int idx = 0; idx < TUDG_NINT; ++idx) {
@@ -1133,7 +998,7 @@ static void tudg_build(int n_angle, std::vector<double>& tab, double& g0_out) {
     double sc = 1.0;
     for (int d = 0; d < N; ++d) { row[1 + d] = mono[d] * sc; sc /= hw; }
   }
-  g0_out = g0;
+  g0_out = quad.wsum;  // G(0)
 }
 
 // The table as the kernels see it, for host-side checks (tests/test_host.py evaluates it in NumPy against the direct sum;
@@ -1166,6 +1031,13 @@ static int tudg_table(int n_angle, GTab* out) {
   return 0;
 }
 
+// one thread per wavenumber of the shard, 256 per workgroup
+static int tud_launch(void (*kernel)(TudArgs), const TudArgs& a, size_t lds_bytes, hipStream_t st) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((a.g.n + 255) / 256)), dim3(256), lds_bytes, st, a);
+  RTX_LAUNCH_CHECK();
+  return 0;
+}
+
 template <int NA>
 static int launch_tud(TudArgs& a, int na, hipStream_t st) {
   const int na_pad = na == 0 ? NA : ((na + NA - 1) / NA) * NA;  // at least one block: it carries tau and L-up
@@ -1176,13 +1048,8 @@ static int launch_tud(TudArgs& a, int na, hipStream_t st) {
   for (int q = na; q < na_pad; ++q) { a.ang_c[q] = na > 0 ? a.ang_c[na - 1] : (float)(-LOG2E); a.ang_w[q] = 0.f; }
   a.ang_cmin = cmin; a.ang_cmax = cmax;
   a.n_ang = na_pad;
-  const long long blocks = (a.g.n + 255) / 256;
-  if (a.n_layers <= TUD_COL_LAYERS)
-    hipLaunchKernelGGL((tud_kernel<NA, true>), dim3((unsigned)blocks), dim3(256), (size_t)a.n_layers * 256 * sizeof(float), st, a);
-  else
-    hipLaunchKernelGGL((tud_kernel<NA, false>), dim3((unsigned)blocks), dim3(256), (size_t)TUD_STAGE * 256 * sizeof(float), st, a);
-  RTX_LAUNCH_CHECK();
-  return 0;
+  if (a.n_layers <= TUD_COL_LAYERS) return tud_launch(tud_kernel<NA, true>, a, (size_t)a.n_layers * 256 * sizeof(float), st);
+  return tud_launch(tud_kernel<NA, false>, a, (size_t)TUD_STAGE * 256 * sizeof(float), st);
 }
 
 extern "C" int rtx_tud(const float* OD, int64_t ld, const rtx_grid* grid, int n_layers, const double* T_h, int n_alt,
@@ -1202,15 +1069,14 @@ extern "C" int rtx_tud(const float* OD, int64_t ld, const rtx_grid* grid, int n_
   a.OD = OD; a.ld = ld; a.ld_out = ld_out; a.g = to_dev(grid);
   a.n_layers = n_layers; a.n_alt = n_alt; a.n_mu = n_mu; a.n_down = n_down; a.return_od = return_od;
   a.tau = tau; a.Lu = Lu; a.Ld = Ld; a.Ld_ang = Ld_angles;
-  double t_max = 0.0, t_min = 0.0;
-  for (int k = 0; k < n_layers; ++k) {
-    if (!(T_h[k] > 0.0)) RTX_FAIL("layer %d temperature %g", k, T_h[k]);
-    a.c2l2e_over_T[k] = 100.0 * RT_C2 * LOG2E / T_h[k];
-    if (k == 0 || T_h[k] > t_max) t_max = T_h[k];
-    if (k == 0 || T_h[k] < t_min) t_min = T_h[k];
+  if (tud_layer_consts(T_h, n_layers, a.c2l2e_over_T)) return 1;
+  double t_max = T_h[0], t_min = T_h[0];
+  for (int k = 1; k < n_layers; ++k) {
+    if (T_h[k] > t_max) t_max = T_h[k];
+    if (T_h[k] < t_min) t_min = T_h[k];
   }
-  a.c2l2e_over_Tmax = 100.0 * RT_C2 * LOG2E / t_max;
-  a.c2l2e_over_Tmin = 100.0 * RT_C2 * LOG2E / t_min;
+  a.c2l2e_over_Tmax = c2l2e_over(t_max);
+  a.c2l2e_over_Tmin = c2l2e_over(t_min);
   for (int ia = 0; ia < n_alt; ++ia) {
     int c = 0;
     for (int k = 0; k < n_layers; ++k)
@@ -1218,22 +1084,16 @@ extern "C" int rtx_tud(const float* OD, int64_t ld, const rtx_grid* grid, int n_
     a.count[ia] = c;
   }
   for (int m = 0; m < n_mu; ++m) { a.mu[m] = (float)mu_h[m]; a.mu_c[m] = (float)(-LOG2E * mu_h[m]); }
-  // angles = linspace(0, pi/2, nA, endpoint=False) (:368); weights cos*sin (:387). theta=0 has
-  // weight exactly 0 (sin 0 = 0) and is skipped; an odd count is padded with a weight-0 stream.
-  double wsum = 0.0;
+  // theta=0 has weight exactly 0 (sin 0 = 0) and is skipped; an odd count is padded with a weight-0 stream.
+  const TudQuadrature quad = tud_quadrature(n_angle);
   int na = 0;
-  const double dth = (M_PI / 2.0) / (double)n_angle;  // np.linspace step
-  for (int ii = 0; ii < n_angle; ++ii) {
-    const double th = (double)ii * dth;
-    const double w = cos(th) * sin(th);
-    wsum += w;
-    if (ii == 0 && !Ld_angles) continue;  // with per-stream output every stream is evaluated
-    a.ang_c[na] = (float)(-LOG2E / cos(th));
-    a.ang_w[na] = (float)w;
+  for (int ii = Ld_angles ? 0 : 1; ii < n_angle; ++ii) {  // with per-stream output every stream is evaluated
+    a.ang_c[na] = (float)(-LOG2E / cos(quad.th[ii]));
+    a.ang_w[na] = (float)quad.w[ii];
     ++na;
   }
   a.n_ang_real = na;
-  a.inv_wsum = (float)(1.0 / wsum);  // n_angle==1: 1/0 = inf, acc=0 -> NaN like the reference's 0/0
+  a.inv_wsum = (float)(1.0 / quad.wsum);  // n_angle==1: 1/0 = inf, acc=0 -> NaN like the reference's 0/0
   if (na == 0) a.inv_wsum = NAN;
   // streams per register block: the smallest instantiated width that holds them all (N_angle = 30 -> 29
   // evaluated -> 29 registers, no padding); more than 32 streams run in blocks of 32
@@ -1245,8 +1105,7 @@ extern "C" int rtx_tud(const float* OD, int64_t ld, const rtx_grid* grid, int n_
   if (!Ld_angles && !force_streams) {
     GTab gt;
     if (tudg_table(n_angle, &gt)) return 1;
-    a.gtab = gt.dev; a.g_nint = TUDG_NINT; a.g0 = gt.g0;
-    const long long blocks = (a.g.n + 255) / 256;
+    a.gtab = gt.dev; a.g0 = gt.g0;
     bool prefix = true;  // every altitude's mask = its first count layers?
     for (int ia = 0; ia < n_alt && prefix; ++ia)
       for (int k = 0; k < n_layers; ++k)
@@ -1257,21 +1116,13 @@ extern "C" int rtx_tud(const float* OD, int64_t ld, const rtx_grid* grid, int n_
     // instantiation the single-rank run does; a shard offset that is a multiple of 64 then has the same waves, hence bits
     const double nu_lo = grid->xmin;
     const bool pn = nu_lo > 0.0 && (4.0 / nu_lo + RT_C2 * 100.0 / t_min) * 63.0 * grid->step <= 7e-3;
-    a.planck_nodes = pn ? 1 : 0;
-    if (n_alt * n_mu == 1) {
-      if (pn) hipLaunchKernelGGL(tud_g_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, a);
-      else hipLaunchKernelGGL(tud_g_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, a);
-    } else if (prefix) {
-      // one slant path (the reference's main caller: 9 altitudes, nadir): the instantiation without the per-slant guards
-      if (n_mu == 1) {
-        if (pn) hipLaunchKernelGGL((tud_g_snap_kernel<1, true>), dim3((unsigned)blocks), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((tud_g_snap_kernel<1, false>), dim3((unsigned)blocks), dim3(256), 0, st, a);
-      } else if (pn) hipLaunchKernelGGL((tud_g_snap_kernel<TUD_MAX_MU, true>), dim3((unsigned)blocks), dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((tud_g_snap_kernel<TUD_MAX_MU, false>), dim3((unsigned)blocks), dim3(256), 0, st, a);
-    }
-    else hipLaunchKernelGGL(tud_g_pairs_kernel<TUDG_PB>, dim3((unsigned)blocks), dim3(256), 0, st, a);
-    RTX_LAUNCH_CHECK();
-    return 0;
+    void (*kernel)(TudArgs);
+    if (n_alt * n_mu == 1) kernel = pn ? tud_g_kernel<true> : tud_g_kernel<false>;
+    // one slant path (the reference's main caller: 9 altitudes, nadir): the instantiation without the per-slant guards
+    else if (prefix && n_mu == 1) kernel = pn ? tud_g_snap_kernel<1, true> : tud_g_snap_kernel<1, false>;
+    else if (prefix) kernel = pn ? tud_g_snap_kernel<TUD_MAX_MU, true> : tud_g_snap_kernel<TUD_MAX_MU, false>;
+    else kernel = tud_g_pairs_kernel<TUDG_PB>;
+    return tud_launch(kernel, a, 0, st);
   }
   if (na <= 4) return launch_tud<4>(a, na, st);
   if (na <= 8) return launch_tud<8>(a, na, st);

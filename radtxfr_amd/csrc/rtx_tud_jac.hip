@@ -23,12 +23,7 @@
 #include <math.h>
 #include <string.h>
 
-#include "rtx_common.h"
-
-#define RT_C2 1.43877736830e-02  // radiative_transfer.py:72
-#define RT_C1 1.19104295315e-16  // radiative_transfer.py:71
-#define LOG2E 1.4426950408889634
-#define LN2 0.6931471805599453
+#include "rtx_tud_common.h"
 
 #define TUDJ_MAX_LAYERS 128
 #define TUDJ_MAX_ALT 16
@@ -65,15 +60,8 @@ struct TudJacArgs {
 // e^-y for y >= 0 given in fp64: the argument rounded once to fp32, then v_exp_f32 (|y| up to ~87 matters)
 __device__ __forceinline__ float exp_neg(double y) { return __builtin_amdgcn_exp2f((float)(-y * LOG2E)); }
 
-// 1 - e^-y, accurate to ~1e-7 relative also for a thin layer (the form of rtx_tud.hip's em_thin)
-__device__ __forceinline__ float one_minus_exp_neg(float y) {
-  const float z = -y * (float)LOG2E;  // log2 of the transmittance
-  if (z > -0.0625f) {
-    const float q = fmaf(fmaf(fmaf(9.6181291076e-3f, z, 5.5504108665e-2f), z, 2.4022650696e-1f), z, 6.9314718056e-1f);
-    return -z * q;
-  }
-  return 1.0f - __builtin_amdgcn_exp2f(z);
-}
+// 1 - e^-y, accurate to ~1e-7 relative also for a thin layer: the TUD kernels' emissivity of the transmittance's log2
+__device__ __forceinline__ float one_minus_exp_neg(float y) { return emissivity(-y * (float)LOG2E); }
 
 // B(nu, T_k) as rtx_tud evaluates it and its analytic temperature derivative: with u = c2 nu / T (t = u log2 e, the fp64
 // exponent planck_f32 forms), dB/dT = B (u / T) e^u / (e^u - 1) = B (u / T) (1 + B / c1x3).
@@ -266,24 +254,19 @@ extern "C" int rtx_tud_jacobian(const float* OD, const float* OD_plus, const flo
     if (layers_h[k] < 0 || layers_h[k] >= n_layers) RTX_FAIL("layer index %d outside [0,%d)", layers_h[k], n_layers);
     a.lay[k] = layers_h[k];
   }
-  for (int k = 0; k < n_layers; ++k) {
-    if (!(T_h[k] > 0.0)) RTX_FAIL("layer %d temperature %g", k, T_h[k]);
-    a.c2l2e_over_T[k] = 100.0 * RT_C2 * LOG2E / T_h[k];
-  }
-  for (int ia = 0; ia < n_alt; ++ia) {
+  if (tud_layer_consts(T_h, n_layers, a.c2l2e_over_T)) return 1;
+  for (int ia = 0; ia < n_alt; ++ia) {  // (rtx_tud packs the same masks per altitude; here the bits go per layer)
     int c = 0;
     for (int k = 0; k < n_layers; ++k)
       if (mask_h[(size_t)ia * n_layers + k]) { a.lbits[k] |= 1u << ia; ++c; }
     a.count[ia] = c;
     for (int k = 0; k < c; ++k) a.lbits[k] |= 1u << (16 + ia);
   }
-  // angles = linspace(0, pi/2, nA, endpoint=False) (:368), weights cos*sin / sum (:387-388); theta = 0 has weight 0
-  const double dth = (M_PI / 2.0) / (double)n_angle;
-  double wsum = 0.0;
-  for (int q = 0; q < n_angle; ++q) wsum += cos(q * dth) * sin(q * dth);
+  // the quadrature of rtx_tud, weights normalised (:387-388); theta = 0 has weight 0
+  const TudQuadrature quad = tud_quadrature(n_angle);
   int ns = 0;
   for (int q = 1; q < n_angle; ++q) {
-    const double th = (double)q * dth, c = cos(th), w = c * sin(th) / wsum;
+    const double c = cos(quad.th[q]), w = quad.w[q] / quad.wsum;
     a.str_ic[ns] = 1.0 / c;
     a.str_w[ns] = (float)w;
     a.str_wc[ns] = (float)(w / c);
