@@ -398,6 +398,39 @@ int rtx_cubic_end(const double* Ysm, int64_t ld, int n_rows, int64_t i_first, in
 int rtx_cubic_resample_unchecked(const double* Ysm, int64_t ld, int n_rows, int64_t n, double x0, double h,
                                  const double* x_out, int64_t n_out, double* out, int64_t ld_out, void* stream);
 
+/* ---- hapi's spectrum functions and slit-function convolution -------------------------------------------
+ * rtx_hapi_spectrum replaces transmittanceSpectrum / absorptionSpectrum / radianceSpectrum, misc/hapi.py:11582-11680,
+ * elementwise in fp64 and in the reference's order of operations:
+ *   RTX_SPECTRUM_TRANSMITTANCE  exp(-k l)
+ *   RTX_SPECTRUM_ABSORPTION     1 - exp(-k l)
+ *   RTX_SPECTRUM_RADIANCE       (1 - exp(-k l)) * 2 hh cc^2 nu^3 / (exp(hh cc nu / (cBolts T)) - 1) * 1e-7, with hapi's own
+ *                               constants hh, cc, cBolts (misc/hapi.py:84-86), W/sr/cm^2/cm^-1 (:11677)
+ *   k [n_rows][ld] float32 (k_is_f64 = 0) or float64 (1): absorption coefficients, wavenumber-contiguous rows;
+ *   l path length in cm, T in K (read for RADIANCE only); out [n_rows][ld_out] float64;
+ *   wavenumbers (RADIANCE only): X[n] fp64 when X != NULL, else `grid` (grid->n == n). */
+#define RTX_SPECTRUM_TRANSMITTANCE 0
+#define RTX_SPECTRUM_ABSORPTION 1
+#define RTX_SPECTRUM_RADIANCE 2
+int rtx_hapi_spectrum(int kind, const rtx_grid* grid, const double* X, const void* k, int k_is_f64, int n_rows,
+                      int64_t n, int64_t ld, double l, double T, double* out, int64_t ld_out, void* stream);
+/* rtx_fir_same: a window of the zero-padded linear convolution, what numpy.convolve computes inside convolveSpectrum /
+ * convolveSpectrumSame / convolveSpectrumFull (misc/hapi.py:11826-11900):
+ *   out[r][o] = out_scale * sum_{k=0}^{m-1} taps_h[k] * in[r][first + o - k],  o in [0, n_out),  in[r][j] = 0 outside [0, n).
+ * [first, first + n_out) must lie inside the n + m - 1 points of the full convolution: first = 0, n_out = n + m - 1 is
+ * mode 'full'; first = (min(n,m) - 1) / 2 (integer division), n_out = max(n,m) is mode 'same' (checked
+ * against NumPy for every n, m < 40; tests/test_spectra_host.py). in: [n_rows][ld_in] float32 (in_is_f64 = 0) or float64 (1), device; taps_h: m >= 1 doubles on the HOST;
+ * out: [n_rows][ld_out] float64, device. fp64 throughout: a float32 sample is widened exactly, and every output is ONE
+ * fma chain over k = 0 .. m-1 in ascending order, so results are bit-identical run to run and do not depend on n_rows,
+ * on the window or on which other outputs are computed. A direct sum (no FFT). The device copy of a slit is cached by
+ * content (16 slits per process): only the first call with a new slit allocates and synchronises.
+ * Errors: m < 1, n < 1, n_rows < 1, a window outside the full convolution, a leading dimension smaller than its row.
+ * rtx_fir_tile_points / rtx_fir_chunk_taps: outputs per workgroup and taps staged per pass (for tests at the edges). */
+int rtx_fir_same(const void* in, int in_is_f64, int64_t ld_in, int n_rows, int64_t n, const double* taps_h,
+                 int64_t m, double out_scale, int64_t first, int64_t n_out, double* out, int64_t ld_out,
+                 void* stream);
+int rtx_fir_tile_points(void);
+int rtx_fir_chunk_taps(void);
+
 /* ------------------------------------------------------------------------------------------
  * Single-process collectives over the GPUs of one node. The reference has no multi-GPU code; its scripts are plain
  * Python programs that fan work out with multiprocessing (Generate_LWIR_TUD.py:117-150). These three calls let ONE host

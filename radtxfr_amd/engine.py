@@ -866,6 +866,42 @@ def fir_reflect(Y, taps, centre):
     return out
 
 
+def same_window(n, m):
+    """(first, n_out) of numpy.convolve(a[n], v[m], mode='same') inside the full convolution: max(n, m) points from
+    (min(n, m) - 1) // 2 (NumPy swaps the operands when v is the longer one; checked against NumPy, tests/test_spectra_host.py)."""
+    return (min(n, m) - 1) // 2, max(n, m)
+
+
+def fir_same(Y, taps, out_scale, first, n_out):
+    """Y [rows][n] float32/float64 device tensor -> [rows][n_out] float64: out_scale times the points [first, first + n_out)
+    of the zero-padded linear convolution of every row with `taps` (host fp64) (rtx_fir_same)."""
+    lib = _lib.load()
+    assert Y.is_cuda and Y.dim() == 2 and Y.stride(1) == 1 and Y.dtype in (torch.float32, torch.float64)
+    rows, n = Y.shape
+    taps = np.ascontiguousarray(taps, dtype=np.float64)
+    out = torch.empty((rows, int(n_out)), dtype=torch.float64, device=Y.device)
+    ld = Y.stride(0) if rows > 1 else n  # the stride of a size-1 dimension is arbitrary
+    with torch.cuda.device(Y.device):
+        _lib.check(lib.rtx_fir_same(_ptr(Y), int(Y.dtype == torch.float64), ld, rows, n, taps.ctypes.data, taps.size,
+                                    float(out_scale), int(first), int(n_out), _ptr(out), max(int(n_out), 1), _stream_ptr()))
+    return out
+
+
+def hapi_spectrum(kind, K, l, T=0.0, X=None):
+    """K [rows][n] float32/float64 device tensor of absorption coefficients -> [rows][n] float64 (rtx_hapi_spectrum):
+    kind 0 transmittance, 1 absorption, 2 radiance (X: [n] fp64 device wavenumbers, T in K)."""
+    lib = _lib.load()
+    assert K.is_cuda and K.dim() == 2 and K.stride(1) == 1 and K.dtype in (torch.float32, torch.float64)
+    rows, n = K.shape
+    if X is not None:
+        assert X.is_cuda and X.dtype == torch.float64 and X.dim() == 1 and X.is_contiguous() and X.numel() == n
+    out = torch.empty((rows, n), dtype=torch.float64, device=K.device)
+    with torch.cuda.device(K.device):
+        _lib.check(lib.rtx_hapi_spectrum(int(kind), None, _ptr(X), _ptr(K), int(K.dtype == torch.float64), rows, n,
+                                         K.stride(0) if rows > 1 else n, float(l), float(T), _ptr(out), max(n, 1), _stream_ptr()))
+    return out
+
+
 def cubic_resample(Ysm, x0, h, x_out, checked=True):
     """Cubic spline through every sample of the uniform axis x0 + i*h, at x_out (device fp64): [rows][n_out] fp64.
     checked=False: the caller has verified the range of x_out on the host; no device read-back, no synchronisation."""

@@ -8,10 +8,13 @@ meaning and error behaviour:
     PYTIPS / partitionSum pieces  misc/hapi.py:9568-9582, 10030
     abundance, molecularMass      misc/hapi.py:5088-5124
     volumeConcentration           misc/hapi.py:10163-10164
+    transmittanceSpectrum, absorptionSpectrum, radianceSpectrum   misc/hapi.py:11582-11680   -> rtx_hapi_spectrum
+    SLIT_* (host NumPy), convolveSpectrum, convolveSpectrumSame, convolveSpectrumFull
+                                  misc/hapi.py:11742-11900   -> rtx_fir_same (fp64 direct FIR)
 
-The database client (fetch/select/...), the other line profiles and the slit functions are out of
-scope. There is no CPU fallback: without the HIP library and a
-GPU, absorptionCoefficient_Voigt raises.
+The database client (fetch/select/...) and the other line profiles are out of scope (SURVEY.md
+section 2, rows 12-13). There is no CPU fallback: without the HIP library and a GPU,
+absorptionCoefficient_Voigt and the spectrum / convolution functions raise.
 """
 import math
 
@@ -442,3 +445,184 @@ def db_begin(db=None):
 def tableList():
     """Names of the cached tables (misc/hapi.py:5168)."""
     return list(LOCAL_TABLE_CACHE.keys())
+
+
+# ---- spectra from an absorption coefficient, and their convolution with a slit function --------------------------------
+# (misc/hapi.py:11582-11680, 11742-11900: steps 2 and 3 of the usual hapi workflow after absorptionCoefficient_*)
+cBolts = engine.CBOLTS   # erg/K  (misc/hapi.py:84)
+cc = 2.99792458e10       # cm/s   (:85)
+hh = 6.626196e-27        # erg s  (:86)
+
+
+def _spectral_rows(A, n):
+    """A spectrum (n,) or a batch (n, nS), spectral axis first; NumPy or torch (float32 / float64) -> (rows, back):
+    rows [nS][n] device tensor with contiguous rows, back(out [nS][m]) -> (m,) or (m, nS) of the caller's kind: NumPy
+    float64 for NumPy in, a torch tensor on the input's device for torch in."""
+    as_torch = isinstance(A, torch.Tensor)
+    dev = engine.device()
+    if as_torch:
+        src_dev = A.device
+        t = A if A.dtype in (torch.float32, torch.float64) else A.to(torch.float64)
+        t = t.to(dev if not A.is_cuda else A.device)
+    else:
+        src_dev = None
+        t = torch.as_tensor(np.ascontiguousarray(A, dtype=np.float64), device=dev)
+    if t.dim() not in (1, 2) or t.shape[0] != n:
+        raise ValueError("spectrum of shape %s on a wavenumber grid of %d points (spectral axis first)" % (tuple(t.shape), n))
+    one = t.dim() == 1
+    rows = t[None].contiguous() if one else t.t().contiguous()
+
+    def back(out):
+        out = out[0] if one else out.t().contiguous()
+        if as_torch:
+            return out.to(src_dev)
+        return out.cpu().numpy()
+
+    return rows, back
+
+
+def _save_to_file(File, Format, Omegas, Xsect):
+    """misc/hapi.py:10286-10293."""
+    O = Omegas.detach().cpu().numpy() if isinstance(Omegas, torch.Tensor) else np.asarray(Omegas)
+    Y = Xsect.detach().cpu().numpy() if isinstance(Xsect, torch.Tensor) else np.asarray(Xsect)
+    with open(File, "w") as f:
+        for i in range(len(O)):
+            f.write((Format + "\n") % (O[i], Y[i]))
+
+
+def _spectrum(kind, Omegas, AbsorptionCoefficient, Environment, File, Format, Wavenumber):
+    if Wavenumber is not None: Omegas = Wavenumber
+    l = Environment["l"]
+    T = Environment["T"] if kind == 2 else 0.0
+    rows, back = _spectral_rows(AbsorptionCoefficient, len(Omegas))
+    X = None
+    if kind == 2:
+        X = (Omegas.to(device=rows.device, dtype=torch.float64) if isinstance(Omegas, torch.Tensor)
+             else torch.as_tensor(np.ascontiguousarray(Omegas, dtype=np.float64), device=rows.device)).contiguous()
+    Xsect = back(engine.hapi_spectrum(kind, rows, l, T, X))
+    if File: _save_to_file(File, Format, Omegas, Xsect)
+    return Omegas, Xsect
+
+
+def transmittanceSpectrum(Omegas, AbsorptionCoefficient, Environment={"l": 100.}, File=None, Format="%e %e", Wavenumber=None):
+    """exp(-AbsorptionCoefficient * l), l = Environment['l'] in cm; same inputs / outputs as misc/hapi.py:11582-11611.
+    AbsorptionCoefficient: (n,) or (n, nS) (a batch, spectral axis first), NumPy -> NumPy float64, torch -> torch on its device."""
+    return _spectrum(0, Omegas, AbsorptionCoefficient, Environment, File, Format, Wavenumber)
+
+
+def absorptionSpectrum(Omegas, AbsorptionCoefficient, Environment={"l": 100.}, File=None, Format="%e %e", Wavenumber=None):
+    """1 - exp(-AbsorptionCoefficient * l); misc/hapi.py:11613-11642. Types as transmittanceSpectrum."""
+    return _spectrum(1, Omegas, AbsorptionCoefficient, Environment, File, Format, Wavenumber)
+
+
+def radianceSpectrum(Omegas, AbsorptionCoefficient, Environment={"l": 100., "T": 296.}, File=None, Format="%e %e", Wavenumber=None):
+    """(1 - exp(-AbsorptionCoefficient * l)) * Planck(Omegas, T) in W/sr/cm^2/cm^-1 with hapi's own hh, cc, cBolts and its
+    1.0E-7 factor (misc/hapi.py:11644-11680), not radiative_transfer's c1 / c2. Types as transmittanceSpectrum."""
+    return _spectrum(2, Omegas, AbsorptionCoefficient, Environment, File, Format, Wavenumber)
+
+
+# Slit functions (x, g) -> y on the host: the slit has 1e2-1e5 points. Written from the formulas of misc/hapi.py:11742-11823
+# with the reference's quirks kept: the Gaussian and dispersion slits take g as the FULL width (they halve it), the cosine
+# slit is not clipped outside one period, the diffraction and Michelson slits return 1 -- not the limit -- at exactly x == 0.
+def SLIT_RECTANGULAR(x, g):
+    """1/g for |x| <= g/2, else 0."""
+    x = np.asarray(x, dtype=np.float64)
+    return np.where(np.abs(x) <= g / 2, 1 / g, 0.0)
+
+
+def SLIT_TRIANGULAR(x, g):
+    """(1 - |x|/g)/g for |x| <= g, else 0."""
+    x = np.asarray(x, dtype=np.float64)
+    return np.where(np.abs(x) <= g, 1 / g * (1 - np.abs(x) / g), 0.0)
+
+
+def SLIT_GAUSSIAN(x, g):
+    """sqrt(ln2/pi)/h * exp(-ln2 (x/h)^2), h = g/2 the half-width at half-maximum."""
+    h = g / 2
+    return np.sqrt(np.log(2)) / (np.sqrt(np.pi) * h) * np.exp(-np.log(2) * (np.asarray(x, dtype=np.float64) / h) ** 2)
+
+
+def SLIT_DISPERSION(x, g):
+    """h/pi/(x^2 + h^2), h = g/2 the Lorentzian half-width at half-maximum."""
+    h = g / 2
+    return h / np.pi / (np.asarray(x, dtype=np.float64) ** 2 + h ** 2)
+
+
+def SLIT_COSINUS(x, g):
+    """(cos(pi x/g) + 1)/(2g), every period of it."""
+    return (np.cos(np.pi / g * np.asarray(x, dtype=np.float64)) + 1) / (2 * g)
+
+
+def SLIT_DIFFRACTION(x, g):
+    """sin^2(pi x/g)/(pi x/g)^2/g; 1 at x == 0."""
+    x = np.asarray(x, dtype=np.float64)
+    y = np.ones(len(x))
+    nz = x != 0
+    a = np.pi / g * x[nz]
+    y[nz] = np.sin(a) ** 2 / a ** 2 / g
+    return y
+
+
+def SLIT_MICHELSON(x, g):
+    """2/g sin(2 pi x/g)/(2 pi x/g), the ideal Michelson interferometer with maximum path difference 1/g; 1 at x == 0."""
+    x = np.asarray(x, dtype=np.float64)
+    y = np.ones(len(x))
+    nz = x != 0
+    a = 2 * np.pi / g * x[nz]
+    y[nz] = 2 / g * np.sin(a) / a
+    return y
+
+
+def _fir(CrossSection, n, taps, scale, first, n_out):
+    """scale * (points [first, first + n_out) of the zero-padded convolution of CrossSection (n,) / (n, nS) with taps), on the
+    GPU (rtx_fir_same); the only device step of convolveSpectrum*."""
+    rows, back = _spectral_rows(CrossSection, n)
+    return back(engine.fir_same(rows, taps, scale, first, n_out))
+
+
+def _convolve(Omega, CrossSection, Resolution, AF_wing, SlitFunction, full):
+    """The body the three convolveSpectrum* share: slit on x = [-AF_wing, AF_wing] at the grid's step, then the window of
+    the zero-padded convolution that numpy.convolve returns ('same' cut to len(Omega) points, or 'full'), times step."""
+    step = Omega[1] - Omega[0]
+    step = float(step.item() if isinstance(step, torch.Tensor) else step)
+    if full:
+        x = np.arange(-AF_wing, AF_wing + step, step)  # plain arange, as the reference (:11891)
+    else:
+        if step >= Resolution: raise Exception("step must be less than resolution")
+        x = arange_(-AF_wing, AF_wing + step, step)
+    slit = np.asarray(SlitFunction(x, Resolution), dtype=np.float64)
+    if not full:
+        slit = slit / (sum(slit) * step)  # simple normalization (:11861; the reference's sum is Python's, left to right)
+    n, m = len(Omega), len(slit)
+    # numpy.convolve(..., 'same') has max(n, m) points; the reference keeps the first n of them (:11865, :11884)
+    first, n_out = (0, n + m - 1) if full else (engine.same_window(n, m)[0], n)
+    return _fir(CrossSection, n, slit, step, first, n_out), slit
+
+
+def convolveSpectrum(Omega, CrossSection, Resolution=0.1, AF_wing=10., SlitFunction=SLIT_RECTANGULAR, Wavenumber=None):
+    """Convolution with an instrument (slit) function, cut to the part the slit covers fully; misc/hapi.py:11826-11865.
+    Returns (Omega[l:r], Y[l:r], l, r, slit), l = len(slit)//2, r = len(Omega) - len(slit)//2 (the reference computes
+    len(slit)/2, a float on Python 3, and raises TypeError at the slice: DESIGN.md section 1). SlitFunction: a SLIT_*
+    or any callable (x, g) -> y. CrossSection: (n,) or (n, nS), NumPy -> NumPy float64, torch -> torch on its device.
+    The sum runs on the GPU in fp64, directly (rtx_fir_same; no FFT)."""
+    if Wavenumber is not None: Omega = Wavenumber
+    Y, slit = _convolve(Omega, CrossSection, Resolution, AF_wing, SlitFunction, False)
+    left_bnd = len(slit) // 2
+    right_bnd = len(Omega) - len(slit) // 2
+    return Omega[left_bnd:right_bnd], Y[left_bnd:right_bnd], left_bnd, right_bnd, slit
+
+
+def convolveSpectrumSame(Omega, CrossSection, Resolution=0.1, AF_wing=10., SlitFunction=SLIT_RECTANGULAR, Wavenumber=None):
+    """convolveSpectrum on the whole of Omega (zero-padded ends); misc/hapi.py:11868-11884. Returns
+    (Omega, Y, 0, len(Omega), slit). With a slit longer than the spectrum Y is what the reference returns: the first
+    len(Omega) points of numpy's max(n, m)-point 'same' result."""
+    if Wavenumber is not None: Omega = Wavenumber
+    Y, slit = _convolve(Omega, CrossSection, Resolution, AF_wing, SlitFunction, False)
+    return Omega[0:len(Omega)], Y, 0, len(Omega), slit
+
+
+def convolveSpectrumFull(Omega, CrossSection, Resolution=0.1, AF_wing=10., SlitFunction=SLIT_RECTANGULAR):
+    """The full convolution (len(Omega) + len(slit) - 1 points) with the un-normalised slit; misc/hapi.py:11886-11900
+    without its debug prints. Returns (Omega, Y, None, None)."""
+    Y, _ = _convolve(Omega, CrossSection, Resolution, AF_wing, SlitFunction, True)
+    return Omega, Y, None, None
