@@ -431,6 +431,41 @@ int rtx_fir_same(const void* in, int in_is_f64, int64_t ld_in, int n_rows, int64
 int rtx_fir_tile_points(void);
 int rtx_fir_chunk_taps(void);
 
+/* ---- optical depths from AFIT_XS cross-section tables -----------------------------------
+ * The reference writes one cross-section file per molecule and (T, p) state (misc/RT_gen_AbsXS_files.py:45-92) and has no
+ * reader for them; this is the consumer. An rtx_xs_lut is the device copy of such a set: n_rows fp32 rows of nx points
+ * on one uniform axis, x fastest, each row 16-byte aligned; which molecule and node a row belongs to, and the power of
+ * two each molecule's rows were multiplied by, is the caller's book-keeping (radtxfr_amd/afit_xs.py: XsLut).
+ *   rtx_xs_lut_create    n_mol molecules, n_rows rows in all, zero-filled. Allocates device memory and synchronises.
+ *   rtx_xs_lut_free      waits for the device, then releases the table and its term buffers.
+ *   rtx_xs_lut_bytes     device bytes of the table.
+ *   rtx_xs_lut_set_rows  rows [row0, row0 + n_rows) <- rows_h[n_rows][nx] (host, dense; page-locked memory makes the copy
+ *                        asynchronous: the caller keeps it unchanged until `stream` has passed the copy).
+ *   rtx_xs_lut_get_rows  the inverse, into rows_h; synchronises `stream`.
+ *   rtx_xs_od            od_f32[l][i] = sum_{m < n_mol} sum_{c < 4} weight_h[l][m][c] * row rows_h[l][m][c] at point
+ *                        x_offset + i, for l < n_layers, i < n: fp32 [n_layers][ld], the layout rtx_voigt_sum writes, so
+ *                        rtx_tud takes it unchanged. rows_h / weight_h are HOST arrays [n_layers][n_mol][4] (the four
+ *                        corners of the bracketing (T, p) cell, weights carrying column amount, bilinear factor and the
+ *                        molecule's power of two); every row index is checked against the table, every weight must be
+ *                        finite. Per point the sum is one fp32 fmaf chain in the order given (molecule, then corner); a
+ *                        term whose weight is exactly 0 is skipped and its row is not read. The value of a point is thus a
+ *                        function of (table, layer, point) alone: bit-identical for every x_offset / n cut of an axis.
+ *                        The terms are copied (hipMemcpyAsync on `stream`, staged before returning) into a grow-only
+ *                        device buffer owned by the table, one per stream that has used it: the first call on a stream,
+ *                        or a larger one, allocates and therefore synchronises; every other call only enqueues.
+ *                        16-byte accesses when x_offset and ld are multiples of 4 and od_f32 is 16-byte aligned
+ *                        (point by point for the ragged end of the last tile); otherwise point by point throughout.
+ *   rtx_xs_tile_points   consecutive points one workgroup owns (for tests at the edges). */
+typedef struct rtx_xs_lut rtx_xs_lut;
+int rtx_xs_lut_create(int n_mol, int64_t n_rows, int64_t nx, rtx_xs_lut** out);
+int rtx_xs_lut_free(rtx_xs_lut* lut);
+int64_t rtx_xs_lut_bytes(const rtx_xs_lut* lut);
+int rtx_xs_lut_set_rows(rtx_xs_lut* lut, int64_t row0, int64_t n_rows, const float* rows_h, void* stream);
+int rtx_xs_lut_get_rows(const rtx_xs_lut* lut, int64_t row0, int64_t n_rows, float* rows_h, void* stream);
+int rtx_xs_od(rtx_xs_lut* lut, int64_t x_offset, int64_t n, int n_layers, const int32_t* rows_h, const float* weight_h,
+              float* od_f32, int64_t ld, void* stream);
+int rtx_xs_tile_points(void);
+
 /* ------------------------------------------------------------------------------------------
  * Single-process collectives over the GPUs of one node. The reference has no multi-GPU code; its scripts are plain
  * Python programs that fan work out with multiprocessing (Generate_LWIR_TUD.py:117-150). These three calls let ONE host

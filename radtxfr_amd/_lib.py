@@ -74,6 +74,13 @@ PROTOTYPES = {
     "rtx_fir_chunk_taps": (_i32, []),
     "rtx_brightness_temperature": (_i32, [_vp, _i64, _vp, _i64, _i32, _dbl, _vp, _vp]),
     "rtx_bt2l": (_i32, [_vp, _i64, _vp, _i64, _i32, _dbl, _vp, _vp]),
+    "rtx_xs_lut_create": (_i32, [_i32, _i64, _i64, C.POINTER(_vp)]),
+    "rtx_xs_lut_free": (_i32, [_vp]),
+    "rtx_xs_lut_bytes": (_i64, [_vp]),
+    "rtx_xs_lut_set_rows": (_i32, [_vp, _i64, _i64, _vp, _vp]),
+    "rtx_xs_lut_get_rows": (_i32, [_vp, _i64, _i64, _vp, _vp]),
+    "rtx_xs_od": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "rtx_xs_tile_points": (_i32, []),
     "rtx_comm_init_all": (_i32, [_i32, _vp, _i32, C.POINTER(_vp)]),
     "rtx_comm_backend": (_i32, [_vp]),
     "rtx_allgather": (_i32, [_vp, _vp, _vp, _i64, _vp]),

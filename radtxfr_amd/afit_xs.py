@@ -9,7 +9,13 @@ File layout (little endian), as the reference's `AFIT_XS_write` produces it (its
 Default file name: XS-{ID:02d}-{T:04d}K-{P:06d}Pa.bin (:73).
 
 The reference computes one (T, p) state per hapi call; here all states of the grid go through ONE prologue + line-sum
-launch as "layers" (rtx_line_prep + rtx_voigt_sum), 128 states at a time."""
+launch as "layers" (rtx_line_prep + rtx_voigt_sum), 128 states at a time.
+
+XsLut is the consumer the reference lacks: the files (or cross_section_grid's arrays) as one device-resident table from
+which rt.compute_OD / compute_TUD / compute_TUD_batch(xs_lut=...) look optical depths up per layer instead of summing
+lines."""
+import ctypes as C
+import os
 import struct
 
 import numpy as np
@@ -141,3 +147,258 @@ def generate_xs_files(SourceTables, ID, T, P_atm, X, descr, WavenumberWingHW=50.
             fn = "XS-{0:02d}-{1:04d}K-{2:06d}Pa.bin".format(int(ID), int(t), int(101325 * p))
             names.append(AFIT_XS_write(X, xs[it, ip], t, 101325 * p, ID, descr, File=os.path.join(directory, fn)))
     return names
+
+
+# ---- the table as a look-up: XsLut ---------------------------------------------------------
+def group_xs_files(paths):
+    """from_files' parsing step, host only: AFIT_XS files -> from_grids entries, one per molecule in ascending ID, T and
+    P_atm (header Pa / 101325) ascending, xs[iT][iP] the file of that node. ValueError: a file whose n does not match its
+    length, files on different axes, a molecule whose files do not form a full T x P rectangle."""
+    by_id, axis = {}, None
+    for fn in paths:
+        with open(fn, "rb") as f:
+            head = f.read(_HEADER.size)
+        if len(head) < _HEADER.size or head[:2] != b"v1":
+            raise ValueError("%s is not an AFIT_XS v1 file" % fn)
+        n = _HEADER.unpack(head)[3]
+        if n != int(n) or n < 2 or os.path.getsize(fn) != _HEADER.size + 8 * int(n):
+            raise ValueError("%s: the header says n = %r points, the file holds %g" % (fn, n, (os.path.getsize(fn) - _HEADER.size) / 8.0))
+        d = AFIT_XS_read(fn)
+        ax = (d["Xmin"], d["Xmax"], d["n"])
+        if axis is None:
+            axis = (ax, fn)
+        elif ax != axis[0]:
+            raise ValueError("AFIT_XS files on different axes: %s has (Xmin, Xmax, n) = %r, %s has %r" % (axis[1], axis[0], fn, ax))
+        by_id.setdefault(d["ID"], []).append((float(d["T"]), float(d["P"]) / 101325.0, d["Y"], fn))
+    entries = []
+    for mid in sorted(by_id):
+        files = by_id[mid]
+        Ts = sorted({f[0] for f in files})
+        Ps = sorted({f[1] for f in files})
+        cells = {(f[0], f[1]): f for f in files}
+        if len(files) != len(Ts) * len(Ps) or len(cells) != len(files):
+            missing = [(t, p) for t in Ts for p in Ps if (t, p) not in cells]
+            raise ValueError("molecule %d: %d files do not form a full T x P rectangle of %d x %d nodes (missing (T [K], p [atm]): %r)"
+                             % (mid, len(files), len(Ts), len(Ps), missing[:4]))
+        xs = np.stack([np.stack([cells[(t, p)][2] for p in Ps]) for t in Ts])
+        entries.append({"ID": mid, "T": np.array(Ts), "P_atm": np.array(Ps), "X": np.linspace(*axis[0][:2], axis[0][2]), "xs": xs})
+    if not entries:
+        raise ValueError("XsLut.from_files: no files")
+    return entries
+
+
+def check_xs_entries(entries):
+    """Validate from_grids entries (host only): [(ID, T[nT], P_atm[nP], xs[nT][nP][nX])] and the common engine.Grid."""
+    out, grid, X0 = [], None, None
+    for e in entries:
+        mid = int(e["ID"])
+        T = np.atleast_1d(np.asarray(e["T"], dtype=np.float64))
+        P = np.atleast_1d(np.asarray(e["P_atm"], dtype=np.float64))
+        X = np.asarray(e["X"], dtype=np.float64).ravel()
+        xs = np.asarray(e["xs"], dtype=np.float64)
+        if T.ndim != 1 or T.size < 1 or np.any(np.diff(T) <= 0) or not np.all(np.isfinite(T)):
+            raise ValueError("XsLut: molecule %d: T must be strictly ascending, got %r" % (mid, T))
+        if P.ndim != 1 or P.size < 1 or np.any(np.diff(P) <= 0) or not np.all(np.isfinite(P)) or P[0] <= 0:
+            raise ValueError("XsLut: molecule %d: P_atm must be strictly ascending and > 0, got %r" % (mid, P))
+        if grid is None:
+            try:
+                grid, X0 = engine.Grid.from_axis(X), X
+            except NotImplementedError as err:
+                raise ValueError("XsLut: X must be a uniform ascending axis (%s)" % err)
+        elif X.size != X0.size or np.max(np.abs(X - X0)) > 1e-9 * grid.step:
+            raise ValueError("XsLut: molecule %d is on another axis (%d points from %.9g to %.9g) than molecule %d (%d points from "
+                             "%.9g to %.9g)" % (mid, X.size, X[0], X[-1], out[0][0], X0.size, X0[0], X0[-1]))
+        if xs.shape != (T.size, P.size, X.size):
+            raise ValueError("XsLut: molecule %d: xs has shape %r, expected [nT][nP][nX] = %r" % (mid, xs.shape, (T.size, P.size, X.size)))
+        if not np.all(np.isfinite(xs)) or xs.min() < 0:
+            raise ValueError("XsLut: molecule %d: cross sections must be finite and >= 0" % mid)
+        if any(mid == o[0] for o in out):
+            raise ValueError("XsLut: molecule %d is given twice" % mid)
+        out.append((mid, T, P, xs))
+    if not out:
+        raise ValueError("XsLut: no entries")
+    return out, grid
+
+
+def bracket(nodes, v, log=False):
+    """The interpolation rule on one axis, host float64: (i, f) with nodes[i] <= v <= nodes[i+1] and f the fraction of the
+    way from node i to node i + 1, linear in v (log=False: T) or in ln v (log=True: p). v on a node gives f exactly 0 (1 on
+    the last node). An axis with one node is not interpolated: (0, 0) for every v. No range check here."""
+    nodes = np.asarray(nodes, dtype=np.float64)
+    v = np.atleast_1d(np.asarray(v, dtype=np.float64))
+    if nodes.size == 1:
+        return np.zeros(v.size, dtype=np.int64), np.zeros(v.size)
+    i = np.clip(np.searchsorted(nodes, v, side="right") - 1, 0, nodes.size - 2)
+    a, b = nodes[i], nodes[i + 1]
+    if log:
+        a, b, v = np.log(a), np.log(b), np.log(v)
+    return i, (v - a) / (b - a)
+
+
+def layer_terms(tables, T, P_atm, PL_km, MF_VAL, MF_ID):
+    """Node rows and weights of every (layer, molecule), host float64.
+    tables: [(ID, T_nodes, P_nodes, row0)] in table order, row0 the table row of node (0, 0) (rows iT * nP + iP follow).
+    Returns rows int32 [L][M][4] and w float64 [L][M][4] for the corners (iT, iP), (iT, iP+1), (iT+1, iP), (iT+1, iP+1):
+        w = N * [(1-fT)(1-fP), (1-fT) fP, fT (1-fP), fT fP],   N = MF_VAL * 1e-6 * volumeConcentration(p, T) * PL * 1e5
+    with (iT, fT) linear in T and (iP, fP) linear in ln p (bracket). A molecule of the table that MF_ID lacks, or whose
+    MF_VAL is 0 in a layer, has weight 0 there (and is not range-checked). ValueError: a molecule of MF_ID the table lacks; a
+    layer outside the node range of a molecule it uses (no extrapolation, no clamping)."""
+    T = np.atleast_1d(np.asarray(T, dtype=np.float64))
+    p = np.atleast_1d(np.asarray(P_atm, dtype=np.float64))
+    PL = np.atleast_1d(np.asarray(PL_km, dtype=np.float64))
+    nL = T.size
+    MF = np.asarray(MF_VAL, dtype=np.float64).reshape(nL, -1)
+    ids = [int(v) for v in np.asarray(MF_ID).ravel()]
+    have = [t[0] for t in tables]
+    lacking = [m for m in ids if m not in have]
+    if lacking:
+        raise ValueError("xs_lut: MF_ID names molecule(s) %r, the table holds %r" % (lacking, have))
+    nvol = engine.volumeConcentration(p, T)
+    rows = np.zeros((nL, len(tables), 4), dtype=np.int32)
+    w = np.zeros((nL, len(tables), 4))
+    for m, (mid, Tn, Pn, row0) in enumerate(tables):
+        rows[:, m, :] = row0
+        if mid not in ids:
+            continue
+        N = nvol * (MF[:, ids.index(mid)] * 1e-6) * PL * 1e5  # layer_weights_od's operations, in its order
+        for name, unit, nodes, v in (("T", "K", Tn, T), ("p", "atm", Pn, p)):
+            bad = (N != 0) & ((v < nodes[0]) | (v > nodes[-1])) if nodes.size > 1 else np.zeros(nL, dtype=bool)
+            if bad.any():
+                l = int(np.flatnonzero(bad)[0])
+                raise ValueError("xs_lut: layer %d (%s = %.9g %s) lies outside molecule %d's table range [%.9g, %.9g] %s; there is "
+                                 "no extrapolation" % (l, name, v[l], unit, mid, nodes[0], nodes[-1], unit))
+        iT, fT = bracket(Tn, T)
+        iP, fP = bracket(Pn, p, log=True)
+        iT1, iP1 = np.minimum(iT + 1, Tn.size - 1), np.minimum(iP + 1, Pn.size - 1)
+        rows[:, m, :] = row0 + np.stack([iT * Pn.size + iP, iT * Pn.size + iP1, iT1 * Pn.size + iP, iT1 * Pn.size + iP1], axis=1)
+        w[:, m, :] = N[:, None] * np.stack([(1 - fT) * (1 - fP), (1 - fT) * fP, fT * (1 - fP), fT * fP], axis=1)
+    return rows, w
+
+
+def align_axis(table_grid, grid):
+    """Index of grid's first point (of the whole axis, shard offset not counted) on table_grid when `grid` coincides with a
+    contiguous run of it -- same spacing, every point within 1e-9 of a step of a table point -- else ValueError naming both
+    axes. There is no spectral interpolation."""
+    tg, n = table_grid, grid.n_total
+    k = int(round((grid.xmin - tg.xmin) / tg.step))
+    ok = 0 <= k and k + n <= tg.n_total
+    if ok:  # both ends within the bound: the points between are linear in the index on both axes
+        tol = 1e-9 * tg.step + 4 * np.spacing(max(abs(tg.xmin), abs(tg.xmax)))  # plus the rounding of the axis values themselves
+        ok = abs(grid.xmin - tg.x_at(k - tg.offset)) <= tol and abs(grid.xmax - tg.x_at(k + n - 1 - tg.offset)) <= tol
+    if not ok:
+        raise ValueError("xs_lut: the requested axis (%d points from %.9g to %.9g, step %.9g) is not a contiguous run of the table's "
+                         "axis (%d points from %.9g to %.9g, step %.9g); there is no spectral interpolation"
+                         % (n, grid.xmin, grid.xmax, grid.step, tg.n_total, tg.xmin, tg.xmax, tg.step))
+    return k
+
+
+_UPLOAD = {}  # one reusable pinned staging block for XsLut uploads (grow-only, like _STAGE for the way out)
+_UPLOAD_BYTES = 64 << 20
+
+
+class XsLut:
+    """Cross-section tables of several molecules, resident on the current device as fp32 rows [molecule][iT][iP][x] (x
+    fastest) behind an rtx_xs_lut handle (include/radtxfr_hip.h). Each molecule's rows are multiplied by its own power of
+    two, 2**exponent(ID), so that its largest value lands in [1, 2) (1e-19 ... 1e-30 cm^2 is not fp32 material; the line
+    strengths use the same device); the weights of a look-up carry 2**-exponent.
+
+        lut = XsLut.from_grids([dict(ID=1, T=T, P_atm=P, X=X, xs=cross_section_grid(tbl, T, P, X, Components=...)), ...])
+        lut = XsLut.from_files(generate_xs_files(...) + ...)
+        rt.compute_TUD(Xmin, Xmax, xs_lut=lut, ...)
+
+    Public: molecules (IDs in table order), grid (engine.Grid of the axis), nodes(ID) -> (T, P_atm), exponent(ID),
+    rows(ID) (the device rows read back, float32 [nT][nP][nX]), nbytes, device; free() or del releases the device memory.
+    Interpolation rule and summation order: layer_terms, DESIGN.md section 4.11."""
+
+    def __init__(self, entries):
+        tabs, self.grid = check_xs_entries(entries)
+        engine.require_gpu()
+        self._lib = _lib.load()
+        self.device = engine.device()
+        self.molecules = tuple(t[0] for t in tabs)
+        self._tables, self._exp, row0 = [], {}, 0
+        for mid, T, P, xs in tabs:
+            self._tables.append((mid, T, P, row0))
+            mx = float(xs.max())
+            self._exp[mid] = 1 - int(np.frexp(mx)[1]) if mx > 0 else 0  # mx * 2**e in [1, 2)
+            row0 += T.size * P.size
+        self.n_rows = row0
+        self._scale = np.array([2.0 ** -self._exp[m] for m in self.molecules])  # folded into the fp32 weights
+        h = C.c_void_p()
+        _lib.check(self._lib.rtx_xs_lut_create(len(tabs), self.n_rows, self.grid.n_total, C.byref(h)))
+        self._h = h
+        nx = self.grid.n_total
+        per = max(1, min(self.n_rows, _UPLOAD_BYTES // (4 * nx)))
+        pinned = _UPLOAD.get("buf")
+        if pinned is None or pinned.numel() < per * nx:
+            pinned = _UPLOAD["buf"] = torch.empty((per * nx,), dtype=torch.float32, pin_memory=True)
+        stage = pinned[:per * nx].view(per, nx).numpy()
+        st = torch.cuda.current_stream()
+        for (mid, T, P, r0), (_, _, _, xs) in zip(self._tables, tabs):
+            flat = xs.reshape(-1, nx)
+            for a in range(0, flat.shape[0], per):
+                k = min(per, flat.shape[0] - a)
+                np.ldexp(flat[a:a + k], self._exp[mid], out=stage[:k], casting="same_kind")  # exact scaling, one rounding to fp32
+                _lib.check(self._lib.rtx_xs_lut_set_rows(self._h, r0 + a, k, stage.ctypes.data_as(C.c_void_p), C.c_void_p(st.cuda_stream)))
+                st.synchronize()  # the block is refilled next
+
+    @classmethod
+    def from_grids(cls, entries):
+        """entries: one dict per molecule with ID, T[nT] (K, strictly ascending), P_atm[nP] (strictly ascending, > 0), X[nX]
+        (uniform, the same for all) and xs[nT][nP][nX] float64 cm^2/molecule (finite, >= 0): what cross_section_grid
+        returns. nT == 1 or nP == 1 is allowed; that axis is then not interpolated (any layer value is accepted on it)."""
+        return cls(list(entries))
+
+    @classmethod
+    def from_files(cls, paths):
+        """The same table from AFIT_XS files (group_xs_files: grouped by ID, T and P from the headers)."""
+        return cls(group_xs_files(list(paths)))
+
+    def _table(self, ID):
+        for t in self._tables:
+            if t[0] == int(ID):
+                return t
+        raise KeyError("XsLut holds molecules %r, not %r" % (self.molecules, ID))
+
+    def nodes(self, ID):
+        _, T, P, _ = self._table(ID)
+        return T.copy(), P.copy()
+
+    def exponent(self, ID):
+        return self._exp[self._table(ID)[0]]
+
+    @property
+    def nbytes(self):
+        return int(self._lib.rtx_xs_lut_bytes(self._handle()))
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("this XsLut has been freed")
+        return self._h
+
+    def rows(self, ID):
+        mid, T, P, r0 = self._table(ID)
+        out = np.empty((T.size * P.size, self.grid.n_total), dtype=np.float32)
+        _lib.check(self._lib.rtx_xs_lut_get_rows(self._handle(), r0, out.shape[0], out.ctypes.data_as(C.c_void_p),
+                                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return out.reshape(T.size, P.size, -1)
+
+    def align(self, grid):
+        return align_axis(self.grid, grid)
+
+    def layer_terms(self, T, P_atm, PL_km, MF_VAL, MF_ID):
+        """rtx_xs_od's host inputs for one atmosphere: rows int32 [L][M][4], weights float32 [L][M][4] (layer_terms' float64
+        weights times the molecule's 2**-exponent, rounded once)."""
+        rows, w = layer_terms(self._tables, T, P_atm, PL_km, MF_VAL, MF_ID)
+        return np.ascontiguousarray(rows), np.ascontiguousarray((w * self._scale[None, :, None]).astype(np.float32))
+
+    def free(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            self._lib.rtx_xs_lut_free(h)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass

@@ -1,0 +1,195 @@
+// Optical depths from AFIT_XS cross-section tables: the table lives on the device as fp32 rows
+// [row][x] (one row per molecule and (T, p) node, x fastest), and rtx_xs_od forms
+//   OD[l][x] = sum_m sum_{c=0..3} w[l][m][c] * row[rows[l][m][c]][x]
+// from host-made node rows and weights. One kernel, bandwidth-bound: no LDS, a handful of registers.
+#include <mutex>
+#include <vector>
+
+#include "rtx_common.h"
+
+#define XS_BLOCK 256
+#define XS_PER 4                       // points per thread: one 16-byte access
+#define XS_TILE (XS_BLOCK * XS_PER)    // consecutive points owned by a workgroup
+
+// per-stream device copy of the terms of the last rtx_xs_od on that stream (grow-only): two streams may run the same table
+// at once (compute_TUD_batch's two runners), and within a stream the copy is ordered behind the previous kernel
+struct XsTerms {
+  hipStream_t stream;
+  int* rows;
+  float* w;
+  size_t cap;  // terms
+};
+
+struct rtx_xs_lut {
+  int n_mol;
+  long long n_rows, nx, ldx;  // ldx: row stride in floats, a multiple of 4 (every row starts 16-byte aligned)
+  float* data;                // [n_rows][ldx]
+  int dev;
+  std::mutex mu;
+  std::vector<XsTerms> terms;
+};
+
+// A workgroup owns XS_TILE consecutive points and walks all layers: a node's segment of the tile comes from HBM about
+// once and from cache for every further layer (and corner) that names it. `rows` / `w` are wave-uniform: they travel
+// through the scalar cache. Per point the sum is ONE fmaf chain in term order (molecule, then corner), terms with w == 0
+// skipped and their row not read: a pure function of (table, layer, point), whatever the tile, x_off or n.
+// VEC: x_off % 4 == 0 and the output rows are 16-byte aligned, so a thread's four points are one 16-byte load per term
+// and one 16-byte store; the ragged end of the last tile, and every point otherwise, goes point by point.
+template <bool VEC>
+__global__ __launch_bounds__(XS_BLOCK) void xs_od_kernel(const float* __restrict__ tab, long long ldx, long long x_off, long long n,
+                                                         int n_layers, int n_terms, const int* __restrict__ rows,
+                                                         const float* __restrict__ w, float* __restrict__ od, long long ld) {
+  const long long i0 = (long long)blockIdx.x * XS_TILE + (long long)threadIdx.x * XS_PER;
+  if (i0 >= n) return;
+  const float* __restrict__ src = tab + x_off + i0;
+  const bool full = VEC && i0 + XS_PER <= n;
+  for (int l = 0; l < n_layers; ++l) {
+    const int* __restrict__ rl = rows + (size_t)l * n_terms;
+    const float* __restrict__ wl = w + (size_t)l * n_terms;
+    float* __restrict__ dst = od + (size_t)l * (size_t)ld + (size_t)i0;
+    if (full) {
+      float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      for (int t = 0; t < n_terms; ++t) {
+        const float wt = wl[t];
+        if (wt == 0.0f) continue;
+        const float4 v = *reinterpret_cast<const float4*>(src + (size_t)rl[t] * (size_t)ldx);
+        acc.x = fmaf(wt, v.x, acc.x);
+        acc.y = fmaf(wt, v.y, acc.y);
+        acc.z = fmaf(wt, v.z, acc.z);
+        acc.w = fmaf(wt, v.w, acc.w);
+      }
+      *reinterpret_cast<float4*>(dst) = acc;
+    } else {
+      const int cnt = n - i0 < XS_PER ? (int)(n - i0) : XS_PER;
+      for (int j = 0; j < cnt; ++j) {
+        float acc = 0.0f;
+        for (int t = 0; t < n_terms; ++t) {
+          const float wt = wl[t];
+          if (wt == 0.0f) continue;
+          acc = fmaf(wt, src[(size_t)rl[t] * (size_t)ldx + j], acc);
+        }
+        dst[j] = acc;
+      }
+    }
+  }
+}
+
+extern "C" int rtx_xs_tile_points(void) { return XS_TILE; }
+
+extern "C" int rtx_xs_lut_create(int n_mol, int64_t n_rows, int64_t nx, rtx_xs_lut** out) {
+  if (!out) RTX_FAIL("out is NULL");
+  *out = nullptr;
+  if (n_mol < 1 || n_rows < n_mol || nx < 1) RTX_FAIL("n_mol=%d n_rows=%lld nx=%lld", n_mol, (long long)n_rows, (long long)nx);
+  if (n_rows > 0x7fffffffLL) RTX_FAIL("n_rows=%lld too large", (long long)n_rows);
+  rtx_xs_lut* L = new rtx_xs_lut();
+  L->n_mol = n_mol;
+  L->n_rows = n_rows;
+  L->nx = nx;
+  L->ldx = (nx + 3) / 4 * 4;
+  L->data = nullptr;
+  hipError_t e = hipGetDevice(&L->dev);
+  const size_t bytes = (size_t)n_rows * (size_t)L->ldx * sizeof(float);
+  if (e == hipSuccess) e = hipMalloc((void**)&L->data, bytes);
+  if (e == hipSuccess) e = hipMemset(L->data, 0, bytes);  // the pad columns are read by no kernel; rows not yet set are 0
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    if (L->data) (void)hipFree(L->data);
+    delete L;
+    RTX_FAIL("rtx_xs_lut_create: %lld rows of %lld points (%.1f MB) -> %s", (long long)n_rows, (long long)nx, bytes / 1.0e6,
+             hipGetErrorString(e));
+  }
+  *out = L;
+  return 0;
+}
+
+extern "C" int rtx_xs_lut_free(rtx_xs_lut* L) {
+  if (!L) return 0;
+  (void)hipFree(L->data);  // hipFree waits for the device: no kernel still reads the table or the terms
+  for (XsTerms& t : L->terms) {
+    (void)hipFree(t.rows);
+    (void)hipFree(t.w);
+  }
+  delete L;
+  return 0;
+}
+
+extern "C" int64_t rtx_xs_lut_bytes(const rtx_xs_lut* L) {
+  return L ? (int64_t)((size_t)L->n_rows * (size_t)L->ldx * sizeof(float)) : 0;
+}
+
+static int xs_check_rows(const rtx_xs_lut* L, int64_t row0, int64_t n_rows, const void* p) {
+  if (!L || !p) RTX_FAIL("a required pointer is NULL");
+  if (row0 < 0 || n_rows < 0 || row0 > L->n_rows - n_rows)
+    RTX_FAIL("rows [%lld, %lld) outside the table's %lld", (long long)row0, (long long)(row0 + n_rows), (long long)L->n_rows);
+  return 0;
+}
+
+extern "C" int rtx_xs_lut_set_rows(rtx_xs_lut* L, int64_t row0, int64_t n_rows, const float* rows_h, void* stream) {
+  if (xs_check_rows(L, row0, n_rows, rows_h)) return 1;
+  if (n_rows == 0) return 0;
+  RTX_HIP(hipMemcpy2DAsync(L->data + (size_t)row0 * (size_t)L->ldx, (size_t)L->ldx * sizeof(float), rows_h, (size_t)L->nx * sizeof(float),
+                           (size_t)L->nx * sizeof(float), (size_t)n_rows, hipMemcpyHostToDevice, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int rtx_xs_lut_get_rows(const rtx_xs_lut* L, int64_t row0, int64_t n_rows, float* rows_h, void* stream) {
+  if (xs_check_rows(L, row0, n_rows, rows_h)) return 1;
+  if (n_rows == 0) return 0;
+  RTX_HIP(hipMemcpy2DAsync(rows_h, (size_t)L->nx * sizeof(float), L->data + (size_t)row0 * (size_t)L->ldx, (size_t)L->ldx * sizeof(float),
+                           (size_t)L->nx * sizeof(float), (size_t)n_rows, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  RTX_HIP(hipStreamSynchronize((hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int rtx_xs_od(rtx_xs_lut* L, int64_t x_offset, int64_t n, int n_layers, const int32_t* rows_h, const float* weight_h,
+                         float* od_f32, int64_t ld, void* stream) {
+  if (!L || !rows_h || !weight_h || !od_f32) RTX_FAIL("a required pointer is NULL");
+  if (n_layers < 1) RTX_FAIL("n_layers=%d", n_layers);
+  if (x_offset < 0 || n < 0 || x_offset > L->nx - n)
+    RTX_FAIL("points [%lld, %lld) outside the table's axis of %lld points", (long long)x_offset, (long long)(x_offset + n),
+             (long long)L->nx);
+  if (ld < n) RTX_FAIL("ld=%lld smaller than n=%lld", (long long)ld, (long long)n);
+  if (n == 0) return 0;
+  if ((n + XS_TILE - 1) / XS_TILE > 0x7fffffffLL) RTX_FAIL("n=%lld too large", (long long)n);
+  int dev = 0;
+  RTX_HIP(hipGetDevice(&dev));
+  if (dev != L->dev) RTX_FAIL("the table lives on device %d, the current device is %d", L->dev, dev);
+  const int n_terms = 4 * L->n_mol;
+  const size_t cnt = (size_t)n_layers * (size_t)n_terms;
+  for (size_t t = 0; t < cnt; ++t) {  // a row index from outside is never trusted; a non-finite weight would poison a whole layer
+    if (rows_h[t] < 0 || rows_h[t] >= L->n_rows) RTX_FAIL("rows_h[%zu]=%d outside the table's %lld rows", t, rows_h[t], (long long)L->n_rows);
+    if (!isfinite(weight_h[t])) RTX_FAIL("weight_h[%zu] is not finite", t);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  // the lock is held until the kernel is enqueued: a larger call on another stream may grow ITS buffer meanwhile, never this one
+  std::lock_guard<std::mutex> lock(L->mu);
+  XsTerms* tb = nullptr;
+  for (XsTerms& t : L->terms)
+    if (t.stream == st) tb = &t;
+  if (!tb) {
+    L->terms.push_back(XsTerms{st, nullptr, nullptr, 0});
+    tb = &L->terms.back();
+  }
+  if (tb->cap < cnt) {  // grow-only; hipFree waits for the kernels that still read the old block
+    if (tb->rows) (void)hipFree(tb->rows);
+    if (tb->w) (void)hipFree(tb->w);
+    tb->rows = nullptr;
+    tb->w = nullptr;
+    tb->cap = 0;
+    RTX_HIP(hipMalloc((void**)&tb->rows, cnt * sizeof(int)));
+    RTX_HIP(hipMalloc((void**)&tb->w, cnt * sizeof(float)));
+    tb->cap = cnt;
+  }
+  RTX_HIP(hipMemcpyAsync(tb->rows, rows_h, cnt * sizeof(int), hipMemcpyHostToDevice, st));  // pageable: staged before returning
+  RTX_HIP(hipMemcpyAsync(tb->w, weight_h, cnt * sizeof(float), hipMemcpyHostToDevice, st));
+  const unsigned tiles = (unsigned)((n + XS_TILE - 1) / XS_TILE);
+  const bool vec = (x_offset % 4 == 0) && (ld % 4 == 0) && (((uintptr_t)od_f32 & 15) == 0);
+  if (vec)
+    hipLaunchKernelGGL(xs_od_kernel<true>, dim3(tiles), dim3(XS_BLOCK), 0, st, L->data, L->ldx, (long long)x_offset, (long long)n, n_layers,
+                       n_terms, tb->rows, tb->w, od_f32, (long long)ld);
+  else
+    hipLaunchKernelGGL(xs_od_kernel<false>, dim3(tiles), dim3(XS_BLOCK), 0, st, L->data, L->ldx, (long long)x_offset, (long long)n, n_layers,
+                       n_terms, tb->rows, tb->w, od_f32, (long long)ld);
+  RTX_LAUNCH_CHECK();
+  return 0;
+}

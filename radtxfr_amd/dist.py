@@ -70,6 +70,13 @@ def _no_broadening(fn, broadening):
                                   "radiative_transfer.compute_TUD / compute_TUD_batch" % (fn, broadening))
 
 
+def _no_xs_lut(fn, xs_lut):
+    """The sharded drivers sum lines: their shard plans are made from the line table (tud_shard_plan)."""
+    if xs_lut is not None:
+        raise NotImplementedError("%s: xs_lut is not supported by the sharded drivers; use radiative_transfer.compute_TUD / "
+                                  "compute_TUD_batch(xs_lut=...)" % fn)
+
+
 def _all_gather_flat(send, world, group=None):
     """ONE all_gather_into_tensor of equal flat blocks. RCCL ("nccl") gathers device buffers in place over xGMI; the
     gloo backend (CPU tests, and rehearsals of the N > 1 path with several ranks sharing one GPU) has no device
@@ -140,13 +147,15 @@ def tud_shard_plan(line_table, Xmin, Xmax, n_total, Ts, Ps, world, balance=True)
 
 
 def compute_TUD_sharded(Xmin, Xmax, DVOUT, line_table, Zs, Ts, Ps, PLs, MFs_VAL, MFs_ID, Altitudes=(500,), theta_r=0.0,
-                        N_angle=30, group=None, balance=True, broadening=None):
+                        N_angle=30, group=None, balance=True, broadening=None, xs_lut=None):
     """compute_TUD (radiative_transfer.py:274-392) with the spectral axis sharded over the ranks of
     `group`; every rank returns the full (X, tau, Lu, Ld) as float32 device tensors (X as NumPy fp64).
     One sensor altitude / slant path per call. Shards are tile-aligned (tud_shard_plan): the spectra are
-    bit-identical for every world size, including 1. broadening: None only (NotImplementedError otherwise)."""
+    bit-identical for every world size, including 1. broadening: None only, xs_lut: None only (NotImplementedError
+    otherwise)."""
     from . import engine
     _no_broadening("compute_TUD_sharded", broadening)
+    _no_xs_lut("compute_TUD_sharded", xs_lut)
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     n_total = int(np.ceil((Xmax - Xmin) / DVOUT))
     grid_full = engine.Grid(Xmin, Xmax, n_total)
@@ -184,9 +193,10 @@ class LocalShardedTud:
     One sensor altitude and slant path per object (the packed block carries three rows)."""
 
     def __init__(self, devices, Xmin, Xmax, DVOUT, line_table, Zs, Ts, Ps, Altitudes=(500,), theta_r=0.0, N_angle=30, balance=True,
-                 backend=-1, broadening=None):
+                 backend=-1, broadening=None, xs_lut=None):
         from . import comm, engine
         _no_broadening("LocalShardedTud", broadening)
+        _no_xs_lut("LocalShardedTud", xs_lut)
         self.devices = [int(d) for d in devices]
         world = len(self.devices)
         self.n_total = int(np.ceil((Xmax - Xmin) / DVOUT))

@@ -536,6 +536,30 @@ def optical_depths(lines, grid, T, P_pa, PL_km, MF_VAL, MF_ID, out=None, broaden
     return out
 
 
+def xs_od(lut, grid_or_offset, T, P_atm, PL, MF, ID, out_f32=None):
+    """OD[nL][n] float32 on the device from a cross-section table (afit_xs.XsLut; rtx_xs_od): the layout optical_depths
+    returns, so tud() and everything after it take it unchanged. grid_or_offset: a Grid whose axis coincides with a run of
+    the table's (ValueError otherwise; a shard of it gives that shard), or the index of the first point on the table's
+    axis, n then taken from out_f32. T [K], P_atm [atm], PL [km] per layer, MF[nL][nM] ppmv, ID[nM] HITRAN molecule
+    numbers. The node rows and weights are made on the host in float64 (afit_xs.layer_terms: linear in T and in ln p,
+    ValueError outside the table or for a molecule it lacks). Bit-identical for every cut of the axis."""
+    T = np.atleast_1d(np.asarray(T, dtype=np.float64))
+    rows, w = lut.layer_terms(T, P_atm, PL, MF, ID)
+    if isinstance(grid_or_offset, Grid):
+        off, n = lut.align(grid_or_offset) + grid_or_offset.offset, grid_or_offset.n
+    else:
+        off, n = int(grid_or_offset), None if out_f32 is None else out_f32.shape[1]
+        if n is None:
+            raise ValueError("engine.xs_od: an offset needs out_f32 (its row length is the number of points)")
+    if out_f32 is None:
+        out_f32 = torch.empty((T.size, (n + 3) // 4 * 4), dtype=torch.float32, device=device())[:, :n]  # rows 16 bytes apart
+    assert out_f32.dtype == torch.float32 and out_f32.is_cuda and out_f32.dim() == 2 and out_f32.shape[0] == T.size
+    assert out_f32.shape[1] >= n and out_f32.stride(1) == 1
+    _lib.check(_lib.load().rtx_xs_od(lut._handle(), off, n, T.size, rows.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p),
+                                     _ptr(out_f32), out_f32.stride(0) if T.size > 1 else max(out_f32.shape[1], n), _stream_ptr()))
+    return out_f32
+
+
 def tud(OD, grid, T, Z, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=False, per_angle=False, out=None):
     """tau[nAlt*nMu][n], Lu[nAlt*nMu][n], Ld[n] float32 device tensors from OD[nL][n] (rtx_tud).
     out=(tau, Lu, Ld): write into caller-owned tensors (tau/Lu [nAlt*nMu][>=n] with a common row stride),
@@ -605,13 +629,20 @@ class TudRunner:
     line-sum + TUD enqueued back to back). Outputs are float32 device tensors owned by the runner (or `out`), overwritten
     by the next run(): tau, Lu [nAlt*nMu][n], Ld [n], OD [nL][n].
     broadening: None (the fused rtx_compute_tud), "self" or ("self", gas, ...): each species broadened by its per-layer
-    mix (broadening_fractions), run as rtx_line_prep_mix + rtx_voigt_sum + rtx_tud -- the same line-sum and TUD kernels."""
+    mix (broadening_fractions), run as rtx_line_prep_mix + rtx_voigt_sum + rtx_tud -- the same line-sum and TUD kernels.
+    xs_lut: an afit_xs.XsLut instead of `lines` (None then): the optical depths come from the table (rtx_xs_od + rtx_tud);
+    `grid` must coincide with a run of the table's axis. Not with broadening (fixed when the table was made)."""
 
     def __init__(self, lines, grid, Z, n_layers=None, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=False, out=None,
-                 OD=None, plan=None, broadening=None):
+                 OD=None, plan=None, broadening=None, xs_lut=None):
         self.lib = _lib.load()
         self.lines, self.grid = lines, grid
         self.foreign = broadening_gases(broadening)
+        self.xs_lut = xs_lut
+        if xs_lut is not None:
+            if broadening is not None:
+                raise NotImplementedError("xs_lut with broadening=%r: a table's broadening was fixed when it was made" % (broadening,))
+            self._xs_off = xs_lut.align(grid) + grid.offset
         Z = np.atleast_1d(np.asarray(Z, dtype=np.float64))
         self.nL = int(Z.size if n_layers is None else n_layers)
         Z_s = np.array([Altitudes], dtype=np.float64).ravel()
@@ -634,6 +665,11 @@ class TudRunner:
         self.set_outputs(self.tau, self.Lu, self.Ld)
         # plan: a VoigtPlan of the caller's (two pipelines on one device must not share per-(line, layer) records);
         # default = the table's cached plan, shared by everything that runs on the device's current stream
+        if xs_lut is not None:
+            self.plan = None
+            if OD is None:  # rows 16 bytes apart whatever n: rtx_xs_od's vector stores
+                self.OD = torch.empty((self.nL, (grid.n + 3) // 4 * 4), dtype=torch.float32, device=dev)[:, :grid.n]
+            return
         self.plan = plan if plan is not None else lines.plan(self.nL, grid.n)
         self._env = np.empty(2 * self.nL + 2 * len(lines.species) * self.nL + len(lines.species), dtype=np.float64)
 
@@ -652,6 +688,17 @@ class TudRunner:
         nL, lines = self.nL, self.lines
         T = np.ascontiguousarray(T, dtype=np.float64)
         assert T.size == nL
+        if self.xs_lut is not None:
+            vp, st = C.c_void_p, _stream_ptr()
+            rows, wx = self.xs_lut.layer_terms(T, np.asarray(P_pa, dtype=np.float64) / 101325.0, PL_km, MF_VAL, MF_ID)
+            with trace_range("rtx_xs_od + rtx_tud"):
+                _lib.check(self.lib.rtx_xs_od(self.xs_lut._handle(), self._xs_off, self.grid.n, nL, rows.ctypes.data_as(vp),
+                                              wx.ctypes.data_as(vp), vp(self.OD.data_ptr()), self.OD.stride(0), st))
+                _lib.check(self.lib.rtx_tud(
+                    vp(self.OD.data_ptr()), self.OD.stride(0), self.grid.byref(), nL, T.ctypes.data_as(vp), self.shape[0],
+                    self.mask.ctypes.data_as(vp), self.shape[1], self.mu.ctypes.data_as(vp), self.n_down, self.N_angle, self.returnOD,
+                    self._ptrs[0], self._ptrs[1], self._ptrs[2], None, self._ld_out, st))
+            return self.tau, self.Lu, self.Ld
         w, p_atm = layer_weights_od(lines.species, T, P_pa, PL_km, MF_VAL, MF_ID)
         qratio, mass = species_factors(lines.species, T, partitionFunction, weight=w)
         nS = len(lines.species)

@@ -163,14 +163,33 @@ def _resolve_table(spec, diluents=()):
     raise TypeError("opts['line_table'] must be a table name, a column dict or an engine.LineTable")
 
 
+def _xs_lut_option(fn, o):
+    """The per-call xs_lut= option (an afit_xs.XsLut, or None): optical depths looked up in a cross-section table instead of
+    summed over lines. Never stored in `options`. A table's broadening was fixed when it was made: NotImplementedError
+    with any broadening=."""
+    lut = o.get("xs_lut")
+    if lut is not None and o.get("broadening") is not None:
+        raise NotImplementedError("%s: xs_lut with broadening=%r is not supported: a table's broadening was fixed when it was made "
+                                  "(afit_xs.cross_section_grid's GammaL / Diluent); use broadening=None" % (fn, o.get("broadening")))
+    return lut
+
+
 def compute_OD(Xmin_in, Xmax_in, opts=options, **kwargs):
     """Monochromatic optical depth of one homogeneous layer, signature of :395-456.
-    kwargs honoured: T [K], P [Pa], PL [km], MF_VAL [ppmv], MF_ID (HITRAN ids), DVOUT, line_table.
+    kwargs honoured: T [K], P [Pa], PL [km], MF_VAL [ppmv], MF_ID (HITRAN ids), DVOUT, line_table, xs_lut.
+    xs_lut (per call, an afit_xs.XsLut): look the optical depth up in a cross-section table (bilinear in T and ln p between
+    its nodes) instead of summing lines; line_table is then neither needed nor touched. ValueError: the axis is
+    not a run of the table's, (T, P) outside the table, a molecule of MF_ID the table lacks.
     Returns (X_out, OD_out)."""
     o = dict(opts)
     o.update(kwargs)
     DVOUT = o.get("DVOUT", 0.025)
     X = make_spectral_axis(Xmin_in, Xmax_in, DVOUT)
+    lut = _xs_lut_option("compute_OD", o)
+    if lut is not None:
+        OD = engine.xs_od(lut, engine.Grid(Xmin_in, Xmax_in, X.size), [o["T"]], [o["P"] / 101325.0], [o["PL"]],
+                          np.asarray(o["MF_VAL"], dtype=np.float64)[None, :], o["MF_ID"])
+        return X, OD[0].double().cpu().numpy()
     tbl = _resolve_table(o.get("line_table"))
     grid = engine.Grid(Xmin_in, Xmax_in, X.size)
     OD = engine.optical_depths(tbl, grid, [o["T"]], [o["P"]], [o["PL"]], np.asarray(o["MF_VAL"], dtype=np.float64)[None, :],
@@ -232,7 +251,7 @@ def _tud_shapes(tau2, Lu2, nZ, nMu):
 _SIDE_STREAMS = {}
 
 
-def _compute_tud_chunked(tbl, grid, Z, T, P, PL, MF, ID, Z_s, theta, nA, returnOD, n_chunks, broadening=None):
+def _compute_tud_chunked(tbl, grid, Z, T, P, PL, MF, ID, Z_s, theta, nA, returnOD, n_chunks, broadening=None, xs_lut=None):
     """compute_TUD's device work in n_chunks tile-aligned wavenumber chunks, each chunk's widening and device-to-host copy
     (side stream) under the next chunk's kernels: a single call is PCIe-bound (132 MB of float64 at C3 size: 2.7 ms against
     1.9 ms of kernels), and chunks cut on line-sum tile boundaries give the unchunked bits. Returns (tau_h, Lu_h, Ld_h,
@@ -255,7 +274,7 @@ def _compute_tud_chunked(tbl, grid, Z, T, P, PL, MF, ID, Z_s, theta, nA, returnO
     Ld = torch.empty((n,), dtype=torch.float32, device=dev)
     max_len = int(np.diff(offs).max())
     OD = torch.empty((nL, max_len), dtype=torch.float32, device=dev)
-    plan = tbl.plan(nL, n)
+    plan = tbl.plan(nL, n) if xs_lut is None else None
     side = _SIDE_STREAMS.get(dev.index)
     if side is None:
         side = _SIDE_STREAMS[dev.index] = torch.cuda.Stream()
@@ -267,7 +286,7 @@ def _compute_tud_chunked(tbl, grid, Z, T, P, PL, MF, ID, Z_s, theta, nA, returnO
         sl = slice(off, off + ln)
         run = engine.TudRunner(tbl, grid.shard(grid.offset + off, ln), Z, n_layers=nL, Altitudes=Z_s, theta_r=theta, N_angle=nA,
                                returnOD=returnOD, out=(tau[:, sl], Lu[:, sl], Ld[sl]), OD=OD[:, :ln], plan=plan,
-                               broadening=broadening)
+                               broadening=broadening, xs_lut=xs_lut)
         run.run(T, P, PL, MF, ID)
         ready = torch.cuda.Event()
         ready.record()
@@ -305,10 +324,16 @@ def compute_TUD(Xmin, Xmax, opts=options, **kwargs):
     its own partial pressure. ("self", "h2o", ...) adds foreign broadeners by HITRAN formula, each at its layer mixing
     ratio, read from the table's gamma_<formula>, n_<formula>, ... columns; a line of that gas takes self, air the remainder
     (engine.broadening_fractions).
+    xs_lut (keyword only, not in `options`): an afit_xs.XsLut. The optical depths are then looked up in the cross-section
+    table -- bilinear in T and ln p between its nodes, DESIGN 4.11 -- instead of summed over lines; line_table is neither
+    needed nor touched, and everything after the optical depths is the same code. ValueError: the axis is not a contiguous
+    run of the table's, a layer outside the table's (T, p) range, a molecule of MFs_ID the table lacks.
+    NotImplementedError: xs_lut together with any broadening= (fixed when the table was made).
     """
     trace = [time.perf_counter()] if _TRACE else None
     o = dict(opts)
     o.update(kwargs)
+    lut = _xs_lut_option("compute_TUD", o)
     broadening = o.get("broadening")
     foreign = engine.broadening_gases(broadening)
     Z = np.asarray(o["Zs"], dtype=np.float64)
@@ -325,7 +350,7 @@ def compute_TUD(Xmin, Xmax, opts=options, **kwargs):
     grid = engine.Grid(Xmin, Xmax, X_.size)
     if trace:
         trace.append(time.perf_counter())
-    tbl = _resolve_table(o.get("line_table"), foreign or ())
+    tbl = _resolve_table(o.get("line_table"), foreign or ()) if lut is None else None
     if trace:
         trace.append(time.perf_counter())
     if o.get("copy_axis"):
@@ -335,7 +360,7 @@ def compute_TUD(Xmin, Xmax, opts=options, **kwargs):
         chunks = 4 if grid.n >= 2000000 else 2 if grid.n >= 500000 else 1
     if chunks > 1 and mu_s.size <= engine.TUD_MAX_MU and not o["save"]:
         got = _compute_tud_chunked(tbl, grid, Z, T, P, PL, MF, ID, Z_s, np.asarray(o["theta_r"], dtype=np.float64), nA,
-                                   bool(o["returnOD"]), int(chunks), broadening=broadening)
+                                   bool(o["returnOD"]), int(chunks), broadening=broadening, xs_lut=lut)
         if got is not None:
             tau_h, Lu_h, Ld_h, (nZ, nMu) = got
             if trace:
@@ -348,12 +373,15 @@ def compute_TUD(Xmin, Xmax, opts=options, **kwargs):
     if mu_s.size <= engine.TUD_MAX_MU and not o["save"]:
         # the common case: one call into the library (rtx_compute_tud)
         run = engine.TudRunner(tbl, grid, Z, n_layers=T.size, Altitudes=Z_s, theta_r=np.asarray(o["theta_r"], dtype=np.float64),
-                               N_angle=nA, returnOD=bool(o["returnOD"]), broadening=broadening)
+                               N_angle=nA, returnOD=bool(o["returnOD"]), broadening=broadening, xs_lut=lut)
         tau, Lu, Ld = run.run(T, P, PL, MF, ID)
         nZ, nMu = run.shape
         OD = run.OD
     else:
-        OD = engine.optical_depths(tbl, grid, T, P, PL, MF, ID, broadening=broadening)  # [nL][nX] float32 on the device
+        if lut is not None:
+            OD = engine.xs_od(lut, grid, T, P / 101325.0, PL, MF, ID)
+        else:
+            OD = engine.optical_depths(tbl, grid, T, P, PL, MF, ID, broadening=broadening)  # [nL][nX] float32 on the device
         res = engine.tud(OD, grid, T, Z, Altitudes=Z_s, theta_r=np.asarray(o["theta_r"], dtype=np.float64), N_angle=nA,
                          returnOD=bool(o["returnOD"]), per_angle=bool(o["save"]))
         tau, Lu, Ld, (nZ, nMu) = res[:4]
@@ -384,21 +412,22 @@ class _TudPipeline:
     outputs: the copy of one is in flight while the other is being computed), each on a compute stream of its own, a
     side stream for the device-to-host copies, a pinned staging ring."""
 
-    def __init__(self, dev, tbl, grid, Z, nL, Z_s, theta_r, N_angle, returnOD, broadening=None):
+    def __init__(self, dev, tbl, grid, Z, nL, Z_s, theta_r, N_angle, returnOD, broadening=None, xs_lut=None):
         self.dev = int(dev)
         with torch.cuda.device(self.dev):
-            self.lines = tbl.on_device(self.dev)
+            self.lines = tbl.on_device(self.dev) if xs_lut is None else None
             self.side = torch.cuda.Stream()
             # two runners, each with a stream, per-(line, layer) records and an optical-depth buffer of its own (another
             # pipeline may share the device and the table's cached plan): the prologue and TUD pass of one atmosphere overlap
             # the line-sum of the next (engine.TudPipelines)
             self.computes = [torch.cuda.Stream(), torch.cuda.Stream()]
-            self.plans = [engine.VoigtPlan(self.lines, nL, grid.n) for _ in range(2)]
+            # (a cross-section table needs no records: its per-atmosphere terms are kept per stream, rtx_xs_od)
+            self.plans = [engine.VoigtPlan(self.lines, nL, grid.n) if xs_lut is None else None for _ in range(2)]
             self.runs = []
             for st, pl in zip(self.computes, self.plans):
                 with torch.cuda.stream(st):
                     self.runs.append(engine.TudRunner(self.lines, grid, Z, n_layers=nL, Altitudes=Z_s, theta_r=theta_r, N_angle=N_angle,
-                                                      returnOD=returnOD, plan=pl, broadening=broadening))
+                                                      returnOD=returnOD, plan=pl, broadening=broadening, xs_lut=xs_lut))
         self.busy = [None, None]  # copy-done event of each runner's outputs
         self.staging = _hostio.Staging(depth=2)
         self.k = 0
@@ -442,7 +471,8 @@ class _TudPipeline:
         with torch.cuda.device(self.dev):
             torch.cuda.synchronize()
             for pl in self.plans:
-                pl.close()
+                if pl is not None:
+                    pl.close()
 
 
 def compute_TUD_batch(Xmin, Xmax, atmospheres, opts=options, reduce=None, devices=None, out_dtype=np.float64, **kwargs):
@@ -464,9 +494,16 @@ def compute_TUD_batch(Xmin, Xmax, atmospheres, opts=options, reduce=None, device
     Returns a list of (X, tau, Lu, Ld) with the shapes compute_TUD gives (X_out instead of X when reduce is set). Full
     float64 spectra are views of page-locked blocks while fewer than _hostio.PINNED_RESULT_CAP bytes are lent out (1 GiB:
     the first eight C3-sized results), ordinary pageable arrays beyond that and for every other output (float32 crosses
-    PCIe into a reusable pinned ring, a host thread pool widens: host-memory bound, ~10 ms per 132 MB result)."""
+    PCIe into a reusable pinned ring, a host thread pool widens: host-memory bound, ~10 ms per 132 MB result).
+    xs_lut (keyword only): as for compute_TUD -- every atmosphere's optical depths come from the cross-section table, the line
+    table is not touched, results equal per-call compute_TUD(xs_lut=) bit for bit. NotImplementedError: xs_lut with any
+    broadening=, or with devices= naming more than one device (a table lives on one device)."""
     o = dict(opts)
     o.update(kwargs)
+    lut = _xs_lut_option("compute_TUD_batch", o)
+    if lut is not None and devices is not None and len({int(d) for d in devices}) > 1:
+        raise NotImplementedError("compute_TUD_batch: xs_lut with devices=%r is not supported: a cross-section table lives on one "
+                                  "device" % (devices,))
     if o["save"]:
         raise ValueError("compute_TUD_batch: save is a single-call option")
     if np.dtype(out_dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
@@ -486,11 +523,14 @@ def compute_TUD_batch(Xmin, Xmax, atmospheres, opts=options, reduce=None, device
         raise ValueError("compute_TUD_batch: devices=%r, visible GPUs: %d" % (devices, torch.cuda.device_count()))
     X_ = _cached_axis(Xmin, Xmax, o["DVOUT"])
     grid = engine.Grid(Xmin, Xmax, X_.size)
+    if lut is not None and lut.device.index != devs[0]:
+        raise ValueError("compute_TUD_batch: xs_lut lives on device %d, devices=%r" % (lut.device.index, devices))
     with torch.cuda.device(devs[0]):
-        tbl = _resolve_table(o.get("line_table"), foreign or ())
+        tbl = _resolve_table(o.get("line_table"), foreign or ()) if lut is None else None
     nL = np.asarray(o["Ts"]).size
     theta = np.asarray(o["theta_r"], dtype=np.float64)
-    pipes = [_TudPipeline(d, tbl, grid, Z, nL, Z_s, theta, int(o["N_angle"]), bool(o["returnOD"]), broadening=broadening) for d in devs]
+    pipes = [_TudPipeline(d, tbl, grid, Z, nL, Z_s, theta, int(o["N_angle"]), bool(o["returnOD"]), broadening=broadening, xs_lut=lut)
+             for d in devs]
     nZ, nMu = pipes[0].runs[0].shape
     pending = []  # (pipeline, ticket, X of the result) in input order
     results = []
@@ -588,9 +628,13 @@ def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, redu
     moves with T; a finite difference of it carries those steps). Everything else is analytic.
     reduce = dict(dX=..., N=4, window="hanning"): reduceResolution of the base outputs and of every J row on the device
     (engine.reduce_resolution_cached). Without it, full-resolution results above 4 GiB are refused (ValueError): pass
-    reduce= or fewer layers=. Arguments are checked before any device work."""
+    reduce= or fewer layers=. Arguments are checked before any device work.
+    NotImplementedError: xs_lut= (the derivatives are built on the line-sum: dOD/dT holds every line's window fixed)."""
     o = dict(opts)
     o.update(kwargs)
+    if o.get("xs_lut") is not None:
+        raise NotImplementedError("compute_TUD_jacobian: xs_lut is not supported (dOD/dT is a difference of line-sums with fixed "
+                                  "windows); use line_table=")
     wrt, lay, _ = _jacobian_args(Xmin, Xmax, o, wrt, layers, reduce, fd_step_T)
     Z = np.asarray(o["Zs"], dtype=np.float64)
     T = np.asarray(o["Ts"], dtype=np.float64)
