@@ -5,7 +5,10 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <vector>
+
 #include "../../include/radtxfr_hip.h"
+#include "rtx_devmem.h"
 
 // ---- error plumbing (thread-local text behind rtx_last_error) ---------------------------------
 void rtx_set_error(const char* fmt, ...);
@@ -115,22 +118,22 @@ struct __attribute__((aligned(16))) LineRecSD {
 };
 
 struct rtx_lines {
-  long long n;
-  int n_species;
-  double *nu, *sw, *elower, *gamma_air, *gamma_self, *n_air, *n_self, *delta_air, *deltap_air, *delta_self;
-  double *sd_air, *sd_self;  // optional speed-dependence columns (rtx_lines_set_sd), NULL = 0
-  double* deltap_self;       // optional (rtx_lines_set_deltap_self), NULL = 0
-  double* zn;                // per line: exp(-c2 E''/Tref) (1 - exp(-c2 nu/Tref)), the layer-independent half of S(T), formed once at creation
-  int* species;
+  long long n = 0;
+  int n_species = 0;
+  DevBuf<double> nu, sw, elower, gamma_air, gamma_self, n_air, n_self, delta_air, deltap_air, delta_self;
+  DevBuf<double> sd_air, sd_self;  // optional speed-dependence columns (rtx_lines_set_sd), empty = 0
+  DevBuf<double> deltap_self;      // optional (rtx_lines_set_deltap_self), empty = 0
+  DevBuf<double> zn;               // per line: exp(-c2 E''/Tref) (1 - exp(-c2 nu/Tref)), the layer-independent half of S(T), formed once at creation
+  DevBuf<int> species;
   // host side, for the bound on candidates per tile (hot-tile split, below): the sorted centres and column extremes
-  double* nu_host;
-  double ga_max, gs_max, n_lo, n_hi;
-  double na_lo, na_hi, ns_lo, ns_hi;  // n ranges of the air and the self column sets on their own (self after its n_air fallback)
+  std::vector<double> nu_host;
+  double ga_max = 0.0, gs_max = 0.0, n_lo = 1e300, n_hi = -1e300;
+  double na_lo = 1e300, na_hi = -1e300, ns_lo = 1e300, ns_hi = -1e300;  // n ranges of the air and the self column sets on their own (self after its n_air fallback)
   // extra broadener column sets (rtx_lines_set_broadeners): [n_extra][n] each, every column filled (absent gamma / delta /
   // deltap / SD = 0, absent n = n_air), so the mixed prologue reads them without tests
-  int n_extra;
-  double *x_gamma, *x_n, *x_delta, *x_deltap, *x_sd;
-  double *x_gmax, *x_nlo, *x_nhi;  // host, [n_extra]: |gamma| maximum and n range of each set (hot-tile bound)
+  int n_extra = 0;
+  DevBuf<double> x_gamma, x_n, x_delta, x_deltap, x_sd;
+  std::vector<double> x_gmax, x_nlo, x_nhi;  // host, [n_extra]: |gamma| maximum and n range of each set (hot-tile bound)
 };
 
 // ---- hot tiles ---------------------------------------------------------------------------------------
@@ -156,41 +159,34 @@ struct __attribute__((aligned(16))) SplitItem {
 };
 
 struct rtx_prep {
-  long long n_lines;
-  int max_layers;
-  int n_layers;        // of the last rtx_line_prep
-  LineRec* rec;        // [max_layers][n_lines]
-  LineRec64* rec64;    // [max_layers][n_lines]
-  int* ic;             // [n_lines] local grid index nearest the UNSHIFTED centre (sorted)
-  int2* win;           // [max_layers][n_lines] the records' windows (lo, hi) on their own: what tile_ranges_kernel scans (8 of a record's 48 bytes)
-  int* maxhw;          // [max_layers] max window half-width in grid points (+margin)
-  int2* ranges;        // [max_layers][max_tiles] candidate line range per line-sum tile
-  int* smally;         // [max_layers] set when a line of that layer has a Weideman band with y < 1
-  LineRecSD* recsd;    // [max_layers][n_lines], allocated by the first speed-dependent prologue
-  long long max_tiles;
-  double* env;         // device copy of T,p,qratio,weight,mass (packed)
-  size_t env_cap;
-  double scale;
+  long long n_lines = 0;
+  int max_layers = 0;
+  int n_layers = 0;           // of the last rtx_line_prep
+  DevBuf<LineRec> rec;        // [max_layers][n_lines]
+  DevBuf<LineRec64> rec64;    // [max_layers][n_lines]
+  DevBuf<int> ic;             // [n_lines] local grid index nearest the UNSHIFTED centre (sorted)
+  DevBuf<int2> win;           // [max_layers][n_lines] the records' windows (lo, hi) on their own: what tile_ranges_kernel scans (8 of a record's 48 bytes)
+  DevBuf<int> maxhw;          // [maxhw | smally | n_items] = 2 * max_layers + 1 ints: one memset per prologue. [max_layers] max window half-width in grid points (+margin)
+  int* smally = nullptr;      // inside maxhw: [max_layers] set when a line of that layer has a Weideman band with y < 1
+  int* n_items = nullptr;     // inside maxhw: the counter of the hot-tile work list
+  DevBuf<int2> ranges;        // [max_layers][max_tiles] candidate line range per line-sum tile
+  DevBuf<LineRecSD> recsd;    // [max_layers][n_lines], allocated by the first speed-dependent prologue
+  long long max_tiles = 0;
+  DevBuf<double> env;         // device copy of T,p,qratio,weight,mass (packed)
+  double scale = 0.0;
   // hot-tile split: work list and workspace sized from a HOST-side bound on the candidates per tile (no device read-back)
-  int* n_items;        // device counter (lives behind maxhw / smally: one memset per prologue)
-  SplitItem* items;    // [items_cap]
-  float* part_ws;      // [items_cap][tile points]
-  long long items_cap;
-  long long split_bound;  // extra parts the current (grid, window) bound allows for; 0 = no tile can be hot
-  double split_W;         // window half-width [cm^-1] the bound was computed for (valid for any smaller one)
-  double split_xmin, split_step;
-  long long split_off, split_n;
-  int split_layers;
-  const void* split_lines;  // the table the bound was made for
-  // explicit axis (rtx_line_prep_axis): device copy of the axis, grow-only; `axis` tells which prologue ran last
-  double* X;
-  long long x_cap;
-  long long nx;
-  int axis;
-  // window temperatures of rtx_line_prep_window: device copy, grow-only
-  double* twin;
-  int twin_cap;
-  // diluent fractions of rtx_line_prep_mix / _axis_mix: device copy [n_dil][n_species][n_layers], grow-only
-  double* frac;
-  size_t frac_cap;
+  DevBuf<SplitItem> items;    // the work list; its capacity is the bound it was sized for
+  DevBuf<float> part_ws;      // [items.cap()][tile points]
+  long long split_bound = 0;  // extra parts the current (grid, window) bound allows for; 0 = no tile can be hot
+  double split_W = 0.0;       // window half-width [cm^-1] the bound was computed for (valid for any smaller one)
+  double split_xmin = 0.0, split_step = 0.0;
+  long long split_off = 0, split_n = 0;
+  int split_layers = 0;
+  const void* split_lines = nullptr;  // the table the bound was made for
+  // explicit axis (rtx_line_prep_axis): device copy of the axis; `axis` tells which prologue ran last
+  DevBuf<double> X;
+  long long nx = 0;
+  int axis = 0;
+  DevBuf<double> twin;  // window temperatures of rtx_line_prep_window: device copy
+  DevBuf<double> frac;  // diluent fractions of rtx_line_prep_mix / _axis_mix: device copy [n_dil][n_species][n_layers]
 };

@@ -40,30 +40,32 @@ int rtx_check_grid(const rtx_grid* g) {
   return 0;
 }
 
-// ---- line table ------------------------------------------------------------------------------------
-static int upload(double** dst, const double* src_h, long long n, bool zero_if_null) {
-  *dst = nullptr;
-  if (!src_h && !zero_if_null) return 0;
-  RTX_HIP(hipMalloc((void**)dst, sizeof(double) * (size_t)(n > 0 ? n : 1)));
-  if (src_h)
-    RTX_HIP(hipMemcpy(*dst, src_h, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-  else
-    RTX_HIP(hipMemset(*dst, 0, sizeof(double) * (size_t)n));
+// ---- device memory (rtx_devmem.h) -----------------------------------------------------------------
+int rtx_dev_alloc(void** p, size_t bytes) {
+  *p = nullptr;
+  const hipError_t e = hipMalloc(p, bytes);
+  if (e == hipSuccess) return 0;
+  *p = nullptr;
+  RTX_FAIL("device allocation of %zu bytes -> %s", bytes, hipGetErrorString(e));
+}
+void rtx_dev_free(void* p) {
+  if (p) (void)hipFree(p);
+}
+int rtx_dev_h2d(void* d, const void* h, size_t bytes) {
+  RTX_HIP(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));
   return 0;
 }
 
+// ---- line table ------------------------------------------------------------------------------------
+// A column of n doubles (one element for an empty table, so that the pointer is never NULL); an optional column that is
+// absent stays empty.
+static int upload(DevBuf<double>& dst, const double* src_h, long long n, bool required) {
+  if (!src_h && !required) return 0;
+  if (dst.reserve((size_t)(n > 0 ? n : 1))) return 1;
+  return n > 0 ? rtx_dev_h2d(dst.get(), src_h, sizeof(double) * (size_t)n) : 0;
+}
+
 extern "C" int rtx_lines_free(rtx_lines* L) {
-  if (!L) return 0;
-  double* p[] = {L->nu, L->sw, L->elower, L->gamma_air, L->gamma_self, L->n_air, L->n_self, L->delta_air, L->deltap_air, L->delta_self,
-                 L->sd_air, L->sd_self, L->deltap_self, L->zn};
-  for (double* q : p)
-    if (q) (void)hipFree(q);
-  if (L->species) (void)hipFree(L->species);
-  double* x[] = {L->x_gamma, L->x_n, L->x_delta, L->x_deltap, L->x_sd};
-  for (double* q : x)
-    if (q) (void)hipFree(q);
-  free(L->x_gmax); free(L->x_nlo); free(L->x_nhi);
-  free(L->nu_host);
   delete L;
   return 0;
 }
@@ -84,41 +86,19 @@ extern "C" int rtx_lines_create(int64_t n, int n_species, const double* nu_h, co
     if (species_h[i] < 0 || species_h[i] >= n_species) RTX_FAIL("species index out of range at row %lld", (long long)i);
   }
   rtx_lines* L = new rtx_lines();
-  memset(L, 0, sizeof(*L));
   L->n = n;
   L->n_species = n_species;
-  int rc = 0;
-  rc |= upload(&L->nu, nu_h, n, true);
-  rc |= upload(&L->sw, sw_h, n, true);
-  rc |= upload(&L->elower, elower_h, n, true);
-  rc |= upload(&L->gamma_air, gamma_air_h, n, true);
-  rc |= upload(&L->gamma_self, gamma_self_h, n, true);
-  rc |= upload(&L->n_air, n_air_h, n, true);
-  rc |= upload(&L->n_self, n_self_h, n, false);
-  rc |= upload(&L->delta_air, delta_air_h, n, true);
-  rc |= upload(&L->deltap_air, deltap_air_h, n, false);
-  rc |= upload(&L->delta_self, delta_self_h, n, false);
-  if (!rc) {
-    hipError_t e = hipMalloc((void**)&L->species, sizeof(int) * (size_t)(n > 0 ? n : 1));
-    if (e == hipSuccess && n > 0) e = hipMemcpy(L->species, species_h, sizeof(int) * (size_t)n, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      rtx_set_error("species upload failed: %s", hipGetErrorString(e));
-      rc = 1;
-    }
-  }
-  if (!rc) rc = rtx_lines_fill_zn(L);
-  if (!rc && n > 0) {
-    L->nu_host = (double*)malloc(sizeof(double) * (size_t)n);
-    if (!L->nu_host) { rtx_set_error("out of host memory"); rc = 1; }
-  }
-  if (rc) {
-    rtx_lines_free(L);
+  if (upload(L->nu, nu_h, n, true) || upload(L->sw, sw_h, n, true) || upload(L->elower, elower_h, n, true) ||
+      upload(L->gamma_air, gamma_air_h, n, true) || upload(L->gamma_self, gamma_self_h, n, true) ||
+      upload(L->n_air, n_air_h, n, true) || upload(L->n_self, n_self_h, n, false) || upload(L->delta_air, delta_air_h, n, true) ||
+      upload(L->deltap_air, deltap_air_h, n, false) || upload(L->delta_self, delta_self_h, n, false) ||
+      L->species.reserve((size_t)(n > 0 ? n : 1)) || (n > 0 && rtx_dev_h2d(L->species.get(), species_h, sizeof(int) * (size_t)n)) ||
+      rtx_lines_fill_zn(L)) {
+    delete L;
     return 1;
   }
-  L->n_lo = 1e300; L->n_hi = -1e300;
-  L->na_lo = L->ns_lo = 1e300; L->na_hi = L->ns_hi = -1e300;
+  L->nu_host.assign(nu_h, nu_h + n);
   for (int64_t i = 0; i < n; ++i) {
-    L->nu_host[i] = nu_h[i];
     L->ga_max = fmax(L->ga_max, fabs(gamma_air_h[i]));
     L->gs_max = fmax(L->gs_max, fabs(gamma_self_h[i]));
     const double na = n_air_h[i], ns = (n_self_h && n_self_h[i] != 0.0) ? n_self_h[i] : na;
@@ -132,58 +112,49 @@ extern "C" int rtx_lines_create(int64_t n, int n_species, const double* nu_h, co
 }
 extern "C" int64_t rtx_lines_count(const rtx_lines* L) { return L ? L->n : -1; }
 
+// An optional column: replaces the previous one; NULL (or an empty table) leaves none.
+static int set_optional(DevBuf<double>& dst, const double* src_h, long long n) {
+  dst.reset();
+  return src_h && n > 0 ? dst.upload(src_h, (size_t)n) : 0;
+}
+
 extern "C" int rtx_lines_set_sd(rtx_lines* L, const double* sd_air_h, const double* sd_self_h) {
   if (!L) RTX_FAIL("lines is NULL");
-  const double* src[2] = {sd_air_h, sd_self_h};
-  double** dst[2] = {&L->sd_air, &L->sd_self};
-  for (int c = 0; c < 2; ++c) {
-    if (*dst[c]) { (void)hipFree(*dst[c]); *dst[c] = nullptr; }
-    if (!src[c] || L->n == 0) continue;
-    RTX_HIP(hipMalloc((void**)dst[c], (size_t)L->n * sizeof(double)));
-    RTX_HIP(hipMemcpy(*dst[c], src[c], (size_t)L->n * sizeof(double), hipMemcpyHostToDevice));
-  }
-  return 0;
+  return set_optional(L->sd_air, sd_air_h, L->n) || set_optional(L->sd_self, sd_self_h, L->n);
 }
 
 extern "C" int rtx_lines_set_deltap_self(rtx_lines* L, const double* deltap_self_h) {
   if (!L) RTX_FAIL("lines is NULL");
-  if (L->deltap_self) { (void)hipFree(L->deltap_self); L->deltap_self = nullptr; }
-  if (!deltap_self_h || L->n == 0) return 0;
-  RTX_HIP(hipMalloc((void**)&L->deltap_self, (size_t)L->n * sizeof(double)));
-  RTX_HIP(hipMemcpy(L->deltap_self, deltap_self_h, (size_t)L->n * sizeof(double), hipMemcpyHostToDevice));
-  return 0;
+  return set_optional(L->deltap_self, deltap_self_h, L->n);
 }
 
 // Extra broadener column sets (gamma_<sp>, n_<sp>, delta_<sp>, deltap_<sp>, SD_<sp> of misc/hapi.py:11090-11128, 10860-10890):
 // replaces the table's previous set. Every device column is filled, the reference's fallbacks applied here once: an absent
-// gamma / delta / deltap / SD column is 0, an absent n column is n_air (a foreign n of 0 stays 0).
+// gamma / delta / deltap / SD column is 0, an absent n column is n_air (a foreign n of 0 stays 0). The new set is built
+// aside and taken over whole: a failure leaves the table with no extra set.
 extern "C" int rtx_lines_set_broadeners(rtx_lines* L, int n_extra, const double* const* gamma_h, const double* const* n_h,
                                         const double* const* delta_h, const double* const* deltap_h, const double* const* sd_h) {
   if (!L) RTX_FAIL("lines is NULL");
   if (n_extra < 0 || n_extra > RTX_MAX_BROADENERS) RTX_FAIL("n_extra=%d outside [0,%d]", n_extra, RTX_MAX_BROADENERS);
-  double** dst[5] = {&L->x_gamma, &L->x_n, &L->x_delta, &L->x_deltap, &L->x_sd};
-  for (double** d : dst)
-    if (*d) { (void)hipFree(*d); *d = nullptr; }
-  free(L->x_gmax); free(L->x_nlo); free(L->x_nhi);
-  L->x_gmax = L->x_nlo = L->x_nhi = nullptr;
+  DevBuf<double>* dst[5] = {&L->x_gamma, &L->x_n, &L->x_delta, &L->x_deltap, &L->x_sd};
+  for (DevBuf<double>* d : dst) d->reset();
+  L->x_gmax.clear(); L->x_nlo.clear(); L->x_nhi.clear();
   L->n_extra = 0;
   if (n_extra == 0) return 0;
-  L->x_gmax = (double*)calloc((size_t)n_extra, sizeof(double));
-  L->x_nlo = (double*)calloc((size_t)n_extra, sizeof(double));
-  L->x_nhi = (double*)calloc((size_t)n_extra, sizeof(double));
-  if (!L->x_gmax || !L->x_nlo || !L->x_nhi) RTX_FAIL("out of host memory");
   const size_t n = (size_t)L->n, cnt = (size_t)n_extra * (n > 0 ? n : 1);
   const double* const* src[5] = {gamma_h, n_h, delta_h, deltap_h, sd_h};
+  DevBuf<double> cols[5];
   for (int c = 0; c < 5; ++c) {
-    RTX_HIP(hipMalloc((void**)dst[c], cnt * sizeof(double)));
+    if (cols[c].reserve(cnt)) return 1;
     for (int j = 0; j < n_extra && n > 0; ++j) {
-      double* col = *dst[c] + (size_t)j * n;
+      double* col = cols[c].get() + (size_t)j * n;
       const double* h = src[c] ? src[c][j] : nullptr;
-      if (h) RTX_HIP(hipMemcpy(col, h, n * sizeof(double), hipMemcpyHostToDevice));
-      else if (c == 1) RTX_HIP(hipMemcpy(col, L->n_air, n * sizeof(double), hipMemcpyDeviceToDevice));
+      if (h) { if (rtx_dev_h2d(col, h, n * sizeof(double))) return 1; }
+      else if (c == 1) RTX_HIP(hipMemcpy(col, L->n_air.get(), n * sizeof(double), hipMemcpyDeviceToDevice));
       else RTX_HIP(hipMemset(col, 0, n * sizeof(double)));
     }
   }
+  std::vector<double> gmax(n_extra), nlo(n_extra), nhi(n_extra);
   for (int j = 0; j < n_extra; ++j) {
     const double* g = gamma_h ? gamma_h[j] : nullptr;
     const double* nn = n_h ? n_h[j] : nullptr;
@@ -193,28 +164,16 @@ extern "C" int rtx_lines_set_broadeners(rtx_lines* L, int n_extra, const double*
       if (g) gm = fmax(gm, fabs(g[i]));
       if (nn) { lo = fmin(lo, nn[i]); hi = fmax(hi, nn[i]); }
     }
-    L->x_gmax[j] = gm; L->x_nlo[j] = lo; L->x_nhi[j] = hi;
+    gmax[j] = gm; nlo[j] = lo; nhi[j] = hi;
   }
+  for (int c = 0; c < 5; ++c) *dst[c] = std::move(cols[c]);
+  L->x_gmax = std::move(gmax); L->x_nlo = std::move(nlo); L->x_nhi = std::move(nhi);
   L->n_extra = n_extra;
   return 0;
 }
 
 // ---- prep object -------------------------------------------------------------------------------------
 extern "C" int rtx_prep_free(rtx_prep* P) {
-  if (!P) return 0;
-  if (P->rec) (void)hipFree(P->rec);
-  if (P->rec64) (void)hipFree(P->rec64);
-  if (P->ic) (void)hipFree(P->ic);
-  if (P->win) (void)hipFree(P->win);
-  if (P->maxhw) (void)hipFree(P->maxhw);  // smally lives in the same allocation
-  if (P->env) (void)hipFree(P->env);
-  if (P->ranges) (void)hipFree(P->ranges);
-  if (P->recsd) (void)hipFree(P->recsd);
-  if (P->items) (void)hipFree(P->items);
-  if (P->part_ws) (void)hipFree(P->part_ws);
-  if (P->X) (void)hipFree(P->X);
-  if (P->twin) (void)hipFree(P->twin);
-  if (P->frac) (void)hipFree(P->frac);
   delete P;
   return 0;
 }
@@ -228,26 +187,20 @@ extern "C" int rtx_prep_create(const rtx_lines* lines, int max_layers, int64_t m
   if (max_layers < 1 || max_layers > 4096) RTX_FAIL("max_layers must be in [1,4096]");
   if (max_points < 1 || max_points > 2000000000LL) RTX_FAIL("max_points must be in [1,2e9]");
   rtx_prep* P = new rtx_prep();
-  memset(P, 0, sizeof(*P));
   P->n_lines = lines->n;
   P->max_layers = max_layers;
-  size_t nrec = (size_t)(lines->n > 0 ? lines->n : 1) * (size_t)max_layers;
-  P->env_cap = (size_t)max_layers * (2 + 2 * (size_t)lines->n_species) + (size_t)lines->n_species;
+  const size_t n1 = (size_t)(lines->n > 0 ? lines->n : 1), nrec = n1 * (size_t)max_layers;
   const int tile = rtx_voigt_tile_points();
   P->max_tiles = (max_points + tile - 1) / tile;
-  hipError_t e = hipMalloc((void**)&P->rec, nrec * sizeof(LineRec));
-  if (e == hipSuccess) e = hipMalloc((void**)&P->rec64, nrec * sizeof(LineRec64));
-  if (e == hipSuccess) e = hipMalloc((void**)&P->ic, sizeof(int) * (size_t)(lines->n > 0 ? lines->n : 1));
-  if (e == hipSuccess) e = hipMalloc((void**)&P->win, nrec * sizeof(int2));
-  if (e == hipSuccess) e = hipMalloc((void**)&P->maxhw, (2 * (size_t)max_layers + 1) * sizeof(int));  // [maxhw | smally | n_items]: one memset per prologue
-  if (e == hipSuccess) { P->smally = P->maxhw + max_layers; P->n_items = P->maxhw + 2 * max_layers; }
-  if (e == hipSuccess) e = hipMalloc((void**)&P->env, sizeof(double) * P->env_cap);
-  if (e == hipSuccess) e = hipMalloc((void**)&P->ranges, sizeof(int2) * (size_t)P->max_tiles * (size_t)max_layers);
-  if (e != hipSuccess) {
-    rtx_set_error("rtx_prep_create: %s (%zu records)", hipGetErrorString(e), nrec);
-    rtx_prep_free(P);
+  if (P->rec.reserve(nrec) || P->rec64.reserve(nrec) || P->ic.reserve(n1) || P->win.reserve(nrec) ||
+      P->maxhw.reserve(2 * (size_t)max_layers + 1) ||
+      P->env.reserve((size_t)max_layers * (2 + 2 * (size_t)lines->n_species) + (size_t)lines->n_species) ||
+      P->ranges.reserve((size_t)P->max_tiles * (size_t)max_layers)) {
+    delete P;
     return 1;
   }
+  P->smally = P->maxhw.get() + max_layers;
+  P->n_items = P->maxhw.get() + 2 * max_layers;
   *out = P;
   return 0;
 }
@@ -275,8 +228,9 @@ __global__ __launch_bounds__(256) void lines_zn_kernel(const double* __restrict_
 }
 int rtx_lines_fill_zn(rtx_lines* L) {
   if (L->n == 0) return 0;
-  RTX_HIP(hipMalloc((void**)&L->zn, sizeof(double) * (size_t)L->n));
-  hipLaunchKernelGGL(lines_zn_kernel, dim3((unsigned)((L->n + 255) / 256)), dim3(256), 0, 0, L->nu, L->elower, L->zn, (long long)L->n);
+  if (L->zn.reserve((size_t)L->n)) return 1;
+  hipLaunchKernelGGL(lines_zn_kernel, dim3((unsigned)((L->n + 255) / 256)), dim3(256), 0, 0, L->nu.get(), L->elower.get(), L->zn.get(),
+                     (long long)L->n);
   RTX_LAUNCH_CHECK();
   RTX_HIP(hipDeviceSynchronize());
   return 0;
@@ -735,7 +689,7 @@ static int rtx_split_bound(rtx_prep* P, const rtx_lines* L, const rtx_grid* g, i
   for (int s = 0; s < L->n_species; ++s)
     if (mass_h[s] > 0.0) m_min = fmin(m_min, mass_h[s]);
   if (!(m_min < 1e300)) m_min = 1.0;
-  const double nu_max = L->nu_host[L->n - 1];
+  const double nu_max = L->nu_host.back();
   double gd = sqrt(2.0 * H_CBOLTS * t_max * log(2.0) / (m_min * H_CMASSMOL * 1000.0) / (H_CC * H_CC)) * fabs(nu_max);
   if (profile == RTX_PROFILE_DOPPLER) gd = (1.1774100225 / 2.99792458e8) * sqrt(1.3806503e-23 / 1.66053873e-27) * sqrt(t_max) * fabs(nu_max) / sqrt(m_min);
   const double W = fmax(omega_wing, fmax(omega_wing_hw * g0, omega_wing_hw * gd)) + 2.0 * g->step;
@@ -757,15 +711,13 @@ static int rtx_split_bound(rtx_prep* P, const rtx_lines* L, const rtx_grid* g, i
     if (cnt > RTX_SPLIT_MIN) extra += (cnt - 1) / RTX_SPLIT_PART;
   }
   extra *= n_layers;
-  if (extra > P->items_cap) {  // grow-only; rare (a new table / grid / much wider wings): allocates, hence synchronises
-    if (extra > 1000000LL)  // 4 GB of partial tiles: callers with many states per launch split the launch (afit_xs.py)
-      RTX_FAIL("hot-tile work list of %lld items (over 1000000): fewer layers / states per call, or a shorter grid shard", extra);
-    if (P->items) { RTX_HIP(hipFree(P->items)); P->items = nullptr; }
-    if (P->part_ws) { RTX_HIP(hipFree(P->part_ws)); P->part_ws = nullptr; }
-    P->items_cap = 0;
-    RTX_HIP(hipMalloc((void**)&P->items, (size_t)extra * sizeof(SplitItem)));
-    RTX_HIP(hipMalloc((void**)&P->part_ws, (size_t)extra * (size_t)tile * sizeof(float)));
-    P->items_cap = extra;
+  if (extra > 1000000LL)  // 4 GB of partial tiles: callers with many states per launch split the launch (afit_xs.py)
+    RTX_FAIL("hot-tile work list of %lld items (over 1000000): fewer layers / states per call, or a shorter grid shard", extra);
+  // rare growth (a new table / grid / much wider wings); the two go together: the list's capacity stands for both
+  if (P->items.reserve((size_t)extra) || P->part_ws.reserve((size_t)extra * (size_t)tile)) {
+    P->items.reset(); P->part_ws.reset();
+    P->split_bound = 0; P->split_W = 0.0;
+    return 1;
   }
   P->split_bound = extra;
   P->split_W = Wc; P->split_xmin = g->xmin; P->split_step = g->step; P->split_off = g->offset; P->split_n = g->n;
@@ -791,9 +743,9 @@ static int prep_begin(rtx_prep* P, const rtx_lines* L, int n_layers, const doubl
     if (!(T_h[k] > 0.0) || !(p_atm_h[k] >= 0.0)) RTX_FAIL("layer %d: T=%g p=%g not physical", k, T_h[k], p_atm_h[k]);
   const int ns = L->n_species;
   const size_t nT = (size_t)n_layers, nQ = (size_t)ns * n_layers;
-  if (2 * nT + 2 * nQ + ns > P->env_cap) RTX_FAIL("environment tables exceed prep capacity");
+  if (2 * nT + 2 * nQ + ns > P->env.cap()) RTX_FAIL("environment tables exceed prep capacity");
   env_args = 2 * nT + 2 * nQ + ns <= RTX_ENV_MAX;
-  double* d = P->env;
+  double* d = P->env.get();
   if (!env_args) {
     // pageable-source async copies are staged by the runtime before returning: caller may reuse its arrays
     RTX_HIP(hipMemcpyAsync(d, T_h, nT * sizeof(double), hipMemcpyHostToDevice, st));
@@ -802,11 +754,11 @@ static int prep_begin(rtx_prep* P, const rtx_lines* L, int n_layers, const doubl
     RTX_HIP(hipMemcpyAsync(d + 2 * nT + nQ, weight_h, nQ * sizeof(double), hipMemcpyHostToDevice, st));
     RTX_HIP(hipMemcpyAsync(d + 2 * nT + 2 * nQ, mass_h, ns * sizeof(double), hipMemcpyHostToDevice, st));
   }
-  RTX_HIP(hipMemsetAsync(P->maxhw, 0, (2 * (size_t)P->max_layers + 1) * sizeof(int), st));  // maxhw, smally and n_items
-  a.nu = L->nu; a.sw = L->sw; a.elower = L->elower; a.gamma_air = L->gamma_air; a.gamma_self = L->gamma_self;
-  a.n_air = L->n_air; a.n_self = L->n_self; a.delta_air = L->delta_air; a.deltap_air = L->deltap_air;
-  a.delta_self = L->delta_self; a.species = L->species;
-  a.sd_air = L->sd_air; a.sd_self = L->sd_self; a.deltap_self = L->deltap_self; a.recsd = P->recsd; a.zn = L->zn;
+  RTX_HIP(hipMemsetAsync(P->maxhw.get(), 0, P->maxhw.cap() * sizeof(int), st));  // maxhw, smally and n_items
+  a.nu = L->nu.get(); a.sw = L->sw.get(); a.elower = L->elower.get(); a.gamma_air = L->gamma_air.get(); a.gamma_self = L->gamma_self.get();
+  a.n_air = L->n_air.get(); a.n_self = L->n_self.get(); a.delta_air = L->delta_air.get(); a.deltap_air = L->deltap_air.get();
+  a.delta_self = L->delta_self.get(); a.species = L->species.get();
+  a.sd_air = L->sd_air.get(); a.sd_self = L->sd_self.get(); a.deltap_self = L->deltap_self.get(); a.recsd = P->recsd.get(); a.zn = L->zn.get();
   a.n_lines = L->n; a.n_layers = n_layers; a.n_species = ns;
   if (env_args) {  // offsets (in doubles) into a.env, carried in the pointer fields
     a.T = (const double*)(size_t)0; a.p = (const double*)nT; a.qratio = (const double*)(2 * nT);
@@ -824,13 +776,12 @@ static int prep_begin(rtx_prep* P, const rtx_lines* L, int n_layers, const doubl
   a.X = nullptr; a.nx = 0; a.Twin = nullptr;
   a.n_dil = 0; a.frac = nullptr;
   for (int d = 0; d < RTX_MIX_MAX; ++d) a.dil_idx[d] = 0;
-  a.x_gamma = L->x_gamma; a.x_n = L->x_n; a.x_delta = L->x_delta; a.x_deltap = L->x_deltap; a.x_sd = L->x_sd;
-  a.rec = P->rec; a.rec64 = P->rec64; a.ic = P->ic; a.win = P->win; a.maxhw = P->maxhw; a.smally = P->smally;
+  a.x_gamma = L->x_gamma.get(); a.x_n = L->x_n.get(); a.x_delta = L->x_delta.get(); a.x_deltap = L->x_deltap.get(); a.x_sd = L->x_sd.get();
+  a.rec = P->rec.get(); a.rec64 = P->rec64.get(); a.ic = P->ic.get(); a.win = P->win.get(); a.maxhw = P->maxhw.get(); a.smally = P->smally;
   return 0;
 }
 
-// The diluent mix of rtx_line_prep_mix / _axis_mix: checks it and copies the fractions into the prep object's buffer (grow-only:
-// a larger set than before allocates, hence synchronises). After prep_begin.
+// The diluent mix of rtx_line_prep_mix / _axis_mix: checks it and copies the fractions into the prep object's buffer. After prep_begin.
 static int mix_begin(rtx_prep* P, const rtx_lines* L, int n_layers, int n_dil, const int32_t* dil_h, const double* frac_h,
                      hipStream_t st, PrepArgs& a) {
   if (n_dil < 0 || n_dil > RTX_MIX_MAX) RTX_FAIL("n_dil=%d outside [0,%d]", n_dil, RTX_MIX_MAX);
@@ -839,90 +790,91 @@ static int mix_begin(rtx_prep* P, const rtx_lines* L, int n_layers, int n_dil, c
     if (dil_h[d] < 0 || dil_h[d] >= 2 + L->n_extra)
       RTX_FAIL("diluent %d: column set %d outside [0,%d) (0 air, 1 self, 2.. rtx_lines_set_broadeners)", d, dil_h[d], 2 + L->n_extra);
   const size_t nf = (size_t)n_dil * (size_t)L->n_species * (size_t)n_layers;
-  if (nf > P->frac_cap) {
-    if (P->frac) { RTX_HIP(hipFree(P->frac)); P->frac = nullptr; }
-    P->frac_cap = 0;
-    const size_t cap = (size_t)RTX_MIX_MAX * (size_t)L->n_species * (size_t)P->max_layers;
-    RTX_HIP(hipMalloc((void**)&P->frac, cap * sizeof(double)));
-    P->frac_cap = cap;
+  if (nf) {  // sized once, for the most a call may bring
+    if (P->frac.reserve((size_t)RTX_MIX_MAX * (size_t)L->n_species * (size_t)P->max_layers)) return 1;
+    RTX_HIP(hipMemcpyAsync(P->frac.get(), frac_h, nf * sizeof(double), hipMemcpyHostToDevice, st));  // staged before returning
   }
-  if (nf) RTX_HIP(hipMemcpyAsync(P->frac, frac_h, nf * sizeof(double), hipMemcpyHostToDevice, st));  // staged before returning
   a.n_dil = n_dil;
   for (int d = 0; d < n_dil; ++d) a.dil_idx[d] = dil_h[d];
-  a.frac = P->frac;
+  a.frac = P->frac.get();
   return 0;
 }
 
-// Grid prologue of rtx_line_prep_profile (mix == NULL: dil_air / dil_self) and rtx_line_prep_mix.
+// ---- host drivers of the prologue ------------------------------------------------------------------------------------
+// The diluents of rtx_line_prep_mix / _axis_mix (NULL: the call-wide dil_air / dil_self).
 struct MixIn {
   int n_dil;
   const int32_t* dil;
   const double* frac;
 };
-static int line_prep_grid(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid, int n_layers, const double* T_h,
-                          const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
-                          double dil_air, double dil_self, const MixIn* mix, double omega_wing, double omega_wing_hw,
-                          double intensity_threshold, double scale, int profile, void* stream) {
-  if (!P || !L) RTX_FAIL("prep/lines is NULL");
-  if (profile < RTX_PROFILE_VOIGT || profile > RTX_PROFILE_SDVOIGT) RTX_FAIL("profile=%d", profile);
-  if (mix && profile == RTX_PROFILE_DOPPLER) RTX_FAIL("rtx_line_prep_mix: the Doppler profile takes no diluent");
-  if (profile == RTX_PROFILE_SDVOIGT && !P->recsd) {
-    const size_t nrec = (size_t)(P->n_lines > 0 ? P->n_lines : 1) * (size_t)P->max_layers;
-    RTX_HIP(hipMalloc((void**)&P->recsd, nrec * sizeof(LineRecSD)));
-  }
-  if (rtx_check_grid(grid)) return 1;
-  hipStream_t st = (hipStream_t)stream;
-  PrepArgs a;
-  bool env_args = false;
-  if (prep_begin(P, L, n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, dil_air, dil_self, omega_wing, omega_wing_hw,
-                 intensity_threshold, scale, profile, st, a, env_args))
+// What every prologue takes besides its spectral axis.
+struct PrepIn {
+  int n_layers;
+  const double *T_h, *p_atm_h, *qratio_h, *weight_h, *mass_h;
+  double dil_air, dil_self;
+  const MixIn* mix;
+  double omega_wing, omega_wing_hw, intensity_threshold, scale;
+  int profile;
+  hipStream_t st;
+};
+
+// First half of a prologue: the checks and per-layer tables (prep_begin), then the diluent mix.
+static int prep_start(rtx_prep* P, const rtx_lines* L, const PrepIn& in, PrepArgs& a, bool& env_args) {
+  if (prep_begin(P, L, in.n_layers, in.T_h, in.p_atm_h, in.qratio_h, in.weight_h, in.mass_h, in.dil_air, in.dil_self, in.omega_wing,
+                 in.omega_wing_hw, in.intensity_threshold, in.scale, in.profile, in.st, a, env_args))
     return 1;
-  if (mix && mix_begin(P, L, n_layers, mix->n_dil, mix->dil, mix->frac, st, a)) return 1;
-  const double g0 = mix ? gamma0_bound_mix(L, n_layers, T_h, p_atm_h, mix->n_dil, mix->dil, mix->frac)
-                        : gamma0_bound(L, n_layers, T_h, p_atm_h, dil_air, dil_self);
-  if (rtx_split_bound(P, L, grid, n_layers, T_h, mass_h, g0, omega_wing, omega_wing_hw, profile)) return 1;
-  P->n_layers = n_layers;
-  P->scale = scale;
-  P->axis = 0;
-  if (L->n == 0) return 0;
-  a.g = to_dev(grid);
-  dim3 grd((unsigned)((L->n + 255) / 256), (unsigned)n_layers);
-  if (mix) {
-    if (env_args) hipLaunchKernelGGL((line_prep_kernel<true, false, true>), grd, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((line_prep_kernel<false, false, true>), grd, dim3(256), 0, st, a);
-  } else {
-    if (env_args) hipLaunchKernelGGL((line_prep_kernel<true, false, false>), grd, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((line_prep_kernel<false, false, false>), grd, dim3(256), 0, st, a);
-  }
+  return in.mix ? mix_begin(P, L, in.n_layers, in.mix->n_dil, in.mix->dil, in.mix->frac, in.st, a) : 0;
+}
+
+// Second half: notes what ran on the prep object and launches the kernel, one thread per (line, layer). The kernel is
+// line_prep_axis_kernel<env_args, mix> on an axis, else line_prep_kernel<env_args, a.Twin given, mix> (a.Twin excludes mix).
+static int prep_launch(rtx_prep* P, const rtx_lines* L, const PrepIn& in, bool axis, bool empty, bool env_args, const PrepArgs& a) {
+  typedef void (*Kernel)(PrepArgs);
+  static const Kernel grid_k[2][3] = {
+      {line_prep_kernel<false, false, false>, line_prep_kernel<false, false, true>, line_prep_kernel<false, true, false>},
+      {line_prep_kernel<true, false, false>, line_prep_kernel<true, false, true>, line_prep_kernel<true, true, false>}};
+  static const Kernel axis_k[2][2] = {{line_prep_axis_kernel<false, false>, line_prep_axis_kernel<false, true>},
+                                      {line_prep_axis_kernel<true, false>, line_prep_axis_kernel<true, true>}};
+  P->n_layers = in.n_layers;
+  P->scale = in.scale;
+  P->axis = axis;
+  if (empty) return 0;
+  const Kernel k = axis ? axis_k[env_args][in.mix != nullptr] : grid_k[env_args][a.Twin ? 2 : in.mix ? 1 : 0];
+  hipLaunchKernelGGL(k, dim3((unsigned)((L->n + 255) / 256), (unsigned)in.n_layers), dim3(256), 0, in.st, a);
   RTX_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" int rtx_line_prep_profile(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid, int n_layers, const double* T_h,
-                             const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
-                             double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
-                             double intensity_threshold, double scale, int profile, void* stream) {
-  return line_prep_grid(P, L, grid, n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, dil_air, dil_self, nullptr, omega_wing,
-                        omega_wing_hw, intensity_threshold, scale, profile, stream);
-}
-
-extern "C" int rtx_line_prep_mix(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid, int n_layers, const double* T_h,
-                                 const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
-                                 int n_dil, const int32_t* dil_h, const double* frac_h, double omega_wing, double omega_wing_hw,
-                                 double intensity_threshold, double scale, int profile, void* stream) {
-  const MixIn mix = {n_dil, dil_h, frac_h};
-  return line_prep_grid(P, L, grid, n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, 0.0, 0.0, &mix, omega_wing, omega_wing_hw,
-                        intensity_threshold, scale, profile, stream);
-}
-
-static int line_prep_axis(rtx_prep* P, const rtx_lines* L, const double* X_h, int64_t nx, int n_layers, const double* T_h,
-                          const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
-                          double dil_air, double dil_self, const MixIn* mix, double omega_wing, double omega_wing_hw,
-                          double intensity_threshold, double scale, int profile, void* stream) {
+// Grid prologue of rtx_line_prep_profile, rtx_line_prep_mix (in.mix) and rtx_line_prep_window (T_win_h: every window, hence
+// the candidate half-widths and the hot-tile bound, at those temperatures; its device copy belongs to the prep object).
+static int line_prep_grid(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid, const double* T_win_h, const PrepIn& in) {
   if (!P || !L) RTX_FAIL("prep/lines is NULL");
-  if (profile < RTX_PROFILE_VOIGT || profile > RTX_PROFILE_DOPPLER)
-    RTX_FAIL("rtx_line_prep_axis: profile=%d (Voigt, Lorentz or Doppler; the speed-dependent sum needs a uniform grid)", profile);
-  if (mix && profile == RTX_PROFILE_DOPPLER) RTX_FAIL("rtx_line_prep_axis_mix: the Doppler profile takes no diluent");
+  if (in.profile < RTX_PROFILE_VOIGT || in.profile > RTX_PROFILE_SDVOIGT) RTX_FAIL("profile=%d", in.profile);
+  if (in.mix && in.profile == RTX_PROFILE_DOPPLER) RTX_FAIL("rtx_line_prep_mix: the Doppler profile takes no diluent");
+  if (in.mix && T_win_h) RTX_FAIL("window temperatures and a diluent mix do not go together");
+  if (in.profile == RTX_PROFILE_SDVOIGT && P->recsd.reserve((size_t)(P->n_lines > 0 ? P->n_lines : 1) * (size_t)P->max_layers)) return 1;
+  if (rtx_check_grid(grid)) return 1;
+  PrepArgs a;
+  bool env_args = false;
+  if (prep_start(P, L, in, a, env_args)) return 1;
+  if (T_win_h) {
+    if (P->twin.reserve((size_t)P->max_layers)) return 1;
+    RTX_HIP(hipMemcpyAsync(P->twin.get(), T_win_h, (size_t)in.n_layers * sizeof(double), hipMemcpyHostToDevice, in.st));  // staged before returning
+    a.Twin = P->twin.get();
+  }
+  const double* T_w = T_win_h ? T_win_h : in.T_h;
+  const double g0 = in.mix ? gamma0_bound_mix(L, in.n_layers, T_w, in.p_atm_h, in.mix->n_dil, in.mix->dil, in.mix->frac)
+                           : gamma0_bound(L, in.n_layers, T_w, in.p_atm_h, in.dil_air, in.dil_self);
+  if (rtx_split_bound(P, L, grid, in.n_layers, T_w, in.mass_h, g0, in.omega_wing, in.omega_wing_hw, in.profile)) return 1;
+  a.g = to_dev(grid);
+  return prep_launch(P, L, in, false, L->n == 0, env_args, a);
+}
+
+static int line_prep_axis(rtx_prep* P, const rtx_lines* L, const double* X_h, int64_t nx, const PrepIn& in) {
+  if (!P || !L) RTX_FAIL("prep/lines is NULL");
+  if (in.profile < RTX_PROFILE_VOIGT || in.profile > RTX_PROFILE_DOPPLER)
+    RTX_FAIL("rtx_line_prep_axis: profile=%d (Voigt, Lorentz or Doppler; the speed-dependent sum needs a uniform grid)", in.profile);
+  if (in.mix && in.profile == RTX_PROFILE_DOPPLER) RTX_FAIL("rtx_line_prep_axis_mix: the Doppler profile takes no diluent");
   const long long cap = P->max_tiles * (long long)rtx_voigt_tile_points();
   if (nx < 0 || nx > cap) RTX_FAIL("axis of %lld points outside the prep capacity [0, %lld]", (long long)nx, cap);
   if (nx > 0 && !X_h) RTX_FAIL("axis is NULL");
@@ -930,44 +882,48 @@ static int line_prep_axis(rtx_prep* P, const rtx_lines* L, const double* X_h, in
     if (!isfinite(X_h[i])) RTX_FAIL("axis point %lld is not finite", (long long)i);
     if (i > 0 && X_h[i] < X_h[i - 1]) RTX_FAIL("axis must be non-decreasing (point %lld)", (long long)i);
   }
-  hipStream_t st = (hipStream_t)stream;
   PrepArgs a;
   bool env_args = false;
-  if (prep_begin(P, L, n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, dil_air, dil_self, omega_wing, omega_wing_hw,
-                 intensity_threshold, scale, profile, st, a, env_args))
-    return 1;
-  if (mix && mix_begin(P, L, n_layers, mix->n_dil, mix->dil, mix->frac, st, a)) return 1;
-  if (nx > P->x_cap) {  // grow-only: allocates, hence synchronises
-    if (P->X) { RTX_HIP(hipFree(P->X)); P->X = nullptr; }
-    P->x_cap = 0;
-    RTX_HIP(hipMalloc((void**)&P->X, (size_t)nx * sizeof(double)));
-    P->x_cap = nx;
-  }
-  if (nx > 0) RTX_HIP(hipMemcpyAsync(P->X, X_h, (size_t)nx * sizeof(double), hipMemcpyHostToDevice, st));  // staged before returning
-  P->n_layers = n_layers;
-  P->scale = scale;
-  P->axis = 1;
+  if (prep_start(P, L, in, a, env_args)) return 1;
+  if (P->X.reserve((size_t)nx)) return 1;
+  if (nx > 0) RTX_HIP(hipMemcpyAsync(P->X.get(), X_h, (size_t)nx * sizeof(double), hipMemcpyHostToDevice, in.st));  // staged before returning
   P->nx = nx;
-  if (L->n == 0 || nx == 0) return 0;
-  a.X = P->X; a.nx = nx;
-  dim3 grd((unsigned)((L->n + 255) / 256), (unsigned)n_layers);
-  if (mix) {
-    if (env_args) hipLaunchKernelGGL((line_prep_axis_kernel<true, true>), grd, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((line_prep_axis_kernel<false, true>), grd, dim3(256), 0, st, a);
-  } else {
-    if (env_args) hipLaunchKernelGGL((line_prep_axis_kernel<true, false>), grd, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((line_prep_axis_kernel<false, false>), grd, dim3(256), 0, st, a);
-  }
-  RTX_LAUNCH_CHECK();
-  return 0;
+  a.X = P->X.get(); a.nx = nx;
+  return prep_launch(P, L, in, true, L->n == 0 || nx == 0, env_args, a);
+}
+
+// The entry points: each packs its arguments and names its driver.
+#define RTX_PREP_IN(dil_air, dil_self, mix, profile)                                                                          \
+  PrepIn { n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, dil_air, dil_self, mix, omega_wing, omega_wing_hw, intensity_threshold, \
+           scale, profile, (hipStream_t)stream }
+
+extern "C" int rtx_line_prep_profile(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid, int n_layers, const double* T_h,
+                             const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
+                             double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
+                             double intensity_threshold, double scale, int profile, void* stream) {
+  return line_prep_grid(P, L, grid, nullptr, RTX_PREP_IN(dil_air, dil_self, nullptr, profile));
+}
+
+extern "C" int rtx_line_prep(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid, int n_layers, const double* T_h,
+                             const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
+                             double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
+                             double intensity_threshold, double scale, void* stream) {
+  return line_prep_grid(P, L, grid, nullptr, RTX_PREP_IN(dil_air, dil_self, nullptr, RTX_PROFILE_VOIGT));
+}
+
+extern "C" int rtx_line_prep_mix(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid, int n_layers, const double* T_h,
+                                 const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
+                                 int n_dil, const int32_t* dil_h, const double* frac_h, double omega_wing, double omega_wing_hw,
+                                 double intensity_threshold, double scale, int profile, void* stream) {
+  const MixIn mix = {n_dil, dil_h, frac_h};
+  return line_prep_grid(P, L, grid, nullptr, RTX_PREP_IN(0.0, 0.0, &mix, profile));
 }
 
 extern "C" int rtx_line_prep_axis(rtx_prep* P, const rtx_lines* L, const double* X_h, int64_t nx, int n_layers, const double* T_h,
                                   const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
                                   double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
                                   double intensity_threshold, double scale, int profile, void* stream) {
-  return line_prep_axis(P, L, X_h, nx, n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, dil_air, dil_self, nullptr, omega_wing,
-                        omega_wing_hw, intensity_threshold, scale, profile, stream);
+  return line_prep_axis(P, L, X_h, nx, RTX_PREP_IN(dil_air, dil_self, nullptr, profile));
 }
 
 extern "C" int rtx_line_prep_axis_mix(rtx_prep* P, const rtx_lines* L, const double* X_h, int64_t nx, int n_layers, const double* T_h,
@@ -975,22 +931,12 @@ extern "C" int rtx_line_prep_axis_mix(rtx_prep* P, const rtx_lines* L, const dou
                                       int n_dil, const int32_t* dil_h, const double* frac_h, double omega_wing, double omega_wing_hw,
                                       double intensity_threshold, double scale, int profile, void* stream) {
   const MixIn mix = {n_dil, dil_h, frac_h};
-  return line_prep_axis(P, L, X_h, nx, n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, 0.0, 0.0, &mix, omega_wing, omega_wing_hw,
-                        intensity_threshold, scale, profile, stream);
-}
-
-extern "C" int rtx_line_prep(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid, int n_layers, const double* T_h,
-                             const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
-                             double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
-                             double intensity_threshold, double scale, void* stream) {
-  return rtx_line_prep_profile(P, L, grid, n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, dil_air, dil_self, omega_wing,
-                               omega_wing_hw, intensity_threshold, scale, RTX_PROFILE_VOIGT, stream);
+  return line_prep_axis(P, L, X_h, nx, RTX_PREP_IN(0.0, 0.0, &mix, profile));
 }
 
 // The grid prologue with the windows held at other temperatures: the derivative of the truncated line-sum with every
-// line's support fixed (rtx_tud_jacobian's dOD/dT). Everything but the windows is taken at T_h; OmegaWingF, hence
-// the windows, the candidate half-widths and the hot-tile bound, at T_win_h. T_win_h is copied into a device buffer owned by
-// the prep object (grow-only). With T_win_h == T_h the records are those of rtx_line_prep_profile.
+// line's support fixed (rtx_tud_jacobian's dOD/dT). Everything but the windows is taken at T_h. With
+// T_win_h == T_h the records are those of rtx_line_prep_profile.
 extern "C" int rtx_line_prep_window(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid, int n_layers, const double* T_h,
                                     const double* T_win_h, const double* p_atm_h, const double* qratio_h, const double* weight_h,
                                     const double* mass_h, double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
@@ -1002,31 +948,5 @@ extern "C" int rtx_line_prep_window(rtx_prep* P, const rtx_lines* L, const rtx_g
   if (!T_win_h) RTX_FAIL("T_win_h is NULL");
   for (int k = 0; k < n_layers; ++k)
     if (!(T_win_h[k] > 0.0)) RTX_FAIL("layer %d: window temperature %g not physical", k, T_win_h[k]);
-  hipStream_t st = (hipStream_t)stream;
-  PrepArgs a;
-  bool env_args = false;
-  if (prep_begin(P, L, n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, dil_air, dil_self, omega_wing, omega_wing_hw,
-                 intensity_threshold, scale, profile, st, a, env_args))
-    return 1;
-  if (n_layers > P->twin_cap) {  // grow-only: allocates, hence synchronises
-    if (P->twin) { RTX_HIP(hipFree(P->twin)); P->twin = nullptr; }
-    P->twin_cap = 0;
-    RTX_HIP(hipMalloc((void**)&P->twin, (size_t)P->max_layers * sizeof(double)));
-    P->twin_cap = P->max_layers;
-  }
-  RTX_HIP(hipMemcpyAsync(P->twin, T_win_h, (size_t)n_layers * sizeof(double), hipMemcpyHostToDevice, st));  // staged before returning
-  if (rtx_split_bound(P, L, grid, n_layers, T_win_h, mass_h, gamma0_bound(L, n_layers, T_win_h, p_atm_h, dil_air, dil_self), omega_wing,
-                      omega_wing_hw, profile))
-    return 1;
-  P->n_layers = n_layers;
-  P->scale = scale;
-  P->axis = 0;
-  if (L->n == 0) return 0;
-  a.g = to_dev(grid);
-  a.Twin = P->twin;
-  dim3 grd((unsigned)((L->n + 255) / 256), (unsigned)n_layers);
-  if (env_args) hipLaunchKernelGGL((line_prep_kernel<true, true, false>), grd, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((line_prep_kernel<false, true, false>), grd, dim3(256), 0, st, a);
-  RTX_LAUNCH_CHECK();
-  return 0;
+  return line_prep_grid(P, L, grid, T_win_h, RTX_PREP_IN(dil_air, dil_self, nullptr, profile));
 }

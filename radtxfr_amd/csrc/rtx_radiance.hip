@@ -557,24 +557,18 @@ __global__ __launch_bounds__(256) void ils_rows_reduce_kernel(IlsRowsArgs r) {
   reinterpret_cast<float4*>(a.Yout + (size_t)b * a.nS)[col4] = o;
 }
 
-// grow-only workspace of the one-pass form, per (device, stream): two rtx_ils calls in flight on different streams (or
-// from different host threads on their own streams) must not share partial sums and the overflow flag; calls on ONE stream
-// are ordered by it. A workspace is re-allocated only to grow, and hipFree waits for the device, so a launch already
-// enqueued on that stream never loses its buffer.
+// workspace of the one-pass form, per (device, stream): two rtx_ils calls in flight on different streams (or from
+// different host threads on their own streams) must not share partial sums and the overflow flag; calls on ONE stream
+// are ordered by it. The map lives as long as the process.
 static int ils_rows_workspace(size_t bytes, hipStream_t st, void** out) {
   static std::mutex mu;
-  static std::map<std::pair<int, hipStream_t>, std::pair<void*, size_t>> ws;
+  static auto* const ws = new std::map<std::pair<int, hipStream_t>, DevBuf<char>>();
   int dev = 0;
   RTX_HIP(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lock(mu);
-  auto& e = ws[std::make_pair(dev, st)];
-  if (e.second < bytes) {
-    if (e.first) RTX_HIP(hipFree(e.first));
-    e.first = nullptr; e.second = 0;
-    RTX_HIP(hipMalloc(&e.first, bytes));
-    e.second = bytes;
-  }
-  *out = e.first;
+  DevBuf<char>& b = (*ws)[std::make_pair(dev, st)];
+  if (b.reserve(bytes)) return 1;
+  *out = b.get();
   return 0;
 }
 

@@ -81,33 +81,15 @@ extern "C" int rtx_fir_reflect(const void* in, int in_is_f64, int64_t ld_in, int
   if (n_rows > 65535) RTX_FAIL("n_rows=%d too large", n_rows);
   hipStream_t st = (hipStream_t)stream;
   // device copies of the windows seen so far (a caller smooths every spectrum of a run with the same one or two windows):
-  // a hit costs a memcmp; only a new window is uploaded (synchronously: taps_h may be a temporary of the caller)
-  // The lock is held until the kernel that reads the taps is enqueued: an eviction by another host thread (hipFree, which
-  // waits for the device) can then only come after the launch, never between the look-up and it.
-  double* d_taps = nullptr;
-  struct Win { int dev; std::vector<double> h; double* d; };
-  static std::mutex mu;
-  static std::vector<Win> cache;
-  std::lock_guard<std::mutex> lock(mu);
-  {
-    int dev = 0;
-    RTX_HIP(hipGetDevice(&dev));
-    for (const Win& w : cache)
-      if (w.dev == dev && (int)w.h.size() == n_taps && memcmp(w.h.data(), taps_h, (size_t)n_taps * sizeof(double)) == 0) { d_taps = w.d; break; }
-    if (!d_taps) {
-      if (cache.size() >= 64) {  // bounded: forget the oldest
-        (void)hipFree(cache.front().d);
-        cache.erase(cache.begin());
-      }
-      Win w;
-      w.dev = dev;
-      w.h.assign(taps_h, taps_h + n_taps);
-      RTX_HIP(hipMalloc((void**)&w.d, (size_t)n_taps * sizeof(double)));
-      RTX_HIP(hipMemcpy(w.d, taps_h, (size_t)n_taps * sizeof(double), hipMemcpyHostToDevice));
-      d_taps = w.d;
-      cache.push_back(std::move(w));
-    }
-  }
+  // a hit costs a memcmp; only a new window is uploaded
+  static DevTableCache<double>* const cache = new DevTableCache<double>(64);
+  int dev = 0;
+  RTX_HIP(hipGetDevice(&dev));
+  DevTableCache<double>::Hit taps;  // holds the cache's lock until this function returns, after the launch
+  if (cache->get(dev, taps_h, (size_t)n_taps * sizeof(double),
+                 [&](std::vector<double>& h) { h.assign(taps_h, taps_h + n_taps); return 0; }, &taps))
+    return 1;
+  const double* d_taps = taps.d;
   const dim3 grid((unsigned)((n + FIR_TILE - 1) / FIR_TILE), (unsigned)n_rows);
   if (in_is_f64)
     hipLaunchKernelGGL(fir_reflect_kernel<double>, grid, dim3(FIR_BLOCK), 0, st, (const double*)in, (long long)ld_in, (long long)n, d_taps,

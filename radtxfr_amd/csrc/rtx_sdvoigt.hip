@@ -522,45 +522,38 @@ __global__ __launch_bounds__(256) void sdvoigt_tile_kernel(SdArgs a, SdTab tab) 
 
 // Chebyshev nodes (first kind) on [0, L - 1] and the Lagrange basis of every node at the L integer points, formed once per
 // device in long double on the host.
-static int sd_tables(SdTab* out) {
-  static std::mutex mu;
-  static SdTab cache[64];
-  static bool have[64] = {false};
+// The N nodes on [0, L - 1] and, appended to mT, the N x L basis values [node][point].
+static void sd_lagrange(int N, int L, double* off, std::vector<double>& mT) {
+  std::vector<long double> x(N);
+  const long double h = (long double)(L - 1) / 2.0L, pi = 3.14159265358979323846264338327950288L;
+  for (int j = 0; j < N; ++j) x[j] = h + h * cosl((2 * j + 1) * pi / (2.0L * N));
+  for (int j = 0; j < N; ++j) {
+    off[j] = (double)x[j];
+    for (int p = 0; p < L; ++p) {
+      long double v = 1.0L;
+      for (int m = 0; m < N; ++m)
+        if (m != j) v *= ((long double)p - x[m]) / (x[j] - x[m]);
+      mT.push_back((double)v);
+    }
+  }
+}
+// The node positions are host constants, made once; the basis lives on the device as one table per device, [tmT | rmT].
+// `held` keeps the cache's lock for the caller, until its launch.
+static int sd_tables(SdTab* out, DevTableCache<double>::Hit* held) {
+  struct Host { SdTab t; std::vector<double> m; };
+  static const Host* const host = [] {
+    Host* h = new Host();
+    sd_lagrange(SD_TN, SD_TILE, h->t.toff, h->m);
+    sd_lagrange(SD_RN, 64, h->t.roff, h->m);
+    return h;
+  }();
+  static DevTableCache<double>* const cache = new DevTableCache<double>(0);
   int dev = 0;
   RTX_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) RTX_FAIL("device %d", dev);
-  std::lock_guard<std::mutex> lock(mu);
-  if (!have[dev]) {
-    SdTab t;
-    auto build = [](int N, int L, double* off, std::vector<double>& mT) {
-      std::vector<long double> x(N);
-      const long double h = (long double)(L - 1) / 2.0L, pi = 3.14159265358979323846264338327950288L;
-      for (int j = 0; j < N; ++j) x[j] = h + h * cosl((2 * j + 1) * pi / (2.0L * N));
-      mT.assign((size_t)N * L, 0.0);
-      for (int j = 0; j < N; ++j) {
-        off[j] = (double)x[j];
-        for (int p = 0; p < L; ++p) {
-          long double v = 1.0L;
-          for (int m = 0; m < N; ++m)
-            if (m != j) v *= ((long double)p - x[m]) / (x[j] - x[m]);
-          mT[(size_t)j * L + p] = (double)v;
-        }
-      }
-    };
-    std::vector<double> tm, rm;
-    build(SD_TN, SD_TILE, t.toff, tm);
-    build(SD_RN, 64, t.roff, rm);
-    double *d_tm = nullptr, *d_rm = nullptr;
-    RTX_HIP(hipMalloc((void**)&d_tm, tm.size() * sizeof(double)));
-    RTX_HIP(hipMalloc((void**)&d_rm, rm.size() * sizeof(double)));
-    RTX_HIP(hipMemcpy(d_tm, tm.data(), tm.size() * sizeof(double), hipMemcpyHostToDevice));
-    RTX_HIP(hipMemcpy(d_rm, rm.data(), rm.size() * sizeof(double), hipMemcpyHostToDevice));
-    t.tmT = d_tm;
-    t.rmT = d_rm;
-    cache[dev] = t;
-    have[dev] = true;
-  }
-  *out = cache[dev];
+  if (cache->get(dev, nullptr, 0, [&](std::vector<double>& m) { m = host->m; return 0; }, held)) return 1;
+  *out = host->t;
+  out->tmT = held->d;
+  out->rmT = held->d + (size_t)SD_TN * SD_TILE;
   return 0;
 }
 
@@ -569,7 +562,7 @@ extern "C" int rtx_sdvoigt_sum(const rtx_prep* P, const rtx_grid* grid, int n_la
   if (!P) RTX_FAIL("prep is NULL");
   if (P->axis) RTX_FAIL("the last prologue was rtx_line_prep_axis: the speed-dependent sum needs a uniform grid");
   if (rtx_check_grid(grid)) return 1;
-  if (!P->recsd) RTX_FAIL("rtx_line_prep_profile(..., RTX_PROFILE_SDVOIGT, ...) has not been run on this prep object");
+  if (!P->recsd.get()) RTX_FAIL("rtx_line_prep_profile(..., RTX_PROFILE_SDVOIGT, ...) has not been run on this prep object");
   if (n_layers < 1 || n_layers > P->n_layers) RTX_FAIL("n_layers=%d, the prologue was run for %d", n_layers, P->n_layers);
   if (!out_f32 && !out_f64) RTX_FAIL("no output given");
   if (ld < grid->n) RTX_FAIL("leading dimension smaller than the shard");
@@ -577,7 +570,7 @@ extern "C" int rtx_sdvoigt_sum(const rtx_prep* P, const rtx_grid* grid, int n_la
   if (grid->n > 2000000000LL) RTX_FAIL("grid shard of %lld points", (long long)grid->n);
   hipStream_t st = (hipStream_t)stream;
   SdArgs a;
-  a.rec = P->rec; a.recsd = P->recsd; a.ic = P->ic; a.maxhw = P->maxhw; a.n_lines = P->n_lines;
+  a.rec = P->rec.get(); a.recsd = P->recsd.get(); a.ic = P->ic.get(); a.maxhw = P->maxhw.get(); a.n_lines = P->n_lines;
   a.g = to_dev(grid);
   a.out32 = out_f32; a.out64 = out_f64; a.ld = ld; a.scale = P->scale;
   const char* e_k = getenv("RADTXFR_SD_KERNEL");  // "gather": the point-by-point cross-check (read per call: tests switch it)
@@ -586,7 +579,8 @@ extern "C" int rtx_sdvoigt_sum(const rtx_prep* P, const rtx_grid* grid, int n_la
     hipLaunchKernelGGL(sdvoigt_kernel, dim3((unsigned)((grid->n + 255) / 256), (unsigned)n_layers), dim3(256), 0, st, a);
   } else {
     SdTab tab;
-    if (sd_tables(&tab)) return 1;
+    DevTableCache<double>::Hit held;
+    if (sd_tables(&tab, &held)) return 1;
     hipLaunchKernelGGL(sdvoigt_tile_kernel, dim3((unsigned)((grid->n + SD_TILE - 1) / SD_TILE), (unsigned)n_layers), dim3(256), 0, st, a, tab);
   }
   RTX_LAUNCH_CHECK();

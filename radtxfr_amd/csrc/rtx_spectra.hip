@@ -146,31 +146,14 @@ extern "C" int rtx_fir_same(const void* in, int in_is_f64, int64_t ld_in, int n_
   if (n_out == 0) return 0;
   if ((n_out + FS_TILE - 1) / FS_TILE > 0x7fffffffLL) RTX_FAIL("n_out=%lld too large", (long long)n_out);
   hipStream_t st = (hipStream_t)stream;
-  // device copies of the slits seen so far, as rtx_fir_reflect keeps its windows: a hit costs a memcmp, a new slit is
-  // uploaded synchronously (taps_h may be a temporary of the caller). The lock is held until the kernel that reads the taps
-  // is enqueued, so an eviction by another host thread (hipFree waits for the device) cannot come between look-up and launch.
-  struct Slit { int dev; std::vector<double> h; double* d; };
-  static std::mutex mu;
-  static std::vector<Slit> cache;
-  std::lock_guard<std::mutex> lock(mu);
-  double* d_taps = nullptr;
+  // device copies of the slits seen so far: a hit costs a memcmp, only a new slit is uploaded
+  static DevTableCache<double>* const cache = new DevTableCache<double>(16);
   int dev = 0;
   RTX_HIP(hipGetDevice(&dev));
-  for (const Slit& s : cache)
-    if (s.dev == dev && (int64_t)s.h.size() == m && memcmp(s.h.data(), taps_h, (size_t)m * sizeof(double)) == 0) { d_taps = s.d; break; }
-  if (!d_taps) {
-    if (cache.size() >= 16) {  // bounded: forget the oldest
-      (void)hipFree(cache.front().d);
-      cache.erase(cache.begin());
-    }
-    Slit s;
-    s.dev = dev;
-    s.h.assign(taps_h, taps_h + m);
-    RTX_HIP(hipMalloc((void**)&s.d, (size_t)m * sizeof(double)));
-    RTX_HIP(hipMemcpy(s.d, taps_h, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
-    d_taps = s.d;
-    cache.push_back(std::move(s));
-  }
+  DevTableCache<double>::Hit taps;  // holds the cache's lock until this function returns, after the launches
+  if (cache->get(dev, taps_h, (size_t)m * sizeof(double), [&](std::vector<double>& h) { h.assign(taps_h, taps_h + m); return 0; }, &taps))
+    return 1;
+  const double* d_taps = taps.d;
   const unsigned tiles = (unsigned)((n_out + FS_TILE - 1) / FS_TILE);
   for (int r0 = 0; r0 < n_rows; r0 += 65535) {  // grid.y holds 65535 rows
     const int nr = n_rows - r0 < 65535 ? n_rows - r0 : 65535;

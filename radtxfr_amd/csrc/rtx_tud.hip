@@ -953,7 +953,6 @@ __global__ __launch_bounds__(256) void tud_g_snap_kernel(TudArgs a) {
 }
 
 // Host side of G: piecewise Chebyshev interpolants of degree TUDG_DEG in fp64, stored as monomials in (S - mid).
-struct GTab { double* dev; double g0; };
 static void tudg_build(int n_angle, std::vector<double>& tab, double& g0_out) {
   const TudQuadrature quad = tud_quadrature(n_angle);
   std::vector<double> sec;
@@ -1013,22 +1012,12 @@ extern "C" int rtx_tud_gtable(int n_angle, double* table_h, double* g0_h) {
   return 0;
 }
 
-static int tudg_table(int n_angle, GTab* out) {
-  static std::mutex mu;
-  static std::map<std::pair<int, int>, GTab> cache;  // (device, n_angle)
+// The device copy of the table, one per (device, n_angle), never forgotten.
+static int tudg_table(int n_angle, DevTableCache<double>::Hit* out) {
+  static DevTableCache<double>* const cache = new DevTableCache<double>(0);
   int dev = 0;
   RTX_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = cache.find({dev, n_angle});
-  if (it != cache.end()) { *out = it->second; return 0; }
-  std::vector<double> tab;
-  GTab t;
-  tudg_build(n_angle, tab, t.g0);
-  RTX_HIP(hipMalloc(&t.dev, tab.size() * sizeof(double)));
-  RTX_HIP(hipMemcpy(t.dev, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
-  cache[{dev, n_angle}] = t;
-  *out = t;
-  return 0;
+  return cache->get(dev, &n_angle, sizeof(n_angle), [&](std::vector<double>& tab) { double g0; tudg_build(n_angle, tab, g0); return 0; }, out);
 }
 
 // one thread per wavenumber of the shard, 256 per workgroup
@@ -1103,9 +1092,9 @@ extern "C" int rtx_tud(const float* OD, int64_t ld, const rtx_grid* grid, int n_
   static int force_streams = -1;
   if (force_streams < 0) { const char* e = getenv("RADTXFR_TUD_KERNEL"); force_streams = (e && !strcmp(e, "streams")) ? 1 : 0; }
   if (!Ld_angles && !force_streams) {
-    GTab gt;
+    DevTableCache<double>::Hit gt;  // with the cache's lock, held until the launch below has returned
     if (tudg_table(n_angle, &gt)) return 1;
-    a.gtab = gt.dev; a.g0 = gt.g0;
+    a.gtab = gt.d; a.g0 = quad.wsum;  // G(0)
     bool prefix = true;  // every altitude's mask = its first count layers?
     for (int ia = 0; ia < n_alt && prefix; ++ia)
       for (int k = 0; k < n_layers; ++k)

@@ -142,10 +142,10 @@ int rtx_voigt_sum_scatter(const rtx_prep* P, const rtx_grid* grid, int n_layers,
 
 static void launch_tile_ranges(const rtx_prep* P, const rtx_grid* grid, int n_layers, int n_tiles, int tile, hipStream_t st, int split) {
   RangeArgs ra;
-  const bool cut = split && P->split_bound > 0 && P->items;
-  ra.items = cut ? P->items : nullptr; ra.n_items = P->n_items; ra.items_cap = P->items_cap;
-  ra.ic = P->ic; ra.maxhw = P->maxhw; ra.win = P->win; ra.n_lines = P->n_lines; ra.n_tiles = n_tiles; ra.tile = tile;
-  ra.n_layers = n_layers; ra.n = grid->n; ra.ranges = P->ranges;
+  const bool cut = split && P->split_bound > 0 && P->items.get();
+  ra.items = cut ? P->items.get() : nullptr; ra.n_items = P->n_items; ra.items_cap = (long long)P->items.cap();
+  ra.ic = P->ic.get(); ra.maxhw = P->maxhw.get(); ra.win = P->win.get(); ra.n_lines = P->n_lines; ra.n_tiles = n_tiles; ra.tile = tile;
+  ra.n_layers = n_layers; ra.n = grid->n; ra.ranges = P->ranges.get();
   int n_steps = 1;  // 17-ary search: each step divides the bracket by 17 (rounded up), one more finishes the last <= 16 elements
                     // (the step count is checked against bisect for every size class in a NumPy restatement: tests/test_host.py)
   for (long long w = P->n_lines; w > 0; w /= (RNG_G + 1)) ++n_steps;

@@ -160,7 +160,7 @@ extern "C" int rtx_voigt_sum_axis(const rtx_prep* P, int n_layers, float* out_f3
   rtx_launch_tile_ranges_n(P, P->nx, n_layers, n_tiles, AX_TILE, st);
   RTX_LAUNCH_CHECK();
   AxisArgs a;
-  a.rec = P->rec; a.rec64 = P->rec64; a.ranges = P->ranges; a.X = P->X;
+  a.rec = P->rec.get(); a.rec64 = P->rec64.get(); a.ranges = P->ranges.get(); a.X = P->X.get();
   a.n_lines = P->n_lines; a.n_tiles = n_tiles; a.nx = (int)P->nx;
   a.out32 = out_f32; a.out64 = out_f64; a.ld = ld; a.inv_scale = 1.0 / P->scale;
   hipLaunchKernelGGL(voigt_axis_kernel, dim3((unsigned)n_tiles, (unsigned)n_layers), dim3(256), 0, st, a);

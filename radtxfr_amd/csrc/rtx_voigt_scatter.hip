@@ -904,16 +904,16 @@ int rtx_voigt_sum_scatter(const rtx_prep* P, const rtx_grid* grid, int n_layers,
   const int n_tiles = (int)n_tiles_ll;
   // the work list of hot-tile parts is rebuilt by every call (a caller may sum twice after one prologue, e.g. once per
   // output precision): its counter starts from zero each time
-  if (nodal && P->split_bound > 0 && P->items) RTX_HIP(hipMemsetAsync(P->n_items, 0, sizeof(int), st));
+  if (nodal && P->split_bound > 0 && P->items.get()) RTX_HIP(hipMemsetAsync(P->n_items, 0, sizeof(int), st));
   launch_ranges(P, grid, n_layers, n_tiles, TILE, st, nodal);  // the point-by-point cross-check takes every tile whole
   RTX_LAUNCH_CHECK();
   ScArgs a;
-  a.rec = P->rec; a.rec64 = P->rec64; a.ranges = P->ranges; a.smally = P->smally; a.n_lines = P->n_lines;
+  a.rec = P->rec.get(); a.rec64 = P->rec64.get(); a.ranges = P->ranges.get(); a.smally = P->smally; a.n_lines = P->n_lines;
   a.n_tiles = n_tiles; a.tiles_per_xcd = xcd_slots(n_tiles);
   a.g = to_dev(grid);
   a.out32 = out_f32; a.out64 = out_f64; a.ld = ld; a.inv_scale = 1.0 / P->scale;
   a.stamp = nullptr;
-  a.items = P->items; a.n_items = P->n_items; a.part_ws = P->part_ws;
+  a.items = P->items.get(); a.n_items = P->n_items; a.part_ws = P->part_ws.get();
 #if RTX_SC_STAMP
   static unsigned long long* d_stamp = nullptr;
   static size_t stamp_cap = 0;
@@ -933,7 +933,7 @@ int rtx_voigt_sum_scatter(const rtx_prep* P, const rtx_grid* grid, int n_layers,
     hipLaunchKernelGGL((voigt_nodal_kernel<false>), dim3(8 * a.tiles_per_xcd, n_layers), dim3(64 * SC_NW), (size_t)lds_pad, st, a);
     RTX_LAUNCH_CHECK();
     hipLaunchKernelGGL((voigt_nodal_kernel<true>), dim3(8 * ((a.tiles_per_xcd + 15) / 16), n_layers), dim3(64 * SC_NW), 0, st, a);
-    if (P->split_bound > 0 && P->items) {  // the table can have hot tiles: their extra parts, then the sums in part order
+    if (P->split_bound > 0 && P->items.get()) {  // the table can have hot tiles: their extra parts, then the sums in part order
       RTX_LAUNCH_CHECK();
       const unsigned cap = (unsigned)P->split_bound;
       hipLaunchKernelGGL((voigt_nodal_parts_kernel<false>), dim3(cap), dim3(64 * SC_NW), 0, st, a);

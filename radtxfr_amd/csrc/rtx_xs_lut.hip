@@ -15,15 +15,14 @@
 // at once (compute_TUD_batch's two runners), and within a stream the copy is ordered behind the previous kernel
 struct XsTerms {
   hipStream_t stream;
-  int* rows;
-  float* w;
-  size_t cap;  // terms
+  DevBuf<int> rows;
+  DevBuf<float> w;
 };
 
 struct rtx_xs_lut {
   int n_mol;
   long long n_rows, nx, ldx;  // ldx: row stride in floats, a multiple of 4 (every row starts 16-byte aligned)
-  float* data;                // [n_rows][ldx]
+  DevBuf<float> data;         // [n_rows][ldx]
   int dev;
   std::mutex mu;
   std::vector<XsTerms> terms;
@@ -86,14 +85,12 @@ extern "C" int rtx_xs_lut_create(int n_mol, int64_t n_rows, int64_t nx, rtx_xs_l
   L->n_rows = n_rows;
   L->nx = nx;
   L->ldx = (nx + 3) / 4 * 4;
-  L->data = nullptr;
   hipError_t e = hipGetDevice(&L->dev);
   const size_t bytes = (size_t)n_rows * (size_t)L->ldx * sizeof(float);
-  if (e == hipSuccess) e = hipMalloc((void**)&L->data, bytes);
-  if (e == hipSuccess) e = hipMemset(L->data, 0, bytes);  // the pad columns are read by no kernel; rows not yet set are 0
+  if (e == hipSuccess && L->data.reserve((size_t)n_rows * (size_t)L->ldx)) e = hipErrorOutOfMemory;
+  if (e == hipSuccess) e = hipMemset(L->data.get(), 0, bytes);  // the pad columns are read by no kernel; rows not yet set are 0
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) {
-    if (L->data) (void)hipFree(L->data);
     delete L;
     RTX_FAIL("rtx_xs_lut_create: %lld rows of %lld points (%.1f MB) -> %s", (long long)n_rows, (long long)nx, bytes / 1.0e6,
              hipGetErrorString(e));
@@ -103,12 +100,6 @@ extern "C" int rtx_xs_lut_create(int n_mol, int64_t n_rows, int64_t nx, rtx_xs_l
 }
 
 extern "C" int rtx_xs_lut_free(rtx_xs_lut* L) {
-  if (!L) return 0;
-  (void)hipFree(L->data);  // hipFree waits for the device: no kernel still reads the table or the terms
-  for (XsTerms& t : L->terms) {
-    (void)hipFree(t.rows);
-    (void)hipFree(t.w);
-  }
   delete L;
   return 0;
 }
@@ -127,7 +118,7 @@ static int xs_check_rows(const rtx_xs_lut* L, int64_t row0, int64_t n_rows, cons
 extern "C" int rtx_xs_lut_set_rows(rtx_xs_lut* L, int64_t row0, int64_t n_rows, const float* rows_h, void* stream) {
   if (xs_check_rows(L, row0, n_rows, rows_h)) return 1;
   if (n_rows == 0) return 0;
-  RTX_HIP(hipMemcpy2DAsync(L->data + (size_t)row0 * (size_t)L->ldx, (size_t)L->ldx * sizeof(float), rows_h, (size_t)L->nx * sizeof(float),
+  RTX_HIP(hipMemcpy2DAsync(L->data.get() + (size_t)row0 * (size_t)L->ldx, (size_t)L->ldx * sizeof(float), rows_h, (size_t)L->nx * sizeof(float),
                            (size_t)L->nx * sizeof(float), (size_t)n_rows, hipMemcpyHostToDevice, (hipStream_t)stream));
   return 0;
 }
@@ -135,7 +126,7 @@ extern "C" int rtx_xs_lut_set_rows(rtx_xs_lut* L, int64_t row0, int64_t n_rows, 
 extern "C" int rtx_xs_lut_get_rows(const rtx_xs_lut* L, int64_t row0, int64_t n_rows, float* rows_h, void* stream) {
   if (xs_check_rows(L, row0, n_rows, rows_h)) return 1;
   if (n_rows == 0) return 0;
-  RTX_HIP(hipMemcpy2DAsync(rows_h, (size_t)L->nx * sizeof(float), L->data + (size_t)row0 * (size_t)L->ldx, (size_t)L->ldx * sizeof(float),
+  RTX_HIP(hipMemcpy2DAsync(rows_h, (size_t)L->nx * sizeof(float), L->data.get() + (size_t)row0 * (size_t)L->ldx, (size_t)L->ldx * sizeof(float),
                            (size_t)L->nx * sizeof(float), (size_t)n_rows, hipMemcpyDeviceToHost, (hipStream_t)stream));
   RTX_HIP(hipStreamSynchronize((hipStream_t)stream));
   return 0;
@@ -167,29 +158,21 @@ extern "C" int rtx_xs_od(rtx_xs_lut* L, int64_t x_offset, int64_t n, int n_layer
   for (XsTerms& t : L->terms)
     if (t.stream == st) tb = &t;
   if (!tb) {
-    L->terms.push_back(XsTerms{st, nullptr, nullptr, 0});
+    L->terms.emplace_back();
     tb = &L->terms.back();
+    tb->stream = st;
   }
-  if (tb->cap < cnt) {  // grow-only; hipFree waits for the kernels that still read the old block
-    if (tb->rows) (void)hipFree(tb->rows);
-    if (tb->w) (void)hipFree(tb->w);
-    tb->rows = nullptr;
-    tb->w = nullptr;
-    tb->cap = 0;
-    RTX_HIP(hipMalloc((void**)&tb->rows, cnt * sizeof(int)));
-    RTX_HIP(hipMalloc((void**)&tb->w, cnt * sizeof(float)));
-    tb->cap = cnt;
-  }
-  RTX_HIP(hipMemcpyAsync(tb->rows, rows_h, cnt * sizeof(int), hipMemcpyHostToDevice, st));  // pageable: staged before returning
-  RTX_HIP(hipMemcpyAsync(tb->w, weight_h, cnt * sizeof(float), hipMemcpyHostToDevice, st));
+  if (tb->rows.reserve(cnt) || tb->w.reserve(cnt)) return 1;
+  RTX_HIP(hipMemcpyAsync(tb->rows.get(), rows_h, cnt * sizeof(int), hipMemcpyHostToDevice, st));  // pageable: staged before returning
+  RTX_HIP(hipMemcpyAsync(tb->w.get(), weight_h, cnt * sizeof(float), hipMemcpyHostToDevice, st));
   const unsigned tiles = (unsigned)((n + XS_TILE - 1) / XS_TILE);
   const bool vec = (x_offset % 4 == 0) && (ld % 4 == 0) && (((uintptr_t)od_f32 & 15) == 0);
   if (vec)
-    hipLaunchKernelGGL(xs_od_kernel<true>, dim3(tiles), dim3(XS_BLOCK), 0, st, L->data, L->ldx, (long long)x_offset, (long long)n, n_layers,
-                       n_terms, tb->rows, tb->w, od_f32, (long long)ld);
+    hipLaunchKernelGGL(xs_od_kernel<true>, dim3(tiles), dim3(XS_BLOCK), 0, st, L->data.get(), L->ldx, (long long)x_offset, (long long)n, n_layers,
+                       n_terms, tb->rows.get(), tb->w.get(), od_f32, (long long)ld);
   else
-    hipLaunchKernelGGL(xs_od_kernel<false>, dim3(tiles), dim3(XS_BLOCK), 0, st, L->data, L->ldx, (long long)x_offset, (long long)n, n_layers,
-                       n_terms, tb->rows, tb->w, od_f32, (long long)ld);
+    hipLaunchKernelGGL(xs_od_kernel<false>, dim3(tiles), dim3(XS_BLOCK), 0, st, L->data.get(), L->ldx, (long long)x_offset, (long long)n, n_layers,
+                       n_terms, tb->rows.get(), tb->w.get(), od_f32, (long long)ld);
   RTX_LAUNCH_CHECK();
   return 0;
 }
