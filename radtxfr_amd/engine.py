@@ -788,6 +788,8 @@ def apparent_radiance(X, emis, Ts, tau, La, Ld, dT=None, return_Ls=False):
     nT = dT.numel() if dT is not None else 1
     L = torch.empty((nX, nE, nA, nT), dtype=torch.float32, device=emis.device)
     Ls = torch.empty_like(L) if return_Ls else None
+    if L.numel() == 0:  # an empty dT has no pointer: the library would take it for "no dT axis" and ask for L
+        return L, Ls
     _lib.check(lib.rtx_apparent_radiance(_ptr(X), nX, _ptr(emis), nE, _ptr(Ts), nA, _ptr(tau), _ptr(La), _ptr(Ld),
                                          _ptr(dT), nT if dT is not None else 0, _ptr(L), _ptr(Ls), _stream_ptr()))
     return L, Ls

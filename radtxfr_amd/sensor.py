@@ -96,7 +96,7 @@ def chebyshev_lagrange(Q):
     coef = np.zeros((Q, Q))
     for q in range(Q):
         others = np.delete(s, q)
-        poly = np.poly(others) / np.prod(s[q] - others)  # highest power first
+        poly = np.atleast_1d(np.poly(others)) / np.prod(s[q] - others)  # highest power first (Q = 1: np.poly gives a scalar)
         coef[q] = poly[::-1]
     return s, coef
 
