@@ -300,6 +300,34 @@ int rtx_ils(int kind, const rtx_grid* grid, const double* X, int64_t nx, const f
             float* Y_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Band averages under TABULATED spectral response functions: any sensor, not only MAKO. The
+ * definition is this project's own (the reference has the two MAKO shapes only). Band b is a
+ * table of knots (x_j, r_j), x strictly ascending, r finite and >= 0 (the caller checks that):
+ *   R_b(x) = the piecewise-linear function through the knots, 0 outside [x_first, x_last], both
+ *            ends included (two knots of value 1 are a boxcar);
+ *   D_i    = the trapezoid cell of point i of the axis passed: (X[i+1] - X[i-1]) / 2 inside,
+ *            half the distance to its one neighbour at either end, 1 when nx == 1;
+ *   Y_out[b][s] = sum_i R_b(X_i) D_i Y[i][s]  /  sum_i R_b(X_i) D_i.
+ * A band whose denominator is 0 (no axis point under it, or wholly outside the axis) comes out
+ * NaN, as rtx_ils' empty band does (quirk 13), and its wsum_out is 0.
+ *   X == NULL -> the uniform grid (grid->n == nx), else an explicit ascending fp64 device axis;
+ *   Y [nx][nS] float32, spectral axis first, ldY = row stride;
+ *   knot_start[nB + 1]: HOST, ascending; band b owns knots [knot_start[b], knot_start[b+1]),
+ *     2 .. rtx_srf_max_knots() of them;  knot_x / knot_r: DEVICE, all bands' knots concatenated;
+ *   Y_out [nB][nS] float32 (rtx_ils' layout);  wsum_out: NULL or [nB], the denominators.
+ * Bad sizes, a NULL required pointer, ldY < nS or a bad knot_start fail before anything is launched.
+ * Determinism: Y_out[b][s] is a pure function of (axis, band b's knots, column s of Y): the same
+ * bits run to run, for any subset or order of the bands of a call, and for any number of columns
+ * around column s (both load widths). Sums run over rows ascending inside chunks of
+ * rtx_srf_chunk_points() rows cut from the axis' first point, then over the chunks ascending.
+ * Calls on one stream share a grow-only workspace; only a call that grows it synchronises. */
+int rtx_srf_apply(const rtx_grid* grid, const double* X, int64_t nx, const float* Y, int64_t nS,
+                  int64_t ldY, int nB, const int32_t* knot_start, const double* knot_x,
+                  const float* knot_r, float* Y_out, float* wsum_out, void* stream);
+int rtx_srf_chunk_points(void); /* consecutive axis points one workgroup owns (for tests at the edges) */
+int rtx_srf_max_knots(void);    /* largest knot count one band may have */
+
+/* ------------------------------------------------------------------------------------------
  * Knot spectra -> monochromatic axis, column-wise np.interp. The reference's emissivity databases
  * live on ~1 cm^-1 knots (Generate_ASTER_emissivity_DB.py:48-52,81) and are resampled with
  * np.interp / interp1d before compute_LWIR_apparent_radiance (LWIR_HSI_Generator.py:151-167).

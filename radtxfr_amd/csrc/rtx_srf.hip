@@ -1,0 +1,296 @@
+// Band averages under tabulated spectral response functions (include/radtxfr_hip.h, rtx_srf_apply):
+//
+//   Y_out[b][s] = sum_i R_b(X_i) D_i Y[i][s]  /  sum_i R_b(X_i) D_i
+//
+// R_b: the piecewise-linear function through band b's knots, 0 outside [x_first, x_last], both ends included;
+// D_i: the trapezoid cell of axis point i. The definition is this project's own (the reference has only the MAKO shapes).
+//
+// Structure, after ils_rows_kernel (rtx_radiance.hip): a workgroup owns SRF_CH consecutive rows of Y x 1024 columns, reads
+// them once and keeps the sums of the bands that reach its chunk; a second kernel adds a band's chunk sums in ascending
+// chunk order and normalises. The bands of a call are taken SRF_SLOTS at a time (three launches per group), so a band's
+// slot in the workspace is its index in the group: no list of bands per chunk, no overflow, no atomics. A workgroup whose
+// chunk no band of the group reaches returns before it reads anything, so Y is read once where the bands of a group lie
+// side by side (band lists sorted by wavenumber: the usual case) and never more often than bands cover a row.
+//
+// Determinism: Y_out[b][s] is a pure function of (axis, band b's knots, column s of Y). The weight of row i under band b
+// is computed in fp64 from the axis and the band's own knots and rounded to fp32 once; a (band, chunk, column) sum is ONE
+// fp32 fmaf chain over the chunk's rows in ascending order, whatever lane, wave or load width carries it and whichever
+// other bands share the pass (a row of weight 0 is skipped, not multiplied); the chunk sums are added in fp64 in
+// ascending chunk order. Chunks are cut at multiples of SRF_CH from the axis' first point.
+#include <map>
+#include <mutex>
+#include <utility>
+
+#include "rtx_common.h"
+
+#define SRF_CH 1024         // rows per chunk
+#define SRF_MAX_KNOTS 1024  // per band: the knot table of one band is staged in LDS (12 KiB)
+#define SRF_SLOTS 16        // bands per launch group = slots per chunk in the workspace
+#define SRF_CAP 4           // bands per pass over the chunk's rows: their weights are one float4 per row in LDS
+
+struct SrfArgs {
+  GridDev g;
+  const double* X;
+  long long nx, nS, ldY;
+  const float* Y;
+  const double* kx;  // all bands' knots
+  const float* kr;
+  int ng;                  // bands in this group
+  int ks[SRF_SLOTS + 1];   // their knot ranges [ks[j], ks[j + 1])
+  long long* sup;   // [SRF_SLOTS][2] support [lo, hi) of each band as axis indices
+  float* P;         // [n_chunks][SRF_SLOTS][nS] chunk sums
+  double* W;        // [n_chunks][SRF_SLOTS] chunk sums of the weights
+  float* Yout;      // the group's first row of Y_out
+  float* wsum;      // NULL or the group's first denominator
+};
+
+__device__ __forceinline__ double srf_x(const SrfArgs& a, long long i) { return a.X ? a.X[i] : grid_x(a.g, a.g.offset + i); }
+
+// trapezoid cell of point i on the axis passed
+__device__ __forceinline__ double srf_delta(const SrfArgs& a, long long i) {
+  if (a.nx == 1) return 1.0;
+  const double xm = srf_x(a, i > 0 ? i - 1 : i), xp = srf_x(a, i < a.nx - 1 ? i + 1 : i);
+  return 0.5 * (xp - xm);
+}
+
+// first index with X[i] > v (strict = 1) or X[i] >= v (strict = 0), X ascending (ils_bound's search)
+__device__ long long srf_bound(const SrfArgs& a, double v, int strict) {
+  long long lo = 0, hi = a.nx;
+  while (lo < hi) {
+    const long long mid = (lo + hi) >> 1;
+    const double x = srf_x(a, mid);
+    const bool right = strict ? (x > v) : (x >= v);
+    if (right) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+// the segment of x among nk ascending knots: the largest j with kx[j] <= x, kept inside [0, nk - 2]
+__device__ int srf_segment(const double* kx, int nk, double x) {
+  int lo = 0, hi = nk;  // first index with kx > x
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (kx[mid] > x) hi = mid; else lo = mid + 1;
+  }
+  const int j = lo - 1;
+  return j < 0 ? 0 : (j > nk - 2 ? nk - 2 : j);
+}
+
+__global__ __launch_bounds__(64) void srf_support_kernel(SrfArgs a) {
+  const int j = threadIdx.x;
+  if (j >= a.ng) return;
+  const double x_first = a.kx[a.ks[j]], x_last = a.kx[a.ks[j + 1] - 1];
+  a.sup[2 * j] = srf_bound(a, x_first, 0);
+  a.sup[2 * j + 1] = srf_bound(a, x_last, 1);
+}
+
+// VEC: 16-byte loads of Y (nS % 4 == 0, ldY % 4 == 0, 16-byte aligned); else point by point. The arithmetic is the same.
+template <bool VEC>
+__device__ __forceinline__ float4 srf_load(const SrfArgs& a, long long row, long long col4) {
+  if (VEC) return reinterpret_cast<const float4*>(a.Y + row * a.ldY)[col4];
+  const float* y = a.Y + row * a.ldY;
+  const long long c = 4 * col4;
+  float4 v;
+  v.x = y[c];  // col4 is live: c < nS
+  v.y = c + 1 < a.nS ? y[c + 1] : 0.f;
+  v.z = c + 2 < a.nS ? y[c + 2] : 0.f;
+  v.w = c + 3 < a.nS ? y[c + 3] : 0.f;
+  return v;
+}
+
+template <bool VEC>
+__device__ __forceinline__ void srf_store(const SrfArgs& a, float* p, long long col4, float4 v) {
+  if (VEC) { reinterpret_cast<float4*>(p)[col4] = v; return; }
+  const long long c = 4 * col4;
+  p[c] = v.x;
+  if (c + 1 < a.nS) p[c + 1] = v.y;
+  if (c + 2 < a.nS) p[c + 2] = v.z;
+  if (c + 3 < a.nS) p[c + 3] = v.w;
+}
+
+// a row of weight 0 leaves the sum alone (not fmaf(0, y, acc): a non-finite y under another band must not reach this one)
+__device__ __forceinline__ void srf_fma(float4& acc, float w, const float4& y) {
+  const bool on = w != 0.f;
+  acc.x = on ? fmaf(w, y.x, acc.x) : acc.x;
+  acc.y = on ? fmaf(w, y.y, acc.y) : acc.y;
+  acc.z = on ? fmaf(w, y.z, acc.z) : acc.z;
+  acc.w = on ? fmaf(w, y.w, acc.w) : acc.w;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void srf_rows_kernel(SrfArgs a) {
+  const long long chunk = blockIdx.x;
+  const long long r0 = chunk * SRF_CH, r1 = r0 + SRF_CH < a.nx ? r0 + SRF_CH : a.nx;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long col4 = (long long)blockIdx.y * 256 + threadIdx.x, n4 = (a.nS + 3) >> 2;
+  const bool live = col4 < n4;
+  __shared__ float4 s_w[SRF_CH + 4];        // the pass's SRF_CAP weights of every row of the chunk (+ zeros behind)
+  __shared__ double s_kx[SRF_MAX_KNOTS];    // one band's knots under the chunk
+  __shared__ float s_kr[SRF_MAX_KNOTS];
+  __shared__ int s_lo[SRF_SLOTS], s_hi[SRF_SLOTS];  // support of band j within the chunk as rows [lo, hi) from r0; empty: lo >= hi
+  __shared__ int s_any;
+  if (threadIdx.x == 0) s_any = 0;
+  __syncthreads();
+  if (threadIdx.x < SRF_SLOTS) {
+    int lo = 0, hi = 0;
+    if (threadIdx.x < a.ng) {
+      const long long L = a.sup[2 * threadIdx.x], H = a.sup[2 * threadIdx.x + 1];
+      const long long l = L > r0 ? L : r0, h = H < r1 ? H : r1;
+      if (h > l) { lo = (int)(l - r0); hi = (int)(h - r0); s_any = 1; }
+    }
+    s_lo[threadIdx.x] = lo; s_hi[threadIdx.x] = hi;
+  }
+  __syncthreads();
+  if (!s_any) return;  // no band of the group reaches this chunk: nothing is read
+  float* wcomp = reinterpret_cast<float*>(s_w);
+  for (int j0 = 0; j0 < a.ng; j0 += SRF_CAP) {
+    int ra = SRF_CH, rb = 0;  // rows of the chunk under any band of the pass
+#pragma unroll
+    for (int u = 0; u < SRF_CAP; ++u)
+      if (s_hi[j0 + u] > s_lo[j0 + u]) { ra = min(ra, s_lo[j0 + u]); rb = max(rb, s_hi[j0 + u]); }
+    if (rb <= ra) continue;  // uniform over the workgroup
+    // ---- weights: thread t takes rows t, t + 256, ... of the chunk and walks along the band's segments with them
+    for (int u = 0; u < SRF_CAP; ++u) {
+      const int j = j0 + u;
+      const bool act = s_hi[j] > s_lo[j];  // uniform; j < SRF_SLOTS, and a slot past the group is empty
+      int jA = 0, m = 0, lo = 0, hi = 0;
+      if (act) {
+        lo = s_lo[j]; hi = s_hi[j];
+        const double* kx = a.kx + a.ks[j];
+        const int nk = a.ks[j + 1] - a.ks[j];
+        jA = srf_segment(kx, nk, srf_x(a, r0 + lo));
+        m = srf_segment(kx, nk, srf_x(a, r0 + hi - 1)) + 2 - jA;  // knots jA .. jB + 1
+        for (int q = threadIdx.x; q < m; q += 256) { s_kx[q] = kx[jA + q]; s_kr[q] = a.kr[a.ks[j] + jA + q]; }
+      }
+      __syncthreads();
+      int seg = 0;
+      for (int t = threadIdx.x; t < SRF_CH + 4; t += 256) {
+        float w = 0.f;
+        if (act && t >= lo && t < hi) {
+          const double x = srf_x(a, r0 + t);
+          while (seg + 2 < m && x >= s_kx[seg + 1]) ++seg;
+          const double xa = s_kx[seg], xb = s_kx[seg + 1], ya = (double)s_kr[seg], yb = (double)s_kr[seg + 1];
+          const double R = (yb - ya) / (xb - xa) * (x - xa) + ya;
+          w = (float)(fmax(R, 0.0) * srf_delta(a, r0 + t));
+        }
+        wcomp[4 * t + u] = w;
+      }
+      __syncthreads();  // the weights are written and the knots read before the next band is staged
+    }
+    // ---- the chunk's sums of the weights: wave u adds band u's, lanes over rows, in a fixed order
+    {
+      double v = 0.0;
+      for (int t = lane; t < SRF_CH; t += 64) v += (double)wcomp[4 * t + wave];
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+      const int j = j0 + wave;
+      if (blockIdx.y == 0 && lane == 0 && s_hi[j] > s_lo[j]) a.W[chunk * SRF_SLOTS + j] = v;
+    }
+    // ---- rows: every thread owns four columns and runs each band's sum as one chain over the rows, ascending
+    if (live) {
+      float4 acc[SRF_CAP];
+#pragma unroll
+      for (int u = 0; u < SRF_CAP; ++u) acc[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int t = ra; t < rb; t += 4) {  // four rows in flight
+        float4 y[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) y[q] = t + q < rb ? srf_load<VEC>(a, r0 + t + q, col4) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float4 w = s_w[t + q];  // one address for the whole wave; zeros from rb on
+          srf_fma(acc[0], w.x, y[q]); srf_fma(acc[1], w.y, y[q]); srf_fma(acc[2], w.z, y[q]); srf_fma(acc[3], w.w, y[q]);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < SRF_CAP; ++u) {
+        const int j = j0 + u;
+        if (s_hi[j] > s_lo[j])
+          srf_store<VEC>(a, a.P + (size_t)(chunk * SRF_SLOTS + j) * (size_t)a.nS, col4, acc[u]);
+      }
+    }
+    __syncthreads();  // s_w is rewritten by the next pass
+  }
+}
+
+// one thread per (band, column): the band's chunk sums in ascending chunk order, in fp64, then the quotient
+__global__ __launch_bounds__(256) void srf_reduce_kernel(SrfArgs a) {
+  const int j = blockIdx.x;
+  const long long col = (long long)blockIdx.y * 256 + threadIdx.x;
+  if (col >= a.nS) return;
+  const long long lo = a.sup[2 * j], hi = a.sup[2 * j + 1];
+  double acc = 0.0, N = 0.0;
+  if (hi > lo) {
+    for (long long ch = lo / SRF_CH; ch <= (hi - 1) / SRF_CH; ++ch) {
+      acc += (double)a.P[(size_t)(ch * SRF_SLOTS + j) * (size_t)a.nS + col];
+      N += a.W[ch * SRF_SLOTS + j];
+    }
+  }
+  a.Yout[(size_t)j * a.nS + col] = (float)(acc / N);  // a denominator of 0: 0/0 = NaN, like rtx_ils' empty band
+  if (a.wsum && col == 0) a.wsum[j] = (float)N;
+}
+
+// workspace per (device, stream), like rtx_ils': calls on one stream are ordered by it, calls on different streams must
+// not share chunk sums. Grow-only; the map lives as long as the process.
+static int srf_workspace(size_t bytes, hipStream_t st, void** out) {
+  static std::mutex mu;
+  static auto* const ws = new std::map<std::pair<int, hipStream_t>, DevBuf<char>>();
+  int dev = 0;
+  RTX_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(mu);
+  DevBuf<char>& b = (*ws)[std::make_pair(dev, st)];
+  if (b.reserve(bytes)) return 1;
+  *out = b.get();
+  return 0;
+}
+
+extern "C" int rtx_srf_chunk_points(void) { return SRF_CH; }
+extern "C" int rtx_srf_max_knots(void) { return SRF_MAX_KNOTS; }
+
+extern "C" int rtx_srf_apply(const rtx_grid* grid, const double* X, int64_t nx, const float* Y, int64_t nS, int64_t ldY, int nB,
+                             const int32_t* knot_start_h, const double* knot_x_d, const float* knot_r_d, float* Y_out,
+                             float* wsum_out, void* stream) {
+  if (!X) {
+    if (!grid) RTX_FAIL("neither an axis nor a grid");
+    if (rtx_check_grid(grid)) return 1;
+    if (nx != grid->n) RTX_FAIL("nx=%lld != grid->n=%lld", (long long)nx, (long long)grid->n);
+  }
+  if (nB < 0 || nS < 0 || nx < 0) RTX_FAIL("negative size");
+  if (nB == 0 || nS == 0) return 0;
+  if (!Y || !knot_start_h || !knot_x_d || !knot_r_d || !Y_out) RTX_FAIL("a required pointer is NULL");
+  if (ldY < nS) RTX_FAIL("ldY=%lld < nS=%lld", (long long)ldY, (long long)nS);
+  if (knot_start_h[0] < 0) RTX_FAIL("knot_start[0]=%d is negative", (int)knot_start_h[0]);
+  for (int b = 0; b < nB; ++b) {
+    const long long nk = (long long)knot_start_h[b + 1] - (long long)knot_start_h[b];
+    if (nk < 0) RTX_FAIL("knot_start is not ascending at band %d", b);
+    if (nk < 2) RTX_FAIL("band %d has %lld knots: a response table needs at least 2", b, nk);
+    if (nk > SRF_MAX_KNOTS) RTX_FAIL("band %d has %lld knots: at most %d", b, nk, SRF_MAX_KNOTS);
+  }
+  const long long n_chunks = (nx + SRF_CH - 1) / SRF_CH;
+  if (n_chunks > 0x7fffffffLL) RTX_FAIL("nx=%lld: too many chunks", (long long)nx);
+  const long long ncb = ((nS + 3) / 4 + 255) / 256;  // column blocks of the row kernel
+  if (ncb > 65535) RTX_FAIL("nS=%lld: too many columns for one call", (long long)nS);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t nW = (size_t)n_chunks * SRF_SLOTS, nP = nW * (size_t)nS;
+  void* base = nullptr;
+  if (srf_workspace(nW * sizeof(double) + 2 * SRF_SLOTS * sizeof(long long) + nP * sizeof(float), st, &base)) return 1;
+  SrfArgs a;
+  if (grid) a.g = to_dev(grid); else { a.g.xmin = a.g.xmax = a.g.step = 0; a.g.n_total = a.g.offset = a.g.n = 0; }
+  a.X = X; a.nx = nx; a.nS = nS; a.ldY = ldY; a.Y = Y; a.kx = knot_x_d; a.kr = knot_r_d;
+  a.W = (double*)base; a.sup = (long long*)(a.W + nW); a.P = (float*)(a.sup + 2 * SRF_SLOTS);
+  const bool vec = nS % 4 == 0 && ldY % 4 == 0 && (uintptr_t)Y % 16 == 0;
+  for (int g0 = 0; g0 < nB; g0 += SRF_SLOTS) {
+    a.ng = nB - g0 < SRF_SLOTS ? nB - g0 : SRF_SLOTS;
+    for (int j = 0; j <= SRF_SLOTS; ++j) a.ks[j] = knot_start_h[g0 + (j < a.ng ? j : a.ng)];
+    a.Yout = Y_out + (size_t)g0 * (size_t)nS;
+    a.wsum = wsum_out ? wsum_out + g0 : nullptr;
+    hipLaunchKernelGGL(srf_support_kernel, dim3(1), dim3(64), 0, st, a);
+    RTX_LAUNCH_CHECK();
+    if (n_chunks > 0) {
+      if (vec) hipLaunchKernelGGL(srf_rows_kernel<true>, dim3((unsigned)n_chunks, (unsigned)ncb), dim3(256), 0, st, a);
+      else hipLaunchKernelGGL(srf_rows_kernel<false>, dim3((unsigned)n_chunks, (unsigned)ncb), dim3(256), 0, st, a);
+      RTX_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(srf_reduce_kernel, dim3((unsigned)a.ng, (unsigned)((nS + 255) / 256)), dim3(256), 0, st, a);
+    RTX_LAUNCH_CHECK();
+  }
+  return 0;
+}

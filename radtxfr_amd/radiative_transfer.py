@@ -775,6 +775,32 @@ def ILS_MAKO(X, Y, resFactor=None, returnX=True, fwhm_sf=1.0, shift=0.0, scale=1
     return Y_out
 
 
+def apply_sensor(X, Y, sensor, returnX=True):
+    """Band averages under a sensor's tabulated spectral response functions (sensor.Sensor), with ILS_MAKO's conventions:
+    X (nX,) ascending wavenumbers, Y (nX,) or (nX,nS), NumPy or torch -> X_out (nB,) NumPy = sensor.centres and Y_out (nB,) or
+    (nB,nS) of Y's kind (NumPy: Y's float dtype; torch: a float32 device tensor). A uniform axis goes to the library as a grid,
+    any other ascending axis as it is. A band with no point of X under it comes out NaN."""
+    from . import sensor as _sensor  # sensor.py imports this module
+    as_torch = _is_torch(Y)
+    dev = engine.device()
+    Yd = _dev_f32(Y, dev)
+    one_d = Yd.dim() == 1
+    if one_d:
+        Yd = Yd[:, None].contiguous()
+    Xh = np.asarray(X.detach().cpu().numpy() if _is_torch(X) else X, dtype=np.float64).ravel()
+    try:
+        grid, Xd = engine.Grid.from_axis(Xh), None
+    except (NotImplementedError, ValueError):
+        grid, Xd = None, _dev_f64(Xh, dev)  # explicit axis: non-uniform, or a single point
+    X_out, out = _sensor.apply_srf(sensor, Yd, grid=grid, X=Xd)
+    if one_d:
+        out = out[:, 0]
+    if not as_torch:
+        odt = np.asarray(Y).dtype if np.asarray(Y).dtype in (np.float32, np.float64) else np.float64
+        out = out.cpu().numpy().astype(odt)
+    return (X_out, out) if returnX else out
+
+
 # ---- post-processing of TUD products (SURVEY 8f row 2) ----------------------------------------
 def _uniform_axis(X, what):
     Xh = X.detach().cpu().numpy() if _is_torch(X) else np.asarray(X, dtype=np.float64)

@@ -45,6 +45,174 @@ _CUBE_PLANS_LOCK = threading.Lock()
 _FUSED_PLANS = {}  # band list and knot axis of band_radiance_fused on the device (a few entries, see _cube_plan)
 
 
+MAX_KNOTS = 1024  # per response table: rtx_srf_max_knots() of the library (tests/test_srf_host.py compares the two)
+
+
+def trapezoid_cells(X):
+    """The trapezoid cell of every point of the axis X, as rtx_srf_apply weighs it: (X[i+1] - X[i-1]) / 2 inside, half the
+    distance to its one neighbour at either end, 1 for a one-point axis."""
+    X = np.asarray(X, dtype=np.float64).ravel()
+    if X.size == 1:
+        return np.ones(1)
+    d = np.empty(X.size)
+    d[1:-1] = 0.5 * (X[2:] - X[:-2])
+    d[0], d[-1] = 0.5 * (X[1] - X[0]), 0.5 * (X[-1] - X[-2])
+    return d
+
+
+def _table_centre(x, r):
+    """Response-weighted mean wavenumber of a piecewise-linear table: int x R dx / int R dx, exact."""
+    h, r0, r1 = np.diff(x), r[:-1], r[1:]
+    den = np.sum(h * (r0 + r1)) / 2.0
+    num = np.sum(h * (x[:-1] * (2.0 * r0 + r1) + x[1:] * (r0 + 2.0 * r1))) / 6.0
+    return num / den
+
+
+class Sensor:
+    """An immutable set of bands, each a tabulated relative spectral response function: knots (x_j, r_j) on a wavenumber
+    axis [cm^-1], x strictly ascending, r finite and >= 0. Between the knots the response is linear, outside them 0 (both end
+    knots included: two knots of value 1 are a boxcar); include/radtxfr_hip.h, rtx_srf_apply, has the band average.
+
+    tables: tuple of (x, r) read-only arrays (float64, float32). centres [nB]: what apply_srf returns as X_out, by default
+    each table's response-weighted mean wavenumber. The concatenated knots go to a device once, on first use there."""
+
+    def __init__(self, tables, centres):
+        self.tables = tuple(tables)
+        self.centres = centres
+        self.knot_start = np.zeros(len(self.tables) + 1, dtype=np.int32)
+        self.knot_start[1:] = np.cumsum([x.size for x, _ in self.tables])
+        for a in (self.centres, self.knot_start):
+            a.setflags(write=False)
+        self._dev = {}
+        self._lock = threading.Lock()
+
+    def __len__(self):
+        return len(self.tables)
+
+    @classmethod
+    def from_tables(cls, tables, centres=None):
+        """tables: a list of (x_knots, response) pairs, one per band. Raises ValueError, naming the band, for knots that do
+        not ascend strictly, a negative or non-finite response, a response that is zero everywhere, and fewer than 2 or
+        more than MAX_KNOTS knots."""
+        out = []
+        for b, (x, r) in enumerate(tables):
+            x = np.array(x, dtype=np.float64).ravel()
+            r = np.array(r, dtype=np.float64).ravel()
+            if x.size != r.size:
+                raise ValueError(f"band {b}: {x.size} knots but {r.size} responses")
+            if x.size < 2 or x.size > MAX_KNOTS:
+                raise ValueError(f"band {b}: {x.size} knots, a response table needs 2 to {MAX_KNOTS}")
+            if not np.all(np.isfinite(x)) or not np.all(np.diff(x) > 0):
+                raise ValueError(f"band {b}: the knots must be finite and strictly ascending")
+            if not np.all(np.isfinite(r)) or np.any(r < 0):
+                raise ValueError(f"band {b}: the response must be finite and >= 0")
+            r32 = r.astype(np.float32)
+            if not np.any(r32 > 0):
+                raise ValueError(f"band {b}: the response is zero everywhere")
+            x.setflags(write=False), r32.setflags(write=False)
+            out.append((x, r32))
+        if centres is None:
+            centres = np.array([_table_centre(x, r.astype(np.float64)) for x, r in out], dtype=np.float64)
+        else:
+            centres = np.array(centres, dtype=np.float64).ravel()
+            if centres.size != len(out):
+                raise ValueError(f"{centres.size} centres for {len(out)} bands")
+        return cls(out, centres)
+
+    @classmethod
+    def from_shape(cls, centres, fwhm, shape, knots=65):
+        """Bands of one analytic shape, tabulated on the host: "triangle" (3 knots, exact: base centre -+ fwhm), "boxcar"
+        (2 knots, exact: centre -+ fwhm / 2) or "gaussian" (`knots` points out to -+ 4 fwhm; an odd count puts one on the
+        peak). fwhm: one width or one per band."""
+        c = np.atleast_1d(np.asarray(centres, dtype=np.float64)).ravel()
+        f = np.broadcast_to(np.asarray(fwhm, dtype=np.float64), c.shape)
+        if np.any(~(f > 0)):
+            raise ValueError("fwhm must be positive")
+        if shape == "triangle":
+            tables = [(np.array([ci - fi, ci, ci + fi]), np.array([0.0, 1.0, 0.0])) for ci, fi in zip(c, f)]
+        elif shape == "boxcar":
+            tables = [(np.array([ci - 0.5 * fi, ci + 0.5 * fi]), np.array([1.0, 1.0])) for ci, fi in zip(c, f)]
+        elif shape == "gaussian":
+            tables = []
+            for ci, fi in zip(c, f):
+                d = np.linspace(-4.0 * fi, 4.0 * fi, int(knots))
+                tables.append((ci + d, np.exp(-4.0 * np.log(2.0) * (d / fi) ** 2)))
+        else:
+            raise ValueError(f"shape {shape!r}: triangle, gaussian or boxcar")
+        return cls.from_tables(tables, centres=c)
+
+    @classmethod
+    def mako(cls, x_min, x_max, resFactor=None, fwhm_sf=1.0, shift=0.0, scale=1.0):
+        """mako_bands()'s triangles as 3-knot tables (c - sigma, 0), (c, 1), (c + sigma, 0), c = scale * X_out + shift."""
+        _, c, s = mako_bands(x_min, x_max, resFactor, fwhm_sf, shift, scale)
+        return cls.from_tables([(np.array([ci - si, ci, ci + si]), np.array([0.0, 1.0, 0.0])) for ci, si in zip(c, s)])
+
+    @classmethod
+    def in_wavelength(cls, tables_um, centres=None):
+        """Tables given on a wavelength axis [um], in either order: the knots become wavenumbers 1e4 / um in ascending
+        order. The response values are kept as they are, per unit wavenumber: NO Jacobian factor is applied, so a
+        response measured per unit wavelength has to be converted by the caller. centres, if given, are wavenumbers."""
+        out = []
+        for lam, r in tables_um:
+            x = 1.0e4 / np.asarray(lam, dtype=np.float64).ravel()
+            order = np.argsort(x, kind="stable")
+            out.append((x[order], np.asarray(r, dtype=np.float64).ravel()[order]))
+        return cls.from_tables(out, centres=centres)
+
+    def on_device(self, dev):
+        """(knot_x fp64, knot_r fp32): all bands' knots concatenated, as device tensors cached per device."""
+        key = str(torch.device(dev))
+        with self._lock:
+            hit = self._dev.get(key)
+            if hit is None:
+                kx = np.concatenate([x for x, _ in self.tables]) if self.tables else np.zeros(0)
+                kr = np.concatenate([r for _, r in self.tables]) if self.tables else np.zeros(0, dtype=np.float32)
+                hit = self._dev[key] = (torch.as_tensor(kx, device=dev), torch.as_tensor(kr, device=dev))
+        return hit
+
+
+def apply_srf(sensor, Y, grid=None, X=None, wsum=False):
+    """Band averages of Y [nx][nS] float32 (device, rows contiguous) under the sensor's response tables (rtx_srf_apply):
+    grid = the uniform engine.Grid of the axis, or X = an explicit ascending fp64 device axis. Returns (X_out [nB] NumPy =
+    sensor.centres, Y_out [nB][nS] float32 device); with wsum=True also the denominators [nB] float32 device. A band with
+    no axis point under it comes out NaN."""
+    lib = _lib.load()
+    assert Y.dtype == torch.float32 and Y.is_cuda and Y.dim() == 2 and (Y.stride(1) == 1 or Y.shape[1] <= 1)
+    if (grid is None) == (X is None):
+        raise ValueError("apply_srf needs the axis either as grid= or as X=")
+    nx, nS = Y.shape
+    if nx != (grid.n if X is None else X.numel()):
+        raise ValueError(f"Y has {nx} rows, the axis {grid.n if X is None else X.numel()} points")
+    if X is not None:
+        assert X.dtype == torch.float64 and X.device == Y.device and X.is_contiguous()
+    nB = len(sensor)
+    kx, kr = sensor.on_device(Y.device)
+    out = torch.empty((nB, nS), dtype=torch.float32, device=Y.device)
+    den = torch.empty(nB, dtype=torch.float32, device=Y.device) if wsum else None
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+    _lib.check(lib.rtx_srf_apply(grid.byref() if X is None else None, p(X), nx, p(Y), nS, Y.stride(0) if nx > 1 else max(nS, 1), nB,
+                                 sensor.knot_start.ctypes.data_as(C.c_void_p), p(kx), p(kr), p(out), p(den),
+                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    X_out = np.array(sensor.centres)
+    return (X_out, out, den) if wsum else (X_out, out)
+
+
+def band_radiance_srf(grid, tau, La, Ld, Xk, emis_knots, Ts, sensor, keep_hires=False):
+    """band_radiance() for any sensor: L_b,k = SRF_b( tau*(eps_k*B(Ts) + (1-eps_k)*Ld) + La ) for every emissivity column k,
+    the band average under the sensor's tabulated responses instead of the MAKO triangle. Same arguments as band_radiance()
+    with a Sensor in place of resFactor. Returns (X_out [nB] NumPy, L [nB][nE] float32 device). Three streaming kernels:
+    rtx_interp_knots -> rtx_apparent_radiance -> rtx_srf_apply."""
+    dev = tau.device
+    em = interp_knots(grid, Xk, emis_knots)  # [nX][nE]
+    X_d = torch.as_tensor(grid.axis(), device=dev)
+    Ts_d = torch.as_tensor(np.atleast_1d(np.asarray(Ts, dtype=np.float64)), device=dev)
+    col = lambda v: v.reshape(-1, 1).contiguous()
+    L, _ = engine.apparent_radiance(X_d, em, Ts_d, col(tau), col(La), col(Ld))
+    L = L.reshape(grid.n, -1)  # [nX][nE] (nA = nT = 1)
+    X_out, out = apply_srf(sensor, L, grid=grid)
+    return (X_out, out, L) if keep_hires else (X_out, out)
+
+
 def _fused_plan(grid, Xk, resFactor, kind, dev):
     Xk = np.ascontiguousarray(Xk, dtype=np.float64)
     key = (grid.x_at(0), grid.step, grid.n, resFactor, int(kind), str(dev), Xk.tobytes())
