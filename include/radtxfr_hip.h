@@ -353,6 +353,39 @@ int rtx_band_mix(const float* N, const float* C, const float* M, const int32_t* 
                  int64_t nk, const float* E, int64_t nE, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The same moments for ANY sensor, and for several surface temperatures in one pass: band b is a
+ * response table as rtx_srf_apply takes it, the weights are rtx_srf_apply's to the letter,
+ *   w_b,i = R_b(X_i) D_i   (R_b piecewise linear through the band's knots, 0 outside, both end
+ *                           knots included; D_i the trapezoid cell of the grid),
+ * and with hat_j the hat functions of np.interp on Xk (end values held outside [Xk[0], Xk[nk-1]]:
+ * the first and the last one extend as constants; nk == 1: one constant)
+ *   N[b] = sum_i w,   C[b] = sum_i w (tau Ld + La),
+ *   M[t][b][j] = sum_i w tau (B(nu_i, Ts_t) - Ld) hat_j(nu_i),   jrange[b] = first, last knot touched
+ * in rtx_band_moments' conventions: rtx_band_mix(N, C, M[t], jrange, ...) gives, for temperature t,
+ *   L[b][k] = sum_i w [tau (eps_k B(Ts_t) + (1 - eps_k) Ld) + La] / sum_i w,  eps_k = np.interp(X, Xk, E[:,k]).
+ * Planck is evaluated at every point for every temperature (rtx_planck's constants): no node
+ * interpolation, so a band may be as wide as the grid.
+ *   grid: uniform only;  tau, La, Ld [grid->n] float32 DEVICE;  Xk [nk] fp64 ascending DEVICE;
+ *   Ts_h [nT]: HOST, 1 <= nT <= rtx_srf_moments_max_temps(), each > 0;
+ *   knot_start [nB + 1] HOST, knot_x / knot_r DEVICE: as rtx_srf_apply;
+ *   N_out [nB], C_out [nB], M_out [nT][nB][nk] float32, jrange_out [nB][2] int32: DEVICE. M is written
+ *   on all nk knots (0 outside jrange).
+ * A band with no grid point under it has N = C = 0 and the empty range [0, -1]; rtx_band_mix then
+ * divides 0 by 0: NaN, as rtx_srf_apply and rtx_ils (quirk 13). Bad sizes, a NULL required pointer,
+ * a bad knot_start, nT out of range or a temperature <= 0 fail before anything is launched.
+ * Determinism: N[b], C[b], M[t][b][:] and jrange[b] are a pure function of (grid, band b's knots,
+ * tau, La, Ld, Xk, Ts_t): the same bits run to run, for any subset or order of the bands of a call
+ * and for any subset or order of its temperatures. A sum runs over the points ascending, in fp32,
+ * inside sub-chunks of 64 points cut from the grid's first point; the sub-chunk sums are added in
+ * fp64 in ascending order (N and C: chunks of rtx_srf_chunk_points() points, fp64 throughout). No atomics.
+ * Calls on one stream share rtx_srf_apply's grow-only workspace; only a call that grows it synchronises. */
+int rtx_srf_moments(const rtx_grid* grid, const float* tau, const float* La, const float* Ld,
+                    const double* Ts_h, int nT, const double* Xk, int64_t nk, int nB,
+                    const int32_t* knot_start, const double* knot_x, const float* knot_r,
+                    float* N_out, float* C_out, float* M_out, int32_t* jrange_out, void* stream);
+int rtx_srf_moments_max_temps(void); /* temperatures one call takes */
+
+/* ------------------------------------------------------------------------------------------
  * Fused HSI cube (config C5): every pixel has its own emissivity mixture and surface temperature
  * (LWIR_HSI_Generator.py:151-167: em = mixFrac . emis[ix_em], T = Ts + dT*N(0,1),
  * L = tau*(em*B(T) + (1-em)*Ld) + La), evaluated at monochromatic resolution and passed through

@@ -258,6 +258,73 @@ def band_radiance_fused(grid, tau, La, Ld, Xk, emis_knots, Ts, resFactor=None, k
     return X_out, out
 
 
+_SRF_FUSED_PLANS = {}  # (Xk bytes, device) -> the knot axis on the device, for band_radiance_srf_fused (see _fused_plan)
+
+
+def _srf_fused_plan(Xk, dev):
+    Xk = np.array(Xk, dtype=np.float64).ravel()  # a copy: the caller's array may be read-only
+    key = (str(dev), Xk.tobytes())
+    with _CUBE_PLANS_LOCK:
+        plan = _SRF_FUSED_PLANS.get(key)
+    if plan is None:
+        plan = {"Xk_d": torch.as_tensor(Xk, device=dev)}
+        with _CUBE_PLANS_LOCK:
+            if len(_SRF_FUSED_PLANS) >= _CUBE_PLANS_MAX:
+                _SRF_FUSED_PLANS.pop(next(iter(_SRF_FUSED_PLANS)))
+            _SRF_FUSED_PLANS[key] = plan
+    return plan
+
+
+def srf_moments(grid, tau, La, Ld, Xk_d, Ts, sensor):
+    """rtx_srf_moments for up to rtx_srf_moments_max_temps() temperatures Ts (a sequence): (N [nB], C [nB], M [nT][nB][nk]
+    float32, jrange [nB][2] int32) on tau's device, what rtx_band_mix takes. Xk_d: the fp64 knot axis on that device."""
+    lib = _lib.load()
+    dev = tau.device
+    for v in (tau, La, Ld):
+        assert v.dtype == torch.float32 and v.is_cuda and v.is_contiguous() and v.numel() == grid.n
+    Ts = np.ascontiguousarray(np.atleast_1d(np.asarray(Ts, dtype=np.float64)))
+    nB, nk, nT = len(sensor), Xk_d.numel(), Ts.size
+    kx, kr = sensor.on_device(dev)
+    N = torch.empty(nB, dtype=torch.float32, device=dev)
+    Cb = torch.empty(nB, dtype=torch.float32, device=dev)
+    M = torch.empty((nT, nB, nk), dtype=torch.float32, device=dev)
+    jr = torch.empty((nB, 2), dtype=torch.int32, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    _lib.check(lib.rtx_srf_moments(grid.byref(), p(tau), p(La), p(Ld), Ts.ctypes.data_as(C.c_void_p), nT, p(Xk_d), nk, nB,
+                                   sensor.knot_start.ctypes.data_as(C.c_void_p), p(kx), p(kr), p(N), p(Cb), p(M), p(jr),
+                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return N, Cb, M, jr
+
+
+def band_radiance_srf_fused(grid, tau, La, Ld, Xk, emis_knots, Ts, sensor):
+    """band_radiance_srf() without any [nX][nE] array, for one surface temperature or many: one pass over tau / La / Ld
+    per group of 16 bands (rtx_srf_moments; Planck evaluated at every point for every temperature) and one contraction
+    over each band's emissivity knots per temperature (rtx_band_mix). Same arguments as band_radiance_srf(); Ts may be a
+    sequence (the reference's Ts + dT: Ts=Ts0 + np.asarray(dT)), taken rtx_srf_moments_max_temps() at a time.
+    Returns (X_out [nB] NumPy = sensor.centres, L float32 device: [nB][nE] for a scalar Ts, [nT][nB][nE] for a 1-D Ts).
+    Allocated besides L: the moments M [nT][nB][nk] float32 (N, C [nB], jrange [nB][2]), nothing of size nX."""
+    lib = _lib.load()
+    dev = tau.device
+    scalar = np.ndim(Ts) == 0
+    Ts = np.atleast_1d(np.asarray(Ts, dtype=np.float64))
+    if Ts.ndim != 1 or Ts.size == 0:
+        raise ValueError("Ts: a scalar or a non-empty 1-D sequence")
+    plan = _srf_fused_plan(Xk, dev)
+    nB, nk, nE, nT = len(sensor), plan["Xk_d"].numel(), emis_knots.shape[1], Ts.size
+    assert emis_knots.dtype == torch.float32 and emis_knots.is_cuda and emis_knots.shape[0] == nk
+    emis_knots = emis_knots.contiguous()
+    out = torch.empty((nT, nB, nE), dtype=torch.float32, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    step = lib.rtx_srf_moments_max_temps()
+    for t0 in range(0, nT, step):
+        N, Cb, M, jr = srf_moments(grid, tau, La, Ld, plan["Xk_d"], Ts[t0:t0 + step], sensor)
+        for t in range(M.shape[0]):
+            _lib.check(lib.rtx_band_mix(p(N), p(Cb), p(M[t]), p(jr), nB, nk, p(emis_knots), nE, p(out[t0 + t]), st))
+    X_out = np.array(sensor.centres)
+    return X_out, (out[0] if scalar else out)
+
+
 def chebyshev_lagrange(Q):
     """Chebyshev nodes s_q on (-1,1) and the monomial coefficients coef[q][d] of their Lagrange basis."""
     s = np.cos((2 * np.arange(Q) + 1) * np.pi / (2 * Q))
