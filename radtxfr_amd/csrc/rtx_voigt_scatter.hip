@@ -379,7 +379,8 @@ __global__ __launch_bounds__(256) void voigt_scatter_kernel(ScArgs a) {
 //                    Chebyshev nodes only. The member lanes' ids are compacted with one ds_permute; groups of 8 members
 //                    are evaluated with lane = (member, node), the members' record fields fetched lane-to-lane with
 //                    ds_bpermute (no LDS storage, no second trip to memory). Members whose window covers the whole tile
-//                    ("full": 40 % of them on C3) skip the per-row masks.
+//                    ("full": 40 % of them on C3) skip the per-row masks, unless serving them with the partial members saves
+//                    a group of 8 in the wave's round. The final sum over the 8 member slots of a lane's node runs in registers.
 //   point by point   near-zone rows, the <= 2 rows cut by a window edge, band rows: the member lanes write 64-byte LDS
 //                    entries (record fields, window in u, row masks) and the wave drains them, accumulating into its
 //                    own copy of the tile in LDS (plain read/add/write, no atomics, fixed order).
@@ -409,6 +410,20 @@ __global__ __launch_bounds__(256) void voigt_scatter_kernel(ScArgs a) {
 // 4-row segment (2.7e-7), a quarter of their evaluations, sums carried to the row nodes by a constant 4 x 8 x 8 matrix in the
 // final stage: 2.02 vs 1.95 (distance 6 / 10: 2.03 / 2.04). The extra compaction pass and one more spilled register cost
 // more than the ~40 % of the members it takes off the row level save, as the three-level tree had shown with four waves.
+// Cross-lane sums in registers, fuller groups (kernel time of <false> by rocprofv3, one pipeline, builds interleaved in one session,
+// profiles/linesum_groups_time.txt; tools/count_groups.py is the census behind the counts):
+//  - the final sum over the 8 member slots -- 16 row sums and the two tile-node sums, three xor steps each, 54 ds_bpermute round trips
+//    per wave and tile in three-deep dependent chains right before the barrier, 13 % of the kernel's LDS instructions -- by a DPP add
+//    (row_ror:8), v_permlane16_swap and v_permlane32_swap: the same pairing tree, bit-identical results, the row sums of four tile rows
+//    in one register (4 ds_write_b32 instead of 16): 1.532 -> 1.464 ms (medians of three runs each);
+//  - the full members of a wave's round (~3 on C3: one group of 8 a third full) through the partial pass, row mask ALL_ROWS, whenever
+//    that saves a group (RTX_SC_MERGE; 23 % of the wave rounds, 7 % of the row-level groups): 1.464 -> 1.448 ms; nine runs of the parent
+//    against nine of this form: 1.512-1.536 (median 1.525) -> 1.432-1.456 (1.444) ms, 1.447e8 -> 1.208e8 LDS and 0.975e9 -> 0.960e9 VALU
+//    wave-instructions per launch.
+// Measured and not taken: the candidate lane forming xb = fma(ub, a, c) once per round, so that a group pulls xb in place of c and does
+// not pull ub (7 pulls per group instead of 8, one FMA fewer; x moves by an ulp; 1.173e8 LDS instructions): 1.463 against 1.464 ms on its own
+// (three runs each, ranges overlapping) and 1.427-1.445 (median 1.436) against 1.432-1.456 (1.444) on top of the merged pass (nine runs
+// each): half a percent at best, and not every run of one below every run of the other.
 #ifndef RTX_SC_WAVES
 #define RTX_SC_WAVES 6
 #endif
@@ -428,6 +443,12 @@ __global__ __launch_bounds__(256) void voigt_scatter_kernel(ScArgs a) {
 #define RTX_SC_TILE_LEVEL 1  // full members >= RTX_SC_TILE_DIST points outside a 16-row tile: 16 tile nodes instead of 16 x 8 row nodes
 #endif
 #define RTX_SC_TILE_DIST 512
+#ifndef RTX_SC_RED_REG
+#define RTX_SC_RED_REG 1  // final sum over the 8 member slots in registers (DPP row_ror:8, v_permlane16_swap, v_permlane32_swap) instead of three ds_bpermute steps per row; the same pairing tree, bit-identical sums
+#endif
+#ifndef RTX_SC_MERGE
+#define RTX_SC_MERGE 1  // full members go through the partial pass (row mask ALL_ROWS) when that saves a group of 8 in this wave's round
+#endif
 #ifndef SC_ENT_CAP
 #define SC_ENT_CAP (SC_EDGE_LIST ? 16 : 32)  // point-by-point entries per wave (64 B each). Without the edge list, two waves per workgroup: 16 -> 2.02 ms, 24 -> 1.99, 32 -> 1.96, 48 -> 2.03
 #endif
@@ -690,10 +711,19 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
         }
       }
     }
-    // full members first (no masks), then the partial ones
+    // full members first (no masks), then the partial ones. When one pass over both classes needs fewer groups of 8 than
+    // the two passes apart -- ceil((nF + nP) / 8) < ceil(nF / 8) + ceil(nP / 8): on C3 a wave's round holds ~3 full and 13-26
+    // partial members, so the full pass is mostly one group a third full -- the full members go through the partial pass
+    // with their row mask ALL_ROWS. The decision is wave-uniform and a function of this wave's candidates of this round
+    // alone, so a tile's sums stay a function of the tile and of the lines that reach it.
+    bool merged = false;
+    if (RTX_SC_MERGE) {
+      const int nF = __popcll(__ballot(m_far == ALL_ROWS && !is_t)), nP = __popcll(__ballot(m_far != 0u && m_far != ALL_ROWS));
+      merged = ((nF + nP + 7) >> 3) < ((nF + 7) >> 3) + ((nP + 7) >> 3);
+    }
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
-      const bool is_m = pass == 0 ? (m_far == ALL_ROWS && !is_t) : (m_far != 0u && m_far != ALL_ROWS);
+      const bool is_m = pass == 0 ? (m_far == ALL_ROWS && !is_t && !merged) : (m_far != 0u && (m_far != ALL_ROWS || (merged && !is_t)));
       const unsigned long long rb = __ballot(is_m);
       if (!rb) continue;
       const int nR = __popcll(rb);
@@ -755,7 +785,41 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
   drain();
   if (SC_EDGE_LIST) drain_edges();
 
+  // the final stages take the lane id afresh from v_mbcnt: held since the kernel's start, it (or lane & 7) is live across the
+  // candidate loop, which has no register to spare (one spilled register, measured on the 80-register instantiation)
+  const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
   // sum the 8 member slots of each node (lanes l = 0..7 of equal j), one copy per wave
+#if RTX_SC_RED_REG
+  // In registers, with the pairing tree of the xor 8 / 16 / 32 butterfly, ((v0 + v1) + (v2 + v3)) + ((v4 + v5) + (v6 + v7)),
+  // so the sums are those of the ds_bpermute form bit for bit. xor 8 pairs the two slots of a 16-lane row: a DPP add with
+  // row_ror:8. xor 16 and xor 32 pair whole rows and halves: v_permlane16_swap / v_permlane32_swap exchange them between TWO
+  // registers, so one add serves both and the sums of four tile rows end up in one register, tile row 4 q + i on lane row i.
+  auto ror8 = [](float v) -> float {  // v + (v of lane ^ 8)
+    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, true));
+  };
+  auto swap16 = [](float a, float b) -> float {  // lane rows [a0 + a1, b0 + b1, a2 + a3, b2 + b3]
+    const auto s = __builtin_amdgcn_permlane16_swap((unsigned)__float_as_int(a), (unsigned)__float_as_int(b), false, false);
+    return __int_as_float((int)s[0]) + __int_as_float((int)s[1]);
+  };
+  auto swap32 = [](float a, float b) -> float {  // lane halves [a_lo + a_hi, b_lo + b_hi]
+    const auto s = __builtin_amdgcn_permlane32_swap((unsigned)__float_as_int(a), (unsigned)__float_as_int(b), false, false);
+    return __int_as_float((int)s[0]) + __int_as_float((int)s[1]);
+  };
+  static_assert(ROWS % 4 == 0, "the register reduction takes the tile rows four at a time");
+#pragma unroll
+  for (int q = 0; q < ROWS / 4; ++q) {
+    const float v = swap32(swap16(ror8(nod[4 * q]), ror8(nod[4 * q + 1])), swap16(ror8(nod[4 * q + 2]), ror8(nod[4 * q + 3])));
+    if (!(ln & 8)) reinterpret_cast<float*>(&s_ent[wave][0][0])[(4 * q + (ln >> 4)) * CHEB_N + (ln & 7)] = v;
+  }
+  if (TILE_LEVEL) {  // the wave's 16 tile-node sums and its member count, behind its row sums
+    const float h = swap16(ror8(tnod_a), ror8(tnod_b));  // the two tile-node registers pair with each other
+    const float v = swap32(h, h);                         // lane row 0: nodes j, lane row 1: nodes 15 - j
+    float* ts = reinterpret_cast<float*>(&s_ent[wave][0][0]) + ROWS * CHEB_N;
+    if (ln < 8) ts[ln] = v;
+    if ((ln & ~7) == 16) ts[15 - (ln & 7)] = v;
+    if (ln == 0) ts[16] = __int_as_float(n_tile_members);
+  }
+#else
 #pragma unroll
   for (int r = 0; r < ROWS; ++r) {
     float v = nod[r];
@@ -773,12 +837,13 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
     if (lane < 8) { ts[lane] = va; ts[15 - lane] = vb; }
     if (lane == 0) ts[16] = __int_as_float(n_tile_members);
   }
+#endif
   STAMP(2);
   __syncthreads();
   STAMP(6);  // barrier
   // stage 1: thread (r, jj) adds the waves' row-level sums in a fixed order
   static_assert(SC_NW == 1 || SC_NW == 2 || SC_NW == 4, "one, two or four waves per workgroup");
-  for (int o = wave * 64 + lane; o < ROWS * CHEB_N; o += 64 * SC_NW) {  // o = r * CHEB_N + jj (from the live lane id: no late use of threadIdx.x, which cost a spill)
+  for (int o = wave * 64 + ln; o < ROWS * CHEB_N; o += 64 * SC_NW) {  // o = r * CHEB_N + jj
     float v = reinterpret_cast<const float*>(&s_ent[0][0][0])[o];
     if constexpr (SC_NW >= 2) v += reinterpret_cast<const float*>(&s_ent[1][0][0])[o];
     if constexpr (SC_NW == 4) v += reinterpret_cast<const float*>(&s_ent[2][0][0])[o] + reinterpret_cast<const float*>(&s_ent[3][0][0])[o];
