@@ -426,6 +426,44 @@ int rtx_pixel_cube(int nB, int Q, const double* centre, const double* sigma, dou
 int rtx_sdvoigt_sum(const rtx_prep* prep, const rtx_grid* grid, int n_layers, float* out_f32,
                     double* out_f64, int64_t ld, void* stream);
 
+/* ---- hapi's line-profile functions with explicit parameters --------------------------------------------------
+ * Replace pcqsdhc / PROFILE_HT(P) / PROFILE_SDRAUTIAN / PROFILE_RAUTIAN / PROFILE_SDVOIGT / PROFILE_VOIGT, PROFILE_LORENTZ
+ * and PROFILE_DOPPLER (misc/hapi.py:9850-10160) and the complex probability functions hum1_wei (:9833) and cpf3 (:9645),
+ * as people who fit spectra call them: per-line parameters, no line table, no environment, no windows. fp64 throughout.
+ * The profile is the COMPLETE pcqsdhc: PART1 (Aterm; Bterm for |Z1| <= 4000 and beyond), PART2, PART3 (|sqrt X| <= 4000
+ * and beyond), PART4 (with the cpf3 shell) and the common part (1/pi) A / (1 - (anuVC - eta (c0 - 1.5 c2)) A + eta c2 B),
+ * eta complex, real and imaginary part. Each point is what the reference returns for that point ALONE, sg = array([s])
+ * (its vector call needs every point of a call in one PART); PART3's far form uses PART3's own W (the reference raises
+ * there). Parameters are not validated (GamD = 0, eta = 1: what IEEE arithmetic gives). DESIGN.md section 4.14.
+ *   params[n_lines][10] fp64, device: sg0, GamD, Gam0, Gam2, Shift0, Shift2, anuVC, Re eta, Im eta, pad.
+ *   sg[n] fp64, device: the points, in any order, repeats allowed.
+ *   rtx_profile_eval  every line at every point: out_re / out_im [n_lines][ld] (out_im may be NULL). kind:
+ *       RTX_LS_PCQSDHC  the profile above;
+ *       RTX_LS_LORENTZ  Gam0 / (pi (Gam0^2 + (sg - sg0)^2)), :10150 (reads sg0, Gam0);
+ *       RTX_LS_DOPPLER  cSqrtLn2divSqrtPi exp(-cLn2 ((sg - sg0) / GamD)^2) / GamD with hapi's rounded constants, :10160
+ *                       (reads sg0, GamD). Both are real: out_im, when given, is set to 0.
+ *       A point's value is a function of (its line's parameters, sg) alone: bit-identical wherever it stands in sg.
+ *   rtx_profile_sum   out[i] = sum_l w_re[l] Re LS_l(sg[i]) + w_im[l] Im LS_l(sg[i]), pcqsdhc: the model spectrum of a fit
+ *       (strengths on the real part, first-order mixing coefficients times strengths on the imaginary part). w_re / w_im
+ *       [n_lines] fp64, device; w_im may be NULL (= 0). One thread per point, lines in index order, one association
+ *       (acc = acc + (w_re Re + w_im Im)): bit-reproducible, and independent of n and of the order of sg.
+ *   rtx_cpf_eval      out[i] = hum1_wei(x[i], y[i]) (RTX_CPF_HUM1_WEI: Weideman-24 inside |x| + y < 15, the one-term
+ *       asymptote outside; y may be negative; |z| < 1e154, where (L - iz)^2 overflows as in the reference) or cpf3(x[i], y[i]) (RTX_CPF_CPF3: the 15-term series, meant for |z| ~ 8;
+ *       1/z by a Newton-refined reciprocal, so 1e-150 < |z| < 1e150); out_im may be NULL.
+ * Errors (before any device work): a required pointer NULL, a negative count, ld < n, an unknown kind. n = 0 or
+ * n_lines = 0 succeeds without a launch and writes nothing. Asynchronous on `stream`; nothing is allocated. */
+#define RTX_LS_PCQSDHC 0
+#define RTX_LS_LORENTZ 1
+#define RTX_LS_DOPPLER 2
+#define RTX_CPF_HUM1_WEI 0
+#define RTX_CPF_CPF3 1
+int rtx_profile_eval(int kind, int64_t n_lines, const double* params, const double* sg, int64_t n,
+                     double* out_re, double* out_im, int64_t ld, void* stream);
+int rtx_profile_sum(int64_t n_lines, const double* params, const double* w_re, const double* w_im,
+                    const double* sg, int64_t n, double* out, void* stream);
+int rtx_cpf_eval(int kind, const double* x, const double* y, int64_t n, double* out_re,
+                 double* out_im, void* stream);
+
 /* ---- post-processing of TUD products: smooth / reduceResolution ---------------------
  * Replaces radiative_transfer.py:1266-1324 (smooth: reflect-padded window convolution) and :1327-1350
  * (reduceResolution: symmetrised smoothing + scipy cubic interp1d onto a coarser axis).

@@ -75,6 +75,9 @@ PROTOTYPES = {
     "rtx_cubic_resample_unchecked": (_i32, [_vp, _i64, _i32, _i64, _dbl, _dbl, _vp, _i64, _vp, _i64, _vp]),
     "rtx_hapi_spectrum": (_i32, [_i32, _gp, _vp, _vp, _i32, _i32, _i64, _i64, _dbl, _dbl, _vp, _i64, _vp]),
     "rtx_fir_same": (_i32, [_vp, _i32, _i64, _i32, _i64, _vp, _i64, _dbl, _i64, _i64, _vp, _i64, _vp]),
+    "rtx_profile_eval": (_i32, [_i32, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "rtx_profile_sum": (_i32, [_i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "rtx_cpf_eval": (_i32, [_i32, _vp, _vp, _i64, _vp, _vp, _vp]),
     "rtx_fir_tile_points": (_i32, []),
     "rtx_fir_chunk_taps": (_i32, []),
     "rtx_brightness_temperature": (_i32, [_vp, _i64, _vp, _i64, _i32, _dbl, _vp, _vp]),

@@ -951,6 +951,66 @@ def hapi_spectrum(kind, K, l, T=0.0, X=None):
     return out
 
 
+# ---- line-profile functions with explicit per-line parameters (rtx_profile_eval / _sum, rtx_cpf_eval) -----------------
+LS_PCQSDHC, LS_LORENTZ, LS_DOPPLER = 0, 1, 2
+CPF_HUM1_WEI, CPF_CPF3 = 0, 1
+PROFILE_NPAR = 10  # sg0, GamD, Gam0, Gam2, Shift0, Shift2, anuVC, Re eta, Im eta, pad
+
+
+def _f64_vector(t, what):
+    assert t.is_cuda and t.dtype == torch.float64 and t.dim() == 1 and t.is_contiguous(), what
+
+
+def profile_eval(kind, params, sg, imag=True):
+    """params [nL][10] and sg [n], fp64 device tensors -> (re, im) [nL][n] fp64 (im None when imag=False): every line at
+    every point (rtx_profile_eval); kind LS_PCQSDHC / LS_LORENTZ / LS_DOPPLER."""
+    lib = _lib.load()
+    assert params.is_cuda and params.dtype == torch.float64 and params.dim() == 2 and params.shape[1] == PROFILE_NPAR and params.is_contiguous()
+    _f64_vector(sg, "sg")
+    nL, n = params.shape[0], sg.numel()
+    re = torch.empty((nL, n), dtype=torch.float64, device=sg.device)
+    im = torch.empty((nL, n), dtype=torch.float64, device=sg.device) if imag else None
+    if nL == 0 or n == 0:  # an empty tensor has no pointer to pass
+        return re, im
+    with torch.cuda.device(sg.device):
+        _lib.check(lib.rtx_profile_eval(int(kind), nL, _ptr(params), _ptr(sg), n, _ptr(re), _ptr(im), n, _stream_ptr()))
+    return re, im
+
+
+def profile_sum(params, w_re, w_im, sg):
+    """out[i] = sum_l w_re[l] Re LS_l(sg[i]) + w_im[l] Im LS_l(sg[i]) of the pcqsdhc profile, [n] fp64 (rtx_profile_sum);
+    w_im None = zeros. Lines in index order, bit-reproducible."""
+    lib = _lib.load()
+    assert params.is_cuda and params.dtype == torch.float64 and params.dim() == 2 and params.shape[1] == PROFILE_NPAR and params.is_contiguous()
+    _f64_vector(sg, "sg")
+    _f64_vector(w_re, "w_re")
+    nL, n = params.shape[0], sg.numel()
+    assert w_re.numel() == nL
+    if w_im is not None:
+        _f64_vector(w_im, "w_im")
+        assert w_im.numel() == nL
+    if nL == 0 or n == 0:  # the empty sum; an empty tensor has no pointer to pass
+        return torch.zeros(n, dtype=torch.float64, device=sg.device)
+    out = torch.empty(n, dtype=torch.float64, device=sg.device)
+    with torch.cuda.device(sg.device):
+        _lib.check(lib.rtx_profile_sum(nL, _ptr(params), _ptr(w_re), _ptr(w_im), _ptr(sg), n, _ptr(out), _stream_ptr()))
+    return out
+
+
+def cpf_eval(kind, x, y):
+    """hum1_wei (CPF_HUM1_WEI) or cpf3 (CPF_CPF3) of x + iy elementwise, [n] fp64 device tensors -> (re, im) (rtx_cpf_eval)."""
+    lib = _lib.load()
+    _f64_vector(x, "x")
+    _f64_vector(y, "y")
+    assert x.numel() == y.numel() and x.device == y.device
+    re, im = torch.empty_like(x), torch.empty_like(x)
+    if x.numel() == 0:
+        return re, im
+    with torch.cuda.device(x.device):
+        _lib.check(lib.rtx_cpf_eval(int(kind), _ptr(x), _ptr(y), x.numel(), _ptr(re), _ptr(im), _stream_ptr()))
+    return re, im
+
+
 def cubic_resample(Ysm, x0, h, x_out, checked=True):
     """Cubic spline through every sample of the uniform axis x0 + i*h, at x_out (device fp64): [rows][n_out] fp64.
     checked=False: the caller has verified the range of x_out on the host; no device read-back, no synchronisation."""

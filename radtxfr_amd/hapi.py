@@ -11,10 +11,13 @@ meaning and error behaviour:
     transmittanceSpectrum, absorptionSpectrum, radianceSpectrum   misc/hapi.py:11582-11680   -> rtx_hapi_spectrum
     SLIT_* (host NumPy), convolveSpectrum, convolveSpectrumSame, convolveSpectrumFull
                                   misc/hapi.py:11742-11900   -> rtx_fir_same (fp64 direct FIR)
+    pcqsdhc, PROFILE_HT(P), PROFILE_SDRAUTIAN, PROFILE_RAUTIAN, PROFILE_SDVOIGT, PROFILE_VOIGT, PROFILE_LORENTZ,
+    PROFILE_DOPPLER, hum1_wei, cpf3   misc/hapi.py:9645-10160   -> rtx_profile_eval / rtx_cpf_eval (fp64, complex)
+    profile_lines                 (not in the reference) many lines at once, or their weighted sum -> rtx_profile_sum
 
-The database client (fetch/select/...) and the other line profiles are out of scope (SURVEY.md
+The database client (fetch/select/...) and the Galatry profile are out of scope (SURVEY.md
 section 2, rows 12-13). There is no CPU fallback: without the HIP library and a GPU,
-absorptionCoefficient_Voigt and the spectrum / convolution functions raise.
+absorptionCoefficient_Voigt, the spectrum / convolution functions and the profile functions raise.
 """
 import math
 
@@ -626,3 +629,166 @@ def convolveSpectrumFull(Omega, CrossSection, Resolution=0.1, AF_wing=10., SlitF
     without its debug prints. Returns (Omega, Y, None, None)."""
     Y, _ = _convolve(Omega, CrossSection, Resolution, AF_wing, SlitFunction, True)
     return Omega, Y, None, None
+
+
+# ---- the line-shape functions themselves, with explicit per-line parameters ---------------------------------------------
+# (misc/hapi.py:9645-10160: what people who fit spectra call directly, and the only place where hapi returns the imaginary,
+# dispersion, part that first-order line mixing needs.) Evaluated on the GPU in fp64 by the complete pcqsdhc of
+# csrc/rtx_pcqsdhc.h: every PART, Aterm and Bterm, the common part, complex eta. Each point is what the reference returns
+# when that point is passed ALONE (its vector call assigns PART1's Bterm whole-array and raises when the points of a call
+# split between PART3 and PART4; SURVEY.md section 9). Types as for the spectrum functions: NumPy, list, tuple or scalar sg
+# -> NumPy float64; a torch tensor sg -> torch tensors on its device. The parameters are scalars and are not validated.
+cZero = 0.0  # misc/hapi.py:81
+
+
+def _points(sg):
+    """sg (scalar, list, tuple, NumPy, torch; at most one dimension) -> (fp64 device vector, back): a scalar gives one
+    point, shape (1,), as misc/hapi.py:9893-9894 does; back(t) returns a device result in the caller's kind."""
+    if isinstance(sg, torch.Tensor):
+        if sg.dim() > 1:
+            raise ValueError("sg of shape %s: the profile functions take a vector of wavenumbers" % (tuple(sg.shape),))
+        src = sg.device
+        t = sg.detach().to(device=sg.device if sg.is_cuda else engine.device(), dtype=torch.float64).reshape(-1).contiguous()
+        return t, lambda o: o.to(src)
+    a = np.asarray(sg, dtype=np.float64)
+    if a.ndim > 1:
+        raise ValueError("sg of shape %s: the profile functions take a vector of wavenumbers" % (a.shape,))
+    return torch.as_tensor(np.ascontiguousarray(a.reshape(-1)), device=engine.device()), lambda o: o.cpu().numpy()
+
+
+def _host(v):
+    return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+
+
+def _line_params(sg0, GamD, Gam0, Gam2, Shift0, Shift2, anuVC, eta):
+    """The per-line arguments (scalars, or arrays of one length; scalars broadcast) -> [nL][10] fp64 in rtx_profile_eval's
+    layout: sg0, GamD, Gam0, Gam2, Shift0, Shift2, anuVC, Re eta, Im eta, pad."""
+    eta = _host(eta).astype(np.complex128)
+    cols = [np.asarray(_host(v), dtype=np.float64) for v in (sg0, GamD, Gam0, Gam2, Shift0, Shift2, anuVC)] + [eta.real, eta.imag]
+    if any(c.ndim > 1 for c in cols):
+        raise ValueError("per-line parameters are scalars or vectors of one length")
+    cols = np.broadcast_arrays(*[np.atleast_1d(c) for c in cols])  # ValueError for lengths that do not match
+    P = np.zeros((cols[0].size, engine.PROFILE_NPAR))
+    for j, c in enumerate(cols):
+        P[:, j] = c
+    return P
+
+
+def _profile(kind, sg, *line):
+    t, back = _points(sg)
+    P = torch.as_tensor(_line_params(*line), device=t.device)
+    re, im = engine.profile_eval(kind, P, t, imag=kind == engine.LS_PCQSDHC)
+    return (back(re[0]), back(im[0])) if im is not None else back(re[0])
+
+
+def pcqsdhc(sg0, GamD, Gam0, Gam2, Shift0, Shift2, anuVC, eta, sg):
+    """The partially-correlated quadratic-speed-dependent hard-collision (Hartmann-Tran) profile, misc/hapi.py:9850-10023:
+    (real, imag) of the normalised complex line shape at the wavenumbers sg. eta may be complex (absorptionCoefficient_HT
+    passes a complex Eta, :10641). A scalar sg gives shape (1,)."""
+    return _profile(engine.LS_PCQSDHC, sg, sg0, GamD, Gam0, Gam2, Shift0, Shift2, anuVC, eta)
+
+
+def PROFILE_HT(sg0, GamD, Gam0, Gam2, Shift0, Shift2, anuVC, eta, sg):
+    """Hartmann-Tran profile, misc/hapi.py:10034-10085: pcqsdhc."""
+    return pcqsdhc(sg0, GamD, Gam0, Gam2, Shift0, Shift2, anuVC, eta, sg)
+
+
+PROFILE_HTP = PROFILE_HT  # misc/hapi.py:10087
+
+
+def PROFILE_SDRAUTIAN(sg0, GamD, Gam0, Gam2, Shift0, Shift2, anuVC, sg):
+    """Speed-dependent Rautian profile, misc/hapi.py:10089-10102: pcqsdhc with eta = 0."""
+    return pcqsdhc(sg0, GamD, Gam0, Gam2, Shift0, Shift2, anuVC, cZero, sg)
+
+
+def PROFILE_RAUTIAN(sg0, GamD, Gam0, Shift0, anuVC, eta, sg):
+    """Rautian profile, misc/hapi.py:10104-10115: pcqsdhc with Gam2 = Shift2 = 0 -- and eta = 0: the reference ignores its
+    eta argument (:10115), and so does this."""
+    return pcqsdhc(sg0, GamD, Gam0, cZero, Shift0, cZero, anuVC, cZero, sg)
+
+
+def PROFILE_SDVOIGT(sg0, GamD, Gam0, Gam2, Shift0, Shift2, sg):
+    """Speed-dependent Voigt profile, misc/hapi.py:10117-10129: pcqsdhc with anuVC = eta = 0."""
+    return pcqsdhc(sg0, GamD, Gam0, Gam2, Shift0, Shift2, cZero, cZero, sg)
+
+
+def PROFILE_VOIGT(sg0, GamD, Gam0, sg):
+    """Voigt profile, misc/hapi.py:10131-10140: pcqsdhc with everything but sg0, GamD and Gam0 zero."""
+    return PROFILE_HTP(sg0, GamD, Gam0, cZero, cZero, cZero, cZero, cZero, sg)
+
+
+def PROFILE_LORENTZ(sg0, Gam0, sg):
+    """Gam0 / (pi (Gam0^2 + (sg - sg0)^2)), misc/hapi.py:10142-10150. One array."""
+    return _profile(engine.LS_LORENTZ, sg, sg0, 1.0, Gam0, 0.0, 0.0, 0.0, 0.0, 0.0)
+
+
+def PROFILE_DOPPLER(sg0, GamD, sg):
+    """cSqrtLn2divSqrtPi exp(-cLn2 ((sg - sg0) / GamD)^2) / GamD with hapi's rounded constants, misc/hapi.py:10152-10160.
+    One array."""
+    return _profile(engine.LS_DOPPLER, sg, sg0, GamD, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+
+
+def _cpf(kind, x, y):
+    as_torch = isinstance(x, torch.Tensor)
+    if as_torch:
+        src = x.device
+        dev = x.device if x.is_cuda else engine.device()
+        tx, ty = torch.broadcast_tensors(x.detach().to(device=dev, dtype=torch.float64), torch.as_tensor(y, dtype=torch.float64).to(dev))
+    else:
+        ax, ay = np.broadcast_arrays(np.atleast_1d(np.asarray(x, dtype=np.float64)), np.atleast_1d(np.asarray(_host(y), dtype=np.float64)))
+        dev = engine.device()
+        tx, ty = torch.as_tensor(np.ascontiguousarray(ax), device=dev), torch.as_tensor(np.ascontiguousarray(ay), device=dev)
+    shape = tuple(tx.shape)
+    re, im = engine.cpf_eval(kind, tx.reshape(-1).contiguous(), ty.reshape(-1).contiguous())
+    re, im = re.reshape(shape), im.reshape(shape)
+    return (re.to(src), im.to(src)) if as_torch else (re.cpu().numpy(), im.cpu().numpy())
+
+
+def hum1_wei(x, y, n=24):
+    """w(x + iy) as VARIABLES['CPF'] of the reference computes it, misc/hapi.py:9833-9844: Weideman's 24-term rational
+    expansion where |x| + y < 15, the one-term asymptote elsewhere; y may be negative. (real, imag). Only n = 24 exists on
+    the GPU (its coefficients are compile-time constants)."""
+    if n != 24:
+        raise ValueError("hum1_wei: n=%r; only the 24-term expansion is implemented" % (n,))
+    return _cpf(engine.CPF_HUM1_WEI, x, y)
+
+
+def cpf3(X, Y):
+    """The 15-term asymptotic series of w(X + iY) that pcqsdhc uses around |z| = 8, misc/hapi.py:9645-9670. (real, imag)."""
+    return _cpf(engine.CPF_CPF3, X, Y)
+
+
+def profile_lines(sg, sg0, GamD=None, Gam0=0., Gam2=0., Shift0=0., Shift2=0., anuVC=0., eta=0., profile="HT", weights=None,
+                  mixing=None):
+    """Many lines in one call (not in the reference, which takes one line per call). The per-line arguments are arrays of one
+    length nL; scalars broadcast. profile: "HT" (pcqsdhc, eta may be complex), "LORENTZ" (reads sg0, Gam0) or "DOPPLER"
+    (reads sg0, GamD). No windows: every line reaches every point of sg.
+      weights=None   (real, imag), each [nL][n]: line l at point i, bit-identical to the one-line functions above
+                     (imag is zero for LORENTZ and DOPPLER).
+      weights [nL]   the spectrum  sum_l weights_l (Re LS_l + mixing_l Im LS_l)  of shape [n] (profile "HT" only): strengths
+                     on the absorption part and first-order line-mixing coefficients on the dispersion part; mixing=None
+                     means zeros. Summed on the GPU in line order (rtx_profile_sum): bit-reproducible."""
+    kinds = {"HT": engine.LS_PCQSDHC, "LORENTZ": engine.LS_LORENTZ, "DOPPLER": engine.LS_DOPPLER}
+    if profile not in kinds:
+        raise ValueError("profile=%r; one of 'HT', 'LORENTZ', 'DOPPLER'" % (profile,))
+    if GamD is None:
+        if profile != "LORENTZ":
+            raise ValueError("profile %r needs GamD" % profile)
+        GamD = 1.0  # not read
+    P = _line_params(sg0, GamD, Gam0, Gam2, Shift0, Shift2, anuVC, eta)
+    nL = P.shape[0]
+    w = m = None
+    if weights is not None:
+        if profile != "HT":
+            raise ValueError("weights: the weighted sum is implemented for profile 'HT' (it contains the Voigt family as limits)")
+        w = np.array(np.broadcast_to(np.asarray(_host(weights), dtype=np.float64), (nL,)))  # a writable copy
+        if mixing is not None:
+            m = np.ascontiguousarray(w * np.broadcast_to(np.asarray(_host(mixing), dtype=np.float64), (nL,)))
+    elif mixing is not None:
+        raise ValueError("mixing without weights")
+    t, back = _points(sg)
+    Pd = torch.as_tensor(P, device=t.device)
+    if w is None:
+        re, im = engine.profile_eval(kinds[profile], Pd, t)
+        return back(re), back(im)
+    return back(engine.profile_sum(Pd, torch.as_tensor(w, device=t.device), None if m is None else torch.as_tensor(m, device=t.device), t))
