@@ -38,7 +38,14 @@ __device__ __forceinline__ F weideman_re(F x, F y) {
     // (= 1 only on the real axis, y = 0), so rounding errors are not amplified: in fp32, over the band of the main pass
     // (y >= 1, |z| < 8 or y < 6), the result is within 1.8e-6 of the fp64 reference, the same as the complex Horner form
     // (1.9e-6); in fp64, over 1e-6 <= y < 1, within 1.5e-15 (absolute) of numpy.polyval.
-    const F r = (F)2 * Wr, ns = -fma(Wr, Wr, Wi * Wi);
+    const F r = (F)2 * Wr;
+    F ns = -fma(Wr, Wr, Wi * Wi);
+    // fp32: -s as a value in a vector register of its own, which the compiler may not turn back into s with a source
+    // modifier. A modifier needs the VOP3 encoding, which takes no literal on gfx950, so every coefficient of the two chains
+    // then sat in a scalar register, and a vector instruction with a scalar-register source issues in 3.7 cycles instead
+    // of 2.0 (tools/ubench_enc.hip). With a plain vector operand each step is a v_fmaak_f32 with its coefficient as the
+    // literal. Same operations, same roundings.
+    if constexpr (sizeof(F) == 4) asm("" : "+v"(ns));
     F ob1 = coef[0], ob2 = (F)0, eb1 = coef[1], eb2 = (F)0;
 #pragma unroll
     for (int k = 2; k < 22; k += 2) {
@@ -65,13 +72,17 @@ __device__ __forceinline__ float asym6_re(float x, float y) {
   float inv = __builtin_amdgcn_rcpf(r2);
   inv = fmaf(fmaf(-r2, inv, 1.0f), inv, inv);
   const float zr = x * inv, zi = -y * inv;                         // 1/z
-  const float ur = fmaf(zr, zr, -(zi * zi)), ui = 2.0f * zr * zi;  // 1/z^2
+  const float ur = fmaf(zr, zr, -(zi * zi));  // 1/z^2 = ur + i ui, held as nui = -ui
+  // -ui as a value of its own (weideman_re: a source modifier on the step that adds c[k] would put c[k] in a scalar
+  // register); (-pi) ui = pi (-ui) and pr ui = (-pr)(-ui) exactly, so every rounding is the one it was
+  float nui = -(2.0f * zr * zi);
+  asm("" : "+v"(nui));
   float pr = 945.0f / 32.0f, pi = 0.0f;
   constexpr float c[5] = {105.0f / 16.0f, 15.0f / 8.0f, 0.75f, 0.5f, 1.0f};
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
-    const float tr = fmaf(pr, ur, fmaf(-pi, ui, c[k]));
-    const float ti = fmaf(pr, ui, pi * ur);
+    const float tr = fmaf(pr, ur, fmaf(pi, nui, c[k]));
+    const float ti = fmaf(-pr, nui, pi * ur);
     pr = tr;
     pi = ti;
   }
