@@ -464,6 +464,54 @@ int rtx_profile_sum(int64_t n_lines, const double* params, const double* w_re, c
 int rtx_cpf_eval(int kind, const double* x, const double* y, int64_t n, double* out_re,
                  double* out_im, void* stream);
 
+/* ---- Hartmann-Tran line-sum on a line table ---------------------------------------------------------------------
+ * Replaces the per-line block and the scatter-add of absorptionCoefficient_HT, misc/hapi.py:10474-10651, for tables that
+ * carry Hartmann-Tran columns: the HT-named lookups with their fallbacks to the Voigt-style columns, PROFILE_HT (the
+ * pcqsdhc of rtx_profile_eval) on each line's window, summed in fp64. DESIGN.md section 4.15.
+ *
+ * rtx_lines_set_ht: the HT columns of n_sets broadener column sets. set_h[n_sets] = column set of each (0 air, 1 self,
+ * 2 + j extra set j of rtx_lines_set_broadeners, which must have been called first); cols_h[n_sets][RTX_HT_COLS] = host
+ * pointers to columns of n_lines doubles in the row order of rtx_lines_create, NULL = absent, in this order:
+ *   slots 6 b + 0 .. 6 b + 5 for TrefHT bucket b = 0, 1, 2, 3 (50, 150, 296, 700 K):
+ *       gamma_HT_0_<sp>_<Tref>, n_HT_<sp>_<Tref>, gamma_HT_2_<sp>_<Tref>, delta_HT_0_<sp>_<Tref>, deltap_HT_<sp>_<Tref>,
+ *       delta_HT_2_<sp>_<Tref>;
+ *   slots 24, 25, 26: nu_HT_<sp>, kappa_HT_<sp>, eta_HT_<sp>.
+ * An absent column and a column of zeros behave the same (the reference's try / except, :10505-10637). Replaces the table's
+ * previous HT sets; n_sets = 0 drops them. Allocates device memory and synchronises.
+ *
+ * rtx_ht_create: an object for tables of n_lines lines, up to max_states states and axes of up to max_points points. It
+ * holds no device memory until the first rtx_ht_prep with work to do (which allocates, hence synchronises, once).
+ *
+ * rtx_ht_prep: per (line, state), fp64. X_h[nx]: the axis, host, finite and non-decreasing (repeats allowed, nx = 1
+ * allowed), copied to the device. T_h, p_atm_h, qratio_h, weight_h, mass_h, n_dil, dil_h, frac_h, omega_wing, omega_wing_hw,
+ * intensity_threshold, scale: as rtx_line_prep_mix (frac_h[n_dil][n_species][n_states]). For each line
+ *   S(T) = sw qratio ch(T) / ch(296 K); weight = 0 or S < intensity_threshold drops the line;
+ *   TrefHT = 50 / 150 / 296 / 700 K for T in [0,100) / [100,200) / [200,400) / otherwise (:10394-10398);
+ *   per diluent, in the caller's order (a set may repeat): each parameter from its HT column of that bucket, or from the
+ *   Voigt-style column of the set where the HT value is 0 (self n = 0 and an absent n: n_air; Gamma2: SD * gamma);
+ *   Gamma0 from the Tref of the n lookup, Shift0 and NuVC from the Tref of the deltap lookup; Gamma2, Shift2 times p;
+ *   Eta = sum EtaDB abun (Gamma0T + i Shift0T) / (Gamma0 + i Shift0);
+ *   window [bisect_right(X, nu - W), bisect_right(X, nu + W)), W = max(omega_wing, omega_wing_hw Gamma0, omega_wing_hw GammaD).
+ * rtx_ht_sum: out[k][i] = sum over lines, in line order, of weight S Re PROFILE_HT at X[i] inside the line's window;
+ * out_f64[n_states][ld] and / or out_f32 = (float)(sum * scale). One workgroup per 256 points of a state; a point's bits
+ * do not depend on the rest of the axis or on the other states.
+ * rtx_ht_params: state `state` of the last prologue into DEVICE buffers (any may be NULL): params[n_lines][10] in
+ * rtx_profile_eval's layout, strength[n_lines] = weight S (0: dropped), window[n_lines][2] = lo, hi.
+ * Errors (before any device work): a required pointer NULL, a negative count, more states or points than the object was
+ * created for, ld < n, a column set that does not exist, an axis that is not sorted. n_lines = 0 or nx = 0 succeeds without
+ * a kernel launch (rtx_ht_sum on a table without lines writes zeros). Asynchronous on `stream` otherwise. */
+#define RTX_HT_COLS 27
+typedef struct rtx_ht rtx_ht;
+int rtx_lines_set_ht(rtx_lines* lines, int n_sets, const int32_t* set_h, const double* const* cols_h);
+int rtx_ht_create(int64_t n_lines, int max_states, int64_t max_points, rtx_ht** out);
+int rtx_ht_free(rtx_ht* ht);
+int rtx_ht_prep(rtx_ht* ht, const rtx_lines* lines, const double* X_h, int64_t nx, int n_states, const double* T_h,
+                const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h, int n_dil,
+                const int32_t* dil_h, const double* frac_h, double omega_wing, double omega_wing_hw,
+                double intensity_threshold, double scale, void* stream);
+int rtx_ht_sum(const rtx_ht* ht, int n_states, float* out_f32, double* out_f64, int64_t ld, void* stream);
+int rtx_ht_params(const rtx_ht* ht, int state, double* params, double* strength, int32_t* window, void* stream);
+
 /* ---- post-processing of TUD products: smooth / reduceResolution ---------------------
  * Replaces radiative_transfer.py:1266-1324 (smooth: reflect-padded window convolution) and :1327-1350
  * (reduceResolution: symmetrised smoothing + scipy cubic interp1d onto a coarser axis).

@@ -78,6 +78,12 @@ PROTOTYPES = {
     "rtx_profile_eval": (_i32, [_i32, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
     "rtx_profile_sum": (_i32, [_i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "rtx_cpf_eval": (_i32, [_i32, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "rtx_lines_set_ht": (_i32, [_vp, _i32, _vp, _vp]),
+    "rtx_ht_create": (_i32, [_i64, _i32, _i64, C.POINTER(_vp)]),
+    "rtx_ht_free": (_i32, [_vp]),
+    "rtx_ht_prep": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _vp]),
+    "rtx_ht_sum": (_i32, [_vp, _i32, _vp, _vp, _i64, _vp]),
+    "rtx_ht_params": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp]),
     "rtx_fir_tile_points": (_i32, []),
     "rtx_fir_chunk_taps": (_i32, []),
     "rtx_brightness_temperature": (_i32, [_vp, _i64, _vp, _i64, _i32, _dbl, _vp, _vp]),

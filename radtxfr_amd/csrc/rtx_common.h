@@ -134,6 +134,10 @@ struct rtx_lines {
   int n_extra = 0;
   DevBuf<double> x_gamma, x_n, x_delta, x_deltap, x_sd;
   std::vector<double> x_gmax, x_nlo, x_nhi;  // host, [n_extra]: |gamma| maximum and n range of each set (hot-tile bound)
+  // Hartmann-Tran columns (rtx_lines_set_ht): the columns given, [n_cols][n], and per column set (0 air, 1 self, 2 + j) the
+  // device pointers of its RTX_HT_COLS slots, [2 + RTX_MAX_BROADENERS][RTX_HT_COLS] (NULL: absent); empty = no HT column
+  DevBuf<double> ht_data;
+  DevBuf<const double*> ht_ptr;
 };
 
 // ---- hot tiles ---------------------------------------------------------------------------------------

@@ -124,6 +124,20 @@ def _is_broadener_column(k):
     return isinstance(k, str) and any(k.startswith(f) and k[len(f):] not in ("", "air", "self") for f in BROADENER_FIELDS)
 
 
+# Hartmann-Tran columns (misc/hapi.py:10505-10637): per broadener <sp> and TrefHT, then the three without a temperature
+HT_TREFS = (50, 150, 296, 700)
+HT_FIELDS = ("gamma_HT_0_", "n_HT_", "gamma_HT_2_", "delta_HT_0_", "deltap_HT_", "delta_HT_2_")
+HT_PREFIXES = ("gamma_HT_", "n_HT_", "delta_HT_", "deltap_HT_", "nu_HT_", "kappa_HT_", "eta_HT_")
+
+
+def ht_column_names(sp):
+    """The 27 Hartmann-Tran column names of broadener `sp` (lower-cased, as the reference builds them) in the slot order
+    of rtx_lines_set_ht (include/radtxfr_hip.h)."""
+    sp = str(sp).lower()
+    names = ["%s%s_%d" % (f, sp, t) for t in HT_TREFS for f in HT_FIELDS]
+    return names + ["nu_HT_" + sp, "kappa_HT_" + sp, "eta_HT_" + sp]
+
+
 class LineTable:
     """Device-resident HITRAN-format line table, sorted by nu (include/radtxfr_hip.h: rtx_lines).
     `columns` is the column dict of the reference's table type: LOCAL_TABLE_CACHE[name]['data']
@@ -178,6 +192,52 @@ class LineTable:
         self._order = order
         self._xsrc = {k: v for k, v in columns.items() if _is_broadener_column(k)}
         self._xcols, self._xsig = {}, {}
+        # Hartmann-Tran columns (rtx_lines_set_ht), uploaded on demand by ht_sets(): the source columns (caller's row order)
+        # and the uploaded ones {sp: {slot: sorted column}} with their fingerprints
+        self._htsrc = {k: v for k, v in columns.items() if isinstance(k, str) and k.startswith(HT_PREFIXES)}
+        self._htcols, self._htsig = {}, {}
+
+    def ht_stale(self, sigs):
+        """The broadeners of {sp: fingerprint of its HT columns} (empty: it has none) that this table holds differently."""
+        return [sp for sp, sig in sigs.items() if (sp in self._htcols) != bool(sig) or (sig and self._htsig.get(sp) != sig)]
+
+    def ht_sets(self, names, columns=None, sigs=None):
+        """broadener_sets(names) for the Hartmann-Tran sum (rtx_ht_prep), with the HT columns of every name on the device
+        (rtx_lines_set_ht). A broadener that has HT columns but no Voigt-style one gets a column set of its own (gamma = 0,
+        n = n_air), so that its HT columns have a set to belong to. `columns` / `sigs`: as for broadener_sets, for the HT
+        columns."""
+        src = self._htsrc if columns is None else columns
+        names = [str(n).lower() for n in names]
+        changed = False
+        for sp in dict.fromkeys(names):
+            sig = None if sigs is None else sigs.get(sp)
+            if sp in self._htcols and (sigs is None or self._htsig.get(sp) == sig):
+                continue
+            cols = {j: np.ascontiguousarray(np.asarray(src[c], dtype=np.float64)[:self._order.size][self._order])
+                    for j, c in enumerate(ht_column_names(sp)) if c in src}
+            if cols:
+                self._htcols[sp], self._htsig[sp] = cols, sig
+                changed = True
+            elif sp in self._htcols:
+                del self._htcols[sp]
+                self._htsig.pop(sp, None)
+                changed = True
+        before = list(self._xcols)
+        sets = self.broadener_sets(names)
+        if changed and list(self._xcols) == before:  # (a new extra set has uploaded them already: _upload_broadeners)
+            self._upload_ht()
+        return sets
+
+    def _upload_ht(self):
+        order = list(self._xcols)
+        sps = [sp for sp in self._htcols if sp in ("air", "self") or sp in order]
+        set_h = np.ascontiguousarray([0 if sp == "air" else 1 if sp == "self" else 2 + order.index(sp) for sp in sps], dtype=np.int32)
+        ptrs = (C.c_void_p * max(27 * len(sps), 1))()
+        for s_, sp in enumerate(sps):
+            for j, col in self._htcols[sp].items():
+                ptrs[27 * s_ + j] = col.ctypes.data
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().rtx_lines_set_ht(self._h, len(sps), set_h.ctypes.data_as(C.c_void_p), ptrs))
 
     def broadeners_stale(self, sigs):
         """The broadeners of {sp: fingerprint} whose columns this table does not hold, or holds with another fingerprint."""
@@ -199,7 +259,7 @@ class LineTable:
             if sp in self._xcols and (sigs is None or self._xsig.get(sp) == sig):
                 continue
             cols = {f: src[f + sp] for f in BROADENER_FIELDS if f + sp in src}
-            if cols:
+            if cols or sp in self._htcols:  # (HT columns alone: a set of fallbacks to hold them)
                 self._xcols[sp] = {f: np.ascontiguousarray(np.asarray(v, dtype=np.float64)[:self._order.size][self._order])
                                    for f, v in cols.items()}
                 self._xsig[sp] = sig
@@ -230,6 +290,8 @@ class LineTable:
             arr.append(a)
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().rtx_lines_set_broadeners(self._h, n_x, *arr))
+        if self._htcols:  # the HT sets go by column-set index: attach them again
+            self._upload_ht()
 
     def host_columns(self):
         """The uploaded columns as a host column dict (sorted by nu): what another device's copy is built from."""
@@ -237,6 +299,9 @@ class LineTable:
         cols.update(self._sd)
         for sp, c in self._xcols.items():
             cols.update({f + sp: v for f, v in c.items()})
+        for sp, c in self._htcols.items():
+            names = ht_column_names(sp)
+            cols.update({names[j]: v for j, v in c.items()})
         cols["molec_id"], cols["local_iso_id"] = self.molec_id, self.local_iso_id
         return cols
 
@@ -273,6 +338,9 @@ class LineTable:
         for p in self._plans.values():
             p.close()
         self._plans = {}
+        hp = self.__dict__.pop("_ht_plan", None)
+        if hp is not None:
+            hp.close()
         if self._h:
             with torch.cuda.device(self.device):
                 _lib.load().rtx_lines_free(self._h)
@@ -448,6 +516,86 @@ def voigt_sum_axis(lines, X, T, p_atm, weight, out_f32=None, out_f64=None, dil_a
     _check_outputs(nL, nx, out_f32, out_f64)
     _lib.check(lib.rtx_voigt_sum_axis(plan._h, nL, _ptr(out_f32), _ptr(out_f64), nx, st))
     return out_f32, out_f64
+
+
+class HtPlan:
+    """Per-(line, state) records and the axis of the Hartmann-Tran sum (rtx_ht)."""
+
+    def __init__(self, lines, max_states, max_points):
+        self.max_states, self.max_points = int(max_states), int(max_points)
+        self._h = C.c_void_p(0)
+        _lib.check(_lib.load().rtx_ht_create(lines.n, self.max_states, self.max_points, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            _lib.load().rtx_ht_free(self._h)
+            self._h = C.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _ht_prologue(lines, X, T, p_atm, weight, diluent, omega_wing, omega_wing_hw, intensity_threshold, scale, partitionFunction,
+                 qratio, mass):
+    """rtx_ht_prep on the table's cached HtPlan (grown on demand): (plan, n_states, nx)."""
+    lib = _lib.load()
+    X = np.ascontiguousarray(np.asarray(X, dtype=np.float64).ravel())
+    if not np.all(np.isfinite(X)):
+        raise ValueError("ht_sum: the axis has non-finite points")
+    if X.size > 1 and np.any(X[1:] < X[:-1]):
+        raise ValueError("ht_sum: the axis must be non-decreasing (np.sort it)")
+    nL, env = _prologue_inputs(lines, T, p_atm, weight, partitionFunction, qratio, mass)
+    lines.ht_sets(list(diluent))  # the HT columns of every diluent on the device, before the set indices are taken
+    n_dil, idx, frac = diluent_mix(lines, diluent, nL)
+    plan = lines.__dict__.get("_ht_plan")
+    if plan is None or plan.max_states < nL or plan.max_points < X.size:
+        if plan is not None:
+            plan.close()
+        plan = lines.__dict__["_ht_plan"] = HtPlan(lines, max(nL, plan.max_states if plan else 1),
+                                                   max(X.size, plan.max_points if plan else 1))
+    _lib.check(lib.rtx_ht_prep(plan._h, lines._h, X.ctypes.data_as(C.c_void_p), X.size, nL, *(e[1] for e in env), n_dil, idx[1],
+                               frac[1], float(omega_wing), float(omega_wing_hw), float(intensity_threshold), float(scale),
+                               _stream_ptr()))
+    return plan, nL, X.size
+
+
+def ht_sum(lines, X, T, p_atm, weight, diluent, out_f32=None, out_f64=None, omega_wing=0.0, omega_wing_hw=50.0,
+           intensity_threshold=0.0, scale=1.0, partitionFunction=None, qratio=None, mass=None):
+    """Hartmann-Tran line-sum for n_states homogeneous states (T, p_atm: lists) on the explicit axis X (host, finite,
+    non-decreasing; any spacing, repeats, a single point): rtx_ht_prep + rtx_ht_sum, the per-line block and the sum of
+    absorptionCoefficient_HT (misc/hapi.py:10474-10651) in fp64. diluent = {broadener: fraction}, a fraction a scalar or
+    [nS][nL], in the caller's order; each name reads its HT columns of the state's TrefHT bucket (the states of one call may
+    fall into different buckets) and falls back to its Voigt-style columns. weight[nS][nL] multiplies S(T).
+    Outputs are [nL][X.size] device tensors; without any, a float64 one is made. Returns (out_f32, out_f64)."""
+    plan, nL, nx = _ht_prologue(lines, X, T, p_atm, weight, diluent, omega_wing, omega_wing_hw, intensity_threshold, scale,
+                                partitionFunction, qratio, mass)
+    if out_f32 is None and out_f64 is None:
+        out_f64 = torch.zeros((nL, nx), dtype=torch.float64, device=device())
+    _check_outputs(nL, nx, out_f32, out_f64)
+    if nx == 0:  # an empty tensor has no pointer to pass
+        return out_f32, out_f64
+    _lib.check(_lib.load().rtx_ht_sum(plan._h, nL, _ptr(out_f32), _ptr(out_f64), nx, _stream_ptr()))
+    return out_f32, out_f64
+
+
+def ht_line_params(lines, X, T, p_atm, weight, diluent, omega_wing=0.0, omega_wing_hw=50.0, intensity_threshold=0.0,
+                   partitionFunction=None, qratio=None, mass=None):
+    """What ht_sum's prologue makes of every line, without the sum (rtx_ht_prep + rtx_ht_params): a dict of
+    params [nL][n_lines][10] (device, fp64, rtx_profile_eval's layout: sg0, GamD, Gam0, Gam2, Shift0, Shift2, anuVC, Re eta,
+    Im eta, 0), strength [nL][n_lines] (host; weight * S(T), 0 for a dropped line) and window [nL][n_lines][2] (host, int32:
+    the axis indices [lo, hi) the line is summed over)."""
+    plan, nL, nx = _ht_prologue(lines, X, T, p_atm, weight, diluent, omega_wing, omega_wing_hw, intensity_threshold, 1.0,
+                                partitionFunction, qratio, mass)
+    dev = device()
+    params = torch.zeros((nL, lines.n, 10), dtype=torch.float64, device=dev)
+    strength = torch.zeros((nL, lines.n), dtype=torch.float64, device=dev)
+    window = torch.zeros((nL, lines.n, 2), dtype=torch.int32, device=dev)
+    for k in range(nL):
+        _lib.check(_lib.load().rtx_ht_params(plan._h, k, _ptr(params[k]), _ptr(strength[k]), _ptr(window[k]), _stream_ptr()))
+    return {"params": params, "strength": strength.cpu().numpy(), "window": window.cpu().numpy()}
 
 
 _MF_COLUMNS = {}

@@ -11,6 +11,8 @@ meaning and error behaviour:
     transmittanceSpectrum, absorptionSpectrum, radianceSpectrum   misc/hapi.py:11582-11680   -> rtx_hapi_spectrum
     SLIT_* (host NumPy), convolveSpectrum, convolveSpectrumSame, convolveSpectrumFull
                                   misc/hapi.py:11742-11900   -> rtx_fir_same (fp64 direct FIR)
+    absorptionCoefficient_HT      misc/hapi.py:10302-10653   -> rtx_ht_prep + rtx_ht_sum on tables with *_HT_* columns
+                                  (opt-in: VARIABLES["HT_COLUMNS"]; otherwise the SDVoigt path)
     pcqsdhc, PROFILE_HT(P), PROFILE_SDRAUTIAN, PROFILE_RAUTIAN, PROFILE_SDVOIGT, PROFILE_VOIGT, PROFILE_LORENTZ,
     PROFILE_DOPPLER, hum1_wei, cpf3   misc/hapi.py:9645-10160   -> rtx_profile_eval / rtx_cpf_eval (fp64, complex)
     profile_lines                 (not in the reference) many lines at once, or their weighted sum -> rtx_profile_sum
@@ -129,6 +131,51 @@ def _device_table(names, diluents=()):
         stale = tbl.broadeners_stale(sigs)
         if stale:
             tbl.broadener_sets(stale, columns=_broadener_columns(names, stale), sigs=sigs)
+    return tbl
+
+
+def _tref_ht(T):
+    """TrefHT of absorptionCoefficient_HT for temperature T (misc/hapi.py:10394-10398): 50 / 150 / 296 / 700 K for T in
+    [0, 100) / [100, 200) / [200, 400) / [400, inf); the reference's loop leaves its last value, 700, for any other T."""
+    TrefHT = None
+    for TRange, TrefHT in zip(((0, 100), (100, 200), (200, 400), (400, float("inf"))), (50., 150., 296., 700.)):
+        if T >= TRange[0] and T < TRange[1]:
+            break
+    return TrefHT
+
+
+def _ht_columns_read(species, T):
+    """The *_HT_* columns absorptionCoefficient_HT reads for the lower-cased Diluent keys `species` at temperature T: the
+    six of the TrefHT bucket and nu_HT / kappa_HT / eta_HT of each (misc/hapi.py:10505-10637)."""
+    b = (50., 150., 296., 700.).index(_tref_ht(T))
+    read = []
+    for sp in dict.fromkeys(species):
+        names = engine.ht_column_names(sp)
+        read += names[6 * b:6 * b + 6] + names[24:]
+    return read
+
+
+def _device_table_ht(tbl, names, species):
+    """The Hartmann-Tran columns of `species` (lower case) on the device table, fingerprinted like the broadener columns:
+    a changed column is uploaded again. A table that lacks a column another one has contributes zeros (= absent)."""
+    species = list(dict.fromkeys(species))
+    sigs = {}
+    for sp in species:
+        sig = []
+        for n in names:
+            d, nrow = LOCAL_TABLE_CACHE[n]["data"], LOCAL_TABLE_CACHE[n]["header"]["number_of_rows"]
+            sig.extend((n, c, _column_signature(d[c], nrow)) for c in engine.ht_column_names(sp) if c in d)
+        sigs[sp] = tuple(sig)
+    stale = tbl.ht_stale(sigs)
+    cols = {}
+    for sp in stale:
+        for c in engine.ht_column_names(sp):
+            if any(c in LOCAL_TABLE_CACHE[n]["data"] for n in names):
+                cols[c] = np.concatenate([
+                    np.asarray(LOCAL_TABLE_CACHE[n]["data"][c], dtype=np.float64)[:LOCAL_TABLE_CACHE[n]["header"]["number_of_rows"]]
+                    if c in LOCAL_TABLE_CACHE[n]["data"] else np.zeros(LOCAL_TABLE_CACHE[n]["header"]["number_of_rows"])
+                    for n in names])
+    tbl.ht_sets(species, columns=cols, sigs=sigs)
     return tbl
 
 
@@ -258,11 +305,14 @@ def _absorption_coefficient(profile, Components, SourceTables, partitionFunction
     if set(keys) - {"air", "self"} or len(set(keys)) != len(keys):
         mix = {k: float(v) for k, v in Diluent.items()}
         tbl = _device_table(SourceTables, keys)
+    if profile == 4:  # Hartmann-Tran columns: every key's Voigt-style and HT columns, always on the explicit axis
+        mix = {k: float(v) for k, v in Diluent.items()}
+        tbl = _device_table_ht(_device_table(SourceTables, keys), SourceTables, keys)
     dil = {k.lower(): float(v) for k, v in Diluent.items()}
     # a uniform grid (what Grid.from_axis recognises) takes the grid line-sum; any other sorted grid -- non-uniform,
     # repeated points, fewer than 2 points -- the explicit-axis one (rtx_line_prep_axis + rtx_voigt_sum_axis)
     grid = None
-    if Omegas.size >= 2:
+    if Omegas.size >= 2 and profile != 4:
         try:
             grid = engine.Grid.from_axis(Omegas)
         except NotImplementedError:
@@ -280,6 +330,11 @@ def _absorption_coefficient(profile, Components, SourceTables, partitionFunction
     scale = 2.0 ** (-math.floor(math.log2(smax))) if smax > 0 and math.isfinite(smax) else 1.0
     if tbl.n == 0 or Omegas.size == 0:
         Xsect = np.zeros(Omegas.size)
+    elif profile == 4:
+        out = torch.empty((1, Omegas.size), dtype=torch.float64, device=engine.device())
+        engine.ht_sum(tbl, Omegas, [T], [p], w, mix, out_f64=out, omega_wing=OmegaWing, omega_wing_hw=OmegaWingHW,
+                      intensity_threshold=IntensityThreshold, scale=scale, partitionFunction=partitionFunction)
+        Xsect = out[0].cpu().numpy()
     elif grid is not None:
         out = torch.empty((1, grid.n), dtype=torch.float64, device=engine.device())
         engine.voigt_sum(tbl, grid, [T], [p], w, out_f64=out, dil_air=dil.get("air", 0.0), dil_self=dil.get("self", 0.0),
@@ -391,13 +446,38 @@ def absorptionCoefficient_HT(Components=None, SourceTables=None, partitionFuncti
                              GammaL="gamma_air", HITRAN_units=True, LineShift=True, File=None, Format=None,
                              OmegaGrid=None, WavenumberRange=None, WavenumberStep=None, WavenumberWing=None,
                              WavenumberWingHW=None, WavenumberGrid=None, Diluent={}, EnvDependences=None):
-    """Hartmann-Tran profile, signature of misc/hapi.py:10302-10653 -- for tables WITHOUT Hartmann-Tran columns.
+    """Hartmann-Tran profile, signature of misc/hapi.py:10302-10653 -- by default for tables WITHOUT Hartmann-Tran columns.
 
     The reference looks each parameter up under its HT name first (gamma_HT_0_<species>_<Tref>, n_HT_..., delta_HT_...,
     nu_HT_..., eta_HT_..., :10505-10640) and falls back to the Voigt-style columns; a table that has none of the HT
     names gives nuVC = eta = 0, Gamma2 from SD_<species> (:10590-10599), i.e. exactly absorptionCoefficient_SDVoigt
-    (checked against the reference in the build container: 6e-16). That case is evaluated here; non-zero HT columns raise
-    NotImplementedError (velocity-changing collisions and correlation are not implemented on the GPU)."""
+    (checked against the reference in the build container: 6e-16). That case is evaluated here; by default non-zero HT
+    columns raise NotImplementedError.
+
+    VARIABLES["HT_COLUMNS"] = True: a call that would read a non-zero *_HT_* column (one of its lower-cased Diluent keys,
+    in the TrefHT bucket of its temperature) takes the Hartmann-Tran line-sum -- the reference's lookups and fallbacks per
+    line, PROFILE_HT on each window, fp64, on any sorted grid (rtx_ht_prep + rtx_ht_sum). S(T) and
+    Q(Tref) are always taken from 296 K, which is what the reference computes for a one-row table; its whole-table call
+    agrees with that only for T in [200, 400). Any other call goes to the SDVoigt path as before."""
+    if VARIABLES.get("HT_COLUMNS"):
+        # the columns this call would read: the *_HT_* ones of its lower-cased Diluent keys in its TrefHT bucket. One of them
+        # non-zero: the Hartmann-Tran sum (rtx_ht_prep + rtx_ht_sum); none: the reference's own result is the SDVoigt one
+        keys = [k.lower() for k in Diluent] if Diluent else [{"gamma_air": "air", "gamma_self": "self"}.get(GammaL.lower())]
+        T = (Environment or {"T": 296.0})["T"]
+        read = _ht_columns_read([k for k in keys if k], T)
+        ht = False
+        for name in listOfTuples(SourceTables if SourceTables is not None else "__BUFFER__"):
+            data = LOCAL_TABLE_CACHE.get(name, {}).get("data", {})
+            ht = ht or any(c in data and np.any(np.asarray(data[c], dtype=np.float64) != 0.0) for c in read)
+        if not ht:
+            return absorptionCoefficient_SDVoigt(Components, SourceTables, partitionFunction, Environment, OmegaRange, OmegaStep,
+                                                 OmegaWing, IntensityThreshold, OmegaWingHW, GammaL, HITRAN_units, LineShift, File,
+                                                 Format, OmegaGrid, WavenumberRange, WavenumberStep, WavenumberWing,
+                                                 WavenumberWingHW, WavenumberGrid, Diluent, EnvDependences)
+        return _absorption_coefficient(4, Components, SourceTables, partitionFunction, Environment, OmegaRange, OmegaStep, OmegaWing,
+                                       IntensityThreshold, OmegaWingHW, GammaL, HITRAN_units, LineShift, File, Format, OmegaGrid,
+                                       WavenumberRange, WavenumberStep, WavenumberWing, WavenumberWingHW, WavenumberGrid, Diluent,
+                                       EnvDependences)
     for name in listOfTuples(SourceTables):
         if name is None or name not in LOCAL_TABLE_CACHE:
             continue
@@ -417,7 +497,9 @@ absorptionCoefficient = absorptionCoefficient_HT  # the reference's profile sele
 # ---- loading line files: what the reference's scripts do before the line-sum ---------------------------------------
 # (misc/RT_gen_AbsXS_files.py:12: db_begin(folder)). hapi's SQL-like layer (select / sort / group, misc/hapi.py:433-3216)
 # is out of scope; rows are filtered with NumPy on LOCAL_TABLE_CACHE[name]['data'] instead.
-VARIABLES = {"BACKEND_DATABASE_NAME": "data"}
+# HT_COLUMNS (not in the reference): absorptionCoefficient_HT on tables with non-zero Hartmann-Tran columns. False: such a
+# table raises NotImplementedError; True: it takes the Hartmann-Tran line-sum
+VARIABLES = {"BACKEND_DATABASE_NAME": "data", "HT_COLUMNS": False}
 
 
 def db_begin(db=None):
