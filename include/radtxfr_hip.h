@@ -258,6 +258,28 @@ int rtx_tud_jacobian(const float* OD, const float* OD_plus, const float* OD_minu
                      int n_layers, const double* T_h, int n_alt, const uint8_t* mask_h, double mu, int n_down,
                      int n_angle, int return_od, const int32_t* layers_h, int n_lay, int t_pos, float* J,
                      int64_t ld_J, void* stream);
+/* Adjoint of rtx_tud_jacobian (reverse mode): for n_vec cotangent vectors G on the output rows,
+ *   out[v][w][k] = sum over the shard's grid->n points nu and over the rows of G[v][row][nu] * J[w][k][row][nu],
+ * J exactly what rtx_tud_jacobian defines for the same arguments (all up to t_pos as there); J is never stored.
+ *   G_tau, G_Lu: [n_vec][n_alt][ld_G], G_Ld: [n_vec][ld_G], float32 device arrays; each may be NULL, not all three;
+ *   out: [n_vec][n_wrt][n_lay] float64 on the device, wrt slots as J's (T at t_pos).
+ * A NULL row group is not evaluated: without G_Ld the downwelling stream sweeps are not run, without G_Lu and G_Ld no
+ * Planck function is evaluated, without G_tau `tau` is not read (and may be NULL). With n_angle = 1 the Ld rows of J are
+ * NaN: out is NaN exactly when G_Ld is given. Structural zeros of J give exact 0.0.
+ * Arithmetic: the row factors are the float32 numbers rtx_tud_jacobian multiplies; every product with G and dOD/dx and
+ * every sum is float64. The sum has a fixed order (64 lanes by an xor butterfly, the 4 waves of a 256-point workgroup in
+ * order, the workgroups in order; no atomics): two calls give the same bits, and out[v][w][k] does not depend on the
+ * other layers or vectors of the call, on their order or on how a caller blocks them.
+ * n_vec is at most rtx_tud_vjp_max_vectors() (4) per call: the vectors of a call share the column sweeps, and the
+ * per-workgroup staging in LDS grows with them; callers loop over groups of vectors. Scratch (one float64 per workgroup
+ * and output element) is owned by the library per (device, stream). Refused: everything rtx_tud_jacobian refuses,
+ * n_vec outside [1, max], ld_G < grid->n, out == NULL, all G NULL. grid->n == 0 writes zeros. */
+int rtx_tud_vjp(const float* OD, const float* OD_plus, const float* OD_minus, int64_t ld, double fd_step,
+                const float* K, int n_spec, const float* tau, int64_t ld_tau, const rtx_grid* grid, int n_layers,
+                const double* T_h, int n_alt, const uint8_t* mask_h, double mu, int n_down, int n_angle,
+                int return_od, const int32_t* layers_h, int n_lay, int t_pos, const float* G_tau,
+                const float* G_Lu, const float* G_Ld, int64_t ld_G, int n_vec, double* out, void* stream);
+int rtx_tud_vjp_max_vectors(void);
 /* The tabulated G of rtx_tud, for host-side checks (no device involved): rtx_tud_gtable_size() doubles, rows of
  * {interval centre, a0 .. a6}: G(S) = sum a_k (S - centre)^k on the row's interval; intervals: 16 per binade of
  * S + 2^-6 below S = 16 (row = (bits(float(S) + 2^-6) >> 19) - (bits(2^-6) >> 19)), width 1/2 from there to S = 48.

@@ -1332,19 +1332,11 @@ def jacobian_species_columns(MF_ID, wrt):
     return cols
 
 
-def tud_jacobian(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=False,
-                 wrt=("T",), layers=None, fd_step_T=0.5, block_bytes=JAC_BLOCK_BYTES, on_block=None, mark=None):
-    """compute_TUD's outputs and their Jacobian with respect to layer temperatures and mixing ratios, on the device.
-
-    wrt: "T" and/or molecule ids of MF_ID (T, when present, is computed first whatever its position: J's wrt axis follows
-    `wrt`). layers: layer indices (default all), in output order. Returns (tau, Lu, Ld, OD, J): float32 device tensors,
-    tau / Lu [nAlt][n], Ld [n], OD [nL][n] bit-identical to TudRunner / compute_TUD, J [n_wrt][n_layers][2 nAlt + 1][n]
-    (rows: tau per altitude, L-up per altitude, Ld). With on_block(k0, k1, J_block) J is not kept: each block of layers
-    (at most block_bytes of float32) is handed to the callback as soon as it is written, and None is returned for J.
-    mark(name): called after each stage is enqueued ("base", "T", "species", "jacobian"), for timing.
-
-    dOD/dT is the central difference of two line-sums at T -+ fd_step_T with every line's window at T (voigt_sum_window);
-    dOD/dMF of a species is the line-sum of that species alone at 1 ppmv (OD is linear in each mixing ratio)."""
+def _jacobian_stages(what, lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt, layers,
+                     fd_step_T, mark):
+    """The stages tud_jacobian and tud_vjp share: argument checks, the base state (exactly what compute_TUD runs), the
+    line-sums at T -+ fd_step_T with every line's window at T (skipped without "T" in wrt) and the line-sum of each species
+    of wrt at 1 ppmv. Returns (T, Z, layers, t_pos, tau, Lu, Ld, OD, ODp, ODm, K)."""
     T = np.ascontiguousarray(np.atleast_1d(np.asarray(T, dtype=np.float64)))
     Z = np.atleast_1d(np.asarray(Z, dtype=np.float64))
     nL = T.size
@@ -1363,7 +1355,7 @@ def tud_jacobian(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes=(500,)
         raise ValueError("fd_step_T must be > 0")
     th = np.asarray(theta_r, dtype=np.float64).ravel()
     if th.size != 1:
-        raise NotImplementedError("tud_jacobian: one slant path (theta_r) per call")
+        raise NotImplementedError("%s: one slant path (theta_r) per call" % what)
     jacobian_limits(nL, np.array([Altitudes]).size, N_angle, len(spec_cols))
     dev = device()
     # base state: exactly what compute_TUD runs
@@ -1393,8 +1385,27 @@ def tud_jacobian(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes=(500,)
             voigt_sum(lines, grid, T, p_atm, w, out_f32=K[s])
     if mark:
         mark("species")
-    # J's wrt axis follows `wrt`: the kernel writes T's rows at t_pos and the species (K's order = their order in wrt) around it
+    # the wrt axis of the result follows `wrt`: T at t_pos and the species (K's order = their order in wrt) around it
     t_pos = wrt.index("T") if with_T else 0
+    return T, Z, layers, t_pos, tau, Lu, Ld, OD, ODp, ODm, K
+
+
+def tud_jacobian(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=False,
+                 wrt=("T",), layers=None, fd_step_T=0.5, block_bytes=JAC_BLOCK_BYTES, on_block=None, mark=None):
+    """compute_TUD's outputs and their Jacobian with respect to layer temperatures and mixing ratios, on the device.
+
+    wrt: "T" and/or molecule ids of MF_ID (T, when present, is computed first whatever its position: J's wrt axis follows
+    `wrt`). layers: layer indices (default all), in output order. Returns (tau, Lu, Ld, OD, J): float32 device tensors,
+    tau / Lu [nAlt][n], Ld [n], OD [nL][n] bit-identical to TudRunner / compute_TUD, J [n_wrt][n_layers][2 nAlt + 1][n]
+    (rows: tau per altitude, L-up per altitude, Ld). With on_block(k0, k1, J_block) J is not kept: each block of layers
+    (at most block_bytes of float32) is handed to the callback as soon as it is written, and None is returned for J.
+    mark(name): called after each stage is enqueued ("base", "T", "species", "jacobian"), for timing.
+
+    dOD/dT is the central difference of two line-sums at T -+ fd_step_T with every line's window at T (voigt_sum_window);
+    dOD/dMF of a species is the line-sum of that species alone at 1 ppmv (OD is linear in each mixing ratio)."""
+    T, Z, layers, t_pos, tau, Lu, Ld, OD, ODp, ODm, K = _jacobian_stages(
+        "tud_jacobian", lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt, layers,
+        fd_step_T, mark)
     J = tud_jacobian_from_od(OD, ODp, ODm, fd_step_T, K, tau, grid, T, Z, Altitudes=Altitudes, theta_r=theta_r,
                              N_angle=N_angle, returnOD=returnOD, layers=layers, t_pos=t_pos, block_bytes=block_bytes,
                              on_block=on_block, mark=mark)
@@ -1458,3 +1469,116 @@ def tud_jacobian_from_od(OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z, A
         else:
             J[:, k0:k1] = blk
     return J
+
+
+# ---- adjoint of the TUD Jacobian (rtx_tud_vjp): J^T g for cotangents g on the output rows, J never stored ----------------
+VJP_VEC_GROUP = None  # cotangent vectors per rtx_tud_vjp call; None: the library's maximum (rtx_tud_vjp_max_vectors)
+
+
+def _cotangent(G, lead, n, what):
+    """A cotangent as float32 device rows [n_vec] + lead + [>= n] with unit stride along the wavenumbers, or None."""
+    if G is None:
+        return None
+    if not torch.is_tensor(G):
+        G = torch.as_tensor(np.asarray(G, dtype=np.float32))
+    G = G.to(device=device(), dtype=torch.float32)
+    if G.dim() == len(lead) + 1:
+        G = G[None]
+    if G.dim() != len(lead) + 2 or tuple(G.shape[1:-1]) != tuple(lead) or G.shape[-1] < n or G.shape[0] < 1:
+        raise ValueError("%s: shape %r, expected [n_vec]%r[>= %d] (the vector axis may be left out)"
+                         % (what, tuple(G.shape), list(lead), n))
+    if G.stride(-1) != 1:
+        G = G.contiguous()
+    return G
+
+
+def tud_vjp_from_od(OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z, G_tau=None, G_Lu=None, G_Ld=None, Altitudes=(500,),
+                    theta_r=0.0, N_angle=30, returnOD=False, layers=None, t_pos=0):
+    """rtx_tud_vjp on given float32 device columns (as tud_jacobian_from_od takes them): the adjoint of that Jacobian,
+    grad[v][w][k] = sum over wavenumbers and rows of G[v][row] J[w][k][row], float64 on the device, [n_vec][n_wrt][n_layers],
+    without J being stored. G_tau, G_Lu: [n_vec][nAlt][>= n], G_Ld: [n_vec][>= n], float32 (NumPy or torch), the vector
+    axis optional; a group left None is not evaluated (no G_Ld: no downwelling sweeps; no G_tau: tau may be None). The
+    vectors go to the library VJP_VEC_GROUP at a time; the grouping, like the choice and order of layers, changes no bit."""
+    lib = _lib.load()
+    T = np.ascontiguousarray(np.atleast_1d(np.asarray(T, dtype=np.float64)))
+    Z = np.atleast_1d(np.asarray(Z, dtype=np.float64))
+    nL = T.size
+    layers = np.arange(nL, dtype=np.int32) if layers is None else np.ascontiguousarray(np.asarray(layers, dtype=np.int32).ravel())
+    Z_s = np.array([Altitudes], dtype=np.float64).ravel()
+    mask = np.ascontiguousarray(np.stack([(Z <= zs) for zs in Z_s]).astype(np.uint8))
+    n_down = int(mask[-1].sum())  # quirk 3: the LAST altitude's layer count (:353, :370)
+    th = np.asarray(theta_r, dtype=np.float64).ravel()
+    if th.size != 1:
+        raise NotImplementedError("tud_vjp: one slant path (theta_r) per call")
+    mu = float(1.0 / np.cos(th[0]))
+    with_T = OD_plus is not None
+    n_spec = 0 if K is None else int(K.shape[0])
+    n = grid.n
+    nA = Z_s.size
+    ld = OD.stride(0)
+    assert OD.dtype == torch.float32 and OD.is_cuda and OD.dim() == 2 and OD.shape[0] == nL and OD.shape[1] >= n
+    assert OD.stride(1) == 1
+    for t in (OD_plus, OD_minus):
+        assert t is None or (t.dtype == torch.float32 and t.shape == OD.shape and t.stride() == OD.stride())
+    if K is not None:
+        assert K.dtype == torch.float32 and K.dim() == 3 and K.shape[1] == nL and K.shape[2] >= n
+        assert K.stride(2) == 1 and K.stride(1) == ld and K.stride(0) == nL * ld
+    if tau is not None:
+        assert tau.dtype == torch.float32 and tau.dim() == 2 and tau.shape[0] == nA and tau.shape[1] >= n
+        assert tau.stride(1) == 1
+    G_tau = _cotangent(G_tau, (nA,), n, "G_tau")
+    G_Lu = _cotangent(G_Lu, (nA,), n, "G_Lu")
+    G_Ld = _cotangent(G_Ld, (), n, "G_Ld")
+    given = [g for g in (G_tau, G_Lu, G_Ld) if g is not None]
+    if not given:
+        raise ValueError("tud_vjp: no cotangent (G_tau, G_Lu and G_Ld are all None)")
+    n_vec = int(given[0].shape[0])
+    if any(int(g.shape[0]) != n_vec for g in given):
+        raise ValueError("tud_vjp: the cotangents disagree on the number of vectors: %r" % [int(g.shape[0]) for g in given])
+    # the library takes one leading dimension for the three groups: rows that already share one (padded or not) go as
+    # they are, anything else is packed to ld_G = n
+
+    def row_ld(g):
+        ld_g = g.stride(-2) if g.shape[-2] > 1 else max(n, g.shape[-1])
+        dense = ld_g >= n and g.stride(-1) == 1 and (g.dim() == 2 or g.shape[1] == 1 or g.stride(1) == ld_g)
+        outer = ld_g * (g.shape[1] if g.dim() == 3 else 1)
+        return ld_g if dense and (g.shape[0] == 1 or g.stride(0) == outer) else None
+
+    lds = set(row_ld(g) for g in given)
+    if len(lds) == 1 and None not in lds:
+        ld_G = lds.pop()
+    else:
+        ld_G = n
+        G_tau, G_Lu, G_Ld = (None if g is None else g[..., :n].contiguous() for g in (G_tau, G_Lu, G_Ld))
+    vstride = {id(g): ld_G * (g.shape[1] if g.dim() == 3 else 1) for g in (G_tau, G_Lu, G_Ld) if g is not None}
+    n_wrt = int(with_T) + n_spec
+    out = torch.empty((n_vec, n_wrt, layers.size), dtype=torch.float64, device=OD.device)
+    group = int(VJP_VEC_GROUP or lib.rtx_tud_vjp_max_vectors())
+    T_h, T_p = _h(T)
+    st = _stream_ptr()
+    for v0 in range(0, n_vec, group):
+        v1 = min(v0 + group, n_vec)
+        part = lambda g: None if g is None else C.c_void_p(g.data_ptr() + 4 * v0 * vstride[id(g)])
+        _lib.check(lib.rtx_tud_vjp(
+            _ptr(OD), _ptr(OD_plus), _ptr(OD_minus), ld, float(fd_step_T), _ptr(K), n_spec, _ptr(tau),
+            tau.stride(0) if tau is not None else 0, grid.byref(), nL, T_p, nA, mask.ctypes.data_as(C.c_void_p), mu, n_down,
+            int(N_angle), int(bool(returnOD)), layers.ctypes.data_as(C.c_void_p), layers.size, t_pos, part(G_tau), part(G_Lu),
+            part(G_Ld), ld_G, v1 - v0, _ptr(out[v0:v1]), st))
+    return out
+
+
+def tud_vjp(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, G_tau=None, G_Lu=None, G_Ld=None, Altitudes=(500,), theta_r=0.0,
+            N_angle=30, returnOD=False, wrt=("T",), layers=None, fd_step_T=0.5, mark=None):
+    """compute_TUD's outputs and the gradient of a scalar cost with respect to layer temperatures and mixing ratios, given
+    the cost's cotangents on the outputs: tud_jacobian's stages (the same base state, T -+ fd_step_T line-sums and species
+    line-sums) followed by rtx_tud_vjp instead of rtx_tud_jacobian. wrt, layers, fd_step_T as tud_jacobian; G_* as
+    tud_vjp_from_od. Returns (tau, Lu, Ld, OD, grad), grad float64 [n_vec][n_wrt][n_layers] on the device, its wrt axis
+    following `wrt`. mark(name): after each stage ("base", "T", "species", "vjp")."""
+    T, Z, layers, t_pos, tau, Lu, Ld, OD, ODp, ODm, K = _jacobian_stages(
+        "tud_vjp", lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt, layers,
+        fd_step_T, mark)
+    grad = tud_vjp_from_od(OD, ODp, ODm, fd_step_T, K, tau, grid, T, Z, G_tau=G_tau, G_Lu=G_Lu, G_Ld=G_Ld, Altitudes=Altitudes,
+                           theta_r=theta_r, N_angle=N_angle, returnOD=returnOD, layers=layers, t_pos=t_pos)
+    if mark:
+        mark("vjp")
+    return tau, Lu, Ld, OD, grad

@@ -562,8 +562,9 @@ def compute_TUD_batch(Xmin, Xmax, atmospheres, opts=options, reduce=None, device
 JACOBIAN_HOST_LIMIT = 4 << 30  # bytes of full-resolution float64 results compute_TUD_jacobian returns without reduce=
 
 
-def _jacobian_args(Xmin, Xmax, o, wrt, layers, reduce, fd_step_T):
-    """compute_TUD_jacobian's argument checks, all on the host (no device is touched): (wrt, layers, nX)."""
+def _jacobian_args(Xmin, Xmax, o, wrt, layers, reduce, fd_step_T, host_result=True):
+    """compute_TUD_jacobian's argument checks, all on the host (no device is touched): (wrt, layers, nX). host_result=False:
+    the caller returns no J (compute_TUD_vjp), so the size of a full-resolution J on the host is not a concern."""
     if o.get("broadening") is not None:
         raise NotImplementedError("compute_TUD_jacobian: broadening=%r is not supported (with self-broadening dOD/dMF is no "
                                   "longer OD per ppmv); use broadening=None" % (o.get("broadening"),))
@@ -596,7 +597,9 @@ def _jacobian_args(Xmin, Xmax, o, wrt, layers, reduce, fd_step_T):
     nX = int(np.ceil((Xmax - Xmin) / o["DVOUT"]))  # make_spectral_axis's count
     nZ = np.array([o["Altitudes"]]).size
     engine.jacobian_limits(nL, nZ, int(o["N_angle"]), sum(1 for w in wrt if not isinstance(w, str)))
-    if reduce is None:
+    if not host_result:
+        pass
+    elif reduce is None:
         nbytes = 8 * nX * ((2 * nZ + 1) * (1 + len(wrt) * lay.size))
         if nbytes > JACOBIAN_HOST_LIMIT:
             raise ValueError("compute_TUD_jacobian: the full-resolution result would take %.1f GiB of host memory (limit %.0f GiB): "
@@ -688,6 +691,100 @@ def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, redu
         else:
             J[w] = (np.ascontiguousarray(h[:, :nZ, :]), np.ascontiguousarray(h[:, nZ:2 * nZ, :]), np.ascontiguousarray(h[:, 2 * nZ, :]))
     return X_out, tau_, Lu_, Ld_, J
+
+
+_COTANGENT_KEYS = ("tau", "La", "Ld")
+
+
+def _vjp_cotangents(cotangents, nX, nZ):
+    """compute_TUD_vjp's cotangents, checked on the host: ({key: array or tensor [n_vec][nZ][nX] / [n_vec][nX]}, n_vec or
+    None without a vector axis). Each entry is laid out like the compute_TUD output it belongs to, [nX][nZ] (or [nX] with
+    one altitude) and [nX], with an optional trailing vector axis."""
+    if not isinstance(cotangents, dict) or not cotangents:
+        raise ValueError("compute_TUD_vjp: cotangents must be a non-empty dict with keys among %r" % (_COTANGENT_KEYS,))
+    out, n_vecs = {}, set()
+    for key, g in cotangents.items():
+        if key not in _COTANGENT_KEYS:
+            raise ValueError("compute_TUD_vjp: unknown cotangent key %r (expected keys among %r)" % (key, _COTANGENT_KEYS))
+        if g is None:
+            continue
+        if not _is_torch(g):
+            g = np.asarray(g)
+        base = (nX,) if key == "Ld" else (nX, nZ)
+        shape = tuple(g.shape)
+        if key != "Ld" and nZ == 1 and shape[:2] != base and shape[:1] == (nX,) and len(shape) <= 2:
+            g = g[:, None]  # one altitude: compute_TUD squeezes the altitude axis
+            shape = tuple(g.shape)
+        if shape == base:
+            g, nv = g[..., None], None
+        elif len(shape) == len(base) + 1 and shape[:-1] == base and shape[-1] >= 1:
+            nv = shape[-1]
+        else:
+            raise ValueError("compute_TUD_vjp: cotangent %r has shape %r, expected %r plus an optional trailing vector axis"
+                             % (key, shape, base))
+        n_vecs.add(nv)
+        # [nX]([nZ])[n_vec] -> [n_vec]([nZ])[nX]
+        out[key] = g.permute(*range(g.dim() - 1, -1, -1)) if _is_torch(g) else np.transpose(g)
+    if not out:
+        raise ValueError("compute_TUD_vjp: every cotangent is None")
+    if len(n_vecs) != 1:
+        raise ValueError("compute_TUD_vjp: the cotangents disagree on the vector axis: %r" % sorted(n_vecs, key=str))
+    return out, n_vecs.pop()
+
+
+def compute_TUD_vjp(Xmin, Xmax, cotangents, opts=options, wrt=("T",), layers=None, fd_step_T=0.5, **kwargs):
+    """compute_TUD and the gradient of a scalar cost of its outputs with respect to layer temperatures and mixing ratios:
+    the transpose of compute_TUD_jacobian's J applied to the cost's cotangents, without J ever being stored (reverse mode;
+    DESIGN 4.16).
+
+    cotangents: dict with any of "tau", "La", "Ld": d cost / d output, each laid out like the compute_TUD output of that
+    name ([nX][nAlt] -- [nX] with one altitude -- and [nX]), NumPy arrays or torch tensors (a device tensor is used where
+    it is). An optional trailing axis of length n_vec carries several cotangent vectors at once (they share all the work
+    up to the contraction). A key left out is a row group that is not evaluated: without "Ld" the downwelling stream
+    sweeps, the expensive part of the Jacobian, are not run.
+    kwargs, wrt, layers, fd_step_T: as compute_TUD_jacobian, with the same definition of every derivative. Returns
+    (X, tau, La, Ld, grad): X, tau, La, Ld bit-identical to compute_TUD with the same kwargs; grad {wrt entry: float64
+    [n_layers]}, or [n_layers][n_vec] when a vector axis is given:
+      grad[w][k(, v)] = sum over X and over the outputs with a cotangent of cotangent[(X, row, v)] * J[w][row][X, k],
+    in units of cost per K ("T") and per ppmv (a molecule id). Products with the cotangents and all sums are float64 in a
+    fixed order: the same call gives the same bits, whatever other layers or vectors it carries.
+    There is no reduce=: a cost defined on a reduced axis or on sensor bands, Y = R X_native with R linear
+    (reduceResolution, a slit function, band responses), has the native-grid cotangent R^T (d cost / d Y); the caller
+    applies that transpose and passes the result here.
+    Arguments are checked before any device work. NotImplementedError: more than one theta_r, broadening=, xs_lut=."""
+    o = dict(opts)
+    o.update(kwargs)
+    if "reduce" in o:
+        raise NotImplementedError("compute_TUD_vjp: reduce= is not offered: map the cotangent to the native grid with the "
+                                  "transpose of the reduction and pass that")
+    if o.get("xs_lut") is not None:
+        raise NotImplementedError("compute_TUD_vjp: xs_lut is not supported (dOD/dT is a difference of line-sums with fixed "
+                                  "windows); use line_table=")
+    try:
+        wrt, lay, nX = _jacobian_args(Xmin, Xmax, o, wrt, layers, None, fd_step_T, host_result=False)
+    except (ValueError, NotImplementedError) as e:
+        raise type(e)(str(e).replace("compute_TUD_jacobian", "compute_TUD_vjp")) from None
+    Z_s = np.array([o["Altitudes"]]).ravel()
+    nZ = Z_s.size
+    G, n_vec = _vjp_cotangents(cotangents, nX, nZ)
+    Z = np.asarray(o["Zs"], dtype=np.float64)
+    T = np.asarray(o["Ts"], dtype=np.float64)
+    X_ = _cached_axis(Xmin, Xmax, o["DVOUT"])
+    assert X_.size == nX
+    grid = engine.Grid(Xmin, Xmax, X_.size)
+    tbl = _resolve_table(o.get("line_table"))
+    tau, Lu, Ld, _, grad = engine.tud_vjp(tbl, grid, Z, T, o["Ps"], o["PLs"], o["MFs_VAL"], o["MFs_ID"], G_tau=G.get("tau"),
+                                          G_Lu=G.get("La"), G_Ld=G.get("Ld"), Altitudes=Z_s,
+                                          theta_r=np.asarray(o["theta_r"], dtype=np.float64), N_angle=int(o["N_angle"]),
+                                          returnOD=bool(o["returnOD"]), wrt=wrt, layers=lay, fd_step_T=float(fd_step_T))
+    (tau_h, Lu_h, Ld_h), done = _rows_to_host_f64([tau, Lu, Ld[None, :]])
+    grad_h = grad.cpu().numpy()  # [n_vec][n_wrt][n_layers]
+    done.synchronize()
+    tau_, Lu_ = _tud_shapes(tau_h, Lu_h, nZ, 1)
+    out = {}
+    for w_i, w in enumerate(wrt):
+        out[w] = np.ascontiguousarray(grad_h[:, w_i, :].T) if n_vec is not None else grad_h[0, w_i, :].copy()
+    return X_, tau_, Lu_, Ld_h[0], out
 
 
 def compute_LWIR_apparent_radiance(X, emis, Ts, tau, La, Ld, dT=None, return_Ls=False):
