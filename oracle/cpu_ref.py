@@ -348,18 +348,30 @@ def weideman_coeffs(N=24):
 _W24, _L24 = weideman_coeffs(24)
 
 
-def hum1_wei(x, y):
+def _wide(dtype):
+    """(real type, complex type, pi, sqrt(ln 2)) of a dtype switch: float64 (the constants this module has always used) or
+    longdouble (the same formulas in extended precision; every table value is the float64 one, widened)."""
+    if np.dtype(dtype) == np.float64:
+        return np.float64, np.complex128, np.pi, np.sqrt(np.log(2.0))
+    if np.dtype(dtype) != np.dtype(np.longdouble):
+        raise ValueError("dtype must be np.float64 or np.longdouble")
+    L = np.longdouble
+    return L, np.clongdouble, 4 * np.arctan(L(1)), np.sqrt(np.log(L(2)))
+
+
+def hum1_wei(x, y, dtype=np.float64):
     """misc/hapi.py:9833-9844: Weideman-24 where |x|+y<15, else the 1-term asymptote."""
-    x = np.asarray(x, dtype=np.float64)
-    y = np.asarray(y, dtype=np.float64) + np.zeros_like(x)
+    F, _, pi, _ = _wide(dtype)
+    x = np.asarray(x, dtype=F)
+    y = np.asarray(y, dtype=F) + np.zeros_like(x)
     t = y - 1.0j * x
-    cerf = 1 / np.sqrt(np.pi) * t / (0.5 + t ** 2)
+    cerf = 1 / np.sqrt(pi) * t / (0.5 + t ** 2)
     mask = abs(x) + y < 15.0
     if np.any(mask):
         z = x[mask] + 1.0j * y[mask]
         Z = (_L24 + 1.0j * z) / (_L24 - 1.0j * z)
-        p = np.polyval(_W24, Z)
-        w = 2 * p / (_L24 - 1.0j * z) ** 2 + (1 / np.sqrt(np.pi)) / (_L24 - 1.0j * z)
+        p = np.polyval(_W24 if F is np.float64 else _W24.astype(F), Z)
+        w = 2 * p / (_L24 - 1.0j * z) ** 2 + (1 / np.sqrt(pi)) / (_L24 - 1.0j * z)
         np.place(cerf, mask, w)
     return cerf.real, cerf.imag
 
@@ -672,7 +684,8 @@ def linesum_records(tbl, grid, T, p, omega_wing=0.0, omega_wing_hw=50.0, Diluent
     """line_prep_kernel's geometry for one layer, per line of `tbl` in ascending-nu (stable) order -- the order of the
     device table: local i0 (nearest index to the shifted centre, clamped), window [lo, hi) (local, bisect_right of
     nu -+ W on the global axis, clamped to the shard; empty = 0, 0), zw, fp32 y, cte, sg0, the global gi0 before the
-    local clamp and whether W came from OmegaWing. grid = (xmin, xmax, n_total, offset, n)."""
+    local clamp and whether W came from OmegaWing; for sd_census also W, the unclamped global window glo / ghi, the sort
+    order and line_params' dict P of the sorted table. grid = (xmin, xmax, n_total, offset, n)."""
     xmin, xmax, n_total, offset, n = grid
     step = (xmax - xmin) / (n_total - 1)
     order = np.argsort(np.asarray(tbl["nu"], dtype=np.float64), kind="stable")
@@ -705,7 +718,8 @@ def linesum_records(tbl, grid, T, p, omega_wing=0.0, omega_wing_hw=50.0, Diluent
     i0 = np.clip(gi0 - offset, -100000000, n + 100000000)
     zw = np.where((y < 15.0) & live, np.minimum(np.ceil((15.0 - y) / (step * cte)) + 2.0, 4e7), 0).astype(np.int64)
     return {"i0": i0, "lo": lo, "hi": hi, "zw": zw, "y": y.astype(np.float32), "cte": cte, "sg0": sg0, "gi0": gi0,
-            "W_omega": omega_wing > Whw, "nu": nu, "step": step}
+            "W_omega": omega_wing > Whw, "nu": nu, "step": step, "W": W, "glo": bisect_right(nu - W), "ghi": bisect_right(nu + W),
+            "order": order, "P": P}
 
 
 def _band_row_labels(R, l, r, ia, grid, smally):
@@ -869,9 +883,10 @@ def reduceResolution(X, Y, dX, N=4, window="hanning", X_out=None):
 _CPF3_TT = np.array([0.5, 1.5, 2.5, 3.5, 4.5, 5.5, 6.5, 7.5, 8.5, 9.5, 10.5, 11.5, 12.5, 13.5, 14.5])
 
 
-def cpf3(X, Y):
+def cpf3(X, Y, dtype=np.float64):
     """misc/hapi.py:9645-9670: 15-term asymptotic series of w(z), z = X + iY."""
-    zm1 = 1.0 / (np.asarray(X, dtype=np.float64) + 1.0j * np.asarray(Y, dtype=np.float64))
+    F = _wide(dtype)[0]
+    zm1 = 1.0 / (np.asarray(X, dtype=F) + 1.0j * np.asarray(Y, dtype=F))
     zm2 = zm1 ** 2
     zsum = np.ones_like(zm1)
     zterm = np.ones_like(zm1)
@@ -882,60 +897,361 @@ def cpf3(X, Y):
     return zsum.real, zsum.imag
 
 
-def PROFILE_SDVOIGT(sg0, GamD, Gam0, Gam2, Shift0, Shift2, sg):
+# branch bits of PROFILE_SDVOIGT(..., branches=True): the predicates of pcqsdhc, per point
+SD_P1, SD_P2, SD_P3, SD_P4, SD_CPF3, SD_W24_1, SD_W24_2, SD_P3NEAR, SD_NEG1, SD_NEG2 = (1 << b for b in range(10))
+
+
+def PROFILE_SDVOIGT(sg0, GamD, Gam0, Gam2, Shift0, Shift2, sg, dtype=np.float64, branches=False):
     """misc/hapi.py:10117-10129 -> pcqsdhc (:9850-10024) with anuVC = eta = 0, for which the common part (:10022) is
-    LS = Aterm/pi. Real part only (what absorptionCoefficient_SDVoigt uses, :10897). CPF = hum1_wei (:9846)."""
-    sg = np.asarray(sg, dtype=np.float64)
-    cte = np.sqrt(np.log(2.0)) / GamD
-    rpi = np.sqrt(np.pi)
-    c0 = complex(Gam0, Shift0)
-    c2 = complex(Gam2, Shift2)
+    LS = Aterm/pi. Real part only (what absorptionCoefficient_SDVoigt uses, :10897). CPF = hum1_wei (:9846).
+    dtype np.longdouble: the same formulas, predicates and Weideman coefficients in extended precision (the parameters
+    and the grid are the float64 values). branches: also the int array of SD_* bits (PART, cpf3 shell, |x| + y < 15 of
+    the first / second argument, PART3's near form, a negative real part of the first / second argument)."""
+    F, CT, pi, sln2 = _wide(dtype)
+    sg = np.asarray(sg, dtype=F)
+    cte = sln2 / GamD
+    rpi = np.sqrt(pi)
+    if F is np.float64:
+        c0 = complex(Gam0, Shift0)
+        c2 = complex(Gam2, Shift2)
+    else:
+        c0 = CT(F(Gam0) + 1.0j * F(Shift0))
+        c2 = CT(F(Gam2) + 1.0j * F(Shift2))
+        Gam2, Shift2 = F(Gam2), F(Shift2)
     c0t = c0 - 1.5 * c2
     c2t = c2
-    cw = lambda x, y: (lambda r: r[0] + 1.0j * r[1])(hum1_wei(x, y))
+    cw = lambda x, y: (lambda r: r[0] + 1.0j * r[1])(hum1_wei(x, y, dtype))
+    code = np.zeros(sg.size, dtype=np.int64)
+    w24 = lambda Z: (np.abs(Z.imag) + Z.real < 15.0)
     if abs(c2t) == 0.0:  # PART1 (:9908-9915)
         Z1 = (1.0j * (sg0 - sg) + c0t) * cte
         A = rpi * cte * cw(-Z1.imag, Z1.real)
-        return (A / np.pi).real
+        code[:] = SD_P1 + SD_W24_1 * w24(Z1) + SD_NEG1 * (Z1.real < 0)
+        return ((A / pi).real, code) if branches else (A / pi).real
     X = (1.0j * (sg0 - sg) + c0t) / c2t
     Y = 1.0 / ((2.0 * cte * c2t)) ** 2
     csqrtY = (Gam2 - 1.0j * Shift2) / (2.0 * cte * (Gam2 ** 2 + Shift2 ** 2))
     p2 = np.abs(X) <= 3.0e-8 * abs(Y)
     p3 = (abs(Y) <= 1.0e-15 * np.abs(X)) & ~p2
     p4 = ~(p2 | p3)
-    A = np.zeros(sg.size, dtype=np.complex128)
+    A = np.zeros(sg.size, dtype=CT)
     if np.any(p4):  # PART4 (:9933-9971)
         Z1 = np.sqrt(X[p4] + Y) - csqrtY
         Z2 = Z1 + 2.0 * csqrtY
         x1, y1, x2, y2 = -Z1.imag, Z1.real, -Z2.imag, Z2.real
         S1, S2 = np.sqrt(x1 ** 2 + y1 ** 2), np.sqrt(x2 ** 2 + y2 ** 2)
         use3 = (np.abs(S1 - S2) <= 1.0) & (np.maximum(S1, S2) > 8.0) & (np.minimum(S1, S2) <= 8.0)
-        W1 = np.zeros(Z1.size, dtype=np.complex128)
-        W2 = np.zeros(Z1.size, dtype=np.complex128)
+        W1 = np.zeros(Z1.size, dtype=CT)
+        W2 = np.zeros(Z1.size, dtype=CT)
         if np.any(use3):
-            r1, r2 = cpf3(x1[use3], y1[use3]), cpf3(x2[use3], y2[use3])
+            r1, r2 = cpf3(x1[use3], y1[use3], dtype), cpf3(x2[use3], y2[use3], dtype)
             W1[use3], W2[use3] = r1[0] + 1.0j * r1[1], r2[0] + 1.0j * r2[1]
         if np.any(~use3):
             W1[~use3], W2[~use3] = cw(x1[~use3], y1[~use3]), cw(x2[~use3], y2[~use3])
         A[p4] = rpi * cte * (W1 - W2)
+        code[p4] = SD_P4 + SD_CPF3 * use3 + SD_W24_1 * w24(Z1) + SD_W24_2 * w24(Z2) + SD_NEG1 * (y1 < 0) + SD_NEG2 * (y2 < 0)
     if np.any(p2):  # PART2 (:9974-9989)
         Z1 = (1.0j * (sg0 - sg[p2]) + c0t) * cte
         Z2 = np.sqrt(X[p2] + Y) + csqrtY
         A[p2] = rpi * cte * (cw(-Z1.imag, Z1.real) - cw(-Z2.imag, Z2.real))
+        code[p2] = SD_P2 + SD_W24_1 * w24(Z1) + SD_W24_2 * w24(Z2) + SD_NEG1 * (Z1.real < 0) + SD_NEG2 * (Z2.real < 0)
     if np.any(p3):  # PART3 (:9992-10017; the reference indexes the full X at :10003, which only works when every point is PART3)
         Xt = X[p3]
         sq = np.sqrt(Xt)
         near = np.abs(sq) <= 4.0e3
-        At = np.zeros(Xt.size, dtype=np.complex128)
+        At = np.zeros(Xt.size, dtype=CT)
         if np.any(near):
             At[near] = (2.0 * rpi / c2t) * (1.0 / rpi - sq[near] * cw(-sq[near].imag, sq[near].real))
         if np.any(~near):
             At[~near] = (1.0 / c2t) * (1.0 / Xt[~near] - 1.5 / (Xt[~near] ** 2))
         A[p3] = At
-    return (A / np.pi).real
+        code[p3] = SD_P3 + SD_P3NEAR * near + SD_W24_1 * (near & w24(sq))
+    return ((A / pi).real, code) if branches else (A / pi).real
+
+
+def _gamma2(sub, r, p, Diluent=None, GammaL="gamma_air"):
+    """Gamma2 = sum_species abun * SD_species * p/pref * gamma_species(296 K) of row r (misc/hapi.py:10884-10890)."""
+    dil = Diluent if Diluent else ({"air": 1.0} if GammaL.lower() == "gamma_air" else {"self": 1.0})
+    Gamma2 = 0.0
+    for species, abun in dil.items():
+        sp = species.lower()
+        sd = float(sub["SD_" + sp][r]) if ("SD_" + sp) in sub else 0.0
+        g0db = float(sub["gamma_" + sp][r]) if ("gamma_" + sp) in sub else 0.0
+        Gamma2 += abun * (sd * p / PREF) * g0db
+    return Gamma2
+
+
+def sdvoigt_terms(tbl, T=296.0, p=1.0, OmegaGrid=None, OmegaWing=0.0, OmegaWingHW=50.0, IntensityThreshold=0.0,
+                  Diluent=None, dtype=np.float64):
+    """The line loop of absorptionCoefficient_SDVoigt (HITRAN units, every component at natural abundance) over the
+    (line, point) pairs inside the windows, in `dtype` (np.float64: the values of absorptionCoefficient_SDVoigt, bit for
+    bit; np.longdouble: the same loop in extended precision). Returns {"xs": the sum, "den": sum_l |S_l profile_l|,
+    "lines": [(table row, lo, hi, branch bits of PROFILE_SDVOIGT on Omegas[lo:hi])]}."""
+    F = _wide(dtype)[0]
+    Omegas = np.sort(np.asarray(OmegaGrid, dtype=np.float64))
+    xs, den = np.zeros(Omegas.size, dtype=F), np.zeros(Omegas.size, dtype=F)
+    P = line_params(tbl, T, p, Diluent=Diluent)
+    nu = np.asarray(tbl["nu"], dtype=np.float64)
+    abun = _tables()["abun"]
+    glist = Omegas.tolist()
+    sg = Omegas.astype(F)
+    lines = []
+    for r in range(nu.size):
+        S = P["S"][r]
+        if S < IntensityThreshold:
+            continue
+        GammaD, Gamma0, Shift0 = P["GammaD"][r], P["Gamma0"][r], P["Shift0"][r]
+        W = max(OmegaWing, OmegaWingHW * Gamma0, OmegaWingHW * GammaD)
+        lo = _bisect.bisect(glist, nu[r] - W)
+        hi = _bisect.bisect(glist, nu[r] + W)
+        if hi <= lo:
+            continue
+        ls, code = PROFILE_SDVOIGT(nu[r], GammaD, Gamma0, _gamma2(tbl, r, p, Diluent), Shift0, 0.0, sg[lo:hi], dtype=dtype,
+                                   branches=True)
+        nat = abun[(int(P["M"][r]), int(P["I"][r]))]
+        term = 1.0 / nat * nat * S * ls  # factor / NAT * ABUN * S * ls, as the float64 loop rounds it
+        xs[lo:hi] += term
+        den[lo:hi] += np.abs(term)
+        lines.append((r, lo, hi, code))
+    return {"xs": xs, "den": den, "lines": lines}
 
 
 def absorptionCoefficient_SDVoigt(tbl, **kw):
     """misc/hapi.py:10657-10904: the Voigt loop with PROFILE_SDVOIGT(nu, GammaD, Gamma0, Gamma2, Shift0, 0, grid) and
     Gamma2 = sum_species abun * SD_species * p/pref * gamma_species(296 K) (:10884-10890)."""
     return absorptionCoefficient_Voigt(tbl, _profile="sdvoigt", **kw)
+
+
+# ---- the speed-dependent line-sum's classification (rtx_sdvoigt.hip: sd_zones, sdvoigt_tile_kernel) -------------------
+# Restated so that host tests can show which path a configuration reaches; not an oracle of values.
+SD_TILE, SD_ROWS, SD_TDIST, SD_NEAR, SD_CHUNK = 1024, 16, 256, 2, 256
+
+
+def sd_zones(Gam0, Gam2, cte, step):
+    """sd_zones of rtx_sdvoigt.hip for one record: (a_lo, a_hi, b_lo, b_hi, far4) in cm^-1 from the shifted centre; empty
+    zones have lo = +inf. far4 (the PART4 far switch, 0 where d <= 0) is returned for the census, the kernel keeps it local."""
+    INF = np.inf
+    z = [INF, -INF, INF, -INF, 0.0]
+    m = 2.0 * step
+    if Gam2 == 0.0:
+        if not cte > 0.0:
+            return tuple(z)
+        z[2] = max(0.0, (15.0 - Gam0 * cte) / cte) + m
+        z[3] = INF
+        return tuple(z)
+    a, c2 = Gam0 - 1.5 * Gam2, Gam2
+    inv = 1.0 / Gam2
+    sY = 1.0 / (2.0 * cte * Gam2)
+    if not (c2 > 0.0) or not (a > 0.0) or not (sY > 0.0) or not (cte > 0.0):
+        return tuple(z)
+    Y = sY * sY
+    K = 15.0 + sY
+    K2 = K * K
+    R = a * inv + Y
+    d = 225.0 + 30.0 * sY - a * inv
+    far4 = c2 * ((d * (K2 + R)) / (2.0 * K2)) if d > 0.0 else 0.0
+    z[4] = far4
+    t2 = 3.0e-8 * Y * c2
+    dP2 = np.sqrt(t2 * t2 - a * a) if t2 > a else -1.0
+    t3 = 1.0e15 * Y * c2
+    if not t3 > a:
+        return tuple(z)
+    dP3 = np.sqrt(t3 * t3 - a * a)
+    z[2] = max(far4, dP2) + m
+    z[3] = dP3 - m
+    if dP2 > 0.0 and sY >= 8.0:
+        z[0] = max(0.0, (15.0 - a * cte) / cte) + m
+        z[1] = dP2 - m
+    return tuple(z)
+
+
+def _sd_branch_labels(code):
+    """sdvoigt_profile's branch per point from PROFILE_SDVOIGT's branch bits."""
+    w1, w2 = (code & SD_W24_1) != 0, (code & SD_W24_2) != 0
+    neg = (code & (SD_NEG1 | SD_NEG2)) != 0
+    p1, p2, p3, p4 = ((code & b) != 0 for b in (SD_P1, SD_P2, SD_P3, SD_P4))
+    cp = (code & SD_CPF3) != 0
+    near = (code & SD_P3NEAR) != 0
+    far = p4 & ~w1 & ~w2
+    rest = p4 & ~far & ~cp
+    return {"p1_w24": p1 & w1, "p1_asym": p1 & ~w1, "p2_real": p2 & ~neg, "p2_cplx": p2 & neg, "p3_near": p3 & near,
+            "p3_far": p3 & ~near, "p4_far": far, "p4_cpf3": p4 & cp & ~far, "p4_real_in_in": rest & ~neg & w1 & w2,
+            "p4_real_in_out": rest & ~neg & (w1 != w2), "p4_cplx": rest & neg}
+
+
+def sd_census(tbl, grid, T, p, omega_wing=0.0, omega_wing_hw=50.0, intensity_threshold=0.0, Diluent=None):
+    """Which paths of sdvoigt_tile_kernel one state reaches: a Counter of labels over (tile, candidate), (line, row) and
+    point-by-point (line, point). Candidates of a tile are the lines whose unshifted centre index lies within maxhw of
+    it; chunk c holds candidates [256 c, 256 c + 256) of that range. Built on linesum_records."""
+    from collections import Counter
+    xmin, xmax, n_total, offset, n = grid
+    C = Counter()
+    R = linesum_records(tbl, grid, float(T), float(p), omega_wing, omega_wing_hw, Diluent)
+    P, nu, step, order = R["P"], R["nu"], R["step"], R["order"]
+    sub = {k: np.asarray(v)[order] for k, v in tbl.items()}
+    nl = nu.size
+    Gam2 = np.array([_gamma2(sub, r, float(p), Diluent) for r in range(nl)])
+    dropped = P["S"] < intensity_threshold
+    lo, hi = np.where(dropped, 0, R["lo"]), np.where(dropped, 0, R["hi"])
+    i0 = R["i0"]
+    C["dropped"] = int(dropped.sum())
+    gic = np.clip(np.rint((nu - xmin) / step), -1e9, 1e9).astype(np.int64)
+    ic = np.clip(gic - offset, -100000000, n + 100000000)
+    hw_l = np.where(~dropped & (R["ghi"] > R["glo"]), np.minimum(np.ceil(R["W"] / step) + 2.0, 1e9), 0).astype(np.int64)
+    maxhw = int(hw_l.max()) if nl else 0
+    C["maxhw"] = maxhw
+
+    def gx(i):
+        return xmax if i == n_total - 1 else float(i) * step + xmin
+
+    zones = [sd_zones(P["Gamma0"][l], Gam2[l], R["cte"][l], step) for l in range(nl)]
+    delta = lambda l, pt: abs((nu[l] - gx(offset + pt)) + P["Shift0"][l])
+
+    def in_zone(z, d0, d1):
+        dmin, dmax = min(d0, d1), max(d0, d1)
+        if dmin >= z[0] and dmax <= z[1]:
+            return "a"
+        if dmin >= z[2] and dmax <= z[3]:
+            return "b"
+        return ""
+
+    X = np.array([gx(offset + i) for i in range(n)])
+    codes = {}
+
+    def line_codes(l):
+        if l not in codes:
+            codes[l] = PROFILE_SDVOIGT(nu[l], P["GammaD"][l], P["Gamma0"][l], Gam2[l], P["Shift0"][l], 0.0, X[lo[l]:hi[l]],
+                                       branches=True)[1]
+        return codes[l]
+
+    live = hi > lo
+    C["covers_grid"] = int(np.sum(live & (lo == 0) & (hi == n)))
+    C["narrow"] = int(np.sum(live & (hi - lo < 64) & (lo > 0) & (hi < n)))
+    for ia in range(0, n, SD_TILE):
+        ib = min(ia + SD_TILE, n)
+        first = int(np.searchsorted(ic, ia - maxhw, side="left"))
+        last = int(np.searchsorted(ic, ib - 1 + maxhw, side="right"))
+        nchunk = (last - first + SD_CHUNK - 1) // SD_CHUNK
+        C["chunks_max"] = max(C["chunks_max"], nchunk)
+        if nchunk >= 2:
+            C["second_chunk"] += 1
+        nT, nR = np.zeros(max(nchunk, 1), np.int64), np.zeros(max(nchunk, 1), np.int64)
+        for l in range(first, last):
+            ch = (l - first) // SD_CHUNK
+            if not (hi[l] > ia and lo[l] < ib):
+                C["cand_not_reached"] += 1
+                if hi[l] == lo[l]:
+                    C["cand_dropped" if dropped[l] else "cand_empty_window"] += 1
+                continue
+            z = zones[l]
+            nozones = z[0] == np.inf and z[2] == np.inf
+            covers = lo[l] <= ia and hi[l] >= ib
+            dl, dr = ia - i0[l], i0[l] - (ia + SD_TILE - 1)
+            if covers:
+                for d in (255, 256, 257):
+                    for side, dist in (("left", dl), ("right", dr)):
+                        if dist == d:
+                            C["tile_%s_%d" % (side, d)] += 1
+            for lab, ok in (("lo_eq_ia", lo[l] == ia and ia > 0), ("lo_eq_ia1", lo[l] == ia + 1), ("hi_eq_ib", hi[l] == ib and ib < n),
+                            ("hi_eq_ib1", hi[l] == ib - 1)):
+                if ok:
+                    C[lab] += 1
+            cls = ""
+            if covers and (dl >= SD_TDIST or dr >= SD_TDIST):
+                cls = in_zone(z, delta(l, ia), delta(l, ia + SD_TILE - 1))
+            if covers and (dl >= SD_TDIST or dr >= SD_TDIST) and z[4] > 0.0:
+                gap = int(np.ceil((min(delta(l, ia), delta(l, ia + SD_TILE - 1)) - z[4]) / step))
+                if gap in (1, 2, 3):  # points from the PART4 far switch to the tile's near end
+                    C["tile_switch_gap_%d_%s" % (gap, "tile" if cls else "rows")] += 1
+            if not nozones and z[4] == 0.0 and Gam2[l] != 0.0:
+                C["zone_b_all_far"] += 1
+            if cls:
+                C["tile_" + cls] += 1
+                nT[ch] += 1
+                if ib - ia < SD_TILE:
+                    C["ragged_tile"] += 1
+                for d in (255, 256, 257):
+                    if dl == d or dr == d:
+                        C["tile_level_at_%d" % d] += 1
+                continue
+            C["row_list"] += 1
+            nR[ch] += 1
+            if covers:
+                for d in (255, 256, 257):
+                    if dl == d or dr == d:
+                        C["row_list_at_%d" % d] += 1
+                if (dl >= SD_TDIST or dr >= SD_TDIST) and not nozones:
+                    C["row_list_switch_in_tile"] += 1
+            rc = (int(i0[l]) - ia) >> 6
+            if ia <= i0[l] < ib:
+                C["centre_row_%d" % rc] += 1
+            elif rc in (-2, -1, 16, 17):
+                C["rc_outside"] += 1
+                C["rc_outside_%d" % rc] += 1
+            for r in range(SD_ROWS):
+                pa = ia + 64 * r
+                if pa >= ib:
+                    break
+                pb = min(pa + 63, ib - 1)
+                if not (hi[l] > pa and lo[l] <= pb):
+                    continue
+                full = lo[l] <= pa and hi[l] > pb
+                near = abs(r - rc) <= SD_NEAR
+                if full and lo[l] == pa and pa > 0:
+                    C["row_starts_window"] += 1
+                if full and hi[l] == pb + 1 and hi[l] < n:
+                    C["row_ends_window"] += 1
+                if lo[l] <= pa and hi[l] == pb and not near:
+                    C["window_ends_at_row_last_point"] += 1  # hi > pb fails by one: an edge row, its last point outside
+                zc = ""
+                if full and not near:
+                    zc = in_zone(z, delta(l, pa), delta(l, pa + 63))
+                if zc:
+                    C["row_nodal_" + zc] += 1
+                    if abs(r - rc) == SD_NEAR + 1:
+                        C["row_nodal_3_from_centre"] += 1
+                    if pb < pa + 63:
+                        C["ragged_row"] += 1
+                    # distance (points, rounded up) from the PART4 far switch to the near end of a nodal row
+                    if zc == "b" and z[4] > 0.0:
+                        gap = int(np.ceil((min(delta(l, pa), delta(l, pa + 63)) - z[4]) / step))
+                        if gap in (2, 3):
+                            C["switch_gap_nodal_%d" % gap] += 1
+                    continue
+                if near:
+                    C["row_near"] += 1
+                    if abs(r - rc) == SD_NEAR:
+                        C["row_near_2_from_centre"] += 1
+                elif not full:
+                    C["row_edge"] += 1
+                elif nozones:
+                    C["row_nozones"] += 1
+                else:
+                    C["row_switch"] += 1
+                    if z[4] > 0.0:
+                        gap = int(np.ceil((min(delta(l, pa), delta(l, pa + 63)) - z[4]) / step))
+                        if gap in (1, 2):
+                            C["switch_gap_pointwise_%d" % gap] += 1
+                if not full:
+                    wl, wh = max(lo[l], pa), min(hi[l], pb + 1)
+                    if lo[l] > pa and hi[l] <= pb:
+                        C["both_edges_one_row"] += 1
+                    elif lo[l] > pa or hi[l] <= pb:
+                        C["edge_inside_row"] += 1
+                else:
+                    wl, wh = pa, pb + 1
+                cd = line_codes(l)[wl - lo[l]:wh - lo[l]]
+                for lab, sel in _sd_branch_labels(cd).items():
+                    if sel.any():
+                        C[lab] += int(sel.sum())
+        for c in range(nchunk):
+            if nT[c] > 0:
+                C["nT_%d" % nT[c]] += 1
+                C["nT_mod8_%d" % (nT[c] % 8)] += 1
+            if nT[c] > 0 and nR[c] > 0:
+                C["chunk_mixed"] += 1
+            if c > 0 and nT[c] == 0 and nT[:c].any():
+                C["chunk_no_tile_after_tile"] += 1
+        C["nT_max"] = max(C["nT_max"], int(nT.max()))
+        C["nR_max"] = max(C["nR_max"], int(nR.max()))
+    return C

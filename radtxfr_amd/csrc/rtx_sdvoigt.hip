@@ -72,7 +72,12 @@ __device__ __noinline__ double sdvoigt_profile(const LineRecSD q, const double s
     }
   } else {  // PART4 (:9933-9971)
     cd Z1 = csqrt_(cd{X.r + Y, X.i});
-    Z1.r -= csqrtY;
+    // sqrt(X + Y) - csqrtY loses 2 Y / |X| of its digits where |X| < Y (a small Gamma2: low pressure or a tiny SD; up to 1e-6 of
+    // the profile next to the PART2 threshold, random from point to point -- noise that the node levels would interpolate
+    // and the point-by-point rows would not). There the same number without the cancellation, X / (sqrt(X + Y) + csqrtY):
+    // a sum of two numbers with non-negative real parts. Elsewhere the reference's form.
+    if (aX2 < Y * Y) Z1 = cdiv(X, cd{Z1.r + csqrtY, Z1.i});
+    else Z1.r -= csqrtY;
     const cd Z2 = {Z1.r + 2.0 * csqrtY, Z1.i};
     const double x1 = -Z1.i, y1 = Z1.r, x2 = -Z2.i, y2 = Z2.r;
     if ((SD_ABLATE & 8) || (RTX_SD_FARWING && fabs(x1) + y1 >= 15.0 && fabs(x2) + y2 >= 15.0)) {

@@ -3,7 +3,9 @@
 absorptionCoefficient_SDVoigt, WavenumberStep 0.0025, WavenumberRange [400, 7100], WavenumberWingHW 350 -- 2.68 M points,
 wings of +-25 ... 38 cm^-1 at one atmosphere. Times afit_xs.cross_section_grid per (T, p) state for a synthetic table with the
 C3 line density (18 lines per cm^-1), without speed-dependence columns (fp32 Voigt line-sum) and with SD_air (fp64 path).
-    python tools/time_xs.py [--states 4]"""
+    python tools/time_xs.py [--states 4] [--p 1.0]
+--p: the states' pressure in atm (the caller's files are at ~1 atm; at low pressure |X| < Y over whole windows and
+sdvoigt_profile takes its cancellation-free Z1)."""
 import argparse, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -13,6 +15,7 @@ from radtxfr_amd import afit_xs, hapi, synthetic
 ap = argparse.ArgumentParser()
 ap.add_argument("--states", type=int, default=4)
 ap.add_argument("--lines", type=int, default=122000)
+ap.add_argument("--p", type=float, default=1.0)
 args = ap.parse_args()
 X = np.linspace(400.0, 7100.0, int(round(6700.0 / 0.0025)) + 1)
 tbl = dict(synthetic.synth_line_table(2016, args.lines, 360.0, 7140.0))
@@ -25,7 +28,7 @@ for label, sd in (("no SD columns (Voigt line-sum, fp32)", False), ("SD_air 0.05
     for rep in range(2):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        xs = afit_xs.cross_section_grid("xs", T, [1.0], X, WavenumberWingHW=350.0)
+        xs = afit_xs.cross_section_grid("xs", T, [args.p], X, WavenumberWingHW=350.0)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
     # the device part alone (prologue + line-sum of all states in one launch), HIP events
@@ -39,10 +42,10 @@ for label, sd in (("no SD columns (Voigt line-sum, fp32)", False), ("SD_air 0.05
     for rep in range(3):
         torch.cuda.synchronize()
         ev[0].record()
-        engine.voigt_sum(lines, grid, T, np.ones(args.states), w, out_f64=dev, omega_wing_hw=350.0, scale=2.0 ** 70, profile=3 if sd else 0)
+        engine.voigt_sum(lines, grid, T, np.full(args.states, args.p), w, out_f64=dev, omega_wing_hw=350.0, scale=2.0 ** 70, profile=3 if sd else 0)
         ev[1].record()
         torch.cuda.synchronize()
         ts.append(ev[0].elapsed_time(ev[1]) / args.states)
-    print(f"{label}: {X.size} points x {args.lines} lines, {args.states} states at 1 atm, HW 350: device {np.median(ts):.2f} ms per (T, p) state "
+    print(f"{label}: {X.size} points x {args.lines} lines, {args.states} states at {args.p:g} atm, HW 350: device {np.median(ts):.2f} ms per (T, p) state "
           f"(HIP events, prologue + line-sum); {dt * 1e3 / args.states:.1f} ms per state through afit_xs.cross_section_grid incl. the "
           f"device-to-host copy of {X.size * 8 / 1e6:.0f} MB per state; checksum {xs.sum():.6e}", flush=True)
