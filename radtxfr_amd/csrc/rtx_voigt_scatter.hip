@@ -125,8 +125,14 @@ __device__ __forceinline__ RowGeom row_geom(int qi0, int qlo, int qhi, int qzw, 
 // The record fields may live in SGPRs (scalar visit) or be wave-uniform VGPR values (nodal kernel).
 // MODE 0: the fp32 main pass (the band lanes of y < 1 lines are left to the fp64 pass); MODE 1: the fp64 pass, which adds
 // ONLY those lanes; MODE 2: both in one (the nodal kernel's instantiation for layers that hold y < 1 lines).
-template <int MODE>
-__device__ __forceinline__ void band_row(const ScArgs& a, const LineRec64* __restrict__ rec64, int slot, const LineRec& q, float u, int i,
+// The nodal kernel's drain calls it once per row of a run and has decided per entry what does not depend on the row:
+// CUT = false: the row lies wholly inside the window, no window mask; SER = 1 / 0: q.y >= 6 is known to hold / not to hold
+// (-1: tested here). `slot` is the record's index or a callable that fetches it: only the fp64 paths need it.
+__device__ __forceinline__ int band_slot(int slot) { return slot; }
+template <typename F>
+__device__ __forceinline__ int band_slot(const F& slot) { return slot(); }
+template <int MODE, bool CUT = true, int SER = -1, typename Slot>
+__device__ __forceinline__ void band_row(const ScArgs& a, const LineRec64* __restrict__ rec64, const Slot& slot, const LineRec& q, float u, int i,
                                          float zw_f, float ulo, float uhi, bool small_y, float& num, float& rden, bool& touched) {
   constexpr bool CORE64 = MODE == 1;
   float x;
@@ -138,7 +144,7 @@ __device__ __forceinline__ void band_row(const ScArgs& a, const LineRec64* __res
   if (MODE == 2 && small_y && !outer_row) {
     // Doppler-dominated line: the reference's switch and its Weideman value in fp64 on every lane of the row; lanes
     // outside |x| + y < 15 keep the far-wing value
-    const LineRec64 Q = rec64[slot];
+    const LineRec64 Q = rec64[band_slot(slot)];
     const double sg = grid_x(a.g, a.g.offset + (long long)i);
     const double x64 = -((Q.sg0 - sg) * Q.cte);
     if (fabs(x64) + Q.y < 15.0) {
@@ -152,7 +158,7 @@ __device__ __forceinline__ void band_row(const ScArgs& a, const LineRec64* __res
     bool wz = s32 < 15.0f;
     const bool near = fabsf(s32 - 15.0f) < 2e-3f;
     if (CORE64 || __ballot(near)) {
-      const LineRec64 Q = rec64[slot];
+      const LineRec64 Q = rec64[band_slot(slot)];
       const double sg = grid_x(a.g, a.g.offset + (long long)i);
       const double x64 = -((Q.sg0 - sg) * Q.cte);
       const bool wz64 = fabs(x64) + Q.y < 15.0;
@@ -167,7 +173,7 @@ __device__ __forceinline__ void band_row(const ScArgs& a, const LineRec64* __res
       // 6-term asymptotic series agrees with Weideman-24 to 6.4e-8. For 1 <= y < 6 the series needs |z| >= 8
       // (2e-8; the error relative to Re w grows as y -> 0): a row none of whose band lanes is closer than that --
       // the outer rows of a wide band -- takes the series too; Weideman itself only for the rows around the centre.
-      const bool series = RTX_SC_ASYM && (q.y >= 6.0f || __ballot(wz && fmaf(x, x, q.y * q.y) < 64.0f) == 0ull);
+      const bool series = RTX_SC_ASYM && (SER == 1 || (SER < 0 && q.y >= 6.0f) || __ballot(wz && fmaf(x, x, q.y * q.y) < 64.0f) == 0ull);
       if (wz) {
         if (MODE == 2 && outer_row) num = q.A * asymK_re<12>(x, q.y);
         else if (series) num = q.A * asym6_re(x, q.y);
@@ -183,7 +189,7 @@ __device__ __forceinline__ void band_row(const ScArgs& a, const LineRec64* __res
     // the other pass owns this line's band lanes; here only the far-wing lanes of the row count
     num = (CORE64 || in_band) ? 0.f : num;
   }
-  num = (u >= ulo && u < uhi) ? num : 0.f;
+  if (CUT) num = (u >= ulo && u < uhi) ? num : 0.f;
 }
 
 // One line, taken by one wave: point-by-point rows into the wave's LDS tile. NODAL: only the rows of the near
@@ -424,6 +430,15 @@ __global__ __launch_bounds__(256) void voigt_scatter_kernel(ScArgs a) {
 // not pull ub (7 pulls per group instead of 8, one FMA fewer; x moves by an ulp; 1.173e8 LDS instructions): 1.463 against 1.464 ms on its own
 // (three runs each, ranges overlapping) and 1.427-1.445 (median 1.436) against 1.432-1.456 (1.444) on top of the merged pass (nine runs
 // each): half a percent at best, and not every run of one below every run of the other.
+// Drain: packed entry masks, band rows as one run (profiles/linesum_runs_time.txt, six interleaved runs each; tools/count_runs.py is
+// the census): the band rows wholly inside the window without the window mask, in a loop for y >= 6 and one for 1 <= y < 6, the row
+// counted to the end of the run: 1.4176-1.4249 (median 1.4224) -> 1.3848-1.3985 (1.3930) ms, 3.618e8 -> 3.318e8 SALU and 9.593e8 ->
+// 9.273e8 VALU wave-instructions per launch, bit-identical results. The packed masks alone: 1.4118-1.4229, no gain of their own.
+// Measured and not taken: the near-zone rows as runs (start and length from two s_ff1, one LDS pointer and row offset per run, five
+// rows unrolled with immediate LDS offsets, one compare and branch per row): 1.4231-1.4480 against the parent's 1.4168-1.4317 without
+// the band loops, 1.3982-1.4092 against 1.3848-1.3985 with them -- 63 near-zone rows per tile and layer lie in 29 runs, three quarters
+// of them one or two rows long, and a run costs 13 scalar instructions where the bit-by-bit walk costs 6 per row; one band body with
+// the cut and the series choice as scalar arguments (the compiler makes selects of both: the window compares stay).
 #ifndef RTX_SC_WAVES
 #define RTX_SC_WAVES 6
 #endif
@@ -449,6 +464,9 @@ __global__ __launch_bounds__(256) void voigt_scatter_kernel(ScArgs a) {
 #ifndef RTX_SC_MERGE
 #define RTX_SC_MERGE 1  // full members go through the partial pass (row mask ALL_ROWS) when that saves a group of 8 in this wave's round
 #endif
+#ifndef RTX_SC_BAND_SPLIT
+#define RTX_SC_BAND_SPLIT 1  // band rows wholly inside the window (y >= 1) in loops of their own, without the window mask (drain)
+#endif
 #ifndef SC_ENT_CAP
 #define SC_ENT_CAP (SC_EDGE_LIST ? 16 : 32)  // point-by-point entries per wave (64 B each). Without the edge list, two waves per workgroup: 16 -> 2.02 ms, 24 -> 1.99, 32 -> 1.96, 48 -> 2.03
 #endif
@@ -456,7 +474,10 @@ __global__ __launch_bounds__(256) void voigt_scatter_kernel(ScArgs a) {
 // value right here (band_row MODE 2) instead of in a second pass over the layer.
 // part_out == nullptr: the tile of workgroup slot b, candidates = its (possibly cut) range, result stored to the optical
 // depths. part_out != nullptr: an extra part of a hot tile -- tile b_or_tile, candidates part_rng -- stored to part_out[0 .. TILE).
-template <bool SMALLY>
+// PARTS: the instantiation of the parts kernels. It sends every band row through band_row's full body: with the lighter loops of
+// the drain beside it, voigt_nodal_parts_kernel<false> -- the same 80 registers, and the part's range and output pointer to hold --
+// spills a register. Hot tiles are rare (none on C3), and the values are the same either way.
+template <bool SMALLY, bool PARTS = false>
 __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile, const int k, const int2 part_rng = make_int2(0, 0),
                                            float* __restrict__ part_out = nullptr) {
   constexpr int ROWS = RTX_SC_ROWS;
@@ -504,8 +525,12 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
   // the lanes' node offsets live in LDS, a copy per wave read back by the same wave once per round (s_nodsum is free until the
   // final stage): the kernel sits at its 80-register budget (6 waves per SIMD), and these two would be held for its whole length
   if (lane < 8) {
-    s_nodsum[wave][lane] = CHEB_OFF[lane];
-    if (TILE_LEVEL) s_nodsum[SC_NW + wave][lane] = TCHEB_OFF[lane];
+    // SMALLY loops over tile slots, and the compiler hoists &CHEB_OFF[lane] and &TCHEB_OFF[lane] out of that loop: at 127 of its
+    // 128 registers it then spills one of the pairs. An opaque index keeps the two address instructions inside the loop.
+    int lt = lane;
+    if (SMALLY) asm volatile("" : "+v"(lt));
+    s_nodsum[wave][lane] = CHEB_OFF[lt];
+    if (TILE_LEVEL) s_nodsum[SC_NW + wave][lane] = TCHEB_OFF[lt];
   }
   float tnod_a = 0.f, tnod_b = 0.f;
   int n_tile_members = 0;  // wave-uniform
@@ -519,6 +544,18 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
     return __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane << 2, __float_as_int(v)));
   };
 
+  // Drain. What is fixed per entry is decided once per entry, not once per row: the CU's one scalar unit executes the row loops'
+  // bookkeeping for every wave, and the kernel is bound by instruction issue.
+  //  - e[3] = { m_pp | m_ed << 16,  m_bd | m_cut << 16,  slot,  (y < 1) | (y >= 6) << 1 }: two v_readfirstlane per entry instead of
+  //    four. m_cut: the band rows cut by a window edge, or every band row of a y < 1 line. The flags are read by the entries that
+  //    have band rows (half of them on C3), the slot by the fp64 paths alone.
+  //  - band rows: m_bd is one run of rows. Those wholly inside the window (all of them on C3) take band_row without the window mask
+  //    (two compares, s_and, v_cndmask per row), in a loop of its own for y >= 6 -- the 6-term series on every row, no per-row test
+  //    of y or of |z| >= 8 -- and one for 1 <= y < 6; the rows of m_cut take the full body. The loops count the row up to the end of
+  //    the run (s_add, s_cmp, branch) instead of walking the mask bit by bit (s_ff1, s_add, s_and, s_cmp, branch).
+  // The abscissa is u0 + (float)(64 r) everywhere, as before: u itself need not be exact (a band may reach 4e7 points, the
+  // prologue's clamp of zw, and then |u| > 2^24), so stepping u from row to row would round differently there.
+  static_assert(ROWS <= 16, "an entry packs its row masks as 16-bit halves");
   auto drain = [&]() {
     for (int e = 0; e < n_ent; ++e) {
       const float4 e0 = ent[e][0], e1 = ent[e][1], e2 = ent[e][2], e3 = ent[e][3];
@@ -526,10 +563,10 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
       q.a = e0.x; q.c = e0.y; q.b1 = e0.z; q.b0 = e0.w;
       q.Ay = e1.x; q.Ay0 = e1.y; q.y = e1.z; q.A = e1.w;
       const float u0 = e2.x + lanef, ulo = e2.y, uhi = e2.z, zw_f = e2.w;
-      unsigned m_pp = (unsigned)__builtin_amdgcn_readfirstlane(__float_as_int(e3.x));
-      unsigned m_ed = (unsigned)__builtin_amdgcn_readfirstlane(__float_as_int(e3.w));
-      unsigned m_bd = (unsigned)__builtin_amdgcn_readfirstlane(__float_as_int(e3.y));
-      const int slot = __builtin_amdgcn_readfirstlane(__float_as_int(e3.z));
+      const unsigned w0 = (unsigned)__builtin_amdgcn_readfirstlane(__float_as_int(e3.x));
+      const unsigned w1 = (unsigned)__builtin_amdgcn_readfirstlane(__float_as_int(e3.y));
+      unsigned m_pp = w0 & 0xffffu, m_ed = w0 >> 16, m_bd = w1 & 0xffffu, m_cut = w1 >> 16;
+      auto slot = [&]() -> int { return __builtin_amdgcn_readfirstlane(__float_as_int(ent[e][3].z)); };
       STAMP(3);  // entry read
       if (RTX_SC_ABLATE & 4) m_pp = m_ed = 0u;
       // near-zone rows wholly inside the window: far-wing formula at every point, no lane mask
@@ -553,15 +590,41 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
         p[0] = fmaf(n0, d0, p[0]);
       }
       STAMP(4);  // point-by-point rows
-      if (RTX_SC_ABLATE & 1) m_bd = 0u;
-      const bool small_y = q.y < 1.0f;
-      while (m_bd) {
-        const int r = __builtin_ctz(m_bd);
-        m_bd &= m_bd - 1u;
-        float* p = acc + r * 64 + lane;
-        float num, rden;
-        band_row<SMALLY ? 2 : 0>(a, rec64, slot, q, u0 + (float)(64 * r), ia + 64 * r + lane, zw_f, ulo, uhi, small_y, num, rden, touched);
-        p[0] = fmaf(num, rden, p[0]);
+      if (RTX_SC_ABLATE & 1) m_bd = m_cut = 0u;
+      if (m_bd) {
+        const unsigned fl = (unsigned)__builtin_amdgcn_readfirstlane(__float_as_int(ent[e][3].w));
+        const bool small_y = fl & 1u, ser6 = fl & 2u;
+        if (PARTS || !RTX_SC_BAND_SPLIT) m_cut = m_bd;
+        const unsigned m_run = m_bd & ~m_cut;  // band rows wholly inside the window, y >= 1: one run, fp32 (MODE 0 and 2 agree)
+        if (m_run) {
+          // (the LDS pointer and the row offset stepped in registers across the body, instead of formed from the scalar row as
+          // here: one and two spilled registers in the 80-register instantiations)
+          int r = __builtin_ctz(m_run);
+          const int r_end = r + __popc(m_run);
+          if (ser6) {
+            for (; r < r_end; ++r) {
+              float* p = acc + r * 64 + lane;
+              float num, rden;
+              band_row<0, false, 1>(a, rec64, slot, q, u0 + (float)(64 * r), ia + 64 * r + lane, zw_f, ulo, uhi, false, num, rden, touched);
+              p[0] = fmaf(num, rden, p[0]);
+            }
+          } else {
+            for (; r < r_end; ++r) {
+              float* p = acc + r * 64 + lane;
+              float num, rden;
+              band_row<0, false, 0>(a, rec64, slot, q, u0 + (float)(64 * r), ia + 64 * r + lane, zw_f, ulo, uhi, false, num, rden, touched);
+              p[0] = fmaf(num, rden, p[0]);
+            }
+          }
+        }
+        while (m_cut) {  // the <= 2 band rows cut by a window edge, every band row of a y < 1 line
+          const int r = __builtin_ctz(m_cut);
+          m_cut &= m_cut - 1u;
+          float* p = acc + r * 64 + lane;
+          float num, rden;
+          band_row<SMALLY ? 2 : 0>(a, rec64, slot, q, u0 + (float)(64 * r), ia + 64 * r + lane, zw_f, ulo, uhi, small_y, num, rden, touched);
+          p[0] = fmaf(num, rden, p[0]);
+        }
       }
       STAMP(5);  // band rows
     }
@@ -662,7 +725,12 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
       }
     }
     {
-      bool emit = !(RTX_SC_ABLATE & 8) && !edge_only && (m_pp | m_ed | m_bd) != 0u;
+      // the packed row masks (drain): formed here, so that the emission loop holds two registers, not the masks they come from
+      // band rows that take band_row's full body: cut by a window edge, or of a y < 1 line (fp64 on its inner rows, or its
+      // band lanes left to the other pass: nothing for a lighter body to save)
+      const unsigned m_cut = f1.z < 1.0f ? m_bd : m_bd & ~m_in;
+      const unsigned w0 = m_pp | (m_ed << 16), w1 = m_bd | (m_cut << 16);
+      bool emit = !(RTX_SC_ABLATE & 8) && !edge_only && (w0 | w1) != 0u;
       unsigned long long eb = __ballot(emit);
       while (eb) {
         const int room = SC_ENT_CAP - n_ent;
@@ -672,7 +740,7 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
           d[0] = f0;
           d[1] = f1;
           d[2] = make_float4(ub, (float)(qlo - qi0), (float)(qhi - qi0), qzw > 0 ? (float)qzw : -1.0f);
-          d[3] = make_float4(__int_as_float((int)m_pp), __int_as_float((int)m_bd), __int_as_float(slot), __int_as_float((int)m_ed));
+          d[3] = make_float4(__int_as_float((int)w0), __int_as_float((int)w1), __int_as_float(slot), __int_as_float((f1.z < 1.0f ? 1 : 0) | (f1.z >= 6.0f ? 2 : 0)));
           emit = false;
         }
         const int cnt = __popcll(eb);
@@ -930,7 +998,7 @@ __global__ __launch_bounds__(64 * SC_NW, SMALLY ? RTX_SC_WAVES_SMALLY : RTX_SC_W
   if (i >= *a.n_items) return;
   const SplitItem it = a.items[i];
   if ((a.smally[it.k] != 0) != SMALLY) return;
-  nodal_tile<SMALLY>(a, it.tile, it.k, make_int2(it.lo, it.hi), a.part_ws + (size_t)i * (size_t)(64 * RTX_SC_ROWS));
+  nodal_tile<SMALLY, true>(a, it.tile, it.k, make_int2(it.lo, it.hi), a.part_ws + (size_t)i * (size_t)(64 * RTX_SC_ROWS));
 }
 
 // optical depths of a hot tile = part 0 (stored by the tile's own workgroup) + part 1 + part 2 + ..., added in that order by
