@@ -408,6 +408,55 @@ int rtx_srf_moments(const rtx_grid* grid, const float* tau, const float* La, con
 int rtx_srf_moments_max_temps(void); /* temperatures one call takes */
 
 /* ------------------------------------------------------------------------------------------
+ * Adjoint of rtx_srf_moments + rtx_band_mix: from a cotangent g[t][b][e] = d cost / d L[t][b][e] on the
+ * band radiances
+ *   L[t][b][e] = (1 / N_b) sum_i w_b,i [tau_i (eps_e,i B(nu_i, Ts_t) + (1 - eps_e,i) Ld_i) + La_i],
+ *   w, N, hat_j as at rtx_srf_moments,  eps_e,i = sum_j hat_j(nu_i) E[j][e],
+ * to the native-grid cotangents rtx_tud_vjp takes and the gradients of the surface unknowns. Over
+ * the live bands (N_b > 0) only:
+ *   H[t][b][j] = sum_e g[t][b][e] E[j][e]
+ *   A_t,i = sum_b (w_b,i / N_b) sum_j hat_j(nu_i) H[t][b][j]
+ *   S_i   = sum_t sum_b (w_b,i / N_b) sum_e g[t][b][e]
+ *   G_tau[i] = sum_t A_t,i (B(nu_i, Ts_t) - Ld_i) + S_i Ld_i
+ *   G_La[i]  = S_i
+ *   G_Ld[i]  = tau_i (S_i - sum_t A_t,i)
+ *   dTs[t]   = sum_i A_t,i tau_i dB/dT(nu_i, Ts_t)       (dB/dT as rtx_tud_vjp forms it)
+ *   dE[j][e] = sum_t sum_b g[t][b][e] M[t][b][j] / N_b   (M, N exactly rtx_srf_moments' outputs)
+ * A band with N_b = 0 (NaN in the forward) contributes nothing, whatever its g holds, NaN included;
+ * a point under no live band gets exact 0.0 in the three rows. Nothing of size nX * nE is formed.
+ *   grid, tau, La, Ld, Ts_h, nT, Xk, nk, nB, knot_start, knot_x, knot_r: as rtx_srf_moments (uniform
+ *     grid only, 1 <= nT <= rtx_srf_moments_max_temps());
+ *   E [nk][nE] float32, g [nT][nB][nE] float32: DEVICE, nE >= 1;
+ *   G_tau, G_La, G_Ld [grid->n] float32, dTs [nT] fp64, dE [nk][nE] fp64: DEVICE; any may be NULL and
+ *     is then not computed (dE alone needs no pass over the points; without dE no moments are formed).
+ * Everything rtx_srf_moments refuses, a NULL E or g, nE < 1 and all five outputs NULL fail before
+ * anything is launched. nB == 0 writes zeros.
+ * Arithmetic: w is rtx_srf_moments' fp32 weight, to the letter; N_b its chunk sums in its order,
+ * rounded to fp32 as it stores them (rtx_srf_norms returns them: equal to rtx_srf_moments' N bit for
+ * bit); H is an fp64 sum over e ascending, stored fp32; the hats are the forward's fp32 (1 - f, f);
+ * S and A_t are fp64 sums over the bands in ascending band index; B and dB/dT are fp32 (planck_f32);
+ * each row is formed in fp64 and rounded to fp32 once.
+ * Determinism: the three rows at point i are a pure function of (grid, the bands that cover i, tau,
+ * La, Ld, Xk, E, g, Ts): the same bits run to run, with bands that do not cover i added to or
+ * removed from the call (band order kept), and for a shard (offset, n) of the grid that holds the
+ * full support of every band covering i, its end points excluded (the trapezoid cell of a shard's
+ * end point is half a cell) and its offset a multiple of rtx_srf_chunk_points() (N's chunks are cut
+ * from the shard's first point; any other offset regroups an fp64 sum before its one fp32 rounding).
+ * dTs: per-point fp64 terms summed by an xor butterfly over 64 lanes, then the 16 waves of a chunk in
+ * wave order, then the chunks ascending. dE: fp64 over (t, b) ascending. Same bits run to run; no
+ * atomics. An output's bits do not depend on which other outputs are requested.
+ * Calls on one stream share a grow-only workspace; only a call that grows it synchronises. */
+int rtx_srf_radiance_vjp(const rtx_grid* grid, const float* tau, const float* La, const float* Ld,
+                         const double* Ts_h, int nT, const double* Xk, int64_t nk, int nB,
+                         const int32_t* knot_start, const double* knot_x, const float* knot_r,
+                         const float* E, int64_t nE, const float* g, float* G_tau, float* G_La,
+                         float* G_Ld, double* dTs, double* dE, void* stream);
+/* The denominators N[nB] float32 (DEVICE) alone, as rtx_srf_radiance_vjp forms them: equal to
+ * rtx_srf_moments' N_out bit for bit. Arguments and refusals as there. */
+int rtx_srf_norms(const rtx_grid* grid, int nB, const int32_t* knot_start, const double* knot_x,
+                  const float* knot_r, float* N_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fused HSI cube (config C5): every pixel has its own emissivity mixture and surface temperature
  * (LWIR_HSI_Generator.py:151-167: em = mixFrac . emis[ix_em], T = Ts + dT*N(0,1),
  * L = tau*(em*B(T) + (1-em)*Ld) + La), evaluated at monochromatic resolution and passed through

@@ -65,6 +65,9 @@ PROTOTYPES = {
     "rtx_srf_max_knots": (_i32, []),
     "rtx_srf_moments": (_i32, [_gp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rtx_srf_moments_max_temps": (_i32, []),
+    "rtx_srf_radiance_vjp": (_i32, [_gp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                                     _vp, _vp, _vp]),
+    "rtx_srf_norms": (_i32, [_gp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "rtx_interp_knots": (_i32, [_gp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "rtx_band_moments": (_i32, [_i32, _gp, _vp, _vp, _vp, _dbl, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rtx_band_mix": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp]),

@@ -1568,15 +1568,22 @@ def tud_vjp_from_od(OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z, G_tau=
 
 
 def tud_vjp(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, G_tau=None, G_Lu=None, G_Ld=None, Altitudes=(500,), theta_r=0.0,
-            N_angle=30, returnOD=False, wrt=("T",), layers=None, fd_step_T=0.5, mark=None):
+            N_angle=30, returnOD=False, wrt=("T",), layers=None, fd_step_T=0.5, mark=None, cotangents=None):
     """compute_TUD's outputs and the gradient of a scalar cost with respect to layer temperatures and mixing ratios, given
     the cost's cotangents on the outputs: tud_jacobian's stages (the same base state, T -+ fd_step_T line-sums and species
     line-sums) followed by rtx_tud_vjp instead of rtx_tud_jacobian. wrt, layers, fd_step_T as tud_jacobian; G_* as
     tud_vjp_from_od. Returns (tau, Lu, Ld, OD, grad), grad float64 [n_vec][n_wrt][n_layers] on the device, its wrt axis
-    following `wrt`. mark(name): after each stage ("base", "T", "species", "vjp")."""
+    following `wrt`. mark(name): after each stage ("base", "T", "species", "vjp").
+    cotangents: instead of G_tau / G_Lu / G_Ld, a function (tau, Lu, Ld) -> (G_tau, G_Lu, G_Ld) called once the base state
+    exists, for a cost whose cotangents depend on the outputs themselves (rt.compute_band_radiance_vjp: the sensor stage's
+    adjoint reads tau, Lu and Ld). The optical depths are computed once either way."""
+    if cotangents is not None and (G_tau is not None or G_Lu is not None or G_Ld is not None):
+        raise ValueError("tud_vjp: cotangents= and G_tau / G_Lu / G_Ld exclude each other")
     T, Z, layers, t_pos, tau, Lu, Ld, OD, ODp, ODm, K = _jacobian_stages(
         "tud_vjp", lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt, layers,
         fd_step_T, mark)
+    if cotangents is not None:
+        G_tau, G_Lu, G_Ld = cotangents(tau, Lu, Ld)
     grad = tud_vjp_from_od(OD, ODp, ODm, fd_step_T, K, tau, grid, T, Z, G_tau=G_tau, G_Lu=G_Lu, G_Ld=G_Ld, Altitudes=Altitudes,
                            theta_r=theta_r, N_angle=N_angle, returnOD=returnOD, layers=layers, t_pos=t_pos)
     if mark:

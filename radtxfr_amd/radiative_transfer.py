@@ -748,9 +748,10 @@ def compute_TUD_vjp(Xmin, Xmax, cotangents, opts=options, wrt=("T",), layers=Non
       grad[w][k(, v)] = sum over X and over the outputs with a cotangent of cotangent[(X, row, v)] * J[w][row][X, k],
     in units of cost per K ("T") and per ppmv (a molecule id). Products with the cotangents and all sums are float64 in a
     fixed order: the same call gives the same bits, whatever other layers or vectors it carries.
-    There is no reduce=: a cost defined on a reduced axis or on sensor bands, Y = R X_native with R linear
-    (reduceResolution, a slit function, band responses), has the native-grid cotangent R^T (d cost / d Y); the caller
-    applies that transpose and passes the result here.
+    There is no reduce=: a cost defined on a reduced axis, Y = R X_native with R linear (reduceResolution, a slit
+    function), has the native-grid cotangent R^T (d cost / d Y), which is passed here. For a cost defined on at-sensor
+    band radiances under a sensor's response tables, compute_band_radiance_vjp runs the whole chain, sensor adjoint
+    included, and also returns the gradients of the surface temperature and the emissivity knots.
     Arguments are checked before any device work. NotImplementedError: more than one theta_r, broadening=, xs_lut=."""
     o = dict(opts)
     o.update(kwargs)
@@ -785,6 +786,105 @@ def compute_TUD_vjp(Xmin, Xmax, cotangents, opts=options, wrt=("T",), layers=Non
     for w_i, w in enumerate(wrt):
         out[w] = np.ascontiguousarray(grad_h[:, w_i, :].T) if n_vec is not None else grad_h[0, w_i, :].copy()
     return X_, tau_, Lu_, Ld_h[0], out
+
+
+def compute_band_radiance_vjp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, cotangent, opts=options, wrt=("T",), layers=None,
+                              fd_step_T=0.5, **kwargs):
+    """At-sensor band radiances over a surface and the gradient of a scalar cost defined on them, in one call: the
+    line-sums (base, T -+ fd_step_T, each species of wrt), compute_TUD's tau / La / Ld, the band radiances of
+    sensor.band_radiance_srf_fused under the sensor's response tables, their adjoint (sensor.band_radiance_srf_vjp) and
+    compute_TUD_vjp's adjoint on the native-grid cotangents that gives, which stay on the device. The optical depths are
+    computed once; no Jacobian and nothing of size nX x nE is stored.
+
+    sensor: a sensor.Sensor; Xk [nk] the emissivity knots [cm^-1], emis_knots [nk][nE] (float32; NumPy or a torch tensor);
+    Ts_surface: a scalar or a 1-D sequence of surface temperatures [K]. cotangent = d cost / d L, laid out like L:
+    [nB][nE] for a scalar Ts_surface, [nT][nB][nE] for a sequence, with an optional trailing axis of n_vec cotangent
+    vectors (they share everything up to the sensor adjoint). kwargs, wrt, layers, fd_step_T as compute_TUD_vjp, with
+    exactly one sensor altitude and returnOD=False. Returns (X_out, L, grad):
+      X_out  sensor.centres;
+      L      float32 NumPy, bit-identical to band_radiance_srf_fused on compute_TUD's outputs (NaN for a band with no
+             grid point under it; such a band contributes nothing to any gradient, whatever its cotangent holds);
+      grad   {wrt entry: float64 [n_layers]} as compute_TUD_vjp returns them, plus "Ts_surface" (float64, Ts_surface's
+             shape) and "emis" (float64 [nk][nE]); every entry with a trailing [n_vec] axis when the cotangent has one.
+    Arguments are checked before any device work. NotImplementedError: more than one altitude or theta_r, returnOD=True,
+    broadening=, xs_lut=, reduce=."""
+    name = "compute_band_radiance_vjp"
+    o = dict(opts)
+    o.update(kwargs)
+    if "reduce" in o:
+        raise NotImplementedError(name + ": reduce= is not offered: the cost is defined on the sensor's bands")
+    if o.get("xs_lut") is not None:
+        raise NotImplementedError(name + ": xs_lut is not supported (dOD/dT is a difference of line-sums with fixed windows); "
+                                  "use line_table=")
+    if bool(o["returnOD"]):
+        raise NotImplementedError(name + ": returnOD=True is not supported (the sensor stage takes transmittances)")
+    Z_s = np.array([o["Altitudes"]]).ravel()
+    if Z_s.size != 1:
+        raise NotImplementedError(name + ": exactly one sensor altitude per call (got %d)" % Z_s.size)
+    try:
+        wrt, lay, nX = _jacobian_args(Xmin, Xmax, o, wrt, layers, None, fd_step_T, host_result=False)
+    except (ValueError, NotImplementedError) as e:
+        raise type(e)(str(e).replace("compute_TUD_jacobian", name)) from None
+    Xk = np.ascontiguousarray(np.asarray(Xk, dtype=np.float64).ravel())
+    scalar = np.ndim(Ts_surface) == 0
+    Ts_s = np.atleast_1d(np.asarray(Ts_surface, dtype=np.float64))
+    if Ts_s.ndim != 1 or Ts_s.size == 0 or not np.all(Ts_s > 0.0):
+        raise ValueError(name + ": Ts_surface must be a positive scalar or a non-empty 1-D sequence of positive temperatures")
+    if not _is_torch(emis_knots):
+        emis_knots = np.asarray(emis_knots)
+    if tuple(emis_knots.shape[:1]) != (Xk.size,) or len(emis_knots.shape) != 2 or emis_knots.shape[1] < 1:
+        raise ValueError(name + ": emis_knots has shape %r, expected [%d][nE]" % (tuple(emis_knots.shape), Xk.size))
+    nB, nE, nT = len(sensor), int(emis_knots.shape[1]), Ts_s.size
+    base = (nB, nE) if scalar else (nT, nB, nE)
+    g = cotangent if _is_torch(cotangent) else np.asarray(cotangent)
+    shape = tuple(g.shape)
+    if shape == base:
+        g, n_vec = g[..., None], None
+    elif len(shape) == len(base) + 1 and shape[:-1] == base and shape[-1] >= 1:
+        n_vec = shape[-1]
+    else:
+        raise ValueError(name + ": cotangent has shape %r, expected %r (L's shape) plus an optional trailing vector axis"
+                         % (shape, base))
+    from . import sensor as _sensor  # sensor.py imports this module
+    Z = np.asarray(o["Zs"], dtype=np.float64)
+    T = np.asarray(o["Ts"], dtype=np.float64)
+    X_ = _cached_axis(Xmin, Xmax, o["DVOUT"])
+    assert X_.size == nX
+    grid = engine.Grid(Xmin, Xmax, X_.size)
+    tbl = _resolve_table(o.get("line_table"))
+    dev = engine.device()
+    E_d = _dev_f32(emis_knots, dev).contiguous()
+    g_d = _dev_f32(g, dev)
+    Ts_arg = float(Ts_s[0]) if scalar else Ts_s
+    nv = g_d.shape[-1]
+    kept = {}
+
+    def sensor_stage(tau, Lu, Ld):
+        t_, u_, d_ = tau[0, :nX].contiguous(), Lu[0, :nX].contiguous(), Ld[:nX].contiguous()
+        _, kept["L"] = _sensor.band_radiance_srf_fused(grid, t_, u_, d_, Xk, E_d, Ts_arg, sensor)
+        G = [torch.empty((nv, 1, nX), dtype=torch.float32, device=dev), torch.empty((nv, 1, nX), dtype=torch.float32, device=dev),
+             torch.empty((nv, nX), dtype=torch.float32, device=dev)]
+        kept["Ts"], kept["emis"] = [], []
+        for v in range(nv):
+            r = _sensor.band_radiance_srf_vjp(grid, t_, u_, d_, Xk, E_d, Ts_arg, sensor, g_d[..., v])
+            G[0][v, 0], G[1][v, 0], G[2][v] = r["G_tau"], r["G_La"], r["G_Ld"]
+            kept["Ts"].append(r["Ts"])
+            kept["emis"].append(r["emis"])
+        return G
+
+    _, _, _, _, grad = engine.tud_vjp(tbl, grid, Z, T, o["Ps"], o["PLs"], o["MFs_VAL"], o["MFs_ID"], Altitudes=Z_s,
+                                      theta_r=np.asarray(o["theta_r"], dtype=np.float64), N_angle=int(o["N_angle"]),
+                                      returnOD=False, wrt=wrt, layers=lay, fd_step_T=float(fd_step_T), cotangents=sensor_stage)
+    grad_h = grad.cpu().numpy()  # [n_vec][n_wrt][n_layers]
+    L_h = kept["L"].cpu().numpy()
+    dTs_h = torch.stack(kept["Ts"], dim=-1).cpu().numpy()    # Ts_surface's shape + [n_vec]
+    dE_h = torch.stack(kept["emis"], dim=-1).cpu().numpy()   # [nk][nE][n_vec]
+    out = {}
+    for w_i, w in enumerate(wrt):
+        out[w] = np.ascontiguousarray(grad_h[:, w_i, :].T) if n_vec is not None else grad_h[0, w_i, :].copy()
+    out["Ts_surface"] = np.ascontiguousarray(dTs_h) if n_vec is not None else dTs_h[..., 0].copy()
+    out["emis"] = np.ascontiguousarray(dE_h) if n_vec is not None else dE_h[..., 0].copy()
+    return np.array(sensor.centres), L_h, out
 
 
 def compute_LWIR_apparent_radiance(X, emis, Ts, tau, La, Ld, dT=None, return_Ls=False):

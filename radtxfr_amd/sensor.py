@@ -325,6 +325,86 @@ def band_radiance_srf_fused(grid, tau, La, Ld, Xk, emis_knots, Ts, sensor):
     return X_out, (out[0] if scalar else out)
 
 
+def srf_norms(grid, sensor, dev=None):
+    """The denominators N [nB] float32 (device) of the sensor's bands on `grid`, as rtx_srf_radiance_vjp forms them
+    (rtx_srf_norms): bit for bit rtx_srf_moments' N."""
+    lib = _lib.load()
+    dev = engine.device() if dev is None else dev
+    kx, kr = sensor.on_device(dev)
+    N = torch.empty(len(sensor), dtype=torch.float32, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    _lib.check(lib.rtx_srf_norms(grid.byref(), len(sensor), sensor.knot_start.ctypes.data_as(C.c_void_p), p(kx), p(kr), p(N),
+                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return N
+
+
+_VJP_OUTPUTS = ("G_tau", "G_La", "G_Ld", "Ts", "emis")
+
+
+def band_radiance_srf_vjp(grid, tau, La, Ld, Xk, emis_knots, Ts, sensor, g, outputs=_VJP_OUTPUTS):
+    """The adjoint of band_radiance_srf_fused (rtx_srf_radiance_vjp): from g = d cost / d L, laid out like the L that call
+    returns ([nB][nE] for a scalar Ts, [nT][nB][nE] for a 1-D Ts; float32, device or NumPy), to a dict with
+      "G_tau", "G_La", "G_Ld"  d cost / d tau, La, Ld on the native grid, float32 [nX] on tau's device: the cotangents
+                               engine.tud_vjp_from_od takes;
+      "Ts"                     d cost / d Ts, float64 device, [nT] (0-d for a scalar Ts);
+      "emis"                   d cost / d emis_knots, float64 [nk][nE] device.
+    Same arguments as band_radiance_srf_fused otherwise. A band that comes out NaN there (no grid point under it)
+    contributes nothing, whatever its g holds; a point under no live band gets exact zeros. Nothing of size nX x nE is
+    formed. outputs: the keys wanted (default all); one left out is not computed. A Ts sequence longer than
+    rtx_srf_moments_max_temps() is taken in groups: the groups' rows (and "emis") are added in float64 in group order
+    and the rows rounded to float32 once."""
+    lib = _lib.load()
+    dev = tau.device
+    scalar = np.ndim(Ts) == 0
+    Ts = np.ascontiguousarray(np.atleast_1d(np.asarray(Ts, dtype=np.float64)))
+    if Ts.ndim != 1 or Ts.size == 0:
+        raise ValueError("Ts: a scalar or a non-empty 1-D sequence")
+    outputs = tuple(outputs)
+    if not outputs or any(k not in _VJP_OUTPUTS for k in outputs):
+        raise ValueError("outputs: a non-empty selection of %r (got %r)" % (_VJP_OUTPUTS, outputs))
+    for v in (tau, La, Ld):
+        assert v.dtype == torch.float32 and v.is_cuda and v.is_contiguous() and v.numel() == grid.n
+    plan = _srf_fused_plan(Xk, dev)
+    nB, nk, nE, nT, nX = len(sensor), plan["Xk_d"].numel(), emis_knots.shape[1], Ts.size, grid.n
+    assert emis_knots.dtype == torch.float32 and emis_knots.is_cuda and emis_knots.shape[0] == nk
+    emis_knots = emis_knots.contiguous()
+    if not torch.is_tensor(g):
+        g = torch.as_tensor(np.ascontiguousarray(g, dtype=np.float32))
+    g = g.to(device=dev, dtype=torch.float32)
+    if tuple(g.shape) != ((nB, nE) if scalar else (nT, nB, nE)):
+        raise ValueError("g has shape %r, expected %r (the shape of band_radiance_srf_fused's L)"
+                         % (tuple(g.shape), (nB, nE) if scalar else (nT, nB, nE)))
+    g = g.reshape(nT, nB, nE).contiguous()
+    kx, kr = sensor.on_device(dev)
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    step = lib.rtx_srf_moments_max_temps()
+    rows = [k for k in ("G_tau", "G_La", "G_Ld") if k in outputs]
+    dTs = torch.empty(nT, dtype=torch.float64, device=dev) if "Ts" in outputs else None
+    total = {}  # the float64 sums over the groups of Ts, when there is more than one
+    out = {}
+    for t0 in range(0, nT, step):
+        t1 = min(t0 + step, nT)
+        G = {k: torch.empty(nX, dtype=torch.float32, device=dev) for k in rows}
+        dE = torch.empty((nk, nE), dtype=torch.float64, device=dev) if "emis" in outputs else None
+        _lib.check(lib.rtx_srf_radiance_vjp(grid.byref(), p(tau), p(La), p(Ld), Ts[t0:t1].ctypes.data_as(C.c_void_p), t1 - t0,
+                                            p(plan["Xk_d"]), nk, nB, sensor.knot_start.ctypes.data_as(C.c_void_p), p(kx), p(kr),
+                                            p(emis_knots), nE, p(g[t0:t1]), p(G.get("G_tau")), p(G.get("G_La")), p(G.get("G_Ld")),
+                                            p(dTs[t0:t1]) if dTs is not None else None, p(dE), st))
+        if dE is not None:
+            G["emis"] = dE
+        if nT <= step:
+            out.update(G)
+        else:
+            for k, v in G.items():
+                total[k] = v.to(torch.float64) if k not in total else total[k] + v.to(torch.float64)
+    for k, v in total.items():
+        out[k] = v if k == "emis" else v.to(torch.float32)
+    if dTs is not None:
+        out["Ts"] = dTs[0] if scalar else dTs
+    return out
+
+
 def chebyshev_lagrange(Q):
     """Chebyshev nodes s_q on (-1,1) and the monomial coefficients coef[q][d] of their Lagrange basis."""
     s = np.cos((2 * np.arange(Q) + 1) * np.pi / (2 * Q))
