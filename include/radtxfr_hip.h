@@ -200,6 +200,25 @@ int rtx_voigt_sum(const rtx_prep* prep, const rtx_grid* grid, int n_layers, floa
  * (no Chebyshev-node far wings), deterministic: repeated calls give identical bits. */
 int rtx_voigt_sum_axis(const rtx_prep* prep, int n_layers, float* out_f32, double* out_f64, int64_t ld, void* stream);
 
+/* Analytic temperature derivative of the Voigt line-sum (uniform grid, Voigt profile, call-wide dil_air / dil_self).
+ * rtx_line_prep_dt: rtx_line_prep_profile's arguments without `profile`, plus
+ *   dlnsw_h[n_species][n_layers]  (host) d ln(qratio * weight) / dT per species and layer, the two host inputs' own
+ *                                 temperature dependence (for the optical-depth weights: -Q'(T)/Q(T) - 1/T).
+ * It writes the records of rtx_line_prep_profile(..., RTX_PROFILE_VOIGT) bit for bit (rtx_voigt_sum may follow it) and,
+ * in buffers owned by the prep object (grow-only: the first call allocates, hence synchronises), one derivative record
+ * per (line, layer), formed in fp64.
+ * rtx_voigt_sum_dt: out_*[n_layers][ld] as rtx_voigt_sum's, the sum over lines of d/dT [A K(x, y)] at the layer's
+ * (T, p) with every line's window [lo, hi) held fixed: each point differentiates the branch of hum1_wei it is on
+ * (misc/hapi.py:9833-9844), the step of that function at |x| + y = 15 is not differentiated. An error unless the last
+ * prologue on `prep` was rtx_line_prep_dt. Point by point, deterministic: repeated calls give identical bits, and a shard
+ * that starts on a multiple of rtx_voigt_tile_points() gives the bits of the full grid. Exact 0 outside every window. */
+int rtx_line_prep_dt(rtx_prep* prep, const rtx_lines* lines, const rtx_grid* grid, int n_layers, const double* T_h,
+                     const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
+                     const double* dlnsw_h, double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
+                     double intensity_threshold, double scale, void* stream);
+int rtx_voigt_sum_dt(const rtx_prep* prep, const rtx_grid* grid, int n_layers, float* out_f32, double* out_f64,
+                     int64_t ld, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Planck radiance. Replaces planckian(), radiative_transfer.py:792-848.
  *   X == NULL : spectral axis = grid; else X[nx] (fp64 wavenumbers or micrometres)
@@ -280,6 +299,20 @@ int rtx_tud_vjp(const float* OD, const float* OD_plus, const float* OD_minus, in
                 int return_od, const int32_t* layers_h, int n_lay, int t_pos, const float* G_tau,
                 const float* G_Lu, const float* G_Ld, int64_t ld_G, int n_vec, double* out, void* stream);
 int rtx_tud_vjp_max_vectors(void);
+/* rtx_tud_jacobian and rtx_tud_vjp with the temperature derivative of the optical depths given directly:
+ * dOD_dT[n_layers][ld] (rtx_voigt_sum_dt) in place of OD_plus, OD_minus and fd_step; T is always a wrt entry (at t_pos).
+ * Everything else, every refusal included, as there; dOD_dT == NULL is refused. The kernels are those of the two entry
+ * points above: they receive dOD_dT as OD_plus with fd_step = 1/2 and a library-owned array of n_layers * ld zeros (per
+ * device, grow-only, allocated and cleared on first use: that call synchronises) as OD_minus; (D - 0) * 1 = D exactly. */
+int rtx_tud_jacobian_dod(const float* OD, const float* dOD_dT, int64_t ld, const float* K, int n_spec, const float* tau,
+                         int64_t ld_tau, const rtx_grid* grid, int n_layers, const double* T_h, int n_alt,
+                         const uint8_t* mask_h, double mu, int n_down, int n_angle, int return_od,
+                         const int32_t* layers_h, int n_lay, int t_pos, float* J, int64_t ld_J, void* stream);
+int rtx_tud_vjp_dod(const float* OD, const float* dOD_dT, int64_t ld, const float* K, int n_spec, const float* tau,
+                    int64_t ld_tau, const rtx_grid* grid, int n_layers, const double* T_h, int n_alt,
+                    const uint8_t* mask_h, double mu, int n_down, int n_angle, int return_od, const int32_t* layers_h,
+                    int n_lay, int t_pos, const float* G_tau, const float* G_Lu, const float* G_Ld, int64_t ld_G,
+                    int n_vec, double* out, void* stream);
 /* The tabulated G of rtx_tud, for host-side checks (no device involved): rtx_tud_gtable_size() doubles, rows of
  * {interval centre, a0 .. a6}: G(S) = sum a_k (S - centre)^k on the row's interval; intervals: 16 per binade of
  * S + 2^-6 below S = 16 (row = (bits(float(S) + 2^-6) >> 19) - (bits(2^-6) >> 19)), width 1/2 from there to S = 48.

@@ -117,6 +117,27 @@ struct __attribute__((aligned(16))) LineRecSD {
   double inv_Gam2, csqrtY;  // 1 / Gam2 and 1 / (2 cte Gam2): per-line reciprocals the line-sum would otherwise redo per point
 };
 
+// Temperature-derivative records of rtx_line_prep_dt, one pair per (line, layer), read by rtx_voigt_sum_dt beside the
+// line's LineRec / LineRec64. With g = A K(x, y) the line's contribution at a point,
+//   dg/dT = A [alpha K + K_x x' + K_y y'],  x' = -sx - x h,  y' = gy - y h.
+// fp64 record (32 B): what the band lanes (|x| + y < 15) combine with the complex probability function in fp64.
+struct __attribute__((aligned(16))) LineRecDT64 {
+  double alpha;  // dlnS/dT + dlnw/dT - 1/(2T)
+  double sx;     // Shift0' cte
+  double gy;     // Gamma0' cte
+  double h;      // 1/(2T)
+};
+// fp32 record (32 B): the far-wing derivative as a rational in x and xx = x*x. With p = yh - xx, q = y2 x and
+// R = (xx + b1) xx + b0 (LineRec) = p^2 + q^2:
+//   dg/dT = Ap / R * [ alpha y (yh + xx) + q (2 p / R - 1) x' + ((p^2 - q^2) / R - p) yp ].
+struct __attribute__((aligned(16))) LineRecDT {
+  float alpha, sx, yp, h;  // yp = y' = gy - y h
+  float Ap;                // A / sqrt(pi)
+  float yh;                // y^2 + 1/2
+  float y2;                // 2 y
+  float y;
+};
+
 struct rtx_lines {
   long long n = 0;
   int n_species = 0;
@@ -193,4 +214,9 @@ struct rtx_prep {
   int axis = 0;
   DevBuf<double> twin;  // window temperatures of rtx_line_prep_window: device copy
   DevBuf<double> frac;  // diluent fractions of rtx_line_prep_mix / _axis_mix: device copy [n_dil][n_species][n_layers]
+  // rtx_line_prep_dt: the derivative records [max_layers][n_lines], the device copy of dlnsw_h, and whether it ran last
+  DevBuf<LineRecDT> drec;
+  DevBuf<LineRecDT64> drec64;
+  DevBuf<double> dlnsw;
+  int dT = 0;
 };

@@ -838,6 +838,7 @@ static int prep_launch(rtx_prep* P, const rtx_lines* L, const PrepIn& in, bool a
   P->n_layers = in.n_layers;
   P->scale = in.scale;
   P->axis = axis;
+  P->dT = 0;  // rtx_line_prep_dt sets it once its derivative records are enqueued too
   if (empty) return 0;
   const Kernel k = axis ? axis_k[env_args][in.mix != nullptr] : grid_k[env_args][a.Twin ? 2 : in.mix ? 1 : 0];
   hipLaunchKernelGGL(k, dim3((unsigned)((L->n + 255) / 256), (unsigned)in.n_layers), dim3(256), 0, in.st, a);
@@ -847,7 +848,9 @@ static int prep_launch(rtx_prep* P, const rtx_lines* L, const PrepIn& in, bool a
 
 // Grid prologue of rtx_line_prep_profile, rtx_line_prep_mix (in.mix) and rtx_line_prep_window (T_win_h: every window, hence
 // the candidate half-widths and the hot-tile bound, at those temperatures; its device copy belongs to the prep object).
-static int line_prep_grid(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid, const double* T_win_h, const PrepIn& in) {
+// keep / keep_env: where the caller (rtx_line_prep_dt) receives the kernel arguments and how the per-layer tables travel.
+static int line_prep_grid(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid, const double* T_win_h, const PrepIn& in,
+                          PrepArgs* keep = nullptr, bool* keep_env = nullptr) {
   if (!P || !L) RTX_FAIL("prep/lines is NULL");
   if (in.profile < RTX_PROFILE_VOIGT || in.profile > RTX_PROFILE_SDVOIGT) RTX_FAIL("profile=%d", in.profile);
   if (in.mix && in.profile == RTX_PROFILE_DOPPLER) RTX_FAIL("rtx_line_prep_mix: the Doppler profile takes no diluent");
@@ -867,6 +870,7 @@ static int line_prep_grid(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid,
                            : gamma0_bound(L, in.n_layers, T_w, in.p_atm_h, in.dil_air, in.dil_self);
   if (rtx_split_bound(P, L, grid, in.n_layers, T_w, in.mass_h, g0, in.omega_wing, in.omega_wing_hw, in.profile)) return 1;
   a.g = to_dev(grid);
+  if (keep) { *keep = a; *keep_env = env_args; }
   return prep_launch(P, L, in, false, L->n == 0, env_args, a);
 }
 
@@ -949,4 +953,92 @@ extern "C" int rtx_line_prep_window(rtx_prep* P, const rtx_lines* L, const rtx_g
   for (int k = 0; k < n_layers; ++k)
     if (!(T_win_h[k] > 0.0)) RTX_FAIL("layer %d: window temperature %g not physical", k, T_win_h[k]);
   return line_prep_grid(P, L, grid, T_win_h, RTX_PREP_IN(dil_air, dil_self, nullptr, profile));
+}
+
+// ---- rtx_line_prep_dt: the grid prologue plus the temperature-derivative records ---------------------------
+// The base records, windows and candidate inputs are written by line_prep_kernel itself, launched exactly as
+// rtx_line_prep_profile launches it: the same kernel on the same arguments, hence the same bits. A second kernel, one thread
+// per (line, layer) again, then reads the line's fp64 record (cte, y, A) and forms the derivative records in fp64:
+//   alpha = dln(qratio w)/dT + c2 E"/T^2 - (u/T)/(e^u - 1) - 1/(2T),  u = c2 nu/T  (S(T) of line_strength, cte ~ T^-1/2),
+//   Gamma0' = -sum_d f_d gamma_d p (Tref/T)^n_d n_d / T,  Shift0' = sum_d f_d deltap_d p  (line_phys, d = air, self).
+// A line without a window in the shard (dropped, empty, or skipped by the prologue) is never visited by the sum: zeros.
+struct PrepDTArgs {
+  const double* dlnsw;  // [n_species][n_layers], device copy
+  LineRecDT* drec;
+  LineRecDT64* drec64;
+};
+static_assert(sizeof(PrepArgs) + sizeof(PrepDTArgs) <= 4096, "the derivative prologue's kernel arguments must stay within 4 KB");
+
+template <bool ENV_ARGS>
+__global__ __launch_bounds__(256) void line_prep_dT_kernel(PrepArgs a, PrepDTArgs d) {
+  const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int k = blockIdx.y;
+  if (l >= a.n_lines) return;
+  const double* eT = ENV_ARGS ? a.env + (size_t)a.T : a.T;
+  const double* ep = ENV_ARGS ? a.env + (size_t)a.p : a.p;
+  const size_t o = (size_t)k * (size_t)a.n_lines + (size_t)l;
+  const int2 w = a.win[o];
+  LineRecDT r;
+  LineRecDT64 r64;
+  r.alpha = r.sx = r.yp = r.h = r.Ap = r.y2 = 0.f; r.yh = 0.5f; r.y = 15.f;
+  r64.alpha = r64.sx = r64.gy = r64.h = 0.0;
+  if (w.y > w.x) {
+    const LineRec64 Q = a.rec64[o];
+    const double T = eT[k], p = ep[k];
+    const double nu = a.nu[l];
+    const int sp = a.species[l];
+    const double ltr = log(H_TREF / T);
+    double G0p = 0.0, Sp = 0.0;
+    if (a.dil_air != 0.0) {
+      const double na = a.n_air[l];
+      G0p += a.dil_air * (a.gamma_air[l] * p * exp(na * ltr)) * na;
+      Sp += a.dil_air * ((a.deltap_air ? a.deltap_air[l] : 0.0) * p);
+    }
+    if (a.dil_self != 0.0) {
+      double ns = a.n_self ? a.n_self[l] : a.n_air[l];
+      if (a.n_self && ns == 0.0) ns = a.n_air[l];
+      G0p += a.dil_self * (a.gamma_self[l] * p * exp(ns * ltr)) * ns;
+      Sp += a.dil_self * ((a.deltap_self ? a.deltap_self[l] : 0.0) * p);
+    }
+    G0p = -G0p / T;
+    const double u = H_C2 * nu / T;
+    const double h = 0.5 / T;
+    r64.alpha = d.dlnsw[(size_t)sp * a.n_layers + k] + H_C2 * a.elower[l] / (T * T) - (u / T) / expm1(u) - h;
+    r64.sx = Sp * Q.cte;
+    r64.gy = G0p * Q.cte;
+    r64.h = h;
+    r.alpha = (float)r64.alpha; r.sx = (float)r64.sx; r.yp = (float)(r64.gy - Q.y * h); r.h = (float)h;
+    r.Ap = (float)(Q.A * 0.56418958354775628);
+    r.yh = (float)(Q.y * Q.y + 0.5);
+    r.y2 = (float)(2.0 * Q.y);
+    r.y = (float)Q.y;
+  }
+  d.drec[o] = r;
+  d.drec64[o] = r64;
+}
+
+extern "C" int rtx_line_prep_dt(rtx_prep* P, const rtx_lines* L, const rtx_grid* grid, int n_layers, const double* T_h,
+                                const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
+                                const double* dlnsw_h, double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
+                                double intensity_threshold, double scale, void* stream) {
+  if (!dlnsw_h) RTX_FAIL("dlnsw_h is NULL");
+  if (!P || !L) RTX_FAIL("prep/lines is NULL");
+  const size_t nrec = (size_t)(P->n_lines > 0 ? P->n_lines : 1) * (size_t)P->max_layers;
+  // grow-only: the first call allocates, hence synchronises
+  if (P->drec.reserve(nrec) || P->drec64.reserve(nrec) || P->dlnsw.reserve((size_t)L->n_species * (size_t)P->max_layers)) return 1;
+  PrepArgs a;
+  bool env_args = false;
+  if (line_prep_grid(P, L, grid, nullptr, RTX_PREP_IN(dil_air, dil_self, nullptr, RTX_PROFILE_VOIGT), &a, &env_args)) return 1;
+  if (L->n > 0) {
+    hipStream_t st = (hipStream_t)stream;
+    RTX_HIP(hipMemcpyAsync(P->dlnsw.get(), dlnsw_h, (size_t)L->n_species * (size_t)n_layers * sizeof(double), hipMemcpyHostToDevice, st));  // staged before returning
+    PrepDTArgs d;
+    d.dlnsw = P->dlnsw.get(); d.drec = P->drec.get(); d.drec64 = P->drec64.get();
+    const dim3 blocks((unsigned)((L->n + 255) / 256), (unsigned)n_layers);
+    if (env_args) hipLaunchKernelGGL(line_prep_dT_kernel<true>, blocks, dim3(256), 0, st, a, d);
+    else hipLaunchKernelGGL(line_prep_dT_kernel<false>, blocks, dim3(256), 0, st, a, d);
+    RTX_LAUNCH_CHECK();
+  }
+  P->dT = 1;
+  return 0;
 }

@@ -173,11 +173,37 @@ __global__ __launch_bounds__(256) void tud_jac_kernel(TudJacArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-extern "C" int rtx_tud_jacobian(const float* OD, const float* OD_plus, const float* OD_minus, int64_t ld, double fd_step,
-                                const float* K, int n_spec, const float* tau, int64_t ld_tau, const rtx_grid* grid, int n_layers,
-                                const double* T_h, int n_alt, const uint8_t* mask_h, double mu, int n_down, int n_angle,
-                                int return_od, const int32_t* layers_h, int n_lay, int t_pos, float* J, int64_t ld_J,
-                                void* stream) {
+// Zeros for the *_dod entry points (rtx_tud_jac_common.h).
+#include <mutex>
+int rtx_tud_zero_rows(size_t count, const float** out) {
+  struct Zeros { int dev; DevBuf<float> z; };
+  static std::mutex mu;
+  static std::vector<Zeros>* all = new std::vector<Zeros>();  // never destroyed: no device call from a static destructor
+  int dev = 0;
+  RTX_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(mu);
+  Zeros* e = nullptr;
+  for (Zeros& c : *all)
+    if (c.dev == dev) e = &c;
+  if (!e) {
+    all->emplace_back();
+    e = &all->back();
+    e->dev = dev;
+  }
+  if (count > e->z.cap()) {  // growth frees first, which waits for the kernels that read the old array
+    if (e->z.reserve(count)) return 1;
+    RTX_HIP(hipMemset(e->z.get(), 0, count * sizeof(float)));
+  }
+  *out = e->z.get();
+  return 0;
+}
+
+// dod: OD_plus is dOD/dT itself (rtx_tud_jacobian_dod), OD_minus and fd_step are not the caller's
+static int tud_jacobian_run(const float* OD, const float* OD_plus, const float* OD_minus, bool dod, int64_t ld, double fd_step,
+                            const float* K, int n_spec, const float* tau, int64_t ld_tau, const rtx_grid* grid, int n_layers,
+                            const double* T_h, int n_alt, const uint8_t* mask_h, double mu, int n_down, int n_angle,
+                            int return_od, const int32_t* layers_h, int n_lay, int t_pos, float* J, int64_t ld_J,
+                            void* stream) {
   if (rtx_check_grid(grid)) return 1;
   if (!J) RTX_FAIL("a required pointer is NULL");
   TudJacArgs a;
@@ -187,8 +213,27 @@ extern "C" int rtx_tud_jacobian(const float* OD, const float* OD_plus, const flo
   if (ld_J < grid->n) RTX_FAIL("leading dimension smaller than the shard");
   a.J = J; a.ld_J = ld_J;
   if (grid->n == 0) return 0;
+  if (dod && rtx_tud_zero_rows((size_t)n_layers * (size_t)ld, &a.ODm)) return 1;
   const long long blocks = (grid->n + 255) / 256;
   hipLaunchKernelGGL(tud_jac_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
   RTX_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int rtx_tud_jacobian(const float* OD, const float* OD_plus, const float* OD_minus, int64_t ld, double fd_step,
+                                const float* K, int n_spec, const float* tau, int64_t ld_tau, const rtx_grid* grid, int n_layers,
+                                const double* T_h, int n_alt, const uint8_t* mask_h, double mu, int n_down, int n_angle,
+                                int return_od, const int32_t* layers_h, int n_lay, int t_pos, float* J, int64_t ld_J,
+                                void* stream) {
+  return tud_jacobian_run(OD, OD_plus, OD_minus, false, ld, fd_step, K, n_spec, tau, ld_tau, grid, n_layers, T_h, n_alt, mask_h, mu,
+                          n_down, n_angle, return_od, layers_h, n_lay, t_pos, J, ld_J, stream);
+}
+
+extern "C" int rtx_tud_jacobian_dod(const float* OD, const float* dOD_dT, int64_t ld, const float* K, int n_spec, const float* tau,
+                                    int64_t ld_tau, const rtx_grid* grid, int n_layers, const double* T_h, int n_alt,
+                                    const uint8_t* mask_h, double mu, int n_down, int n_angle, int return_od,
+                                    const int32_t* layers_h, int n_lay, int t_pos, float* J, int64_t ld_J, void* stream) {
+  if (!dOD_dT) RTX_FAIL("dOD_dT is NULL");
+  return tud_jacobian_run(OD, dOD_dT, dOD_dT, true, ld, 0.5, K, n_spec, tau, ld_tau, grid, n_layers, T_h, n_alt, mask_h, mu, n_down,
+                          n_angle, return_od, layers_h, n_lay, t_pos, J, ld_J, stream);
 }

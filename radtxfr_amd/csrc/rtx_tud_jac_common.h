@@ -59,6 +59,14 @@ __device__ __forceinline__ void planck_dT(double c1x3, double x, double ct, floa
 __device__ __forceinline__ double planck_f64(double c1x3, double x, double ct) { return c1x3 / expm1(x * ct * LN2); }
 
 // ---- host ---------------------------------------------------------------------------------------------
+// The *_dod entry points take dOD/dT itself (rtx_voigt_sum_dt) where the others take OD at T -+ fd_step. The kernels are
+// left as they are (a select on a NULL OD_minus moved the register counts of tud_vjp_kernel,
+// profiles/dT_tud_resources.txt): the derivative goes in as OD_plus with fd_step = 1/2 and a library-owned array of zeros as
+// OD_minus, and (D - 0) * 1 is D exactly in fp32. `count` floats of zeros on the current device (rtx_tud_jac.hip):
+// grow-only, one array per device, zeroed when it is allocated and never written again.
+int rtx_tud_zero_rows(size_t count, const float** out);
+
+
 // Checks everything about the column and the request that does not concern the result array, and fills `a` (J and ld_J
 // stay 0). need_tau: the caller reads the base transmittances (always, for J; only with a cotangent on tau, for J^T g).
 static inline int tud_jac_setup(TudJacArgs& a, const float* OD, const float* OD_plus, const float* OD_minus, int64_t ld,

@@ -279,11 +279,12 @@ static void vjp_launch(const TudVjpArgs& v, unsigned blocks, hipStream_t st) {
 
 extern "C" int rtx_tud_vjp_max_vectors(void) { return TUDV_NV; }
 
-extern "C" int rtx_tud_vjp(const float* OD, const float* OD_plus, const float* OD_minus, int64_t ld, double fd_step,
-                           const float* K, int n_spec, const float* tau, int64_t ld_tau, const rtx_grid* grid, int n_layers,
-                           const double* T_h, int n_alt, const uint8_t* mask_h, double mu, int n_down, int n_angle,
-                           int return_od, const int32_t* layers_h, int n_lay, int t_pos, const float* G_tau,
-                           const float* G_Lu, const float* G_Ld, int64_t ld_G, int n_vec, double* out, void* stream) {
+// dod: OD_plus is dOD/dT itself (rtx_tud_vjp_dod), OD_minus and fd_step are not the caller's
+static int tud_vjp_run(const float* OD, const float* OD_plus, const float* OD_minus, bool dod, int64_t ld, double fd_step,
+                       const float* K, int n_spec, const float* tau, int64_t ld_tau, const rtx_grid* grid, int n_layers,
+                       const double* T_h, int n_alt, const uint8_t* mask_h, double mu, int n_down, int n_angle,
+                       int return_od, const int32_t* layers_h, int n_lay, int t_pos, const float* G_tau,
+                       const float* G_Lu, const float* G_Ld, int64_t ld_G, int n_vec, double* out, void* stream) {
   if (rtx_check_grid(grid)) return 1;
   if (!out) RTX_FAIL("out is NULL");
   if (!G_tau && !G_Lu && !G_Ld) RTX_FAIL("no cotangent: G_tau, G_Lu and G_Ld are all NULL");
@@ -301,6 +302,7 @@ extern "C" int rtx_tud_vjp(const float* OD, const float* OD_plus, const float* O
   }
   const long long blocks = (grid->n + 64 * TUDV_WAVES - 1) / (64 * TUDV_WAVES);
   if (blocks > 0x7fffffffLL) RTX_FAIL("grid->n=%lld: too many workgroups", (long long)grid->n);
+  if (dod && rtx_tud_zero_rows((size_t)n_layers * (size_t)ld, &v.c.ODm)) return 1;
   void* ws = nullptr;
   if (vjp_workspace((size_t)blocks * n_out * sizeof(double), st, &ws)) return 1;
   v.G_tau = G_tau; v.G_Lu = G_Lu; v.G_Ld = G_Ld; v.ld_G = ld_G; v.part = (double*)ws; v.nv = n_vec;
@@ -319,4 +321,23 @@ extern "C" int rtx_tud_vjp(const float* OD, const float* OD_plus, const float* O
                      n_out, out);
   RTX_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int rtx_tud_vjp(const float* OD, const float* OD_plus, const float* OD_minus, int64_t ld, double fd_step,
+                           const float* K, int n_spec, const float* tau, int64_t ld_tau, const rtx_grid* grid, int n_layers,
+                           const double* T_h, int n_alt, const uint8_t* mask_h, double mu, int n_down, int n_angle,
+                           int return_od, const int32_t* layers_h, int n_lay, int t_pos, const float* G_tau,
+                           const float* G_Lu, const float* G_Ld, int64_t ld_G, int n_vec, double* out, void* stream) {
+  return tud_vjp_run(OD, OD_plus, OD_minus, false, ld, fd_step, K, n_spec, tau, ld_tau, grid, n_layers, T_h, n_alt, mask_h, mu, n_down,
+                     n_angle, return_od, layers_h, n_lay, t_pos, G_tau, G_Lu, G_Ld, ld_G, n_vec, out, stream);
+}
+
+extern "C" int rtx_tud_vjp_dod(const float* OD, const float* dOD_dT, int64_t ld, const float* K, int n_spec, const float* tau,
+                               int64_t ld_tau, const rtx_grid* grid, int n_layers, const double* T_h, int n_alt,
+                               const uint8_t* mask_h, double mu, int n_down, int n_angle, int return_od, const int32_t* layers_h,
+                               int n_lay, int t_pos, const float* G_tau, const float* G_Lu, const float* G_Ld, int64_t ld_G,
+                               int n_vec, double* out, void* stream) {
+  if (!dOD_dT) RTX_FAIL("dOD_dT is NULL");
+  return tud_vjp_run(OD, dOD_dT, dOD_dT, true, ld, 0.5, K, n_spec, tau, ld_tau, grid, n_layers, T_h, n_alt, mask_h, mu, n_down, n_angle,
+                     return_od, layers_h, n_lay, t_pos, G_tau, G_Lu, G_Ld, ld_G, n_vec, out, stream);
 }

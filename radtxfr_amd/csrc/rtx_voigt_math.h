@@ -64,6 +64,46 @@ __device__ __forceinline__ F weideman_re(F x, F y) {
   return fma((F)2, fma(pr, i2r, -(pi * i2i)), (F)INV_SQRT_PI * ir);
 }
 
+// w(x+iy) = K + iL by the same expansion, both halves kept (rtx_voigt_sum_dt: the temperature derivative of a Voigt line
+// needs Im w beside Re w). weideman_re's operations in its order -- its real part is weideman_re's bit for bit -- with
+// the imaginary part of the last step formed beside the real one. A sibling, not a change: weideman_re stays as it is.
+template <typename F>
+__device__ __forceinline__ void weideman_cplx(F x, F y, F& K, F& Lw) {
+  const F L = (F)W24_L;
+  constexpr const F* coef = []() constexpr -> const F* { if constexpr (sizeof(F) == 4) return (const F*)W24F; else return (const F*)W24D; }();
+  const F dr = L + y, nr = L - y;
+  const F dd = fma(dr, dr, x * x);
+  F inv;
+  if constexpr (sizeof(F) == 4) {
+    inv = __builtin_amdgcn_rcpf(dd);
+    inv = fma(fma(-dd, inv, (F)1), inv, inv);
+  } else {
+    inv = __builtin_amdgcn_rcp(dd);
+    inv = fma(fma(-dd, inv, (F)1), inv, inv);
+    inv = fma(fma(-dd, inv, (F)1), inv, inv);
+  }
+  const F Zr = fma(nr, dr, -(x * x)) * inv;
+  const F Zi = (x * (nr + dr)) * inv;
+  const F Wr = fma(Zr, Zr, -(Zi * Zi)), Wi = (F)2 * Zr * Zi;
+  const F r = (F)2 * Wr;
+  const F ns = -fma(Wr, Wr, Wi * Wi);
+  F ob1 = coef[0], ob2 = (F)0, eb1 = coef[1], eb2 = (F)0;
+#pragma unroll
+  for (int k = 2; k < 22; k += 2) {
+    const F ob0 = fma(r, ob1, fma(ns, ob2, coef[k]));
+    const F eb0 = fma(r, eb1, fma(ns, eb2, coef[k + 1]));
+    ob2 = ob1; ob1 = ob0; eb2 = eb1; eb1 = eb0;
+  }
+  const F or_ = fma(ob1, Wr, fma(ns, ob2, coef[22])), oi = ob1 * Wi;
+  const F er = fma(eb1, Wr, fma(ns, eb2, coef[23])), ei = eb1 * Wi;
+  const F pr = fma(or_, Zr, fma(-oi, Zi, er));
+  const F pi = fma(or_, Zi, fma(oi, Zr, ei));
+  const F ir = dr * inv, ii = x * inv;
+  const F i2r = fma(ir, ir, -(ii * ii)), i2i = (F)2 * ir * ii;
+  K = fma((F)2, fma(pr, i2r, -(pi * i2i)), (F)INV_SQRT_PI * ir);
+  Lw = fma((F)2, fma(pr, i2i, pi * i2r), (F)INV_SQRT_PI * ii);
+}
+
 // Re w(x+iy) for |z| >= 6 by the asymptotic series  w ~ (i/(sqrt(pi) z)) sum_k (2k-1)!! / (2 z^2)^k, k = 0..5.
 // Against the Weideman-24 value (what the reference computes inside |x|+y<15) the truncation error is < 6.5e-8
 // for y >= 6 (checked in fp64 over the whole band); evaluated in fp32 it is at rounding level (3e-7).

@@ -1318,6 +1318,62 @@ def voigt_sum_window(lines, grid, T, T_win, p_atm, weight, out_f32, qratio=None,
     return out_f32
 
 
+DT_METHODS = ("fd", "analytic")
+
+
+def check_dT_method(dT_method):
+    """Raise ValueError unless dT_method names a way to form dOD/dT (host-only check)."""
+    if dT_method not in DT_METHODS:
+        raise ValueError("dT_method: %r, expected one of %r" % (dT_method, DT_METHODS))
+
+
+def species_dlnq_dT(species, T_layers, weight=None):
+    """d ln(qratio) / dT [nS][nL] = -Q'(T_k) / Q(T_k) from TIPS-2011 (tips.partition_sums_dT: analytic). A species that
+    species_factors leaves at q = 1 (no isotopologue, or weight all zero) has derivative 0."""
+    nS, nL = len(species), len(T_layers)
+    out = np.zeros((nS, nL))
+    if weight is None:
+        use = [s for s, mi in enumerate(species) if mi != (0, 0)]
+    else:
+        live = np.asarray(weight).reshape(nS, -1).any(axis=1)
+        use = [s for s, mi in enumerate(species) if mi != (0, 0) and live[s]]
+    if use:
+        key = [species[s] for s in use]
+        out[use] = -tips.partition_sums_dT(key, T_layers) / tips.partition_sums(key, T_layers)
+    return out
+
+
+def voigt_sum_dT(lines, grid, T, p_atm, weight, out_f32=None, dlnw_dT=None, out_f64=None, dil_air=1.0, dil_self=0.0,
+                 omega_wing=0.0, omega_wing_hw=50.0, intensity_threshold=0.0, scale=1.0, qratio=None, mass=None, dlnq_dT=None):
+    """Analytic temperature derivative of voigt_sum's Voigt line-sum (rtx_line_prep_dt + rtx_voigt_sum_dt): per layer,
+    d/dT of the sum at (T, p) with every line's window held fixed. dlnw_dT [nS][nL] (or broadcastable): d ln(weight) / dT,
+    default -1/T, the optical-depth weights of layer_weights_od. dlnq_dT: d ln(qratio) / dT, default TIPS-2011's own
+    derivative (required with a qratio of the caller's). Uniform grids (a Grid), the Voigt profile and the call-wide
+    dil_air / dil_self only. Outputs [nL][grid.n] device tensors; after the call the plan also holds voigt_sum's records."""
+    lib = _lib.load()
+    if not isinstance(grid, Grid):
+        raise TypeError("voigt_sum_dT: a uniform Grid is required (explicit axes are not supported)")
+    if qratio is not None and dlnq_dT is None:
+        raise ValueError("voigt_sum_dT: a caller's qratio needs its dlnq_dT")
+    nL, env = _prologue_inputs(lines, T, p_atm, weight, None, qratio, mass)
+    T_a = env[0][0]
+    nS = len(lines.species)
+    if dlnq_dT is None:
+        dlnq_dT = species_dlnq_dT(lines.species, T_a, weight=weight)
+    if dlnw_dT is None:
+        dlnw_dT = -1.0 / T_a
+    dlnsw = np.ascontiguousarray(np.broadcast_to(np.asarray(dlnq_dT, dtype=np.float64), (nS, nL))
+                                 + np.broadcast_to(np.asarray(dlnw_dT, dtype=np.float64), (nS, nL)))
+    plan = lines.plan(nL, grid.n)
+    st = _stream_ptr()
+    _lib.check(lib.rtx_line_prep_dt(plan._h, lines._h, grid.byref(), nL, *(e[1] for e in env), dlnsw.ctypes.data_as(C.c_void_p),
+                                    float(dil_air), float(dil_self), float(omega_wing), float(omega_wing_hw),
+                                    float(intensity_threshold), float(scale), st))
+    _check_outputs(nL, grid.n, out_f32, out_f64)
+    _lib.check(lib.rtx_voigt_sum_dt(plan._h, grid.byref(), nL, _ptr(out_f32), _ptr(out_f64), grid.n, st))
+    return out_f32, out_f64
+
+
 def jacobian_species_columns(MF_ID, wrt):
     """Column of MFs_VAL each species entry of `wrt` differentiates (its first occurrence in MF_ID, as layer_weights_od maps
     a line's molecule to a column). Raises ValueError for an id not in MF_ID."""
@@ -1333,10 +1389,12 @@ def jacobian_species_columns(MF_ID, wrt):
 
 
 def _jacobian_stages(what, lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt, layers,
-                     fd_step_T, mark):
+                     fd_step_T, mark, dT_method="fd"):
     """The stages tud_jacobian and tud_vjp share: argument checks, the base state (exactly what compute_TUD runs), the
-    line-sums at T -+ fd_step_T with every line's window at T (skipped without "T" in wrt) and the line-sum of each species
-    of wrt at 1 ppmv. Returns (T, Z, layers, t_pos, tau, Lu, Ld, OD, ODp, ODm, K)."""
+    line-sums at T -+ fd_step_T with every line's window at T (skipped without "T" in wrt; dT_method "analytic": one
+    voigt_sum_dT instead, fd_step_T ignored) and the line-sum of each species of wrt at 1 ppmv.
+    Returns (T, Z, layers, t_pos, tau, Lu, Ld, OD, ODp, ODm, K); dT_method "analytic": ODp is dOD/dT itself and ODm None."""
+    check_dT_method(dT_method)
     T = np.ascontiguousarray(np.atleast_1d(np.asarray(T, dtype=np.float64)))
     Z = np.atleast_1d(np.asarray(Z, dtype=np.float64))
     nL = T.size
@@ -1351,7 +1409,7 @@ def _jacobian_stages(what, lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitu
     layers = np.arange(nL, dtype=np.int32) if layers is None else np.ascontiguousarray(np.asarray(layers, dtype=np.int32).ravel())
     if layers.size == 0 or layers.min() < 0 or layers.max() >= nL:
         raise ValueError("layers: indices must lie in [0, %d)" % nL)
-    if with_T and not (fd_step_T > 0.0):
+    if with_T and dT_method == "fd" and not (fd_step_T > 0.0):
         raise ValueError("fd_step_T must be > 0")
     th = np.asarray(theta_r, dtype=np.float64).ravel()
     if th.size != 1:
@@ -1366,7 +1424,11 @@ def _jacobian_stages(what, lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitu
         mark("base")
     n = grid.n
     ODp = ODm = None
-    if with_T:
+    if with_T and dT_method == "analytic":
+        ODp = torch.empty((nL, n), dtype=torch.float32, device=dev)  # the derivative itself; ODm stays None
+        w, p_atm = layer_weights_od(lines.species, T, P_pa, PL_km, MF_VAL, MF_ID)
+        voigt_sum_dT(lines, grid, T, p_atm, w, ODp)
+    elif with_T:
         ODp = torch.empty((nL, n), dtype=torch.float32, device=dev)
         ODm = torch.empty_like(ODp)
         for sgn, out in ((1.0, ODp), (-1.0, ODm)):
@@ -1391,7 +1453,7 @@ def _jacobian_stages(what, lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitu
 
 
 def tud_jacobian(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=False,
-                 wrt=("T",), layers=None, fd_step_T=0.5, block_bytes=JAC_BLOCK_BYTES, on_block=None, mark=None):
+                 wrt=("T",), layers=None, fd_step_T=0.5, block_bytes=JAC_BLOCK_BYTES, on_block=None, mark=None, dT_method="fd"):
     """compute_TUD's outputs and their Jacobian with respect to layer temperatures and mixing ratios, on the device.
 
     wrt: "T" and/or molecule ids of MF_ID (T, when present, is computed first whatever its position: J's wrt axis follows
@@ -1401,21 +1463,28 @@ def tud_jacobian(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes=(500,)
     (at most block_bytes of float32) is handed to the callback as soon as it is written, and None is returned for J.
     mark(name): called after each stage is enqueued ("base", "T", "species", "jacobian"), for timing.
 
-    dOD/dT is the central difference of two line-sums at T -+ fd_step_T with every line's window at T (voigt_sum_window);
+    dOD/dT is the central difference of two line-sums at T -+ fd_step_T with every line's window at T (voigt_sum_window),
+    or with dT_method="analytic" the closed-form derivative of the line-sum with the same fixed windows (voigt_sum_dT: one
+    sum instead of two, fd_step_T ignored); any other dT_method raises ValueError before device work.
     dOD/dMF of a species is the line-sum of that species alone at 1 ppmv (OD is linear in each mixing ratio)."""
     T, Z, layers, t_pos, tau, Lu, Ld, OD, ODp, ODm, K = _jacobian_stages(
         "tud_jacobian", lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt, layers,
-        fd_step_T, mark)
+        fd_step_T, mark, dT_method)
+    dOD = None
+    if dT_method == "analytic":
+        ODp, dOD = None, ODp
     J = tud_jacobian_from_od(OD, ODp, ODm, fd_step_T, K, tau, grid, T, Z, Altitudes=Altitudes, theta_r=theta_r,
                              N_angle=N_angle, returnOD=returnOD, layers=layers, t_pos=t_pos, block_bytes=block_bytes,
-                             on_block=on_block, mark=mark)
+                             on_block=on_block, mark=mark, dOD_dT=dOD)
     return tau, Lu, Ld, OD, J
 
 
 def tud_jacobian_from_od(OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z, Altitudes=(500,), theta_r=0.0, N_angle=30,
-                         returnOD=False, layers=None, t_pos=0, block_bytes=JAC_BLOCK_BYTES, on_block=None, mark=None):
+                         returnOD=False, layers=None, t_pos=0, block_bytes=JAC_BLOCK_BYTES, on_block=None, mark=None,
+                         dOD_dT=None):
     """rtx_tud_jacobian on given float32 device columns: OD [nL][>=n] (the base state), OD_plus / OD_minus at T -+ fd_step_T
-    (or both None: no T rows), K [n_spec][nL][.] OD per ppmv (or None), all with OD's row stride; tau [nAlt][>=n] the base
+    (or both None: no T rows; or dOD_dT [nL][.] instead of the three, the derivative itself: rtx_tud_jacobian_dod),
+    K [n_spec][nL][.] OD per ppmv (or None), all with OD's row stride; tau [nAlt][>=n] the base
     transmittances (None allowed with returnOD). Altitude masks and n_down are formed as TudRunner forms them. Returns J
     [n_wrt][n_layers][2 nAlt + 1][n], T's rows at t_pos and the species in K's order around them, or None with on_block
     (see tud_jacobian)."""
@@ -1431,13 +1500,15 @@ def tud_jacobian_from_od(OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z, A
     if th.size != 1:
         raise NotImplementedError("tud_jacobian: one slant path (theta_r) per call")
     mu = float(1.0 / np.cos(th[0]))
-    with_T = OD_plus is not None
+    if dOD_dT is not None and (OD_plus is not None or OD_minus is not None):
+        raise ValueError("tud_jacobian_from_od: dOD_dT replaces OD_plus / OD_minus / fd_step_T")
+    with_T = OD_plus is not None or dOD_dT is not None
     n_spec = 0 if K is None else int(K.shape[0])
     n = grid.n
     ld = OD.stride(0)
     assert OD.dtype == torch.float32 and OD.is_cuda and OD.dim() == 2 and OD.shape[0] == nL and OD.shape[1] >= n
     assert OD.stride(1) == 1
-    for t in (OD_plus, OD_minus):
+    for t in (OD_plus, OD_minus, dOD_dT):
         assert t is None or (t.dtype == torch.float32 and t.shape == OD.shape and t.stride() == OD.stride())
     if K is not None:
         assert K.dtype == torch.float32 and K.dim() == 3 and K.shape[1] == nL and K.shape[2] >= n
@@ -1458,10 +1529,13 @@ def tud_jacobian_from_od(OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z, A
         k1 = min(k0 + nb, layers.size)
         blk = torch.empty((n_wrt, k1 - k0, nrow, n), dtype=torch.float32, device=dev)
         lay = np.ascontiguousarray(layers[k0:k1])
-        _lib.check(lib.rtx_tud_jacobian(
-            _ptr(OD), _ptr(OD_plus), _ptr(OD_minus), ld, float(fd_step_T), _ptr(K), n_spec, _ptr(tau),
-            tau.stride(0) if tau is not None else 0, grid.byref(), nL, T_p, nA, mask.ctypes.data_as(C.c_void_p), mu, n_down, int(N_angle),
-            int(bool(returnOD)), lay.ctypes.data_as(C.c_void_p), lay.size, t_pos, _ptr(blk), n, st))
+        tail = (_ptr(K), n_spec, _ptr(tau), tau.stride(0) if tau is not None else 0, grid.byref(), nL, T_p, nA,
+                mask.ctypes.data_as(C.c_void_p), mu, n_down, int(N_angle), int(bool(returnOD)), lay.ctypes.data_as(C.c_void_p),
+                lay.size, t_pos, _ptr(blk), n, st)
+        if dOD_dT is not None:
+            _lib.check(lib.rtx_tud_jacobian_dod(_ptr(OD), _ptr(dOD_dT), ld, *tail))
+        else:
+            _lib.check(lib.rtx_tud_jacobian(_ptr(OD), _ptr(OD_plus), _ptr(OD_minus), ld, float(fd_step_T), *tail))
         if mark:
             mark("jacobian")
         if on_block is not None:
@@ -1493,9 +1567,9 @@ def _cotangent(G, lead, n, what):
 
 
 def tud_vjp_from_od(OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z, G_tau=None, G_Lu=None, G_Ld=None, Altitudes=(500,),
-                    theta_r=0.0, N_angle=30, returnOD=False, layers=None, t_pos=0):
-    """rtx_tud_vjp on given float32 device columns (as tud_jacobian_from_od takes them): the adjoint of that Jacobian,
-    grad[v][w][k] = sum over wavenumbers and rows of G[v][row] J[w][k][row], float64 on the device, [n_vec][n_wrt][n_layers],
+                    theta_r=0.0, N_angle=30, returnOD=False, layers=None, t_pos=0, dOD_dT=None):
+    """rtx_tud_vjp on given float32 device columns (as tud_jacobian_from_od takes them, dOD_dT included): the adjoint of that
+    Jacobian, grad[v][w][k] = sum over wavenumbers and rows of G[v][row] J[w][k][row], float64 on the device, [n_vec][n_wrt][n_layers],
     without J being stored. G_tau, G_Lu: [n_vec][nAlt][>= n], G_Ld: [n_vec][>= n], float32 (NumPy or torch), the vector
     axis optional; a group left None is not evaluated (no G_Ld: no downwelling sweeps; no G_tau: tau may be None). The
     vectors go to the library VJP_VEC_GROUP at a time; the grouping, like the choice and order of layers, changes no bit."""
@@ -1511,14 +1585,16 @@ def tud_vjp_from_od(OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z, G_tau=
     if th.size != 1:
         raise NotImplementedError("tud_vjp: one slant path (theta_r) per call")
     mu = float(1.0 / np.cos(th[0]))
-    with_T = OD_plus is not None
+    if dOD_dT is not None and (OD_plus is not None or OD_minus is not None):
+        raise ValueError("tud_vjp_from_od: dOD_dT replaces OD_plus / OD_minus / fd_step_T")
+    with_T = OD_plus is not None or dOD_dT is not None
     n_spec = 0 if K is None else int(K.shape[0])
     n = grid.n
     nA = Z_s.size
     ld = OD.stride(0)
     assert OD.dtype == torch.float32 and OD.is_cuda and OD.dim() == 2 and OD.shape[0] == nL and OD.shape[1] >= n
     assert OD.stride(1) == 1
-    for t in (OD_plus, OD_minus):
+    for t in (OD_plus, OD_minus, dOD_dT):
         assert t is None or (t.dtype == torch.float32 and t.shape == OD.shape and t.stride() == OD.stride())
     if K is not None:
         assert K.dtype == torch.float32 and K.dim() == 3 and K.shape[1] == nL and K.shape[2] >= n
@@ -1559,19 +1635,21 @@ def tud_vjp_from_od(OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z, G_tau=
     for v0 in range(0, n_vec, group):
         v1 = min(v0 + group, n_vec)
         part = lambda g: None if g is None else C.c_void_p(g.data_ptr() + 4 * v0 * vstride[id(g)])
-        _lib.check(lib.rtx_tud_vjp(
-            _ptr(OD), _ptr(OD_plus), _ptr(OD_minus), ld, float(fd_step_T), _ptr(K), n_spec, _ptr(tau),
-            tau.stride(0) if tau is not None else 0, grid.byref(), nL, T_p, nA, mask.ctypes.data_as(C.c_void_p), mu, n_down,
-            int(N_angle), int(bool(returnOD)), layers.ctypes.data_as(C.c_void_p), layers.size, t_pos, part(G_tau), part(G_Lu),
-            part(G_Ld), ld_G, v1 - v0, _ptr(out[v0:v1]), st))
+        tail = (_ptr(K), n_spec, _ptr(tau), tau.stride(0) if tau is not None else 0, grid.byref(), nL, T_p, nA,
+                mask.ctypes.data_as(C.c_void_p), mu, n_down, int(N_angle), int(bool(returnOD)), layers.ctypes.data_as(C.c_void_p),
+                layers.size, t_pos, part(G_tau), part(G_Lu), part(G_Ld), ld_G, v1 - v0, _ptr(out[v0:v1]), st)
+        if dOD_dT is not None:
+            _lib.check(lib.rtx_tud_vjp_dod(_ptr(OD), _ptr(dOD_dT), ld, *tail))
+        else:
+            _lib.check(lib.rtx_tud_vjp(_ptr(OD), _ptr(OD_plus), _ptr(OD_minus), ld, float(fd_step_T), *tail))
     return out
 
 
 def tud_vjp(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, G_tau=None, G_Lu=None, G_Ld=None, Altitudes=(500,), theta_r=0.0,
-            N_angle=30, returnOD=False, wrt=("T",), layers=None, fd_step_T=0.5, mark=None, cotangents=None):
+            N_angle=30, returnOD=False, wrt=("T",), layers=None, fd_step_T=0.5, mark=None, cotangents=None, dT_method="fd"):
     """compute_TUD's outputs and the gradient of a scalar cost with respect to layer temperatures and mixing ratios, given
     the cost's cotangents on the outputs: tud_jacobian's stages (the same base state, T -+ fd_step_T line-sums and species
-    line-sums) followed by rtx_tud_vjp instead of rtx_tud_jacobian. wrt, layers, fd_step_T as tud_jacobian; G_* as
+    line-sums) followed by rtx_tud_vjp instead of rtx_tud_jacobian. wrt, layers, fd_step_T, dT_method as tud_jacobian; G_* as
     tud_vjp_from_od. Returns (tau, Lu, Ld, OD, grad), grad float64 [n_vec][n_wrt][n_layers] on the device, its wrt axis
     following `wrt`. mark(name): after each stage ("base", "T", "species", "vjp").
     cotangents: instead of G_tau / G_Lu / G_Ld, a function (tau, Lu, Ld) -> (G_tau, G_Lu, G_Ld) called once the base state
@@ -1579,13 +1657,17 @@ def tud_vjp(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, G_tau=None, G_Lu=None
     adjoint reads tau, Lu and Ld). The optical depths are computed once either way."""
     if cotangents is not None and (G_tau is not None or G_Lu is not None or G_Ld is not None):
         raise ValueError("tud_vjp: cotangents= and G_tau / G_Lu / G_Ld exclude each other")
+    check_dT_method(dT_method)
     T, Z, layers, t_pos, tau, Lu, Ld, OD, ODp, ODm, K = _jacobian_stages(
         "tud_vjp", lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt, layers,
-        fd_step_T, mark)
+        fd_step_T, mark, dT_method)
+    dOD = None
+    if dT_method == "analytic":
+        ODp, dOD = None, ODp
     if cotangents is not None:
         G_tau, G_Lu, G_Ld = cotangents(tau, Lu, Ld)
     grad = tud_vjp_from_od(OD, ODp, ODm, fd_step_T, K, tau, grid, T, Z, G_tau=G_tau, G_Lu=G_Lu, G_Ld=G_Ld, Altitudes=Altitudes,
-                           theta_r=theta_r, N_angle=N_angle, returnOD=returnOD, layers=layers, t_pos=t_pos)
+                           theta_r=theta_r, N_angle=N_angle, returnOD=returnOD, layers=layers, t_pos=t_pos, dOD_dT=dOD)
     if mark:
         mark("vjp")
     return tau, Lu, Ld, OD, grad

@@ -562,9 +562,11 @@ def compute_TUD_batch(Xmin, Xmax, atmospheres, opts=options, reduce=None, device
 JACOBIAN_HOST_LIMIT = 4 << 30  # bytes of full-resolution float64 results compute_TUD_jacobian returns without reduce=
 
 
-def _jacobian_args(Xmin, Xmax, o, wrt, layers, reduce, fd_step_T, host_result=True):
+def _jacobian_args(Xmin, Xmax, o, wrt, layers, reduce, fd_step_T, host_result=True, dT_method="fd"):
     """compute_TUD_jacobian's argument checks, all on the host (no device is touched): (wrt, layers, nX). host_result=False:
     the caller returns no J (compute_TUD_vjp), so the size of a full-resolution J on the host is not a concern."""
+    if dT_method not in engine.DT_METHODS:
+        raise ValueError("compute_TUD_jacobian: dT_method=%r, expected one of %r" % (dT_method, engine.DT_METHODS))
     if o.get("broadening") is not None:
         raise NotImplementedError("compute_TUD_jacobian: broadening=%r is not supported (with self-broadening dOD/dMF is no "
                                   "longer OD per ppmv); use broadening=None" % (o.get("broadening"),))
@@ -592,7 +594,7 @@ def _jacobian_args(Xmin, Xmax, o, wrt, layers, reduce, fd_step_T, host_result=Tr
         raise ValueError("compute_TUD_jacobian: layers must be a non-empty sequence of layer indices")
     if lay.min() < 0 or lay.max() >= nL:
         raise ValueError("compute_TUD_jacobian: layer index outside [0, %d)" % nL)
-    if "T" in wrt and not (float(fd_step_T) > 0.0):
+    if "T" in wrt and dT_method == "fd" and not (float(fd_step_T) > 0.0):
         raise ValueError("compute_TUD_jacobian: fd_step_T=%r must be > 0" % (fd_step_T,))
     nX = int(np.ceil((Xmax - Xmin) / o["DVOUT"]))  # make_spectral_axis's count
     nZ = np.array([o["Altitudes"]]).size
@@ -609,7 +611,7 @@ def _jacobian_args(Xmin, Xmax, o, wrt, layers, reduce, fd_step_T, host_result=Tr
     return wrt, np.ascontiguousarray(lay, dtype=np.int32), nX
 
 
-def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, reduce=None, fd_step_T=0.5, **kwargs):
+def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, reduce=None, fd_step_T=0.5, dT_method="fd", **kwargs):
     """compute_TUD and the derivatives of its outputs with respect to layer temperatures and mixing ratios in one call:
     what the reference's caller builds from 1 + 3 x 66 perturbed atmospheres (Generate_LWIR_TUD.py:55-71, JacIn, one
     layer and one quantity at a time, relStep 0.001) -- here closed-form chain rule through the TUD recurrences.
@@ -629,6 +631,9 @@ def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, redu
     dOD_l/dT_l is the central difference of line-sums at T -+ fd_step_T [K] with every line's window held at the base T:
     the derivative of the truncated line-sum with each line's support fixed (the reference's cut-off OmegaWingHW x width
     moves with T; a finite difference of it carries those steps). Everything else is analytic.
+    dT_method="analytic": dOD_l/dT_l is the closed-form derivative of the Voigt line-sum with the same fixed windows instead
+    (engine.voigt_sum_dT): one line-sum in place of the two, no step to choose (fd_step_T is ignored). The
+    default "fd" returns what it always did; any other value raises ValueError.
     reduce = dict(dX=..., N=4, window="hanning"): reduceResolution of the base outputs and of every J row on the device
     (engine.reduce_resolution_cached). Without it, full-resolution results above 4 GiB are refused (ValueError): pass
     reduce= or fewer layers=. Arguments are checked before any device work.
@@ -638,7 +643,7 @@ def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, redu
     if o.get("xs_lut") is not None:
         raise NotImplementedError("compute_TUD_jacobian: xs_lut is not supported (dOD/dT is a difference of line-sums with fixed "
                                   "windows); use line_table=")
-    wrt, lay, _ = _jacobian_args(Xmin, Xmax, o, wrt, layers, reduce, fd_step_T)
+    wrt, lay, _ = _jacobian_args(Xmin, Xmax, o, wrt, layers, reduce, fd_step_T, dT_method=dT_method)
     Z = np.asarray(o["Zs"], dtype=np.float64)
     T = np.asarray(o["Ts"], dtype=np.float64)
     X_ = _cached_axis(Xmin, Xmax, o["DVOUT"])
@@ -670,7 +675,7 @@ def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, redu
     tau, Lu, Ld, _, _ = engine.tud_jacobian(tbl, grid, Z, T, o["Ps"], o["PLs"], o["MFs_VAL"], o["MFs_ID"], Altitudes=Z_s,
                                              theta_r=np.asarray(o["theta_r"], dtype=np.float64), N_angle=int(o["N_angle"]),
                                              returnOD=bool(o["returnOD"]), wrt=wrt, layers=lay, fd_step_T=float(fd_step_T),
-                                             on_block=on_block)
+                                             on_block=on_block, dT_method=dT_method)
     if red is not None:
         rows = torch.cat([tau, Lu, Ld[None, :]])
         X_out, r = engine.reduce_resolution_cached(rows, x0, grid.step, grid.n, red["dX"], N=red["N"], window=red["window"])
@@ -732,7 +737,7 @@ def _vjp_cotangents(cotangents, nX, nZ):
     return out, n_vecs.pop()
 
 
-def compute_TUD_vjp(Xmin, Xmax, cotangents, opts=options, wrt=("T",), layers=None, fd_step_T=0.5, **kwargs):
+def compute_TUD_vjp(Xmin, Xmax, cotangents, opts=options, wrt=("T",), layers=None, fd_step_T=0.5, dT_method="fd", **kwargs):
     """compute_TUD and the gradient of a scalar cost of its outputs with respect to layer temperatures and mixing ratios:
     the transpose of compute_TUD_jacobian's J applied to the cost's cotangents, without J ever being stored (reverse mode;
     DESIGN 4.16).
@@ -742,7 +747,7 @@ def compute_TUD_vjp(Xmin, Xmax, cotangents, opts=options, wrt=("T",), layers=Non
     it is). An optional trailing axis of length n_vec carries several cotangent vectors at once (they share all the work
     up to the contraction). A key left out is a row group that is not evaluated: without "Ld" the downwelling stream
     sweeps, the expensive part of the Jacobian, are not run.
-    kwargs, wrt, layers, fd_step_T: as compute_TUD_jacobian, with the same definition of every derivative. Returns
+    kwargs, wrt, layers, fd_step_T, dT_method: as compute_TUD_jacobian, with the same definition of every derivative. Returns
     (X, tau, La, Ld, grad): X, tau, La, Ld bit-identical to compute_TUD with the same kwargs; grad {wrt entry: float64
     [n_layers]}, or [n_layers][n_vec] when a vector axis is given:
       grad[w][k(, v)] = sum over X and over the outputs with a cotangent of cotangent[(X, row, v)] * J[w][row][X, k],
@@ -762,7 +767,7 @@ def compute_TUD_vjp(Xmin, Xmax, cotangents, opts=options, wrt=("T",), layers=Non
         raise NotImplementedError("compute_TUD_vjp: xs_lut is not supported (dOD/dT is a difference of line-sums with fixed "
                                   "windows); use line_table=")
     try:
-        wrt, lay, nX = _jacobian_args(Xmin, Xmax, o, wrt, layers, None, fd_step_T, host_result=False)
+        wrt, lay, nX = _jacobian_args(Xmin, Xmax, o, wrt, layers, None, fd_step_T, host_result=False, dT_method=dT_method)
     except (ValueError, NotImplementedError) as e:
         raise type(e)(str(e).replace("compute_TUD_jacobian", "compute_TUD_vjp")) from None
     Z_s = np.array([o["Altitudes"]]).ravel()
@@ -777,7 +782,8 @@ def compute_TUD_vjp(Xmin, Xmax, cotangents, opts=options, wrt=("T",), layers=Non
     tau, Lu, Ld, _, grad = engine.tud_vjp(tbl, grid, Z, T, o["Ps"], o["PLs"], o["MFs_VAL"], o["MFs_ID"], G_tau=G.get("tau"),
                                           G_Lu=G.get("La"), G_Ld=G.get("Ld"), Altitudes=Z_s,
                                           theta_r=np.asarray(o["theta_r"], dtype=np.float64), N_angle=int(o["N_angle"]),
-                                          returnOD=bool(o["returnOD"]), wrt=wrt, layers=lay, fd_step_T=float(fd_step_T))
+                                          returnOD=bool(o["returnOD"]), wrt=wrt, layers=lay, fd_step_T=float(fd_step_T),
+                                          dT_method=dT_method)
     (tau_h, Lu_h, Ld_h), done = _rows_to_host_f64([tau, Lu, Ld[None, :]])
     grad_h = grad.cpu().numpy()  # [n_vec][n_wrt][n_layers]
     done.synchronize()
@@ -789,7 +795,7 @@ def compute_TUD_vjp(Xmin, Xmax, cotangents, opts=options, wrt=("T",), layers=Non
 
 
 def compute_band_radiance_vjp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, cotangent, opts=options, wrt=("T",), layers=None,
-                              fd_step_T=0.5, **kwargs):
+                              fd_step_T=0.5, dT_method="fd", **kwargs):
     """At-sensor band radiances over a surface and the gradient of a scalar cost defined on them, in one call: the
     line-sums (base, T -+ fd_step_T, each species of wrt), compute_TUD's tau / La / Ld, the band radiances of
     sensor.band_radiance_srf_fused under the sensor's response tables, their adjoint (sensor.band_radiance_srf_vjp) and
@@ -799,7 +805,7 @@ def compute_band_radiance_vjp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, co
     sensor: a sensor.Sensor; Xk [nk] the emissivity knots [cm^-1], emis_knots [nk][nE] (float32; NumPy or a torch tensor);
     Ts_surface: a scalar or a 1-D sequence of surface temperatures [K]. cotangent = d cost / d L, laid out like L:
     [nB][nE] for a scalar Ts_surface, [nT][nB][nE] for a sequence, with an optional trailing axis of n_vec cotangent
-    vectors (they share everything up to the sensor adjoint). kwargs, wrt, layers, fd_step_T as compute_TUD_vjp, with
+    vectors (they share everything up to the sensor adjoint). kwargs, wrt, layers, fd_step_T, dT_method as compute_TUD_vjp, with
     exactly one sensor altitude and returnOD=False. Returns (X_out, L, grad):
       X_out  sensor.centres;
       L      float32 NumPy, bit-identical to band_radiance_srf_fused on compute_TUD's outputs (NaN for a band with no
@@ -822,7 +828,7 @@ def compute_band_radiance_vjp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, co
     if Z_s.size != 1:
         raise NotImplementedError(name + ": exactly one sensor altitude per call (got %d)" % Z_s.size)
     try:
-        wrt, lay, nX = _jacobian_args(Xmin, Xmax, o, wrt, layers, None, fd_step_T, host_result=False)
+        wrt, lay, nX = _jacobian_args(Xmin, Xmax, o, wrt, layers, None, fd_step_T, host_result=False, dT_method=dT_method)
     except (ValueError, NotImplementedError) as e:
         raise type(e)(str(e).replace("compute_TUD_jacobian", name)) from None
     Xk = np.ascontiguousarray(np.asarray(Xk, dtype=np.float64).ravel())
@@ -874,7 +880,8 @@ def compute_band_radiance_vjp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, co
 
     _, _, _, _, grad = engine.tud_vjp(tbl, grid, Z, T, o["Ps"], o["PLs"], o["MFs_VAL"], o["MFs_ID"], Altitudes=Z_s,
                                       theta_r=np.asarray(o["theta_r"], dtype=np.float64), N_angle=int(o["N_angle"]),
-                                      returnOD=False, wrt=wrt, layers=lay, fd_step_T=float(fd_step_T), cotangents=sensor_stage)
+                                      returnOD=False, wrt=wrt, layers=lay, fd_step_T=float(fd_step_T), cotangents=sensor_stage,
+                                      dT_method=dT_method)
     grad_h = grad.cpu().numpy()  # [n_vec][n_wrt][n_layers]
     L_h = kept["L"].cpu().numpy()
     dTs_h = torch.stack(kept["Ts"], dim=-1).cpu().numpy()    # Ts_surface's shape + [n_vec]

@@ -173,6 +173,48 @@ def partition_sums(species, T):
     return out
 
 
+def partition_sums_dT(species, T):
+    """dQ/dT[s][k]: the analytic derivative of the Lagrange polynomial partition_sum evaluates at T[k] -- the same 3- or
+    4-point stencil, chosen the same way (at a table node: the stencil partition_sum picks there) --
+    d/dT prod_{m != j} (T - A_m) = sum_{m != j} prod_{n != j, m} (T - A_n). No difference step."""
+    T = np.atleast_1d(np.asarray(T, dtype=np.float64))
+    if T.size and (T.min() < 70.0 or T.max() > 3000.0):
+        raise Exception("TIPS: T must be between 70K and 3000K.")
+    t = _tab()
+    A = t["tdat"]
+    npt = A.size
+    rows = []
+    for (M, I) in species:
+        key = (int(M), int(I))
+        if key not in t["q"] or not np.isfinite(t["q"][key][0]):
+            raise Exception("TIPS: no data for M,I = %d,%d." % key)
+        rows.append(t["q"][key])
+    B = np.stack(rows) if rows else np.zeros((0, npt))
+    I1 = np.searchsorted(A[1:], T, side="left") + 2
+    three = (I1 < 3) | (I1 == npt)
+    J = np.where(I1 < 3, 2, np.where(I1 == npt, npt - 1, I1 - 1))
+    idx = np.stack([J - 2, J - 1, J, np.minimum(J + 1, npt - 1)])  # [4][nT]; the 4th node unused where `three`
+    An = A[idx]
+    Bn = B[:, idx]
+    live = np.stack([np.ones(T.size, dtype=bool)] * 3 + [~three])  # nodes of each temperature's stencil
+    out = np.zeros((B.shape[0], T.size))
+    for j in range(4):
+        den = np.ones(T.size)
+        dnum = np.zeros(T.size)
+        for m in range(4):
+            if m == j:
+                continue
+            d = An[j] - An[m]
+            den = np.where(live[m], den * np.where(d != 0.0, d, 0.0001), den)
+            prod = np.ones(T.size)
+            for n in range(4):
+                if n != j and n != m:
+                    prod = np.where(live[n], prod * (T - An[n]), prod)
+            dnum = dnum + np.where(live[m], prod, 0.0)
+        out = out + np.where(live[j], dnum / den, 0.0) * Bn[:, j, :]
+    return out
+
+
 def abundance(M, I):
     """Natural abundance, misc/hapi.py:5088-5103."""
     try:
