@@ -831,6 +831,214 @@ def linesum_census(tbl, grid, T, p, omega_wing=0.0, omega_wing_hw=50.0, Diluent=
     return C
 
 
+# ---- the explicit-axis line-sum's prologue and decisions (line_prep_axis_kernel, rtx_voigt_axis.hip) --------------------
+# As above: which code evaluates which (line, tile, row), not an oracle of values.
+AX_TILE = 1024  # AX_TILE; rows of 64 points are counted from the tile's first point
+
+
+def axis_records(tbl, X, T, p, omega_wing=0.0, omega_wing_hw=50.0, Diluent=None, profile=0, lineshift=True):
+    """line_prep_axis_kernel for one layer, per line of `tbl` in ascending-nu (stable) order: window [lo, hi) =
+    bisect_right(X, nu -+ W) (empty: 0, 0; lo_raw / hi_raw before that), ic = bisect_right(X, nu), the band range
+    [zlo, zhi) = [bisect_left(X, sg0 - wz), bisect_right(X, sg0 + wz)) with wz = (15 - y + 0.01)/cte, clamped to the window
+    (zlo_raw / zhi_raw before the clamp), y (fp64; y32 as the record holds it), cte, sg0, W and maxhw = max over live lines
+    of max(ic - lo, hi - ic) + 1. profile 0 Voigt, 1 Lorentz (y = 15, cte = 1/Gamma0: no band), 2 Doppler (y = 0, the
+    function's own GammaD, Shift0 = delta_air p when lineshift)."""
+    X = np.asarray(X, dtype=np.float64)
+    nx = X.size
+    order = np.argsort(np.asarray(tbl["nu"], dtype=np.float64), kind="stable")
+    sub = {k: np.asarray(v)[order] for k, v in tbl.items()}
+    P = line_params(sub, T, p, Diluent=Diluent)
+    nu = np.asarray(sub["nu"], dtype=np.float64)
+    GammaD, Gamma0, Shift0 = P["GammaD"], P["Gamma0"], P["Shift0"]
+    if profile == 2:
+        t = _tables()
+        mass = np.array([t["mass"][(int(m), int(i))] for m, i in zip(P["M"], P["I"])])
+        GammaD = (1.1774100225 / 2.99792458e8) * np.sqrt(1.3806503e-23 / 1.66053873e-27) * np.sqrt(T) * nu / np.sqrt(mass)
+        Gamma0 = np.zeros(nu.size)
+        Shift0 = (np.asarray(sub["delta_air"], dtype=np.float64) if lineshift else np.zeros(nu.size)) * p / PREF
+        W = np.maximum(omega_wing, omega_wing_hw * GammaD)
+    elif profile == 1:
+        W = np.maximum(omega_wing, omega_wing_hw * Gamma0)
+    else:
+        W = np.maximum(omega_wing, np.maximum(omega_wing_hw * Gamma0, omega_wing_hw * GammaD))
+    lo_raw = np.searchsorted(X, nu - W, side="right")
+    hi_raw = np.searchsorted(X, nu + W, side="right")
+    live = hi_raw > lo_raw
+    lo, hi = np.where(live, lo_raw, 0), np.where(live, hi_raw, 0)
+    ic = np.searchsorted(X, nu, side="right")
+    sg0 = nu + Shift0
+    if profile == 1:
+        cte, y = 1.0 / Gamma0, np.full(nu.size, 15.0)
+    else:
+        cte = np.sqrt(np.log(2.0)) / GammaD
+        y = Gamma0 * cte
+    wz = (15.0 - y + 0.01) / cte
+    zlo_raw = np.searchsorted(X, sg0 - wz, side="left")
+    zhi_raw = np.searchsorted(X, sg0 + wz, side="right")
+    has = (y < 15.0) & live
+    zlo = np.where(has, np.maximum(zlo_raw, lo), 0)
+    zhi = np.maximum(np.where(has, np.minimum(zhi_raw, hi), 0), zlo)
+    hw = np.where(live, np.maximum(ic - lo, hi - ic) + 1, 0)
+    return {"lo": lo, "hi": hi, "lo_raw": lo_raw, "hi_raw": hi_raw, "live": live, "ic": ic, "zlo": zlo, "zhi": zhi,
+            "zlo_raw": zlo_raw, "zhi_raw": zhi_raw, "has_band": has, "y": y, "y32": y.astype(np.float32), "cte": cte, "sg0": sg0,
+            "nu": nu, "W": W, "wz": wz, "maxhw": int(hw.max()) if nu.size else 0, "order": order, "nx": nx}
+
+
+def axis_abscissa_f32(X, ia, sg0, cte, form="split"):
+    """axis_line's fp32 abscissa x_i = (X[i] - sg0) cte on the tile that starts at index ia, in np.float32 arithmetic.
+    form="split": the kernel's seven operations, (dh kh + ch) + (err(dh kh) + cl + dh kl + dl kh) on d_i = X[i] - X[ia],
+    c = (X[ia] - sg0) cte and cte as two floats each; form="fma": the one-FMA form fmaf((float)d_i, (float)cte, (float)c)
+    DESIGN 4.8 rejects. fmaf is the exact float64 product (two fp32 factors: 48 bits) plus the addend, rounded once to fp32."""
+    f32, f64 = np.float32, np.float64
+    X = np.asarray(X, dtype=f64)
+    dd = X[ia:ia + AX_TILE] - X[ia]
+    c64 = (X[ia] - f64(sg0)) * f64(cte)
+    fma = lambda a, b, c: (np.asarray(a, f64) * np.asarray(b, f64) + np.asarray(c, f64)).astype(f32)
+    if form == "fma":
+        return fma(dd.astype(f32), f32(cte), f32(c64))
+    if form != "split":
+        raise ValueError(form)
+    dh = dd.astype(f32)
+    dl = (dd - dh.astype(f64)).astype(f32)
+    ch = f32(c64)
+    cl = f32(c64 - f64(ch))
+    kh = f32(cte)
+    kl = f32(f64(cte) - f64(kh))
+    p = dh * kh
+    low = fma(dh, kl, fma(dl, kh, cl + fma(dh, kh, -p)))
+    return (p + ch) + low
+
+
+def axis_census(tbl, X, T, p, omega_wing=0.0, omega_wing_hw=50.0, Diluent=None, profile=0, lineshift=True):
+    """Which windows, candidate ranges and profile branches a rtx_line_prep_axis + rtx_voigt_sum_axis call reaches: a
+    Counter of labels over every layer, (line, tile) and 64-point row of the tile. T, p: per-layer sequences; Diluent:
+    {name: scalar or per-layer fractions}. The switch |x| + y < 15, its 2e-3 collar and the |z| < 8 ballot are evaluated in
+    fp64 on x = -((sg0 - X[i]) cte) (the kernel's fp32 x differs by ~1e-7 of |x|); y < 1 and y >= 6 on the record's fp32 y.
+
+    Windows (per line and layer): lo_row_aligned / lo_tile_aligned / hi_row_aligned / hi_tile_aligned (an edge inside the
+    axis on a multiple of 64 / 1024), one_row (both edges inside one row, neither on its boundary), one_point,
+    empty_between_points (nu -+ W fall between two neighbouring points: no record, no maxhw), edge_point_excluded (an axis
+    point exactly at nu - W), edge_point_included (one exactly at nu + W), covers_axis, centre_left / centre_right (ic = 0 /
+    nx with a window reaching in), centre_on_point, same_nu, band_empty (zlo == zhi before the clamp, window not empty),
+    band_clamped_lo / _hi (the window cuts the band), band_cut_by_axis_end, maxhw_layers_differ.
+    Candidates (per tile and layer): cand_0 ... cand_5, cand_not_mult4, cand_ge_256, idle_waves (1 to 3 candidates),
+    tile_zero_between (no candidate, neighbours on both sides with some), left_reaches_tile1 (ic = 0, window into tile 1),
+    outside_bracket (a line whose window meets the tile but whose ic lies outside [ia - maxhw, ib - 1 + maxhw]: must be 0)
+    and outside_bracket_without_margin (the same with maxhw - 1).
+    Rows (per line, tile, row that meets the window): band_w64 (y < 1: fp64 Weideman lanes), band_wei32, band_series_y6,
+    band_series_ballot (1 <= y < 6, no Weideman lane at |z| < 8), ballot_and_wei32_same_line, far_rational (some in-window
+    lane takes the rational), lorentz_rows, doppler_w64, doppler_dropped (in-window lanes of a Doppler record beyond the
+    band: 0); lanes: recheck_in / recheck_out (inside the collar, fp64 decides < 15 / >= 15), switch_fp32 (band lanes
+    within 0.01 of the switch but outside the collar: the fp32 comparison stands)."""
+    from collections import Counter
+    X = np.asarray(X, dtype=np.float64)
+    nx = X.size
+    T, p = np.atleast_1d(T), np.atleast_1d(p)
+    nL = T.size
+    C = Counter()
+    n_tiles = (nx + AX_TILE - 1) // AX_TILE
+    hws = []
+    for k in range(nL):
+        dil = None if Diluent is None else {n: float(np.broadcast_to(np.asarray(v, dtype=np.float64), (nL,))[k]) for n, v in Diluent.items()}
+        R = axis_records(tbl, X, float(T[k]), float(p[k]), omega_wing, omega_wing_hw, dil, profile, lineshift)
+        if k == 0:
+            ic = R["ic"]  # written from layer 0 (the same in every layer: it depends on nu and X alone)
+        assert np.array_equal(ic, R["ic"])
+        hws.append(R["maxhw"])
+        lo, hi, live, nu, W = R["lo"], R["hi"], R["live"], R["nu"], R["W"]
+        inside = live & (lo > 0)
+        C["lo_row_aligned"] += int(np.sum(inside & (lo % 64 == 0)))
+        C["lo_tile_aligned"] += int(np.sum(inside & (lo % AX_TILE == 0)))
+        C["hi_row_aligned"] += int(np.sum(live & (hi < nx) & (hi % 64 == 0)))
+        C["hi_tile_aligned"] += int(np.sum(live & (hi < nx) & (hi % AX_TILE == 0)))
+        C["one_row"] += int(np.sum(live & (lo // 64 == (hi - 1) // 64) & (lo % 64 != 0) & (hi % 64 != 0)))
+        C["one_point"] += int(np.sum(live & (hi - lo == 1)))
+        C["empty_between_points"] += int(np.sum(~live & (R["lo_raw"] > 0) & (R["lo_raw"] < nx)))
+        C["edge_point_excluded"] += int(np.sum(inside & (X[np.maximum(lo, 1) - 1] == nu - W)))
+        C["edge_point_included"] += int(np.sum(live & (X[np.maximum(hi, 1) - 1] == nu + W)))
+        C["covers_axis"] += int(np.sum(live & (lo == 0) & (hi == nx) & (ic > 0) & (ic < nx)))
+        C["centre_left"] += int(np.sum(live & (ic == 0)))
+        C["centre_right"] += int(np.sum(live & (ic == nx)))
+        C["centre_on_point"] += int(np.sum(live & (ic > 0) & (X[np.maximum(ic, 1) - 1] == nu)))
+        C["same_nu"] += int(np.sum(live[1:] & live[:-1] & (nu[1:] == nu[:-1])))
+        has = R["has_band"]
+        C["band_empty"] += int(np.sum(has & (R["zlo_raw"] == R["zhi_raw"])))
+        C["band_clamped_lo"] += int(np.sum(has & (R["zlo_raw"] < lo) & (R["zhi"] > R["zlo"])))
+        C["band_clamped_hi"] += int(np.sum(has & (R["zhi_raw"] > hi) & (R["zhi"] > R["zlo"])))
+        if nx:
+            C["band_cut_by_axis_end"] += int(np.sum(has & (R["zhi"] > R["zlo"]) &
+                                                    ((R["sg0"] - R["wz"] < X[0]) | (R["sg0"] + R["wz"] > X[-1]))))
+        counts = []
+        ballot_lines, wei_lines = set(), set()
+        for t in range(n_tiles):
+            ia, ib = t * AX_TILE, min((t + 1) * AX_TILE, nx)
+            reach = np.nonzero(live & (hi > ia) & (lo < ib))[0]
+            if reach.size == 0:
+                counts.append(0)
+                C["cand_0"] += 1
+                continue
+            first, last = int(reach[0]), int(reach[-1]) + 1
+            for margin, lab in ((0, "outside_bracket"), (1, "outside_bracket_without_margin")):
+                h = R["maxhw"] - margin
+                l0, l1 = np.searchsorted(ic, ia - h, side="left"), np.searchsorted(ic, ib - 1 + h, side="right")
+                C[lab] += int(first < l0) + int(last > l1)
+            cnt = last - first
+            counts.append(cnt)
+            if cnt <= 5:
+                C["cand_%d" % cnt] += 1
+            C["cand_not_mult4"] += int(cnt % 4 != 0)
+            C["cand_ge_256"] += int(cnt >= 256)
+            C["idle_waves"] += int(cnt < 4)
+            C["left_reaches_tile1"] += int(np.sum(ic[reach] == 0)) if t == 1 else 0
+            for l in reach:
+                t_lo, t_hi = max(int(lo[l]) - ia, 0), min(int(hi[l]), ib) - ia
+                rows = np.arange(t_lo >> 6, (t_hi + 63) >> 6)
+                if profile == 1:
+                    C["lorentz_rows"] += rows.size
+                    continue
+                zlo, zhi = int(R["zlo"][l]), int(R["zhi"][l])
+                row0 = ia + 64 * rows
+                is_band = (row0 + 64 > zlo) & (row0 < zhi)
+                far_lab = "doppler_dropped" if profile == 2 else "far_rational"
+                C[far_lab] += int(np.sum(~is_band))
+                y, y32 = float(R["y"][l]), float(R["y32"][l])
+                for r in rows[is_band]:
+                    i = ia + 64 * r + np.arange(64)
+                    i = i[i < ib]
+                    win = (i >= lo[l]) & (i < hi[l])
+                    in_band = (i >= zlo) & (i < zhi)
+                    x = -((R["sg0"][l] - X[i]) * R["cte"][l])
+                    s = np.abs(x) + y
+                    wz = in_band & (s < 15.0)
+                    if y32 < 1.0:
+                        if wz.any():
+                            C["doppler_w64" if profile == 2 else "band_w64"] += 1
+                    else:
+                        near = in_band & (np.abs(s - 15.0) < 2e-3)
+                        C["recheck_in"] += int(np.sum(near & (s < 15.0)))
+                        C["recheck_out"] += int(np.sum(near & ~(s < 15.0)))
+                        C["switch_fp32"] += int(np.sum(in_band & ~near & (np.abs(s - 15.0) < 0.01)))
+                        if wz.any():
+                            if y32 >= 6.0:
+                                C["band_series_y6"] += 1
+                            elif not np.any(wz & (x * x + y * y < 64.0)):
+                                C["band_series_ballot"] += 1
+                                ballot_lines.add(int(l))
+                            else:
+                                C["band_wei32"] += 1
+                                wei_lines.add(int(l))
+                    if np.any(win & ~wz):
+                        C[far_lab] += 1
+        C["ballot_and_wei32_same_line"] += len(ballot_lines & wei_lines)
+        c = np.asarray(counts)
+        if c.size >= 3:
+            some_before = np.maximum.accumulate(c)[:-2] > 0
+            some_after = np.maximum.accumulate(c[::-1])[::-1][2:] > 0
+            C["tile_zero_between"] += int(np.sum((c[1:-1] == 0) & some_before & some_after))
+    C["maxhw_layers_differ"] += int(len(set(hws)) > 1)
+    return C
+
+
 # ---- post-processing of TUD products (SURVEY 8f row 2) ----------------------------------------
 def smooth(x, window_len=11, window="hanning"):
     """radiative_transfer.py:1266-1324: reflect-pad by window_len-1 samples, convolve with the normalised

@@ -44,13 +44,10 @@ import pytest
 from oracle import cpu_ref as ref
 
 import linesum_cases as LC
+from linesum_metric import F, F32_FLOOR, HALO, TOL, _local_max, pointwise_err  # noqa: F401 (the metric of the module docstring)
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-5
-F = 1e-5
-HALO = 1024
-F32_FLOOR = 1e-36  # below fp32's normal range (1.2e-38) with a margin: compared absolutely
 CASE_TOL = {}  # case -> bound looser than TOL (none needed)
 SCATTER_VS_NODAL = 2e-6
 SCATTER_CASE_TOL = {"a_upper_atmosphere": 1e-5}  # the reference's Weideman-24 in far Doppler wings (module docstring)
@@ -64,38 +61,6 @@ def eng():
     from radtxfr_amd import _lib, engine
     _lib.load()
     return engine
-
-
-def _local_max(a, h=HALO):
-    """max |a_j| over |j - i| <= h, per row (doubling: max over [i, i + 2^k) from max over [i, i + 2^(k-1)))."""
-    a = np.abs(a)
-    n = a.shape[-1]
-    pad = np.full(a.shape[:-1] + (h,), 0.0)
-    b = np.concatenate([pad, a, pad], axis=-1)  # b[i + h] = a[i]
-    m, w = b.copy(), 1
-    while 2 * w <= h:
-        m[..., :-w] = np.maximum(m[..., :-w], m[..., w:])
-        w *= 2
-    # m[i] = max b[i, i + w); cover [i, i + 2h] with windows of length w
-    out = np.zeros_like(a)
-    for s in range(0, 2 * h + 1, w):
-        s = min(s, 2 * h + 1 - w)
-        out = np.maximum(out, m[..., s:s + n])
-    return out
-
-
-def pointwise_err(got, want):
-    """The module's metric over [layers][points]; inf if a structural zero of the oracle is not exactly 0."""
-    got = np.atleast_2d(np.asarray(got, dtype=np.float64))
-    want = np.atleast_2d(np.asarray(want, dtype=np.float64))
-    assert got.shape == want.shape, (got.shape, want.shape)
-    zero = want == 0.0
-    if np.any(got[zero] != 0.0):
-        return float("inf")
-    den = np.maximum(np.maximum(np.abs(want), F * _local_max(want)), F32_FLOOR)
-    e = np.abs(got - want) / den
-    e[zero] = 0.0
-    return float(np.max(e)) if e.size else 0.0
 
 
 def _engine_grid(eng, g):
