@@ -5,6 +5,7 @@ this package) and the C ABI (include/radtxfr_hip.h). Every compute call goes thr
 library; nothing here falls back to NumPy or to the oracle.
 """
 import ctypes as C
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -373,6 +374,15 @@ class VoigtPlan:
             pass
 
 
+def _live_species(species, weight):
+    """Indices of the species a prologue looks partition sums up for: those with an isotopologue and, given weight[nS][nL],
+    a non-zero weight in some layer -- the reference skips the others before any look-up (`continue`, misc/hapi.py:11066)."""
+    if weight is None:
+        return [s for s, mi in enumerate(species) if mi != (0, 0)]
+    live = np.asarray(weight).reshape(len(species), -1).any(axis=1)
+    return [s for s, mi in enumerate(species) if mi != (0, 0) and live[s]]
+
+
 def species_factors(species, T_layers, partitionFunction=None, weight=None):
     """qratio[nS][nL] = Q(Tref)/Q(T_k) (misc/hapi.py:11069-11070) and mass[nS] (:11086).
     A species whose weight[s][:] is all zero is filtered out by the reference BEFORE its partition sums and mass are
@@ -381,11 +391,7 @@ def species_factors(species, T_layers, partitionFunction=None, weight=None):
     nS, nL = len(species), len(T_layers)
     q = np.ones((nS, nL))
     mass = np.ones(nS)
-    if weight is None:
-        use = [s for s, mi in enumerate(species) if mi != (0, 0)]
-    else:
-        live = np.asarray(weight).reshape(nS, -1).any(axis=1)
-        use = [s for s, mi in enumerate(species) if mi != (0, 0) and live[s]]
+    use = _live_species(species, weight)
     if not use:
         return q, mass
     if partitionFunction is None or partitionFunction is tips.PYTIPS:
@@ -446,6 +452,30 @@ def diluent_mix(lines, diluent, nL):
     return len(idx), (idx, idx.ctypes.data_as(C.c_void_p)), (frac, frac.ctypes.data_as(C.c_void_p))
 
 
+def _host_axis(fn, X):
+    """An explicit spectral axis as the prologues take it: contiguous float64 on the host, finite and non-decreasing, as
+    the reference's bisect on the axis itself assumes (misc/hapi.py:11133-11134). ValueError in `fn`'s name otherwise."""
+    X = np.ascontiguousarray(np.asarray(X, dtype=np.float64).ravel())
+    if not np.all(np.isfinite(X)):
+        raise ValueError("%s: the axis has non-finite points" % fn)
+    if X.size > 1 and np.any(X[1:] < X[:-1]):
+        raise ValueError("%s: the axis must be non-decreasing (np.sort it)" % fn)
+    return X
+
+
+def _line_prep(plain, mix, head, lines, nL, diluent, dil_air, dil_self, omega_wing, omega_wing_hw, intensity_threshold, scale,
+               profile, st):
+    """One prologue call after its leading arguments `head` (everything up to mass): entry point `plain` with the call-wide
+    dil_air / dil_self or, with a `diluent` dict, entry point `mix` with diluent_mix's arguments (the loop over Diluent,
+    misc/hapi.py:11090), then the scalar tail the two share (include/radtxfr_hip.h)."""
+    tail = (float(omega_wing), float(omega_wing_hw), float(intensity_threshold), float(scale), int(profile), st)
+    if diluent is None:
+        _lib.check(plain(*head, float(dil_air), float(dil_self), *tail))
+    else:
+        n_dil, idx, frac = diluent_mix(lines, diluent, nL)
+        _lib.check(mix(*head, n_dil, idx[1], frac[1], *tail))
+
+
 def _check_outputs(nL, ld, out_f32, out_f64):
     for o, dt in ((out_f32, torch.float32), (out_f64, torch.float64)):
         if o is not None:
@@ -466,15 +496,8 @@ def voigt_sum(lines, grid, T, p_atm, weight, out_f32=None, out_f64=None, dil_air
     nL, env = _prologue_inputs(lines, T, p_atm, weight, partitionFunction, qratio, mass)
     plan = lines.plan(nL, grid.n)
     st = _stream_ptr()
-    if diluent is None:
-        _lib.check(lib.rtx_line_prep_profile(plan._h, lines._h, grid.byref(), nL, *(e[1] for e in env), float(dil_air),
-                                             float(dil_self), float(omega_wing), float(omega_wing_hw),
-                                             float(intensity_threshold), float(scale), int(profile), st))
-    else:
-        n_dil, idx, frac = diluent_mix(lines, diluent, nL)
-        _lib.check(lib.rtx_line_prep_mix(plan._h, lines._h, grid.byref(), nL, *(e[1] for e in env), n_dil, idx[1], frac[1],
-                                         float(omega_wing), float(omega_wing_hw), float(intensity_threshold), float(scale),
-                                         int(profile), st))
+    _line_prep(lib.rtx_line_prep_profile, lib.rtx_line_prep_mix, (plan._h, lines._h, grid.byref(), nL, *(e[1] for e in env)),
+               lines, nL, diluent, dil_air, dil_self, omega_wing, omega_wing_hw, intensity_threshold, scale, profile, st)
     ld = grid.n
     _check_outputs(nL, ld, out_f32, out_f64)
     if int(profile) == 3:  # speed-dependent Voigt: its own fp64 line-sum
@@ -492,11 +515,7 @@ def voigt_sum_axis(lines, X, T, p_atm, weight, out_f32=None, out_f64=None, dil_a
     11133-11134). profile 0 Voigt, 1 Lorentz, 2 Doppler (the speed-dependent sum needs a uniform grid).
     diluent: as for voigt_sum (rtx_line_prep_axis_mix; profiles 0, 1). Outputs are [nL][X.size] device tensors."""
     lib = _lib.load()
-    X = np.ascontiguousarray(np.asarray(X, dtype=np.float64).ravel())
-    if not np.all(np.isfinite(X)):
-        raise ValueError("voigt_sum_axis: the axis has non-finite points")
-    if X.size > 1 and np.any(X[1:] < X[:-1]):
-        raise ValueError("voigt_sum_axis: the axis must be non-decreasing (np.sort it)")
+    X = _host_axis("voigt_sum_axis", X)
     if int(profile) not in (0, 1, 2):
         raise NotImplementedError("voigt_sum_axis: profile %d; an explicit axis takes Voigt (0), Lorentz (1) or Doppler (2)"
                                   % int(profile))
@@ -504,15 +523,9 @@ def voigt_sum_axis(lines, X, T, p_atm, weight, out_f32=None, out_f64=None, dil_a
     nx = X.size
     plan = lines.plan(nL, max(nx, 1))
     st = _stream_ptr()
-    if diluent is None:
-        _lib.check(lib.rtx_line_prep_axis(plan._h, lines._h, X.ctypes.data_as(C.c_void_p), nx, nL, *(e[1] for e in env),
-                                          float(dil_air), float(dil_self), float(omega_wing), float(omega_wing_hw),
-                                          float(intensity_threshold), float(scale), int(profile), st))
-    else:
-        n_dil, idx, frac = diluent_mix(lines, diluent, nL)
-        _lib.check(lib.rtx_line_prep_axis_mix(plan._h, lines._h, X.ctypes.data_as(C.c_void_p), nx, nL, *(e[1] for e in env),
-                                              n_dil, idx[1], frac[1], float(omega_wing), float(omega_wing_hw),
-                                              float(intensity_threshold), float(scale), int(profile), st))
+    _line_prep(lib.rtx_line_prep_axis, lib.rtx_line_prep_axis_mix,
+               (plan._h, lines._h, X.ctypes.data_as(C.c_void_p), nx, nL, *(e[1] for e in env)),
+               lines, nL, diluent, dil_air, dil_self, omega_wing, omega_wing_hw, intensity_threshold, scale, profile, st)
     _check_outputs(nL, nx, out_f32, out_f64)
     _lib.check(lib.rtx_voigt_sum_axis(plan._h, nL, _ptr(out_f32), _ptr(out_f64), nx, st))
     return out_f32, out_f64
@@ -542,11 +555,7 @@ def _ht_prologue(lines, X, T, p_atm, weight, diluent, omega_wing, omega_wing_hw,
                  qratio, mass):
     """rtx_ht_prep on the table's cached HtPlan (grown on demand): (plan, n_states, nx)."""
     lib = _lib.load()
-    X = np.ascontiguousarray(np.asarray(X, dtype=np.float64).ravel())
-    if not np.all(np.isfinite(X)):
-        raise ValueError("ht_sum: the axis has non-finite points")
-    if X.size > 1 and np.any(X[1:] < X[:-1]):
-        raise ValueError("ht_sum: the axis must be non-decreasing (np.sort it)")
+    X = _host_axis("ht_sum", X)
     nL, env = _prologue_inputs(lines, T, p_atm, weight, partitionFunction, qratio, mass)
     lines.ht_sets(list(diluent))  # the HT columns of every diluent on the device, before the set indices are taken
     n_dil, idx, frac = diluent_mix(lines, diluent, nL)
@@ -708,15 +717,43 @@ def xs_od(lut, grid_or_offset, T, P_atm, PL, MF, ID, out_f32=None):
     return out_f32
 
 
+class TudGeometry(NamedTuple):
+    """What tud_geometry returns."""
+    Z_s: np.ndarray   # sensor altitudes [nAlt]
+    mu: np.ndarray    # slant factors 1 / cos(theta_r) [nMu]
+    mask: np.ndarray  # uint8 [nAlt][nL]: layer k lies below sensor altitude a (Z <= zs)
+    n_down: int       # layers the downwelling sweeps run over
+
+
+def tud_geometry(Z, Altitudes, theta_r):
+    """The sensor geometry of a TUD call as rtx_tud and its derivatives take it (radiative_transfer.py:346-370): a
+    TudGeometry of Z_s and mu (contiguous float64), the contiguous Z <= zs masks and n_down."""
+    Z = np.atleast_1d(np.asarray(Z, dtype=np.float64))
+    Z_s = np.array([Altitudes], dtype=np.float64).ravel()
+    mu = np.ascontiguousarray(np.array([1.0 / np.cos(np.asarray(theta_r, dtype=np.float64))], dtype=np.float64).ravel())
+    mask = np.ascontiguousarray(np.stack([(Z <= zs) for zs in Z_s]).astype(np.uint8))
+    n_down = int(mask[-1].sum())  # quirk 3: nL is overwritten by the LAST altitude's count (:353, :370)
+    return TudGeometry(Z_s, mu, mask, n_down)
+
+
+def _check_tud_outputs(tau, Lu, Ld, nrow, n):
+    """Assert that (tau, Lu, Ld) are float32 device tensors rtx_tud can write nrow rows of n points into -- tau / Lu
+    [nrow][>= n] with unit stride along the wavenumbers and a common row stride, Ld [>= n] -- and return that row stride,
+    the library's ld_out (include/radtxfr_hip.h)."""
+    for t in (tau, Lu):
+        assert t.dtype == torch.float32 and t.is_cuda and t.dim() == 2 and t.shape[0] == nrow
+        assert t.shape[1] >= n and t.stride(1) == 1 and t.stride(0) == tau.stride(0)
+    assert Ld.dtype == torch.float32 and Ld.is_cuda and Ld.numel() >= n and Ld.stride(0) == 1
+    return tau.stride(0) if tau.shape[0] > 1 else max(tau.shape[1], n)  # the stride of a size-1 dimension is arbitrary
+
+
 def tud(OD, grid, T, Z, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=False, per_angle=False, out=None):
     """tau[nAlt*nMu][n], Lu[nAlt*nMu][n], Ld[n] float32 device tensors from OD[nL][n] (rtx_tud).
     out=(tau, Lu, Ld): write into caller-owned tensors (tau/Lu [nAlt*nMu][>=n] with a common row stride),
     e.g. the rows of the packed block a wavenumber shard all-gathers."""
     lib = _lib.load()
     T = np.atleast_1d(np.asarray(T, dtype=np.float64))
-    Z = np.atleast_1d(np.asarray(Z, dtype=np.float64))
-    Z_s = np.array([Altitudes], dtype=np.float64).ravel()
-    mu_s = np.array([1.0 / np.cos(np.asarray(theta_r, dtype=np.float64))], dtype=np.float64).ravel()
+    Z_s, mu_s, mask, n_down = tud_geometry(Z, Altitudes, theta_r)
     nL = T.size
     assert OD.dtype == torch.float32 and OD.is_cuda and OD.dim() == 2 and OD.shape[0] == nL and OD.shape[1] >= grid.n
     assert OD.stride(1) == 1
@@ -743,8 +780,6 @@ def tud(OD, grid, T, Z, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=Fals
         if per_angle:
             return tau.view(-1, grid.n), Lu.view(-1, grid.n), Ld, (Z_s.size, mu_s.size), Ld_ang
         return tau.view(-1, grid.n), Lu.view(-1, grid.n), Ld, (Z_s.size, mu_s.size)
-    mask = np.ascontiguousarray(np.stack([(Z <= zs) for zs in Z_s]).astype(np.uint8))
-    n_down = int(mask[-1].sum())  # quirk 3: nL is overwritten by the LAST altitude's count (:353, :370)
     dev = OD.device
     if out is None:
         tau = torch.empty((Z_s.size * mu_s.size, grid.n), dtype=torch.float32, device=dev)
@@ -752,11 +787,7 @@ def tud(OD, grid, T, Z, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=Fals
         Ld = torch.empty((grid.n,), dtype=torch.float32, device=dev)
     else:
         tau, Lu, Ld = out
-        for t in (tau, Lu):
-            assert t.dtype == torch.float32 and t.is_cuda and t.dim() == 2 and t.shape[0] == Z_s.size * mu_s.size
-            assert t.shape[1] >= grid.n and t.stride(1) == 1 and t.stride(0) == tau.stride(0)
-        assert Ld.dtype == torch.float32 and Ld.is_cuda and Ld.numel() >= grid.n and Ld.stride(0) == 1
-    ld_out = tau.stride(0) if tau.shape[0] > 1 else max(tau.shape[1], grid.n)
+    ld_out = _check_tud_outputs(tau, Lu, Ld, Z_s.size * mu_s.size, grid.n)
     # rows of the per-stream output use the same leading dimension as tau / Lu (include/radtxfr_hip.h: [n_angle][ld_out])
     Ld_ang = torch.empty((int(N_angle), ld_out), dtype=torch.float32, device=dev) if per_angle else None
     T_h, T_p = _h(T)
@@ -793,12 +824,9 @@ class TudRunner:
             self._xs_off = xs_lut.align(grid) + grid.offset
         Z = np.atleast_1d(np.asarray(Z, dtype=np.float64))
         self.nL = int(Z.size if n_layers is None else n_layers)
-        Z_s = np.array([Altitudes], dtype=np.float64).ravel()
-        self.mu = np.ascontiguousarray(np.array([1.0 / np.cos(np.asarray(theta_r, dtype=np.float64))], dtype=np.float64).ravel())
+        Z_s, self.mu, self.mask, self.n_down = tud_geometry(Z, Altitudes, theta_r)
         if self.mu.size > TUD_MAX_MU:
             raise ValueError("TudRunner takes at most %d slant paths" % TUD_MAX_MU)
-        self.mask = np.ascontiguousarray(np.stack([(Z <= zs) for zs in Z_s]).astype(np.uint8))
-        self.n_down = int(self.mask[-1].sum())  # quirk 3: the LAST altitude's layer count (:353, :370)
         self.shape = (Z_s.size, self.mu.size)
         self.N_angle, self.returnOD = int(N_angle), int(bool(returnOD))
         dev = device()
@@ -823,13 +851,8 @@ class TudRunner:
 
     def set_outputs(self, tau, Lu, Ld):
         """Point the next run() at other output tensors (e.g. the other half of a double-buffered packed block)."""
-        nrow = self.shape[0] * self.shape[1]
-        for t in (tau, Lu):
-            assert t.dtype == torch.float32 and t.is_cuda and t.dim() == 2 and t.shape[0] == nrow
-            assert t.shape[1] >= self.grid.n and t.stride(1) == 1 and t.stride(0) == tau.stride(0)
-        assert Ld.dtype == torch.float32 and Ld.is_cuda and Ld.numel() >= self.grid.n and Ld.stride(0) == 1
+        self._ld_out = _check_tud_outputs(tau, Lu, Ld, self.shape[0] * self.shape[1], self.grid.n)
         self.tau, self.Lu, self.Ld = tau, Lu, Ld
-        self._ld_out = tau.stride(0) if tau.shape[0] > 1 else max(tau.shape[1], self.grid.n)
         self._ptrs = (C.c_void_p(tau.data_ptr()), C.c_void_p(Lu.data_ptr()), C.c_void_p(Ld.data_ptr()))
 
     def run(self, T, P_pa, PL_km, MF_VAL, MF_ID, partitionFunction=None):
@@ -860,13 +883,12 @@ class TudRunner:
         vp = C.c_void_p
         if self.foreign is not None:
             dil = broadening_fractions(lines.species, np.asarray(MF_VAL, dtype=np.float64).reshape(nL, -1), MF_ID, self.foreign)
-            n_dil, idx, frac = diluent_mix(lines, dil, nL)
             st = _stream_ptr()
             with trace_range("rtx_line_prep_mix + rtx_voigt_sum + rtx_tud"):
-                _lib.check(self.lib.rtx_line_prep_mix(
-                    self.plan._h, lines._h, self.grid.byref(), nL, vp(base), vp(base + 8 * nL), vp(base + 16 * nL),
-                    vp(base + 8 * (2 * nL + nS * nL)), vp(base + 8 * (2 * nL + 2 * nS * nL)), n_dil, idx[1], frac[1], 0.0, 50.0, 0.0,
-                    1.0, 0, st))
+                _line_prep(None, self.lib.rtx_line_prep_mix,
+                           (self.plan._h, lines._h, self.grid.byref(), nL, vp(base), vp(base + 8 * nL), vp(base + 16 * nL),
+                            vp(base + 8 * (2 * nL + nS * nL)), vp(base + 8 * (2 * nL + 2 * nS * nL))),
+                           lines, nL, dil, None, None, 0.0, 50.0, 0.0, 1.0, 0, st)
                 _lib.check(self.lib.rtx_voigt_sum(self.plan._h, self.grid.byref(), nL, vp(self.OD.data_ptr()), None,
                                                   self.OD.stride(0), st))
                 _lib.check(self.lib.rtx_tud(
@@ -1332,11 +1354,7 @@ def species_dlnq_dT(species, T_layers, weight=None):
     species_factors leaves at q = 1 (no isotopologue, or weight all zero) has derivative 0."""
     nS, nL = len(species), len(T_layers)
     out = np.zeros((nS, nL))
-    if weight is None:
-        use = [s for s, mi in enumerate(species) if mi != (0, 0)]
-    else:
-        live = np.asarray(weight).reshape(nS, -1).any(axis=1)
-        use = [s for s, mi in enumerate(species) if mi != (0, 0) and live[s]]
+    use = _live_species(species, weight)
     if use:
         key = [species[s] for s in use]
         out[use] = -tips.partition_sums_dT(key, T_layers) / tips.partition_sums(key, T_layers)
@@ -1388,12 +1406,28 @@ def jacobian_species_columns(MF_ID, wrt):
     return cols
 
 
+class JacobianStages(NamedTuple):
+    """What _jacobian_stages returns: the device columns tud_jacobian_from_od and tud_vjp_from_od take."""
+    T: np.ndarray        # layer temperatures, contiguous float64 [nL]
+    Z: np.ndarray        # layer altitudes, float64 [nL]
+    layers: np.ndarray   # int32 layer indices, in output order
+    t_pos: int           # position of "T" on the wrt axis
+    tau: torch.Tensor    # base state, float32: tau / Lu [nAlt][n], Ld [n], OD [nL][n]
+    Lu: torch.Tensor
+    Ld: torch.Tensor
+    OD: torch.Tensor
+    OD_plus: Optional[torch.Tensor]   # [nL][n] at T + fd_step_T, windows at T ("fd" with "T" in wrt, else None)
+    OD_minus: Optional[torch.Tensor]  # [nL][n] at T - fd_step_T, likewise
+    dOD_dT: Optional[torch.Tensor]    # [nL][n] the derivative itself ("analytic" with "T" in wrt, else None)
+    K: Optional[torch.Tensor]         # [n_spec][nL][n] OD per ppmv of each species of wrt, or None
+
+
 def _jacobian_stages(what, lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt, layers,
                      fd_step_T, mark, dT_method="fd"):
     """The stages tud_jacobian and tud_vjp share: argument checks, the base state (exactly what compute_TUD runs), the
     line-sums at T -+ fd_step_T with every line's window at T (skipped without "T" in wrt; dT_method "analytic": one
-    voigt_sum_dT instead, fd_step_T ignored) and the line-sum of each species of wrt at 1 ppmv.
-    Returns (T, Z, layers, t_pos, tau, Lu, Ld, OD, ODp, ODm, K); dT_method "analytic": ODp is dOD/dT itself and ODm None."""
+    voigt_sum_dT instead, fd_step_T ignored) and the line-sum of each species of wrt at 1 ppmv (what the reference's
+    caller gets from perturbed atmospheres, Generate_LWIR_TUD.py:55-71). Returns a JacobianStages."""
     check_dT_method(dT_method)
     T = np.ascontiguousarray(np.atleast_1d(np.asarray(T, dtype=np.float64)))
     Z = np.atleast_1d(np.asarray(Z, dtype=np.float64))
@@ -1423,11 +1457,11 @@ def _jacobian_stages(what, lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitu
     if mark:
         mark("base")
     n = grid.n
-    ODp = ODm = None
+    ODp = ODm = dOD = None
     if with_T and dT_method == "analytic":
-        ODp = torch.empty((nL, n), dtype=torch.float32, device=dev)  # the derivative itself; ODm stays None
+        dOD = torch.empty((nL, n), dtype=torch.float32, device=dev)
         w, p_atm = layer_weights_od(lines.species, T, P_pa, PL_km, MF_VAL, MF_ID)
-        voigt_sum_dT(lines, grid, T, p_atm, w, ODp)
+        voigt_sum_dT(lines, grid, T, p_atm, w, dOD)
     elif with_T:
         ODp = torch.empty((nL, n), dtype=torch.float32, device=dev)
         ODm = torch.empty_like(ODp)
@@ -1449,7 +1483,7 @@ def _jacobian_stages(what, lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitu
         mark("species")
     # the wrt axis of the result follows `wrt`: T at t_pos and the species (K's order = their order in wrt) around it
     t_pos = wrt.index("T") if with_T else 0
-    return T, Z, layers, t_pos, tau, Lu, Ld, OD, ODp, ODm, K
+    return JacobianStages(T, Z, layers, t_pos, tau, Lu, Ld, OD, ODp, ODm, dOD, K)
 
 
 def tud_jacobian(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=False,
@@ -1467,16 +1501,60 @@ def tud_jacobian(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes=(500,)
     or with dT_method="analytic" the closed-form derivative of the line-sum with the same fixed windows (voigt_sum_dT: one
     sum instead of two, fd_step_T ignored); any other dT_method raises ValueError before device work.
     dOD/dMF of a species is the line-sum of that species alone at 1 ppmv (OD is linear in each mixing ratio)."""
-    T, Z, layers, t_pos, tau, Lu, Ld, OD, ODp, ODm, K = _jacobian_stages(
-        "tud_jacobian", lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt, layers,
-        fd_step_T, mark, dT_method)
-    dOD = None
-    if dT_method == "analytic":
-        ODp, dOD = None, ODp
-    J = tud_jacobian_from_od(OD, ODp, ODm, fd_step_T, K, tau, grid, T, Z, Altitudes=Altitudes, theta_r=theta_r,
-                             N_angle=N_angle, returnOD=returnOD, layers=layers, t_pos=t_pos, block_bytes=block_bytes,
-                             on_block=on_block, mark=mark, dOD_dT=dOD)
-    return tau, Lu, Ld, OD, J
+    s = _jacobian_stages("tud_jacobian", lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt,
+                         layers, fd_step_T, mark, dT_method)
+    J = tud_jacobian_from_od(s.OD, s.OD_plus, s.OD_minus, fd_step_T, s.K, s.tau, grid, s.T, s.Z, Altitudes=Altitudes,
+                             theta_r=theta_r, N_angle=N_angle, returnOD=returnOD, layers=s.layers, t_pos=s.t_pos,
+                             block_bytes=block_bytes, on_block=on_block, mark=mark, dOD_dT=s.dOD_dT)
+    return s.tau, s.Lu, s.Ld, s.OD, J
+
+
+class _JacobianFront(NamedTuple):
+    """What _jacobian_front returns."""
+    entry: object       # the library entry point the columns select
+    lead: tuple         # its arguments up to return_od
+    layers: np.ndarray  # int32 layer indices, contiguous
+    n_alt: int
+    n_wrt: int
+    keep: tuple         # host arrays `lead` points into
+
+
+def _jacobian_front(what, fd_entry, dod_entry, OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z, Altitudes, theta_r, N_angle,
+                    returnOD, layers, dOD_dT):
+    """What rtx_tud_jacobian and rtx_tud_vjp share ahead of their own arguments (include/radtxfr_hip.h: the first 18 of
+    either), for `what`_from_od: host conversions, the rule that dOD_dT stands in for OD_plus / OD_minus / fd_step_T, the
+    layout checks of the device columns, the sensor geometry (tud_geometry; one slant path) and n_wrt. Returns a
+    _JacobianFront whose entry is fd_entry, or dod_entry with a dOD_dT."""
+    T = np.ascontiguousarray(np.atleast_1d(np.asarray(T, dtype=np.float64)))
+    nL = T.size
+    layers = np.arange(nL, dtype=np.int32) if layers is None else np.ascontiguousarray(np.asarray(layers, dtype=np.int32).ravel())
+    geo = tud_geometry(Z, Altitudes, theta_r)
+    if geo.mu.size != 1:
+        raise NotImplementedError("%s: one slant path (theta_r) per call" % what)
+    if dOD_dT is not None and (OD_plus is not None or OD_minus is not None):
+        raise ValueError("%s_from_od: dOD_dT replaces OD_plus / OD_minus / fd_step_T" % what)
+    with_T = OD_plus is not None or dOD_dT is not None
+    n_spec = 0 if K is None else int(K.shape[0])
+    n, n_alt = grid.n, geo.Z_s.size
+    ld = OD.stride(0)
+    assert OD.dtype == torch.float32 and OD.is_cuda and OD.dim() == 2 and OD.shape[0] == nL and OD.shape[1] >= n
+    assert OD.stride(1) == 1
+    for t in (OD_plus, OD_minus, dOD_dT):
+        assert t is None or (t.dtype == torch.float32 and t.shape == OD.shape and t.stride() == OD.stride())
+    if K is not None:
+        assert K.dtype == torch.float32 and K.dim() == 3 and K.shape[1] == nL and K.shape[2] >= n
+        assert K.stride(2) == 1 and K.stride(1) == ld and K.stride(0) == nL * ld
+    if tau is not None:
+        assert tau.dtype == torch.float32 and tau.dim() == 2 and tau.shape[0] == n_alt and tau.shape[1] >= n
+        assert tau.stride(1) == 1
+    if dOD_dT is not None:
+        entry, head = dod_entry, (_ptr(OD), _ptr(dOD_dT), ld)
+    else:
+        entry, head = fd_entry, (_ptr(OD), _ptr(OD_plus), _ptr(OD_minus), ld, float(fd_step_T))
+    lead = head + (_ptr(K), n_spec, _ptr(tau), tau.stride(0) if tau is not None else 0, grid.byref(), nL,
+                   T.ctypes.data_as(C.c_void_p), n_alt, geo.mask.ctypes.data_as(C.c_void_p), float(geo.mu[0]), geo.n_down,
+                   int(N_angle), int(bool(returnOD)))
+    return _JacobianFront(entry, lead, layers, n_alt, int(with_T) + n_spec, (T, geo.mask))
 
 
 def tud_jacobian_from_od(OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z, Altitudes=(500,), theta_r=0.0, N_angle=30,
@@ -1489,53 +1567,20 @@ def tud_jacobian_from_od(OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z, A
     [n_wrt][n_layers][2 nAlt + 1][n], T's rows at t_pos and the species in K's order around them, or None with on_block
     (see tud_jacobian)."""
     lib = _lib.load()
-    T = np.ascontiguousarray(np.atleast_1d(np.asarray(T, dtype=np.float64)))
-    Z = np.atleast_1d(np.asarray(Z, dtype=np.float64))
-    nL = T.size
-    layers = np.arange(nL, dtype=np.int32) if layers is None else np.ascontiguousarray(np.asarray(layers, dtype=np.int32).ravel())
-    Z_s = np.array([Altitudes], dtype=np.float64).ravel()
-    mask = np.ascontiguousarray(np.stack([(Z <= zs) for zs in Z_s]).astype(np.uint8))
-    n_down = int(mask[-1].sum())  # quirk 3: the LAST altitude's layer count (:353, :370)
-    th = np.asarray(theta_r, dtype=np.float64).ravel()
-    if th.size != 1:
-        raise NotImplementedError("tud_jacobian: one slant path (theta_r) per call")
-    mu = float(1.0 / np.cos(th[0]))
-    if dOD_dT is not None and (OD_plus is not None or OD_minus is not None):
-        raise ValueError("tud_jacobian_from_od: dOD_dT replaces OD_plus / OD_minus / fd_step_T")
-    with_T = OD_plus is not None or dOD_dT is not None
-    n_spec = 0 if K is None else int(K.shape[0])
-    n = grid.n
-    ld = OD.stride(0)
-    assert OD.dtype == torch.float32 and OD.is_cuda and OD.dim() == 2 and OD.shape[0] == nL and OD.shape[1] >= n
-    assert OD.stride(1) == 1
-    for t in (OD_plus, OD_minus, dOD_dT):
-        assert t is None or (t.dtype == torch.float32 and t.shape == OD.shape and t.stride() == OD.stride())
-    if K is not None:
-        assert K.dtype == torch.float32 and K.dim() == 3 and K.shape[1] == nL and K.shape[2] >= n
-        assert K.stride(2) == 1 and K.stride(1) == ld and K.stride(0) == nL * ld
-    if tau is not None:
-        assert tau.dtype == torch.float32 and tau.dim() == 2 and tau.shape[0] == Z_s.size and tau.shape[1] >= n
-        assert tau.stride(1) == 1
-    n_wrt = int(with_T) + n_spec
-    nA = Z_s.size
-    nrow = 2 * nA + 1
+    f = _jacobian_front("tud_jacobian", lib.rtx_tud_jacobian, lib.rtx_tud_jacobian_dod, OD, OD_plus, OD_minus, fd_step_T, K, tau,
+                        grid, T, Z, Altitudes, theta_r, N_angle, returnOD, layers, dOD_dT)
+    layers, n_wrt, n = f.layers, f.n_wrt, grid.n
+    nrow = 2 * f.n_alt + 1
     per_layer = n_wrt * nrow * n * 4
     nb = int(max(1, min(layers.size, int(block_bytes) // max(per_layer, 1))))
     dev = OD.device
     J = None if on_block is not None else torch.empty((n_wrt, layers.size, nrow, n), dtype=torch.float32, device=dev)
-    T_h, T_p = _h(T)
     st = _stream_ptr()
     for k0 in range(0, layers.size, nb):
         k1 = min(k0 + nb, layers.size)
         blk = torch.empty((n_wrt, k1 - k0, nrow, n), dtype=torch.float32, device=dev)
         lay = np.ascontiguousarray(layers[k0:k1])
-        tail = (_ptr(K), n_spec, _ptr(tau), tau.stride(0) if tau is not None else 0, grid.byref(), nL, T_p, nA,
-                mask.ctypes.data_as(C.c_void_p), mu, n_down, int(N_angle), int(bool(returnOD)), lay.ctypes.data_as(C.c_void_p),
-                lay.size, t_pos, _ptr(blk), n, st)
-        if dOD_dT is not None:
-            _lib.check(lib.rtx_tud_jacobian_dod(_ptr(OD), _ptr(dOD_dT), ld, *tail))
-        else:
-            _lib.check(lib.rtx_tud_jacobian(_ptr(OD), _ptr(OD_plus), _ptr(OD_minus), ld, float(fd_step_T), *tail))
+        _lib.check(f.entry(*f.lead, lay.ctypes.data_as(C.c_void_p), lay.size, t_pos, _ptr(blk), n, st))
         if mark:
             mark("jacobian")
         if on_block is not None:
@@ -1574,34 +1619,9 @@ def tud_vjp_from_od(OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z, G_tau=
     axis optional; a group left None is not evaluated (no G_Ld: no downwelling sweeps; no G_tau: tau may be None). The
     vectors go to the library VJP_VEC_GROUP at a time; the grouping, like the choice and order of layers, changes no bit."""
     lib = _lib.load()
-    T = np.ascontiguousarray(np.atleast_1d(np.asarray(T, dtype=np.float64)))
-    Z = np.atleast_1d(np.asarray(Z, dtype=np.float64))
-    nL = T.size
-    layers = np.arange(nL, dtype=np.int32) if layers is None else np.ascontiguousarray(np.asarray(layers, dtype=np.int32).ravel())
-    Z_s = np.array([Altitudes], dtype=np.float64).ravel()
-    mask = np.ascontiguousarray(np.stack([(Z <= zs) for zs in Z_s]).astype(np.uint8))
-    n_down = int(mask[-1].sum())  # quirk 3: the LAST altitude's layer count (:353, :370)
-    th = np.asarray(theta_r, dtype=np.float64).ravel()
-    if th.size != 1:
-        raise NotImplementedError("tud_vjp: one slant path (theta_r) per call")
-    mu = float(1.0 / np.cos(th[0]))
-    if dOD_dT is not None and (OD_plus is not None or OD_minus is not None):
-        raise ValueError("tud_vjp_from_od: dOD_dT replaces OD_plus / OD_minus / fd_step_T")
-    with_T = OD_plus is not None or dOD_dT is not None
-    n_spec = 0 if K is None else int(K.shape[0])
-    n = grid.n
-    nA = Z_s.size
-    ld = OD.stride(0)
-    assert OD.dtype == torch.float32 and OD.is_cuda and OD.dim() == 2 and OD.shape[0] == nL and OD.shape[1] >= n
-    assert OD.stride(1) == 1
-    for t in (OD_plus, OD_minus, dOD_dT):
-        assert t is None or (t.dtype == torch.float32 and t.shape == OD.shape and t.stride() == OD.stride())
-    if K is not None:
-        assert K.dtype == torch.float32 and K.dim() == 3 and K.shape[1] == nL and K.shape[2] >= n
-        assert K.stride(2) == 1 and K.stride(1) == ld and K.stride(0) == nL * ld
-    if tau is not None:
-        assert tau.dtype == torch.float32 and tau.dim() == 2 and tau.shape[0] == nA and tau.shape[1] >= n
-        assert tau.stride(1) == 1
+    f = _jacobian_front("tud_vjp", lib.rtx_tud_vjp, lib.rtx_tud_vjp_dod, OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z,
+                        Altitudes, theta_r, N_angle, returnOD, layers, dOD_dT)
+    layers, nA, n = f.layers, f.n_alt, grid.n
     G_tau = _cotangent(G_tau, (nA,), n, "G_tau")
     G_Lu = _cotangent(G_Lu, (nA,), n, "G_Lu")
     G_Ld = _cotangent(G_Ld, (), n, "G_Ld")
@@ -1627,21 +1647,14 @@ def tud_vjp_from_od(OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z, G_tau=
         ld_G = n
         G_tau, G_Lu, G_Ld = (None if g is None else g[..., :n].contiguous() for g in (G_tau, G_Lu, G_Ld))
     vstride = {id(g): ld_G * (g.shape[1] if g.dim() == 3 else 1) for g in (G_tau, G_Lu, G_Ld) if g is not None}
-    n_wrt = int(with_T) + n_spec
-    out = torch.empty((n_vec, n_wrt, layers.size), dtype=torch.float64, device=OD.device)
+    out = torch.empty((n_vec, f.n_wrt, layers.size), dtype=torch.float64, device=OD.device)
     group = int(VJP_VEC_GROUP or lib.rtx_tud_vjp_max_vectors())
-    T_h, T_p = _h(T)
     st = _stream_ptr()
     for v0 in range(0, n_vec, group):
         v1 = min(v0 + group, n_vec)
         part = lambda g: None if g is None else C.c_void_p(g.data_ptr() + 4 * v0 * vstride[id(g)])
-        tail = (_ptr(K), n_spec, _ptr(tau), tau.stride(0) if tau is not None else 0, grid.byref(), nL, T_p, nA,
-                mask.ctypes.data_as(C.c_void_p), mu, n_down, int(N_angle), int(bool(returnOD)), layers.ctypes.data_as(C.c_void_p),
-                layers.size, t_pos, part(G_tau), part(G_Lu), part(G_Ld), ld_G, v1 - v0, _ptr(out[v0:v1]), st)
-        if dOD_dT is not None:
-            _lib.check(lib.rtx_tud_vjp_dod(_ptr(OD), _ptr(dOD_dT), ld, *tail))
-        else:
-            _lib.check(lib.rtx_tud_vjp(_ptr(OD), _ptr(OD_plus), _ptr(OD_minus), ld, float(fd_step_T), *tail))
+        _lib.check(f.entry(*f.lead, layers.ctypes.data_as(C.c_void_p), layers.size, t_pos, part(G_tau), part(G_Lu), part(G_Ld),
+                           ld_G, v1 - v0, _ptr(out[v0:v1]), st))
     return out
 
 
@@ -1658,16 +1671,13 @@ def tud_vjp(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, G_tau=None, G_Lu=None
     if cotangents is not None and (G_tau is not None or G_Lu is not None or G_Ld is not None):
         raise ValueError("tud_vjp: cotangents= and G_tau / G_Lu / G_Ld exclude each other")
     check_dT_method(dT_method)
-    T, Z, layers, t_pos, tau, Lu, Ld, OD, ODp, ODm, K = _jacobian_stages(
-        "tud_vjp", lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt, layers,
-        fd_step_T, mark, dT_method)
-    dOD = None
-    if dT_method == "analytic":
-        ODp, dOD = None, ODp
+    s = _jacobian_stages("tud_vjp", lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt,
+                         layers, fd_step_T, mark, dT_method)
     if cotangents is not None:
-        G_tau, G_Lu, G_Ld = cotangents(tau, Lu, Ld)
-    grad = tud_vjp_from_od(OD, ODp, ODm, fd_step_T, K, tau, grid, T, Z, G_tau=G_tau, G_Lu=G_Lu, G_Ld=G_Ld, Altitudes=Altitudes,
-                           theta_r=theta_r, N_angle=N_angle, returnOD=returnOD, layers=layers, t_pos=t_pos, dOD_dT=dOD)
+        G_tau, G_Lu, G_Ld = cotangents(s.tau, s.Lu, s.Ld)
+    grad = tud_vjp_from_od(s.OD, s.OD_plus, s.OD_minus, fd_step_T, s.K, s.tau, grid, s.T, s.Z, G_tau=G_tau, G_Lu=G_Lu, G_Ld=G_Ld,
+                           Altitudes=Altitudes, theta_r=theta_r, N_angle=N_angle, returnOD=returnOD, layers=s.layers,
+                           t_pos=s.t_pos, dOD_dT=s.dOD_dT)
     if mark:
         mark("vjp")
-    return tau, Lu, Ld, OD, grad
+    return s.tau, s.Lu, s.Ld, s.OD, grad

@@ -23,6 +23,7 @@ Conscious divergences from the reference:
   * make_spectral_axis casts the point count to int (quirk 1: the reference crashes on NumPy>=1.18).
   * spectra are computed in float32 on the device and returned as float64.
 """
+import functools
 import os
 import threading
 import time
@@ -215,6 +216,34 @@ def _cached_axis(Xmin, Xmax, DVOUT):
     return X
 
 
+class _Call:
+    """One call of the compute_TUD family, parsed: `opts` overlaid with `kwargs` in a copy (quirk 2) as `o`, and what the
+    reference derives from it at the top of compute_TUD (:304-314, :346-349) -- the profile Z, T, P, PL, MF as float64
+    arrays and ID, the sensor altitudes Z_s, theta (float64), N_angle, returnOD and the broadening= option. What can
+    raise or costs time is made on first use, so that a caller's own argument checks come first: lut (the xs_lut option,
+    _xs_lut_option in `fn`'s name), foreign (broadening's foreign gases), X (the cached axis) and grid; table() looks the
+    line table up (None with an xs_lut), and nothing before it touches a table or a device."""
+
+    def __init__(self, fn, Xmin, Xmax, opts, kwargs):
+        self.fn, self.Xmin, self.Xmax = fn, Xmin, Xmax
+        self.o = o = dict(opts)
+        o.update(kwargs)
+        self.Z, self.T, self.P, self.PL, self.MF = (np.asarray(o[k], dtype=np.float64) for k in ("Zs", "Ts", "Ps", "PLs", "MFs_VAL"))
+        self.ID = np.asarray(o["MFs_ID"])
+        self.Z_s = np.array([o["Altitudes"]]).ravel()
+        self.theta = np.asarray(o["theta_r"], dtype=np.float64)
+        self.N_angle, self.returnOD = int(o["N_angle"]), bool(o["returnOD"])
+        self.broadening = o.get("broadening")
+
+    lut = functools.cached_property(lambda self: _xs_lut_option(self.fn, self.o))
+    foreign = functools.cached_property(lambda self: engine.broadening_gases(self.broadening))
+    X = functools.cached_property(lambda self: _cached_axis(self.Xmin, self.Xmax, self.o["DVOUT"]))
+    grid = functools.cached_property(lambda self: engine.Grid(self.Xmin, self.Xmax, self.X.size))
+
+    def table(self):
+        return _resolve_table(self.o.get("line_table"), self.foreign or ()) if self.lut is None else None
+
+
 _STAGING = {}
 _TRACE = float(os.environ.get("RADTXFR_TRACE", "0") or 0)  # developer aid: print the phases of slow compute_TUD calls
 
@@ -331,26 +360,13 @@ def compute_TUD(Xmin, Xmax, opts=options, **kwargs):
     NotImplementedError: xs_lut together with any broadening= (fixed when the table was made).
     """
     trace = [time.perf_counter()] if _TRACE else None
-    o = dict(opts)
-    o.update(kwargs)
-    lut = _xs_lut_option("compute_TUD", o)
-    broadening = o.get("broadening")
-    foreign = engine.broadening_gases(broadening)
-    Z = np.asarray(o["Zs"], dtype=np.float64)
-    T = np.asarray(o["Ts"], dtype=np.float64)
-    P = np.asarray(o["Ps"], dtype=np.float64)
-    PL = np.asarray(o["PLs"], dtype=np.float64)
-    MF = np.asarray(o["MFs_VAL"], dtype=np.float64)
-    ID = np.asarray(o["MFs_ID"])
-    nA = int(o["N_angle"])
-    f = lambda x: np.array([x]).ravel()
-    Z_s = f(o["Altitudes"])
-    mu_s = f(1.0 / np.cos(o["theta_r"]))
-    X_ = _cached_axis(Xmin, Xmax, o["DVOUT"])
-    grid = engine.Grid(Xmin, Xmax, X_.size)
+    c = _Call("compute_TUD", Xmin, Xmax, opts, kwargs)
+    o, lut, broadening = c.o, c.lut, c.broadening
+    Z, T, P, PL, MF, ID, Z_s, nA = c.Z, c.T, c.P, c.PL, c.MF, c.ID, c.Z_s, c.N_angle
+    X_, grid = c.X, c.grid
     if trace:
         trace.append(time.perf_counter())
-    tbl = _resolve_table(o.get("line_table"), foreign or ()) if lut is None else None
+    tbl = c.table()
     if trace:
         trace.append(time.perf_counter())
     if o.get("copy_axis"):
@@ -358,9 +374,9 @@ def compute_TUD(Xmin, Xmax, opts=options, **kwargs):
     chunks = o.get("chunks")
     if chunks is None:  # automatic: worth it once the copy of the result outweighs a chunk's fixed costs
         chunks = 4 if grid.n >= 2000000 else 2 if grid.n >= 500000 else 1
-    if chunks > 1 and mu_s.size <= engine.TUD_MAX_MU and not o["save"]:
-        got = _compute_tud_chunked(tbl, grid, Z, T, P, PL, MF, ID, Z_s, np.asarray(o["theta_r"], dtype=np.float64), nA,
-                                   bool(o["returnOD"]), int(chunks), broadening=broadening, xs_lut=lut)
+    if chunks > 1 and c.theta.size <= engine.TUD_MAX_MU and not o["save"]:
+        got = _compute_tud_chunked(tbl, grid, Z, T, P, PL, MF, ID, Z_s, c.theta, nA, c.returnOD, int(chunks), broadening=broadening,
+                                   xs_lut=lut)
         if got is not None:
             tau_h, Lu_h, Ld_h, (nZ, nMu) = got
             if trace:
@@ -370,10 +386,10 @@ def compute_TUD(Xmin, Xmax, opts=options, **kwargs):
                           % tuple([1e3 * (trace[-1] - trace[0]), chunks] + [1e3 * (b - a) for a, b in zip(trace, trace[1:])]), flush=True)
             tau_, Lu_ = _tud_shapes(tau_h, Lu_h, nZ, nMu)
             return X_, tau_, Lu_, Ld_h[0]
-    if mu_s.size <= engine.TUD_MAX_MU and not o["save"]:
+    if c.theta.size <= engine.TUD_MAX_MU and not o["save"]:
         # the common case: one call into the library (rtx_compute_tud)
-        run = engine.TudRunner(tbl, grid, Z, n_layers=T.size, Altitudes=Z_s, theta_r=np.asarray(o["theta_r"], dtype=np.float64),
-                               N_angle=nA, returnOD=bool(o["returnOD"]), broadening=broadening, xs_lut=lut)
+        run = engine.TudRunner(tbl, grid, Z, n_layers=T.size, Altitudes=Z_s, theta_r=c.theta, N_angle=nA, returnOD=c.returnOD,
+                               broadening=broadening, xs_lut=lut)
         tau, Lu, Ld = run.run(T, P, PL, MF, ID)
         nZ, nMu = run.shape
         OD = run.OD
@@ -382,8 +398,7 @@ def compute_TUD(Xmin, Xmax, opts=options, **kwargs):
             OD = engine.xs_od(lut, grid, T, P / 101325.0, PL, MF, ID)
         else:
             OD = engine.optical_depths(tbl, grid, T, P, PL, MF, ID, broadening=broadening)  # [nL][nX] float32 on the device
-        res = engine.tud(OD, grid, T, Z, Altitudes=Z_s, theta_r=np.asarray(o["theta_r"], dtype=np.float64), N_angle=nA,
-                         returnOD=bool(o["returnOD"]), per_angle=bool(o["save"]))
+        res = engine.tud(OD, grid, T, Z, Altitudes=Z_s, theta_r=c.theta, N_angle=nA, returnOD=c.returnOD, per_angle=bool(o["save"]))
         tau, Lu, Ld, (nZ, nMu) = res[:4]
     if trace:
         trace.append(time.perf_counter())
@@ -403,7 +418,7 @@ def compute_TUD(Xmin, Xmax, opts=options, **kwargs):
         t3 = tau_h.reshape(nZ, nMu, -1).transpose(2, 0, 1)
         u3 = Lu_h.reshape(nZ, nMu, -1).transpose(2, 0, 1)
         np.savez("ComputeTUD.npz", OD=OD.double().cpu().numpy().T, B=planckian(X_, T), tau=t3, Ld=res[4].double().cpu().numpy().T,
-                 Lu=u3, X=X_, angles=angles, Z_s=Z_s, mu_s=mu_s)
+                 Lu=u3, X=X_, angles=angles, Z_s=Z_s, mu_s=np.array([1.0 / np.cos(o["theta_r"])]).ravel())
     return X_, tau_, Lu_, Ld_
 
 
@@ -498,9 +513,8 @@ def compute_TUD_batch(Xmin, Xmax, atmospheres, opts=options, reduce=None, device
     xs_lut (keyword only): as for compute_TUD -- every atmosphere's optical depths come from the cross-section table, the line
     table is not touched, results equal per-call compute_TUD(xs_lut=) bit for bit. NotImplementedError: xs_lut with any
     broadening=, or with devices= naming more than one device (a table lives on one device)."""
-    o = dict(opts)
-    o.update(kwargs)
-    lut = _xs_lut_option("compute_TUD_batch", o)
+    c = _Call("compute_TUD_batch", Xmin, Xmax, opts, kwargs)
+    o, lut = c.o, c.lut
     if lut is not None and devices is not None and len({int(d) for d in devices}) > 1:
         raise NotImplementedError("compute_TUD_batch: xs_lut with devices=%r is not supported: a cross-section table lives on one "
                                   "device" % (devices,))
@@ -508,28 +522,19 @@ def compute_TUD_batch(Xmin, Xmax, atmospheres, opts=options, reduce=None, device
         raise ValueError("compute_TUD_batch: save is a single-call option")
     if np.dtype(out_dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
         raise ValueError("compute_TUD_batch: out_dtype must be float64 or float32")
-    Z = np.asarray(o["Zs"], dtype=np.float64)
-    ID = np.asarray(o["MFs_ID"])
-    f = lambda x: np.array([x]).ravel()
-    Z_s = f(o["Altitudes"])
-    mu_s = f(1.0 / np.cos(o["theta_r"]))
-    if mu_s.size > engine.TUD_MAX_MU:
+    if c.theta.size > engine.TUD_MAX_MU:
         raise ValueError("compute_TUD_batch takes at most %d slant paths" % engine.TUD_MAX_MU)
-    broadening = o.get("broadening")
-    foreign = engine.broadening_gases(broadening)
+    c.foreign  # a broadening= that names no mix: refused before the device is asked for
     engine.require_gpu()
     devs = [torch.cuda.current_device()] if devices is None else [int(d) for d in devices]
     if not devs or any(d < 0 or d >= torch.cuda.device_count() for d in devs):
         raise ValueError("compute_TUD_batch: devices=%r, visible GPUs: %d" % (devices, torch.cuda.device_count()))
-    X_ = _cached_axis(Xmin, Xmax, o["DVOUT"])
-    grid = engine.Grid(Xmin, Xmax, X_.size)
+    X_, grid = c.X, c.grid
     if lut is not None and lut.device.index != devs[0]:
         raise ValueError("compute_TUD_batch: xs_lut lives on device %d, devices=%r" % (lut.device.index, devices))
     with torch.cuda.device(devs[0]):
-        tbl = _resolve_table(o.get("line_table"), foreign or ()) if lut is None else None
-    nL = np.asarray(o["Ts"]).size
-    theta = np.asarray(o["theta_r"], dtype=np.float64)
-    pipes = [_TudPipeline(d, tbl, grid, Z, nL, Z_s, theta, int(o["N_angle"]), bool(o["returnOD"]), broadening=broadening, xs_lut=lut)
+        tbl = c.table()
+    pipes = [_TudPipeline(d, tbl, grid, c.Z, c.T.size, c.Z_s, c.theta, c.N_angle, c.returnOD, broadening=c.broadening, xs_lut=lut)
              for d in devs]
     nZ, nMu = pipes[0].runs[0].shape
     pending = []  # (pipeline, ticket, X of the result) in input order
@@ -546,7 +551,7 @@ def compute_TUD_batch(Xmin, Xmax, atmospheres, opts=options, reduce=None, device
             a = dict(o)
             a.update(atm)
             pipe = pipes[k % len(pipes)]
-            ticket, Xr = pipe.enqueue(a, ID, grid, float(X_[0]), reduce, np.dtype(out_dtype))
+            ticket, Xr = pipe.enqueue(a, c.ID, grid, float(X_[0]), reduce, np.dtype(out_dtype))
             pending.append((pipe, ticket, X_ if Xr is None else Xr))
             # a pipeline's staging ring has two slots: the atmosphere staged two rounds ago on it must be collected first
             while len(pending) > len(pipes):
@@ -562,40 +567,41 @@ def compute_TUD_batch(Xmin, Xmax, atmospheres, opts=options, reduce=None, device
 JACOBIAN_HOST_LIMIT = 4 << 30  # bytes of full-resolution float64 results compute_TUD_jacobian returns without reduce=
 
 
-def _jacobian_args(Xmin, Xmax, o, wrt, layers, reduce, fd_step_T, host_result=True, dT_method="fd"):
-    """compute_TUD_jacobian's argument checks, all on the host (no device is touched): (wrt, layers, nX). host_result=False:
-    the caller returns no J (compute_TUD_vjp), so the size of a full-resolution J on the host is not a concern."""
+def _jacobian_args(fn, Xmin, Xmax, o, wrt, layers, reduce, fd_step_T, host_result=True, dT_method="fd"):
+    """compute_TUD_jacobian's argument checks, all on the host (no device is touched), raised in the name of the calling
+    function `fn`: (wrt, layers, nX). host_result=False: the caller returns no J (compute_TUD_vjp), so the size of a
+    full-resolution J on the host is not a concern."""
     if dT_method not in engine.DT_METHODS:
-        raise ValueError("compute_TUD_jacobian: dT_method=%r, expected one of %r" % (dT_method, engine.DT_METHODS))
+        raise ValueError(fn + ": dT_method=%r, expected one of %r" % (dT_method, engine.DT_METHODS))
     if o.get("broadening") is not None:
-        raise NotImplementedError("compute_TUD_jacobian: broadening=%r is not supported (with self-broadening dOD/dMF is no "
+        raise NotImplementedError(fn + ": broadening=%r is not supported (with self-broadening dOD/dMF is no "
                                   "longer OD per ppmv); use broadening=None" % (o.get("broadening"),))
     if np.asarray(o["theta_r"]).size != 1:
-        raise NotImplementedError("compute_TUD_jacobian: one slant path (a single theta_r) per call")
+        raise NotImplementedError(fn + ": one slant path (a single theta_r) per call")
     if o["save"]:
-        raise ValueError("compute_TUD_jacobian: save=True is a compute_TUD option (the per-stream dump) and is not offered here")
+        raise ValueError(fn + ": save=True is a compute_TUD option (the per-stream dump) and is not offered here")
     if isinstance(wrt, (str, int, np.integer)):
         wrt = (wrt,)
     wrt = tuple(w if isinstance(w, str) else int(w) for w in wrt)
     if not wrt:
-        raise ValueError("compute_TUD_jacobian: wrt is empty")
+        raise ValueError(fn + ": wrt is empty")
     ids = [int(v) for v in np.asarray(o["MFs_ID"]).ravel()]
     for w in wrt:
         if isinstance(w, str):
             if w != "T":
-                raise ValueError("compute_TUD_jacobian: wrt entry %r: \"T\" or a molecule id of MFs_ID %r" % (w, ids))
+                raise ValueError(fn + ": wrt entry %r: \"T\" or a molecule id of MFs_ID %r" % (w, ids))
         elif w not in ids:
-            raise ValueError("compute_TUD_jacobian: wrt molecule id %d is not in MFs_ID %r" % (w, ids))
+            raise ValueError(fn + ": wrt molecule id %d is not in MFs_ID %r" % (w, ids))
     if len(set(wrt)) != len(wrt):
-        raise ValueError("compute_TUD_jacobian: wrt %r names an entry twice" % (wrt,))
+        raise ValueError(fn + ": wrt %r names an entry twice" % (wrt,))
     nL = np.asarray(o["Ts"]).size
     lay = np.arange(nL) if layers is None else np.asarray(layers).ravel()
     if lay.size == 0 or not np.issubdtype(lay.dtype, np.integer):
-        raise ValueError("compute_TUD_jacobian: layers must be a non-empty sequence of layer indices")
+        raise ValueError(fn + ": layers must be a non-empty sequence of layer indices")
     if lay.min() < 0 or lay.max() >= nL:
-        raise ValueError("compute_TUD_jacobian: layer index outside [0, %d)" % nL)
+        raise ValueError(fn + ": layer index outside [0, %d)" % nL)
     if "T" in wrt and dT_method == "fd" and not (float(fd_step_T) > 0.0):
-        raise ValueError("compute_TUD_jacobian: fd_step_T=%r must be > 0" % (fd_step_T,))
+        raise ValueError(fn + ": fd_step_T=%r must be > 0" % (fd_step_T,))
     nX = int(np.ceil((Xmax - Xmin) / o["DVOUT"]))  # make_spectral_axis's count
     nZ = np.array([o["Altitudes"]]).size
     engine.jacobian_limits(nL, nZ, int(o["N_angle"]), sum(1 for w in wrt if not isinstance(w, str)))
@@ -604,11 +610,37 @@ def _jacobian_args(Xmin, Xmax, o, wrt, layers, reduce, fd_step_T, host_result=Tr
     elif reduce is None:
         nbytes = 8 * nX * ((2 * nZ + 1) * (1 + len(wrt) * lay.size))
         if nbytes > JACOBIAN_HOST_LIMIT:
-            raise ValueError("compute_TUD_jacobian: the full-resolution result would take %.1f GiB of host memory (limit %.0f GiB): "
+            raise ValueError(fn + ": the full-resolution result would take %.1f GiB of host memory (limit %.0f GiB): "
                              "pass reduce=dict(dX=...) or fewer layers= / wrt=" % (nbytes / 2.0 ** 30, JACOBIAN_HOST_LIMIT / 2.0 ** 30))
     elif "dX" not in reduce:
-        raise ValueError("compute_TUD_jacobian: reduce needs dX")
+        raise ValueError(fn + ": reduce needs dX")
     return wrt, np.ascontiguousarray(lay, dtype=np.int32), nX
+
+
+def _no_xs_lut(c):
+    """NotImplementedError in the name of the derivative function of call `c` when it carries an xs_lut: the derivatives
+    are built on the line-sum."""
+    if c.o.get("xs_lut") is not None:
+        raise NotImplementedError(c.fn + ": xs_lut is not supported (dOD/dT is a difference of line-sums with fixed windows); "
+                                  "use line_table=")
+
+
+def _vector_axis(g, base):
+    """An array or tensor laid out as `base` plus an optional trailing vector axis: (g with that axis, its length -- None
+    where g came without one), or None when g's shape is neither."""
+    shape = tuple(g.shape)
+    if shape == base:
+        return g[..., None], None
+    if len(shape) == len(base) + 1 and shape[:-1] == base and shape[-1] >= 1:
+        return g, shape[-1]
+    return None
+
+
+def _grad_dict(grad_h, wrt, n_vec):
+    """{wrt entry: float64 [n_layers], or [n_layers][n_vec] with a vector axis} from engine.tud_vjp's grad on the host,
+    [n_vec][n_wrt][n_layers]."""
+    return {w: np.ascontiguousarray(grad_h[:, w_i, :].T) if n_vec is not None else grad_h[0, w_i, :].copy()
+            for w_i, w in enumerate(wrt)}
 
 
 def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, reduce=None, fd_step_T=0.5, dT_method="fd", **kwargs):
@@ -638,19 +670,12 @@ def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, redu
     (engine.reduce_resolution_cached). Without it, full-resolution results above 4 GiB are refused (ValueError): pass
     reduce= or fewer layers=. Arguments are checked before any device work.
     NotImplementedError: xs_lut= (the derivatives are built on the line-sum: dOD/dT holds every line's window fixed)."""
-    o = dict(opts)
-    o.update(kwargs)
-    if o.get("xs_lut") is not None:
-        raise NotImplementedError("compute_TUD_jacobian: xs_lut is not supported (dOD/dT is a difference of line-sums with fixed "
-                                  "windows); use line_table=")
-    wrt, lay, _ = _jacobian_args(Xmin, Xmax, o, wrt, layers, reduce, fd_step_T, dT_method=dT_method)
-    Z = np.asarray(o["Zs"], dtype=np.float64)
-    T = np.asarray(o["Ts"], dtype=np.float64)
-    X_ = _cached_axis(Xmin, Xmax, o["DVOUT"])
-    grid = engine.Grid(Xmin, Xmax, X_.size)
-    tbl = _resolve_table(o.get("line_table"))
-    Z_s = np.array([o["Altitudes"]]).ravel()
-    nZ = Z_s.size
+    c = _Call("compute_TUD_jacobian", Xmin, Xmax, opts, kwargs)
+    _no_xs_lut(c)
+    wrt, lay, _ = _jacobian_args(c.fn, Xmin, Xmax, c.o, wrt, layers, reduce, fd_step_T, dT_method=dT_method)
+    X_, grid = c.X, c.grid
+    tbl = c.table()
+    nZ = c.Z_s.size
     nrow = 2 * nZ + 1
     n_lay = lay.size
     red = None
@@ -672,10 +697,9 @@ def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, redu
                 host[w] = np.empty((h.shape[0], nrow, n_lay))
             host[w][:, :, k0:k1] = h
 
-    tau, Lu, Ld, _, _ = engine.tud_jacobian(tbl, grid, Z, T, o["Ps"], o["PLs"], o["MFs_VAL"], o["MFs_ID"], Altitudes=Z_s,
-                                             theta_r=np.asarray(o["theta_r"], dtype=np.float64), N_angle=int(o["N_angle"]),
-                                             returnOD=bool(o["returnOD"]), wrt=wrt, layers=lay, fd_step_T=float(fd_step_T),
-                                             on_block=on_block, dT_method=dT_method)
+    tau, Lu, Ld, _, _ = engine.tud_jacobian(tbl, grid, c.Z, c.T, c.P, c.PL, c.MF, c.ID, Altitudes=c.Z_s, theta_r=c.theta,
+                                             N_angle=c.N_angle, returnOD=c.returnOD, wrt=wrt, layers=lay,
+                                             fd_step_T=float(fd_step_T), on_block=on_block, dT_method=dT_method)
     if red is not None:
         rows = torch.cat([tau, Lu, Ld[None, :]])
         X_out, r = engine.reduce_resolution_cached(rows, x0, grid.step, grid.n, red["dX"], N=red["N"], window=red["window"])
@@ -719,14 +743,11 @@ def _vjp_cotangents(cotangents, nX, nZ):
         shape = tuple(g.shape)
         if key != "Ld" and nZ == 1 and shape[:2] != base and shape[:1] == (nX,) and len(shape) <= 2:
             g = g[:, None]  # one altitude: compute_TUD squeezes the altitude axis
-            shape = tuple(g.shape)
-        if shape == base:
-            g, nv = g[..., None], None
-        elif len(shape) == len(base) + 1 and shape[:-1] == base and shape[-1] >= 1:
-            nv = shape[-1]
-        else:
+        got = _vector_axis(g, base)
+        if got is None:
             raise ValueError("compute_TUD_vjp: cotangent %r has shape %r, expected %r plus an optional trailing vector axis"
-                             % (key, shape, base))
+                             % (key, tuple(g.shape), base))
+        g, nv = got
         n_vecs.add(nv)
         # [nX]([nZ])[n_vec] -> [n_vec]([nZ])[nX]
         out[key] = g.permute(*range(g.dim() - 1, -1, -1)) if _is_torch(g) else np.transpose(g)
@@ -758,40 +779,25 @@ def compute_TUD_vjp(Xmin, Xmax, cotangents, opts=options, wrt=("T",), layers=Non
     band radiances under a sensor's response tables, compute_band_radiance_vjp runs the whole chain, sensor adjoint
     included, and also returns the gradients of the surface temperature and the emissivity knots.
     Arguments are checked before any device work. NotImplementedError: more than one theta_r, broadening=, xs_lut=."""
-    o = dict(opts)
-    o.update(kwargs)
-    if "reduce" in o:
+    c = _Call("compute_TUD_vjp", Xmin, Xmax, opts, kwargs)
+    if "reduce" in c.o:
         raise NotImplementedError("compute_TUD_vjp: reduce= is not offered: map the cotangent to the native grid with the "
                                   "transpose of the reduction and pass that")
-    if o.get("xs_lut") is not None:
-        raise NotImplementedError("compute_TUD_vjp: xs_lut is not supported (dOD/dT is a difference of line-sums with fixed "
-                                  "windows); use line_table=")
-    try:
-        wrt, lay, nX = _jacobian_args(Xmin, Xmax, o, wrt, layers, None, fd_step_T, host_result=False, dT_method=dT_method)
-    except (ValueError, NotImplementedError) as e:
-        raise type(e)(str(e).replace("compute_TUD_jacobian", "compute_TUD_vjp")) from None
-    Z_s = np.array([o["Altitudes"]]).ravel()
-    nZ = Z_s.size
+    _no_xs_lut(c)
+    wrt, lay, nX = _jacobian_args(c.fn, Xmin, Xmax, c.o, wrt, layers, None, fd_step_T, host_result=False, dT_method=dT_method)
+    nZ = c.Z_s.size
     G, n_vec = _vjp_cotangents(cotangents, nX, nZ)
-    Z = np.asarray(o["Zs"], dtype=np.float64)
-    T = np.asarray(o["Ts"], dtype=np.float64)
-    X_ = _cached_axis(Xmin, Xmax, o["DVOUT"])
+    X_, grid = c.X, c.grid
     assert X_.size == nX
-    grid = engine.Grid(Xmin, Xmax, X_.size)
-    tbl = _resolve_table(o.get("line_table"))
-    tau, Lu, Ld, _, grad = engine.tud_vjp(tbl, grid, Z, T, o["Ps"], o["PLs"], o["MFs_VAL"], o["MFs_ID"], G_tau=G.get("tau"),
-                                          G_Lu=G.get("La"), G_Ld=G.get("Ld"), Altitudes=Z_s,
-                                          theta_r=np.asarray(o["theta_r"], dtype=np.float64), N_angle=int(o["N_angle"]),
-                                          returnOD=bool(o["returnOD"]), wrt=wrt, layers=lay, fd_step_T=float(fd_step_T),
-                                          dT_method=dT_method)
+    tbl = c.table()
+    tau, Lu, Ld, _, grad = engine.tud_vjp(tbl, grid, c.Z, c.T, c.P, c.PL, c.MF, c.ID, G_tau=G.get("tau"), G_Lu=G.get("La"),
+                                          G_Ld=G.get("Ld"), Altitudes=c.Z_s, theta_r=c.theta, N_angle=c.N_angle,
+                                          returnOD=c.returnOD, wrt=wrt, layers=lay, fd_step_T=float(fd_step_T), dT_method=dT_method)
     (tau_h, Lu_h, Ld_h), done = _rows_to_host_f64([tau, Lu, Ld[None, :]])
     grad_h = grad.cpu().numpy()  # [n_vec][n_wrt][n_layers]
     done.synchronize()
     tau_, Lu_ = _tud_shapes(tau_h, Lu_h, nZ, 1)
-    out = {}
-    for w_i, w in enumerate(wrt):
-        out[w] = np.ascontiguousarray(grad_h[:, w_i, :].T) if n_vec is not None else grad_h[0, w_i, :].copy()
-    return X_, tau_, Lu_, Ld_h[0], out
+    return X_, tau_, Lu_, Ld_h[0], _grad_dict(grad_h, wrt, n_vec)
 
 
 def compute_band_radiance_vjp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, cotangent, opts=options, wrt=("T",), layers=None,
@@ -815,22 +821,15 @@ def compute_band_radiance_vjp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, co
     Arguments are checked before any device work. NotImplementedError: more than one altitude or theta_r, returnOD=True,
     broadening=, xs_lut=, reduce=."""
     name = "compute_band_radiance_vjp"
-    o = dict(opts)
-    o.update(kwargs)
-    if "reduce" in o:
+    c = _Call(name, Xmin, Xmax, opts, kwargs)
+    if "reduce" in c.o:
         raise NotImplementedError(name + ": reduce= is not offered: the cost is defined on the sensor's bands")
-    if o.get("xs_lut") is not None:
-        raise NotImplementedError(name + ": xs_lut is not supported (dOD/dT is a difference of line-sums with fixed windows); "
-                                  "use line_table=")
-    if bool(o["returnOD"]):
+    _no_xs_lut(c)
+    if c.returnOD:
         raise NotImplementedError(name + ": returnOD=True is not supported (the sensor stage takes transmittances)")
-    Z_s = np.array([o["Altitudes"]]).ravel()
-    if Z_s.size != 1:
-        raise NotImplementedError(name + ": exactly one sensor altitude per call (got %d)" % Z_s.size)
-    try:
-        wrt, lay, nX = _jacobian_args(Xmin, Xmax, o, wrt, layers, None, fd_step_T, host_result=False, dT_method=dT_method)
-    except (ValueError, NotImplementedError) as e:
-        raise type(e)(str(e).replace("compute_TUD_jacobian", name)) from None
+    if c.Z_s.size != 1:
+        raise NotImplementedError(name + ": exactly one sensor altitude per call (got %d)" % c.Z_s.size)
+    wrt, lay, nX = _jacobian_args(name, Xmin, Xmax, c.o, wrt, layers, None, fd_step_T, host_result=False, dT_method=dT_method)
     Xk = np.ascontiguousarray(np.asarray(Xk, dtype=np.float64).ravel())
     scalar = np.ndim(Ts_surface) == 0
     Ts_s = np.atleast_1d(np.asarray(Ts_surface, dtype=np.float64))
@@ -843,21 +842,15 @@ def compute_band_radiance_vjp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, co
     nB, nE, nT = len(sensor), int(emis_knots.shape[1]), Ts_s.size
     base = (nB, nE) if scalar else (nT, nB, nE)
     g = cotangent if _is_torch(cotangent) else np.asarray(cotangent)
-    shape = tuple(g.shape)
-    if shape == base:
-        g, n_vec = g[..., None], None
-    elif len(shape) == len(base) + 1 and shape[:-1] == base and shape[-1] >= 1:
-        n_vec = shape[-1]
-    else:
+    got = _vector_axis(g, base)
+    if got is None:
         raise ValueError(name + ": cotangent has shape %r, expected %r (L's shape) plus an optional trailing vector axis"
-                         % (shape, base))
+                         % (tuple(g.shape), base))
+    g, n_vec = got
     from . import sensor as _sensor  # sensor.py imports this module
-    Z = np.asarray(o["Zs"], dtype=np.float64)
-    T = np.asarray(o["Ts"], dtype=np.float64)
-    X_ = _cached_axis(Xmin, Xmax, o["DVOUT"])
-    assert X_.size == nX
-    grid = engine.Grid(Xmin, Xmax, X_.size)
-    tbl = _resolve_table(o.get("line_table"))
+    grid = c.grid
+    assert c.X.size == nX
+    tbl = c.table()
     dev = engine.device()
     E_d = _dev_f32(emis_knots, dev).contiguous()
     g_d = _dev_f32(g, dev)
@@ -878,17 +871,13 @@ def compute_band_radiance_vjp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, co
             kept["emis"].append(r["emis"])
         return G
 
-    _, _, _, _, grad = engine.tud_vjp(tbl, grid, Z, T, o["Ps"], o["PLs"], o["MFs_VAL"], o["MFs_ID"], Altitudes=Z_s,
-                                      theta_r=np.asarray(o["theta_r"], dtype=np.float64), N_angle=int(o["N_angle"]),
-                                      returnOD=False, wrt=wrt, layers=lay, fd_step_T=float(fd_step_T), cotangents=sensor_stage,
-                                      dT_method=dT_method)
-    grad_h = grad.cpu().numpy()  # [n_vec][n_wrt][n_layers]
+    _, _, _, _, grad = engine.tud_vjp(tbl, grid, c.Z, c.T, c.P, c.PL, c.MF, c.ID, Altitudes=c.Z_s, theta_r=c.theta,
+                                      N_angle=c.N_angle, returnOD=False, wrt=wrt, layers=lay, fd_step_T=float(fd_step_T),
+                                      cotangents=sensor_stage, dT_method=dT_method)
     L_h = kept["L"].cpu().numpy()
     dTs_h = torch.stack(kept["Ts"], dim=-1).cpu().numpy()    # Ts_surface's shape + [n_vec]
     dE_h = torch.stack(kept["emis"], dim=-1).cpu().numpy()   # [nk][nE][n_vec]
-    out = {}
-    for w_i, w in enumerate(wrt):
-        out[w] = np.ascontiguousarray(grad_h[:, w_i, :].T) if n_vec is not None else grad_h[0, w_i, :].copy()
+    out = _grad_dict(grad.cpu().numpy(), wrt, n_vec)
     out["Ts_surface"] = np.ascontiguousarray(dTs_h) if n_vec is not None else dTs_h[..., 0].copy()
     out["emis"] = np.ascontiguousarray(dE_h) if n_vec is not None else dE_h[..., 0].copy()
     return np.array(sensor.centres), L_h, out

@@ -194,8 +194,8 @@ def test_default_method_is_the_old_entry_point_bit_for_bit(rt, case):
     wrt = ("T", 1)
     J = engine.tud_jacobian(*args, Altitudes=ALTS, wrt=wrt, layers=LAYERS)[4]
     assert torch.equal(J, engine.tud_jacobian(*args, Altitudes=ALTS, wrt=wrt, layers=LAYERS, dT_method="fd")[4])
-    T, Z, layers, t_pos, tau, Lu, Ld, od, ODp, ODm, K = engine._jacobian_stages(
-        "test", *args, ALTS, 0.0, 30, False, wrt, LAYERS, 0.5, None)
+    s = engine._jacobian_stages("test", *args, ALTS, 0.0, 30, False, wrt, LAYERS, 0.5, None)
+    T, Z, layers, t_pos, tau, od, ODp, ODm, K = s.T, s.Z, s.layers, s.t_pos, s.tau, s.OD, s.OD_plus, s.OD_minus, s.K
     assert ODp is not None and ODm is not None
     n, nL, nA = grid.n, T.size, ALTS.size
     mask = np.ascontiguousarray(np.stack([(Z <= zs) for zs in ALTS]).astype(np.uint8))

@@ -54,9 +54,9 @@ def main():
     say("device: %s; cotangent vectors per rtx_tud_vjp call: up to %d" % (torch.cuda.get_device_name(0), lib.rtx_tud_vjp_max_vectors()))
 
     # the shared stages, once: base state, T -+ h line-sums, species line-sums
-    T, Z, layers, t_pos, tau, Lu, Ld, OD, ODp, ODm, K = engine._jacobian_stages(
-        "time_vjp", tbl, grid, a["Zs"], a["Ts"], a["Ps"], a["PLs"], a["MFs_VAL"], a["MFs_ID"], ALTS, 0.0, 30, True, wrt, None, 0.5,
-        None)
+    s = engine._jacobian_stages("time_vjp", tbl, grid, a["Zs"], a["Ts"], a["Ps"], a["PLs"], a["MFs_VAL"], a["MFs_ID"], ALTS, 0.0,
+                                30, True, wrt, None, 0.5, None)
+    T, Z, layers, t_pos, tau, OD, ODp, ODm, K = s.T, s.Z, s.layers, s.t_pos, s.tau, s.OD, s.OD_plus, s.OD_minus, s.K
     gen = torch.Generator(device="cuda").manual_seed(1)
     G = torch.randn((4, 2 * nZ + 1, grid.n), generator=gen, device="cuda", dtype=torch.float32)
     common = dict(Altitudes=ALTS, theta_r=0.0, N_angle=30, returnOD=True, layers=layers, t_pos=t_pos)
