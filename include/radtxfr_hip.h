@@ -313,6 +313,37 @@ int rtx_tud_vjp_dod(const float* OD, const float* dOD_dT, int64_t ld, const floa
                     const uint8_t* mask_h, double mu, int n_down, int n_angle, int return_od, const int32_t* layers_h,
                     int n_lay, int t_pos, const float* G_tau, const float* G_Lu, const float* G_Ld, int64_t ld_G,
                     int n_vec, double* out, void* stream);
+/* Tangent-linear rtx_tud (forward mode): for n_vec tangent vectors v on the wrt slots and ALL n_layers layers,
+ *   out[vec][row][nu] = sum over the wrt slots w and the layers l of J[w][l][row][nu] * V_h[vec][w][l],
+ * J exactly what rtx_tud_jacobian defines for the same first 18 arguments and t_pos (wrt slots as there: T at t_pos, the
+ * species in K's order around it); J is never stored.
+ *   V_h: [n_vec][n_wrt][n_layers] float64 on the HOST, dense; copied to a library-owned device array per (device, stream)
+ *        before the call returns (the caller's array may go at once);
+ *   d_tau, d_Lu: [n_vec][n_alt][ld_out], d_Ld: [n_vec][ld_out], float32 device arrays; each may be NULL, not all three.
+ * A NULL row group is not evaluated and nothing is written for it: without d_Ld the downwelling stream sweeps are not
+ * run, without d_Lu and d_Ld no Planck function is evaluated, without d_tau `tau` is not read (and may be NULL). With
+ * n_angle = 1 the d_Ld row is NaN. Structural zeros of J give exact 0.0, and so does an all-zero vector.
+ * Arithmetic: the tangents go through rtx_tud's recurrences in one pass each (O(n_layers) per point for tau and L-up,
+ * O(n_layers n_angle) for Ld), dOD_l = (dOD/dT)_l v_T[l] + sum_s K_s,l v_s[l] per layer. The transmittances, Planck values,
+ * dB/dT and (dOD/dT)_l are the float32 numbers rtx_tud_jacobian forms; every product with a tangent and every sum of
+ * tangents is float64 in a fixed order; each output is rounded to float32 once. A point's value depends on its column and
+ * on its vector alone: two calls give the same bits, and so do a shard and the same points of a larger call, a vector
+ * alone and the same vector among others.
+ * n_vec is at most rtx_tud_jvp_max_vectors() (4) per call: the vectors of a call share the column reads and the base
+ * recurrences, and their stream tangents stay in registers; callers loop over groups of vectors. Refused: everything
+ * rtx_tud_jacobian refuses about the column, n_vec outside [1, max], ld_out < grid->n, V_h == NULL, a non-finite entry of
+ * V_h, all outputs NULL. grid->n == 0 returns 0 and writes nothing. rtx_tud_jvp_dod: dOD_dT in place of OD_plus, OD_minus
+ * and fd_step, as rtx_tud_vjp_dod. */
+int rtx_tud_jvp(const float* OD, const float* OD_plus, const float* OD_minus, int64_t ld, double fd_step,
+                const float* K, int n_spec, const float* tau, int64_t ld_tau, const rtx_grid* grid, int n_layers,
+                const double* T_h, int n_alt, const uint8_t* mask_h, double mu, int n_down, int n_angle,
+                int return_od, int t_pos, const double* V_h, int n_vec, float* d_tau, float* d_Lu, float* d_Ld,
+                int64_t ld_out, void* stream);
+int rtx_tud_jvp_dod(const float* OD, const float* dOD_dT, int64_t ld, const float* K, int n_spec, const float* tau,
+                    int64_t ld_tau, const rtx_grid* grid, int n_layers, const double* T_h, int n_alt,
+                    const uint8_t* mask_h, double mu, int n_down, int n_angle, int return_od, int t_pos,
+                    const double* V_h, int n_vec, float* d_tau, float* d_Lu, float* d_Ld, int64_t ld_out, void* stream);
+int rtx_tud_jvp_max_vectors(void);
 /* The tabulated G of rtx_tud, for host-side checks (no device involved): rtx_tud_gtable_size() doubles, rows of
  * {interval centre, a0 .. a6}: G(S) = sum a_k (S - centre)^k on the row's interval; intervals: 16 per binade of
  * S + 2^-6 below S = 16 (row = (bits(float(S) + 2^-6) >> 19) - (bits(2^-6) >> 19)), width 1/2 from there to S = 48.

@@ -60,6 +60,11 @@ PROTOTYPES = {
                                      _i32, _vp, _i32, _i32, _vp, _i64, _vp]),
     "rtx_tud_vjp_dod": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _i64, _gp, _i32, _vp, _i32, _vp, _dbl, _i32, _i32,
                                 _i32, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "rtx_tud_jvp": (_i32, [_vp, _vp, _vp, _i64, _dbl, _vp, _i32, _vp, _i64, _gp, _i32, _vp, _i32, _vp, _dbl, _i32, _i32,
+                            _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "rtx_tud_jvp_dod": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _i64, _gp, _i32, _vp, _i32, _vp, _dbl, _i32, _i32,
+                                _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "rtx_tud_jvp_max_vectors": (_i32, []),
     "rtx_tud_gtable_size": (_i32, []),
     "rtx_tud_gtable": (_i32, [_i32, _vp, _vp]),
     "rtx_compute_tud": (_i32, [_vp, _vp, _gp, _i32, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _i32, _vp, _i32, _vp,

@@ -1681,3 +1681,76 @@ def tud_vjp(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, G_tau=None, G_Lu=None
     if mark:
         mark("vjp")
     return s.tau, s.Lu, s.Ld, s.OD, grad
+
+
+# ---- tangent-linear TUD (rtx_tud_jvp): J v for tangents v on (layer T, mixing ratios), J never stored ---------------------
+JVP_VEC_GROUP = None  # tangent vectors per rtx_tud_jvp call; None: the library's maximum (rtx_tud_jvp_max_vectors)
+JVP_ROWS = ("tau", "La", "Ld")
+
+
+def tud_jvp_from_od(OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z, V, Altitudes=(500,), theta_r=0.0, N_angle=30,
+                    returnOD=False, layers=None, t_pos=0, rows=JVP_ROWS, dOD_dT=None):
+    """rtx_tud_jvp on given float32 device columns (as tud_jacobian_from_od takes them, dOD_dT included): the product of that
+    Jacobian with tangent vectors, out[v][row] = sum over wrt slots w and layers k of J[w][k][row] V[v][w][k], without J being
+    stored. V: [n_vec][n_wrt][len(layers)] (the vector axis optional), host numbers, taken as float64; wrt slots as J's
+    (T at t_pos). It is scattered into the dense all-layer array the library takes: layers not named have tangent 0, the
+    entries of a layer index named twice add (in float64, in the order given). rows: which of "tau", "La", "Ld" are
+    evaluated (no "Ld": no downwelling sweeps; no "tau": tau may be None). Returns {row name: float32 device tensor},
+    "tau" / "La" [n_vec][nAlt][n], "Ld" [n_vec][n]. The vectors go to the library JVP_VEC_GROUP at a time; the grouping
+    changes no bit."""
+    lib = _lib.load()
+    f = _jacobian_front("tud_jvp", lib.rtx_tud_jvp, lib.rtx_tud_jvp_dod, OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z,
+                        Altitudes, theta_r, N_angle, returnOD, layers, dOD_dT)
+    layers, nA, n, n_wrt = f.layers, f.n_alt, grid.n, f.n_wrt
+    nL = int(OD.shape[0])
+    rows = tuple(rows)
+    if not rows or any(r not in JVP_ROWS for r in rows) or len(set(rows)) != len(rows):
+        raise ValueError("tud_jvp: rows %r, expected distinct names among %r" % (rows, JVP_ROWS))
+    if layers.size == 0 or layers.min() < 0 or layers.max() >= nL:
+        raise ValueError("tud_jvp: layers: indices must lie in [0, %d)" % nL)
+    V = np.asarray(V.detach().cpu().numpy() if torch.is_tensor(V) else V, dtype=np.float64)
+    if V.ndim == 2:
+        V = V[None]
+    if V.ndim != 3 or V.shape[0] < 1 or V.shape[1:] != (n_wrt, layers.size):
+        raise ValueError("tud_jvp: V has shape %r, expected [n_vec][%d][%d] (the vector axis may be left out)"
+                         % (tuple(V.shape), n_wrt, layers.size))
+    if not np.isfinite(V).all():
+        raise ValueError("tud_jvp: V has non-finite entries")
+    n_vec = V.shape[0]
+    dense = np.zeros((n_vec, n_wrt, nL))
+    for k, l in enumerate(layers):  # one at a time: a repeated index adds in the order given
+        dense[:, :, l] += V[:, :, k]
+    dev = OD.device
+    out = {}
+    if "tau" in rows:
+        out["tau"] = torch.empty((n_vec, nA, n), dtype=torch.float32, device=dev)
+    if "La" in rows:
+        out["La"] = torch.empty((n_vec, nA, n), dtype=torch.float32, device=dev)
+    if "Ld" in rows:
+        out["Ld"] = torch.empty((n_vec, n), dtype=torch.float32, device=dev)
+    group = int(JVP_VEC_GROUP or lib.rtx_tud_jvp_max_vectors())
+    st = _stream_ptr()
+    for v0 in range(0, n_vec, group):
+        v1 = min(v0 + group, n_vec)
+        part = lambda name: _ptr(out[name][v0:v1]) if name in out else None
+        Vg = np.ascontiguousarray(dense[v0:v1])
+        _lib.check(f.entry(*f.lead, t_pos, Vg.ctypes.data_as(C.c_void_p), v1 - v0, part("tau"), part("La"), part("Ld"), n, st))
+    return out
+
+
+def tud_jvp(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, V, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=False,
+            wrt=("T",), layers=None, fd_step_T=0.5, mark=None, rows=JVP_ROWS, dT_method="fd"):
+    """compute_TUD's outputs and their change along tangent directions in (layer temperatures, mixing ratios):
+    tud_jacobian's stages (the same base state, T -+ fd_step_T line-sums and species line-sums) followed by rtx_tud_jvp
+    instead of rtx_tud_jacobian. wrt, layers, fd_step_T, dT_method as tud_jacobian; V [n_vec][n_wrt][len(layers)] and rows as
+    tud_jvp_from_od, V's wrt axis following `wrt`. Returns (tau, Lu, Ld, OD, d) with d as tud_jvp_from_od returns it.
+    mark(name): after each stage ("base", "T", "species", "jvp")."""
+    check_dT_method(dT_method)
+    s = _jacobian_stages("tud_jvp", lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt,
+                         layers, fd_step_T, mark, dT_method)
+    d = tud_jvp_from_od(s.OD, s.OD_plus, s.OD_minus, fd_step_T, s.K, s.tau, grid, s.T, s.Z, V, Altitudes=Altitudes,
+                        theta_r=theta_r, N_angle=N_angle, returnOD=returnOD, layers=s.layers, t_pos=s.t_pos, rows=rows,
+                        dOD_dT=s.dOD_dT)
+    if mark:
+        mark("jvp")
+    return s.tau, s.Lu, s.Ld, s.OD, d

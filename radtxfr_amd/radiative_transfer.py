@@ -800,6 +800,86 @@ def compute_TUD_vjp(Xmin, Xmax, cotangents, opts=options, wrt=("T",), layers=Non
     return X_, tau_, Lu_, Ld_h[0], _grad_dict(grad_h, wrt, n_vec)
 
 
+def _jvp_tangents(tangents, n_lay):
+    """compute_TUD_jvp's tangents (a dict whose keys are checked already), checked on the host: (V float64
+    [n_vec][n_wrt][n_lay], n_vec or None without a vector axis). Each entry is [n_lay] or [n_lay][n_vec]; the wrt axis
+    follows the dict's order."""
+    fn = "compute_TUD_jvp"
+    cols, n_vecs = [], set()
+    for key, v in tangents.items():
+        v = np.asarray(v.detach().cpu().numpy() if _is_torch(v) else v, dtype=np.float64)
+        got = _vector_axis(v, (n_lay,))
+        if got is None:
+            raise ValueError(fn + ": tangent %r has shape %r, expected %r (one entry per layer of layers=) plus an optional "
+                             "trailing vector axis" % (key, tuple(v.shape), (n_lay,)))
+        v, nv = got
+        if not np.isfinite(v).all():
+            raise ValueError(fn + ": tangent %r has non-finite entries" % (key,))
+        n_vecs.add(nv)
+        cols.append(v.T)  # [n_vec][n_lay]
+    if len(n_vecs) != 1:
+        raise ValueError(fn + ": the tangents disagree on the vector axis: %r" % sorted(n_vecs, key=str))
+    return np.ascontiguousarray(np.stack(cols, axis=1)), n_vecs.pop()
+
+
+def compute_TUD_jvp(Xmin, Xmax, tangents, opts=options, layers=None, rows=("tau", "La", "Ld"), fd_step_T=0.5, dT_method="fd",
+                    **kwargs):
+    """compute_TUD and the change of its outputs along directions in (layer temperatures, mixing ratios): compute_TUD_jacobian's
+    J applied to tangent vectors, without J ever being stored (forward mode). The result is spectra, 2 nAlt + 1
+    rows per vector: it fits where J does not.
+
+    tangents: dict {"T" or a molecule id of MFs_ID: array [n_layers], or [n_layers][n_vec] for several directions at once},
+    in K ("T") and ppmv (a molecule id) per layer of `layers` (default all; layers not named do not move; a layer named
+    twice moves by the sum of its entries). The keys are the wrt of compute_TUD_jacobian. rows: which of "tau", "La", "Ld"
+    are evaluated: without "Ld" the downwelling stream sweeps, the expensive part, are not run.
+    kwargs, layers, fd_step_T, dT_method: as compute_TUD_jacobian, with the same definition of every derivative. Returns
+    (X, tau, La, Ld, d): X, tau, La, Ld bit-identical to compute_TUD with the same kwargs; d {"tau", "La", "Ld"} restricted
+    to `rows`, each float64 and shaped like the output of that name, plus a trailing [n_vec] axis when the tangents have one:
+      d[row][X(, alt)(, v)] = sum over the keys w and the layers k of J[w][row][X(, alt), k] * tangents[w][k(, v)].
+    The tangents are carried through the TUD recurrences in float64 and each result is rounded to float32 once; a point's
+    value does not depend on the other vectors of the call. There is no reduce=: the results are spectra, and
+    reduceResolution takes them as it takes any spectrum.
+    Arguments are checked before any device work. NotImplementedError: more than one theta_r, broadening=, xs_lut=."""
+    c = _Call("compute_TUD_jvp", Xmin, Xmax, opts, kwargs)
+    if "reduce" in c.o:
+        raise NotImplementedError("compute_TUD_jvp: reduce= is not offered: the results are spectra, pass them to reduceResolution")
+    _no_xs_lut(c)
+    if isinstance(tangents, dict) and tangents:
+        wrt = tuple(tangents.keys())
+        bad = [k for k in wrt if k != "T" and (isinstance(k, bool) or not isinstance(k, (int, np.integer)))]
+        if bad:
+            raise ValueError("compute_TUD_jvp: unknown tangent key %r (expected \"T\" or a molecule id of MFs_ID)" % (bad[0],))
+    else:
+        raise ValueError("compute_TUD_jvp: tangents must be a non-empty dict {\"T\" or a molecule id of MFs_ID: array}")
+    wrt, lay, nX = _jacobian_args(c.fn, Xmin, Xmax, c.o, wrt, layers, None, fd_step_T, host_result=False, dT_method=dT_method)
+    if isinstance(rows, str):
+        rows = (rows,)
+    rows = tuple(rows)
+    if not rows or any(r not in engine.JVP_ROWS for r in rows) or len(set(rows)) != len(rows):
+        raise ValueError("compute_TUD_jvp: rows %r, expected distinct names among %r" % (rows, engine.JVP_ROWS))
+    V, n_vec = _jvp_tangents(tangents, lay.size)
+    nZ = c.Z_s.size
+    X_, grid = c.X, c.grid
+    assert X_.size == nX
+    tbl = c.table()
+    tau, Lu, Ld, _, d = engine.tud_jvp(tbl, grid, c.Z, c.T, c.P, c.PL, c.MF, c.ID, V, Altitudes=c.Z_s, theta_r=c.theta,
+                                       N_angle=c.N_angle, returnOD=c.returnOD, wrt=wrt, layers=lay, fd_step_T=float(fd_step_T),
+                                       rows=rows, dT_method=dT_method)
+    (tau_h, Lu_h, Ld_h), done = _rows_to_host_f64([tau, Lu, Ld[None, :]])
+    d_h = {name: t.to(torch.float64).cpu().numpy() for name, t in d.items()}  # [n_vec]([nZ])[nX]
+    done.synchronize()
+    tau_, Lu_ = _tud_shapes(tau_h, Lu_h, nZ, 1)
+    out = {}
+    for name in engine.JVP_ROWS:
+        if name not in d_h:
+            continue
+        a = np.transpose(d_h[name])  # [nX]([nZ])[n_vec]
+        if name != "Ld" and nZ == 1:
+            a = a[:, 0]  # one altitude: compute_TUD squeezes the altitude axis
+        out[name] = np.ascontiguousarray(a if n_vec is not None else a[..., 0])
+    return X_, tau_, Lu_, Ld_h[0], out
+
+
 def compute_band_radiance_vjp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, cotangent, opts=options, wrt=("T",), layers=None,
                               fd_step_T=0.5, dT_method="fd", **kwargs):
     """At-sensor band radiances over a surface and the gradient of a scalar cost defined on them, in one call: the
