@@ -1,10 +1,11 @@
-// Ownership of device memory ("Device memory"): an owned, grow-only device array and a keyed cache of
-// process-lifetime device tables. Host-only and free of HIP headers: everything goes through three functions that the
-// library defines once (rtx_lines.hip) and that a host test may define over malloc.
+// Ownership of device memory ("Device memory"): an owned, grow-only device array, scratch per (device,
+// stream) and a keyed cache of process-lifetime device tables. Host-only and free of HIP headers: everything goes through
+// four functions that the library defines once (rtx_lines.hip) and that a host test may define over malloc.
 #pragma once
 #include <stddef.h>
 #include <string.h>
 
+#include <map>
 #include <mutex>
 #include <utility>
 #include <vector>
@@ -12,6 +13,9 @@
 int rtx_dev_alloc(void** p, size_t bytes);  // 0 ok; on failure *p = nullptr and the error text is set
 void rtx_dev_free(void* p);                 // nullptr allowed; waits for the device, like hipFree
 int rtx_dev_h2d(void* d, const void* h, size_t bytes);  // synchronous copy; 0 ok, else the error text is set
+// index of the calling thread's current device; 0 ok, else the error text is set (hidden: the library's exported names stay
+// what they were)
+__attribute__((visibility("hidden"))) int rtx_dev_current(int* dev);
 
 // Move-only owner of a device array of cap() elements. A failed reserve() or upload() leaves it empty: (nullptr, 0).
 template <class T>
@@ -56,6 +60,31 @@ class DevBuf {
  private:
   T* p_ = nullptr;
   size_t cap_ = 0;
+};
+
+// Scratch of an entry point: grow-only device bytes per (current device, stream), the stream a hipStream_t passed as
+// void*. Calls on one stream are ordered by it and may share bytes; calls on different streams (or devices) must not.
+// get() hands out at least `bytes` bytes; the mutex covers the lookup and the reserve only. That is enough: map nodes do
+// not move, and a call on another key only ever grows its own entry, so the pointer stays good until the next get() on
+// the same key asks for more (growth frees first, and the free waits for the kernels enqueued on the old array).
+// Every entry point keeps an object of its own: two of them can be live in one stream's call. One that lives as long as
+// the process is made with `new` and never destroyed: no device call may run from a static destructor.
+class StreamScratch {
+ public:
+  int get(void* stream, size_t bytes, void** out) {
+    *out = nullptr;
+    int dev = 0;
+    if (rtx_dev_current(&dev)) return 1;
+    std::lock_guard<std::mutex> lock(mu_);
+    DevBuf<char>& b = buf_[std::make_pair(dev, stream)];
+    if (b.reserve(bytes)) return 1;
+    *out = b.get();
+    return 0;
+  }
+
+ private:
+  std::mutex mu_;
+  std::map<std::pair<int, void*>, DevBuf<char>> buf_;
 };
 
 // Device tables that live as long as the process, keyed on (device index, a blob of bytes), at most max_entries of them

@@ -55,6 +55,10 @@ int rtx_dev_h2d(void* d, const void* h, size_t bytes) {
   RTX_HIP(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));
   return 0;
 }
+int rtx_dev_current(int* dev) {
+  RTX_HIP(hipGetDevice(dev));
+  return 0;
+}
 
 // ---- line table ------------------------------------------------------------------------------------
 // A column of n doubles (one element for an empty table, so that the pointer is never NULL); an optional column that is

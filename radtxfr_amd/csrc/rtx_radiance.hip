@@ -10,8 +10,6 @@
 // The ILS never builds the reference's dense (nS,nX,nB) temporary: each band only visits the grid
 // points under its own weight function; on a large materialised Y it runs in one pass over the rows
 // (ils_rows_kernel: every row is fetched once although ~3 triangles or ~15 Gaussians cover it).
-#include <map>
-#include <mutex>
 #include <stdlib.h>
 #include <string.h>
 
@@ -559,18 +557,8 @@ __global__ __launch_bounds__(256) void ils_rows_reduce_kernel(IlsRowsArgs r) {
 
 // workspace of the one-pass form, per (device, stream): two rtx_ils calls in flight on different streams (or from
 // different host threads on their own streams) must not share partial sums and the overflow flag; calls on ONE stream
-// are ordered by it. The map lives as long as the process.
-static int ils_rows_workspace(size_t bytes, hipStream_t st, void** out) {
-  static std::mutex mu;
-  static auto* const ws = new std::map<std::pair<int, hipStream_t>, DevBuf<char>>();
-  int dev = 0;
-  RTX_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(mu);
-  DevBuf<char>& b = (*ws)[std::make_pair(dev, st)];
-  if (b.reserve(bytes)) return 1;
-  *out = b.get();
-  return 0;
-}
+// are ordered by it.
+static StreamScratch* const ils_rows_scratch = new StreamScratch();
 
 extern "C" int rtx_ils(int kind, const rtx_grid* grid, const double* X, int64_t nx, const float* Y, int64_t nS, int64_t ldY,
                        int nB, const double* centre_d, const double* sigma_d, float* Y_out, void* stream) {
@@ -601,7 +589,7 @@ extern "C" int rtx_ils(int kind, const rtx_grid* grid, const double* X, int64_t 
       r.a = a; r.n_chunks = (int)n_chunks; r.slots = kind == 0 ? ILS_SLOTS_TRI : ILS_SLOTS_GAUSS;
       const size_t nP = (size_t)n_chunks * r.slots * (size_t)nS, nW = (size_t)n_chunks * r.slots;
       void* base = nullptr;
-      if (ils_rows_workspace((nP + nW) * sizeof(float) + (2 * (size_t)n_chunks + 1) * sizeof(int), st, &base)) return 1;
+      if (ils_rows_scratch->get(st, (nP + nW) * sizeof(float) + (2 * (size_t)n_chunks + 1) * sizeof(int), &base)) return 1;
       r.P = (float*)base; r.Wt = r.P + nP; r.b0 = (int*)(r.Wt + nW); r.overflow = r.b0 + 2 * n_chunks;
       RTX_HIP(hipMemsetAsync(r.overflow, 0, sizeof(int), st));
       if (kind == 0) hipLaunchKernelGGL((ils_rows_kernel<0, ILS_CAP>), dim3((unsigned)n_chunks, (unsigned)((nS / 4 + 63) / 64)), dim3(256), 0, st, r);

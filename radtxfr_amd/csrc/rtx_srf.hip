@@ -17,10 +17,6 @@
 // fp32 fmaf chain over the chunk's rows in ascending order, whatever lane, wave or load width carries it and whichever
 // other bands share the pass (a row of weight 0 is skipped, not multiplied); the chunk sums are added in fp64 in
 // ascending chunk order. Chunks are cut at multiples of SRF_CH from the axis' first point.
-#include <map>
-#include <mutex>
-#include <utility>
-
 #include "rtx_srf_common.h"
 
 #define SRF_CAP 4           // bands per pass over the chunk's rows: their weights are one float4 per row in LDS
@@ -178,18 +174,8 @@ __global__ __launch_bounds__(256) void srf_reduce_kernel(SrfArgs a) {
 }
 
 // workspace per (device, stream), like rtx_ils': calls on one stream are ordered by it, calls on different streams must
-// not share chunk sums. Grow-only; the map lives as long as the process.
-static int srf_workspace(size_t bytes, hipStream_t st, void** out) {
-  static std::mutex mu;
-  static auto* const ws = new std::map<std::pair<int, hipStream_t>, DevBuf<char>>();
-  int dev = 0;
-  RTX_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(mu);
-  DevBuf<char>& b = (*ws)[std::make_pair(dev, st)];
-  if (b.reserve(bytes)) return 1;
-  *out = b.get();
-  return 0;
-}
+// not share chunk sums.
+static StreamScratch* const srf_scratch = new StreamScratch();
 
 extern "C" int rtx_srf_chunk_points(void) { return SRF_CH; }
 extern "C" int rtx_srf_max_knots(void) { return SRF_MAX_KNOTS; }
@@ -220,7 +206,7 @@ extern "C" int rtx_srf_apply(const rtx_grid* grid, const double* X, int64_t nx, 
   hipStream_t st = (hipStream_t)stream;
   const size_t nW = (size_t)n_chunks * SRF_SLOTS, nP = nW * (size_t)nS;
   void* base = nullptr;
-  if (srf_workspace(nW * sizeof(double) + 2 * SRF_SLOTS * sizeof(long long) + nP * sizeof(float), st, &base)) return 1;
+  if (srf_scratch->get(st, nW * sizeof(double) + 2 * SRF_SLOTS * sizeof(long long) + nP * sizeof(float), &base)) return 1;
   SrfArgs a;
   if (grid) a.g = to_dev(grid); else { a.g.xmin = a.g.xmax = a.g.step = 0; a.g.n_total = a.g.offset = a.g.n = 0; }
   a.X = X; a.nx = nx; a.nS = nS; a.ldY = ldY; a.Y = Y; a.kx = knot_x_d; a.kr = knot_r_d;
@@ -521,7 +507,7 @@ extern "C" int rtx_srf_moments(const rtx_grid* grid, const float* tau, const flo
   a.row = (long long)nk + 2 * n_chunks * SRFM_NSUB;
   const size_t nW = (size_t)n_chunks * SRF_SLOTS, nP = (size_t)SRF_SLOTS * (size_t)nT * (size_t)a.row;
   void* base = nullptr;
-  if (srf_workspace(2 * nW * sizeof(double) + 2 * SRF_SLOTS * sizeof(long long) + nP * sizeof(float), st, &base)) return 1;
+  if (srf_scratch->get(st, 2 * nW * sizeof(double) + 2 * SRF_SLOTS * sizeof(long long) + nP * sizeof(float), &base)) return 1;
   a.s.g = to_dev(grid);
   a.s.X = nullptr; a.s.nx = nx; a.s.nS = 0; a.s.ldY = 0; a.s.Y = nullptr; a.s.kx = knot_x_d; a.s.kr = knot_r_d;
   a.s.P = nullptr; a.s.W = nullptr; a.s.Yout = nullptr; a.s.wsum = nullptr;

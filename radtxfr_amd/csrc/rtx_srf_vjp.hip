@@ -21,10 +21,6 @@
 //   srfv_dts_kernel      dTs[t]: the chunks' partials in ascending chunk order
 //   srfv_de_kernel       dE[j][e]: fp64 over (t, b) ascending, M from an rtx_srf_moments run inside the call
 // No atomics. Determinism: see the header.
-#include <map>
-#include <mutex>
-#include <utility>
-
 #include "rtx_srf_common.h"
 #include "rtx_tud_jac_common.h"  // planck_dT
 
@@ -311,18 +307,8 @@ __global__ __launch_bounds__(256) void srfv_de_kernel(SrfvArgs a) {
   a.dE[(size_t)j * (size_t)a.nE + e] = acc;
 }
 
-// workspace per (device, stream), as rtx_srf_apply's: grow-only, the map lives as long as the process
-static int srfv_workspace(size_t bytes, hipStream_t st, void** out) {
-  static std::mutex mu;
-  static auto* const ws = new std::map<std::pair<int, hipStream_t>, DevBuf<char>>();
-  int dev = 0;
-  RTX_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(mu);
-  DevBuf<char>& b = (*ws)[std::make_pair(dev, st)];
-  if (b.reserve(bytes)) return 1;
-  *out = b.get();
-  return 0;
-}
+// workspace per (device, stream), as rtx_srf_apply's
+static StreamScratch* const srfv_scratch = new StreamScratch();
 
 static int srfv_check_bands(const rtx_grid* grid, int nB, const int32_t* knot_start_h) {
   if (!grid) RTX_FAIL("no grid");
@@ -391,7 +377,7 @@ extern "C" int rtx_srf_norms(const rtx_grid* grid, int nB, const int32_t* knot_s
                o_ks = c.take(((size_t)nB + 1) * sizeof(int)), o_wn = c.take((size_t)n_chunks * nB * sizeof(double)),
                o_xk = c.take(sizeof(double));
   char* base = nullptr;
-  if (srfv_workspace(c.off, st, (void**)&base)) return 1;
+  if (srfv_scratch->get(st, c.off, (void**)&base)) return 1;
   SrfvArgs a;
   srfv_base(a, grid, knot_x_d, knot_r_d, nB);
   a.sup = (long long*)(base + o_sup); a.jr = (int2*)(base + o_jr); a.ksd = (int*)(base + o_ks); a.WN = (double*)(base + o_wn);
@@ -441,7 +427,7 @@ extern "C" int rtx_srf_radiance_vjp(const rtx_grid* grid, const float* tau, cons
                o_mn = c.take(dE ? (size_t)nB * sizeof(float) : 0), o_mc = c.take(dE ? (size_t)nB * sizeof(float) : 0),
                o_mj = c.take(dE ? (size_t)nB * sizeof(int2) : 0);
   char* base = nullptr;
-  if (srfv_workspace(c.off, st, (void**)&base)) return 1;
+  if (srfv_scratch->get(st, c.off, (void**)&base)) return 1;
   SrfvArgs a;
   srfv_base(a, grid, knot_x_d, knot_r_d, nB);
   a.tau = tau; a.La = La; a.Ld = Ld; a.E = E; a.g = g; a.Xk = Xk; a.nk = nk; a.nE = nE; a.nT = nT;

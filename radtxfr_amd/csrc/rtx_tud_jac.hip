@@ -198,24 +198,17 @@ int rtx_tud_zero_rows(size_t count, const float** out) {
   return 0;
 }
 
-// dod: OD_plus is dOD/dT itself (rtx_tud_jacobian_dod), OD_minus and fd_step are not the caller's
-static int tud_jacobian_run(const float* OD, const float* OD_plus, const float* OD_minus, bool dod, int64_t ld, double fd_step,
-                            const float* K, int n_spec, const float* tau, int64_t ld_tau, const rtx_grid* grid, int n_layers,
-                            const double* T_h, int n_alt, const uint8_t* mask_h, double mu, int n_down, int n_angle,
-                            int return_od, const int32_t* layers_h, int n_lay, int t_pos, float* J, int64_t ld_J,
-                            void* stream) {
-  if (rtx_check_grid(grid)) return 1;
+static int tud_jacobian_run(const TudColumnIn& c, const int32_t* layers_h, int n_lay, float* J, int64_t ld_J, void* stream) {
+  if (tud_column_check(c)) return 1;
   if (!J) RTX_FAIL("a required pointer is NULL");
   TudJacArgs a;
-  if (tud_jac_setup(a, OD, OD_plus, OD_minus, ld, fd_step, K, n_spec, tau, ld_tau, true, grid, n_layers, T_h, n_alt, mask_h, mu,
-                    n_down, n_angle, return_od, layers_h, n_lay, t_pos))
-    return 1;
-  if (ld_J < grid->n) RTX_FAIL("leading dimension smaller than the shard");
+  if (tud_jac_setup(a, c, true, layers_h, n_lay)) return 1;
+  if (ld_J < c.grid->n) RTX_FAIL("leading dimension smaller than the shard");
   a.J = J; a.ld_J = ld_J;
-  if (grid->n == 0) return 0;
-  if (dod && rtx_tud_zero_rows((size_t)n_layers * (size_t)ld, &a.ODm)) return 1;
-  const long long blocks = (grid->n + 255) / 256;
-  hipLaunchKernelGGL(tud_jac_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  if (c.grid->n == 0) return 0;
+  unsigned blocks;
+  if (tud_blocks(c.grid, 256, &blocks)) return 1;
+  hipLaunchKernelGGL(tud_jac_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
   RTX_LAUNCH_CHECK();
   return 0;
 }
@@ -225,15 +218,16 @@ extern "C" int rtx_tud_jacobian(const float* OD, const float* OD_plus, const flo
                                 const double* T_h, int n_alt, const uint8_t* mask_h, double mu, int n_down, int n_angle,
                                 int return_od, const int32_t* layers_h, int n_lay, int t_pos, float* J, int64_t ld_J,
                                 void* stream) {
-  return tud_jacobian_run(OD, OD_plus, OD_minus, false, ld, fd_step, K, n_spec, tau, ld_tau, grid, n_layers, T_h, n_alt, mask_h, mu,
-                          n_down, n_angle, return_od, layers_h, n_lay, t_pos, J, ld_J, stream);
+  const TudColumnIn c = {OD, OD_plus, OD_minus, ld, fd_step, K, n_spec, tau, ld_tau, grid, n_layers, T_h, n_alt, mask_h, mu,
+                         n_down, n_angle, return_od, t_pos, false};
+  return tud_jacobian_run(c, layers_h, n_lay, J, ld_J, stream);
 }
 
 extern "C" int rtx_tud_jacobian_dod(const float* OD, const float* dOD_dT, int64_t ld, const float* K, int n_spec, const float* tau,
                                     int64_t ld_tau, const rtx_grid* grid, int n_layers, const double* T_h, int n_alt,
                                     const uint8_t* mask_h, double mu, int n_down, int n_angle, int return_od,
                                     const int32_t* layers_h, int n_lay, int t_pos, float* J, int64_t ld_J, void* stream) {
-  if (!dOD_dT) RTX_FAIL("dOD_dT is NULL");
-  return tud_jacobian_run(OD, dOD_dT, dOD_dT, true, ld, 0.5, K, n_spec, tau, ld_tau, grid, n_layers, T_h, n_alt, mask_h, mu, n_down,
-                          n_angle, return_od, layers_h, n_lay, t_pos, J, ld_J, stream);
+  const TudColumnIn c = {OD, dOD_dT, dOD_dT, ld, 0.5, K, n_spec, tau, ld_tau, grid, n_layers, T_h, n_alt, mask_h, mu,
+                         n_down, n_angle, return_od, t_pos, true};
+  return tud_jacobian_run(c, layers_h, n_lay, J, ld_J, stream);
 }

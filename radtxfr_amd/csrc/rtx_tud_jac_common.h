@@ -1,10 +1,15 @@
-// What rtx_tud_jac.hip (the Jacobian J) and rtx_tud_vjp.hip (its adjoint, J^T g) share: the limits, the description of
-// the column and of the request that both kernels take, the host code that checks and fills it, and the device
-// functions the per-lane row factors are formed with. One copy of each, so that the adjoint contracts exactly the
-// numbers the Jacobian stores.
+// What the three derivative kernels of the TUD stage share: rtx_tud_jac.hip (the Jacobian J, stored), rtx_tud_vjp.hip (its
+// adjoint, J^T g) and rtx_tud_jvp.hip (its tangent, J v). The limits, the description of the column and of the request
+// that the kernels take, the entry points' column struct and the host code that checks it, fills the request, counts the
+// workgroups and picks the instantiation, and the device functions the per-lane row factors are formed with. One copy of
+// each. The column sweeps and a layer's row factors are NOT here: each kernel carries its own text of them, kept in step
+// by the bit-identity tests. As device functions of this header they moved registers, occupancy or time in every kernel
+// that called them (profiles/tud_deriv_refactor_isa.txt, profiles/tud_deriv_refactor_time.txt).
 #pragma once
 #include <math.h>
 #include <string.h>
+
+#include <type_traits>
 
 #include "rtx_tud_common.h"
 
@@ -66,59 +71,109 @@ __device__ __forceinline__ double planck_f64(double c1x3, double x, double ct) {
 // grow-only, one array per device, zeroed when it is allocated and never written again.
 int rtx_tud_zero_rows(size_t count, const float** out);
 
+// The column as every entry point of the three files takes it: the 18 leading arguments of rtx_tud_jacobian
+// (include/radtxfr_hip.h) and t_pos. dod: the *_dod form, where OD_plus and OD_minus both hold the caller's dOD_dT and
+// fd_step is 1/2; tud_jac_setup then puts the zeros in OD_minus' place.
+struct TudColumnIn {
+  const float *OD, *OD_plus, *OD_minus;
+  int64_t ld;
+  double fd_step;
+  const float* K;
+  int n_spec;
+  const float* tau;
+  int64_t ld_tau;
+  const rtx_grid* grid;
+  int n_layers;
+  const double* T_h;
+  int n_alt;
+  const uint8_t* mask_h;
+  double mu;
+  int n_down, n_angle, return_od, t_pos;
+  bool dod;
+};
+
+// what every entry point refuses first
+static inline int tud_column_check(const TudColumnIn& c) {
+  if (c.dod && !c.OD_plus) RTX_FAIL("dOD_dT is NULL");
+  return rtx_check_grid(c.grid);
+}
 
 // Checks everything about the column and the request that does not concern the result array, and fills `a` (J and ld_J
 // stay 0). need_tau: the caller reads the base transmittances (always, for J; only with a cotangent on tau, for J^T g).
-static inline int tud_jac_setup(TudJacArgs& a, const float* OD, const float* OD_plus, const float* OD_minus, int64_t ld,
-                                double fd_step, const float* K, int n_spec, const float* tau, int64_t ld_tau, bool need_tau,
-                                const rtx_grid* grid, int n_layers, const double* T_h, int n_alt, const uint8_t* mask_h,
-                                double mu, int n_down, int n_angle, int return_od, const int32_t* layers_h, int n_lay,
-                                int t_pos) {
-  const int with_T = OD_plus != nullptr;
-  if (!OD || !T_h || !mask_h || !layers_h) RTX_FAIL("a required pointer is NULL");
-  if ((OD_plus == nullptr) != (OD_minus == nullptr)) RTX_FAIL("OD_plus and OD_minus are given together or not at all");
-  if (with_T && !(fd_step > 0.0)) RTX_FAIL("fd_step=%g must be > 0", fd_step);
+// Last, for the dod form and a shard that is not empty, the zeros: nothing before that touches the device.
+static inline int tud_jac_setup(TudJacArgs& a, const TudColumnIn& c, bool need_tau, const int32_t* layers_h, int n_lay) {
+  const int n_spec = c.n_spec, n_layers = c.n_layers, n_alt = c.n_alt, t_pos = c.t_pos;
+  const int with_T = c.OD_plus != nullptr;
+  if (!c.OD || !c.T_h || !c.mask_h || !layers_h) RTX_FAIL("a required pointer is NULL");
+  if ((c.OD_plus == nullptr) != (c.OD_minus == nullptr)) RTX_FAIL("OD_plus and OD_minus are given together or not at all");
+  if (with_T && !(c.fd_step > 0.0)) RTX_FAIL("fd_step=%g must be > 0", c.fd_step);
   if (n_spec < 0 || n_spec > TUDJ_MAX_SPEC) RTX_FAIL("n_spec=%d outside [0,%d]", n_spec, TUDJ_MAX_SPEC);
-  if (n_spec > 0 && !K) RTX_FAIL("K is NULL");
+  if (n_spec > 0 && !c.K) RTX_FAIL("K is NULL");
   if (with_T + n_spec < 1) RTX_FAIL("nothing to differentiate (no OD_plus and n_spec = 0)");
-  need_tau = need_tau && !return_od;
-  if (need_tau && !tau) RTX_FAIL("tau is NULL (needed unless return_od)");
+  need_tau = need_tau && !c.return_od;
+  if (need_tau && !c.tau) RTX_FAIL("tau is NULL (needed unless return_od)");
   if (n_layers < 1 || n_layers > TUDJ_MAX_LAYERS) RTX_FAIL("n_layers=%d outside [1,%d]", n_layers, TUDJ_MAX_LAYERS);
   if (n_alt < 1 || n_alt > TUDJ_MAX_ALT) RTX_FAIL("n_alt=%d outside [1,%d]", n_alt, TUDJ_MAX_ALT);
-  if (n_angle < 1 || n_angle > TUDJ_MAX_ANGLES) RTX_FAIL("n_angle=%d outside [1,%d]", n_angle, TUDJ_MAX_ANGLES);
-  if (n_down < 0 || n_down > n_layers) RTX_FAIL("n_down=%d outside [0,%d]", n_down, n_layers);
+  if (c.n_angle < 1 || c.n_angle > TUDJ_MAX_ANGLES) RTX_FAIL("n_angle=%d outside [1,%d]", c.n_angle, TUDJ_MAX_ANGLES);
+  if (c.n_down < 0 || c.n_down > n_layers) RTX_FAIL("n_down=%d outside [0,%d]", c.n_down, n_layers);
   if (n_lay < 1 || n_lay > TUDJ_MAX_LAYERS) RTX_FAIL("n_lay=%d outside [1,%d]", n_lay, TUDJ_MAX_LAYERS);
-  if (!(mu >= 1.0) || !isfinite(mu)) RTX_FAIL("mu=%g must be finite and >= 1", mu);
+  if (!(c.mu >= 1.0) || !isfinite(c.mu)) RTX_FAIL("mu=%g must be finite and >= 1", c.mu);
   if (t_pos < 0 || (with_T ? t_pos > n_spec : t_pos != 0)) RTX_FAIL("t_pos=%d outside [0,%d]", t_pos, with_T ? n_spec : 0);
-  if (ld < grid->n || (need_tau && ld_tau < grid->n)) RTX_FAIL("leading dimension smaller than the shard");
+  if (c.ld < c.grid->n || (need_tau && c.ld_tau < c.grid->n)) RTX_FAIL("leading dimension smaller than the shard");
   memset(&a, 0, sizeof(a));
   for (int k = 0; k < n_lay; ++k) {
     if (layers_h[k] < 0 || layers_h[k] >= n_layers) RTX_FAIL("layer index %d outside [0,%d)", layers_h[k], n_layers);
     a.lay[k] = layers_h[k];
   }
-  if (tud_layer_consts(T_h, n_layers, a.c2l2e_over_T)) return 1;
+  if (tud_layer_consts(c.T_h, n_layers, a.c2l2e_over_T)) return 1;
   for (int ia = 0; ia < n_alt; ++ia) {  // (rtx_tud packs the same masks per altitude; here the bits go per layer)
-    int c = 0;
+    int cnt = 0;
     for (int k = 0; k < n_layers; ++k)
-      if (mask_h[(size_t)ia * n_layers + k]) { a.lbits[k] |= 1u << ia; ++c; }
-    a.count[ia] = c;
-    for (int k = 0; k < c; ++k) a.lbits[k] |= 1u << (16 + ia);
+      if (c.mask_h[(size_t)ia * n_layers + k]) { a.lbits[k] |= 1u << ia; ++cnt; }
+    a.count[ia] = cnt;
+    for (int k = 0; k < cnt; ++k) a.lbits[k] |= 1u << (16 + ia);
   }
   // the quadrature of rtx_tud, weights normalised (:387-388); theta = 0 has weight 0
-  const TudQuadrature quad = tud_quadrature(n_angle);
+  const TudQuadrature quad = tud_quadrature(c.n_angle);
   int ns = 0;
-  for (int q = 1; q < n_angle; ++q) {
-    const double c = cos(quad.th[q]), w = quad.w[q] / quad.wsum;
-    a.str_ic[ns] = 1.0 / c;
+  for (int q = 1; q < c.n_angle; ++q) {
+    const double co = cos(quad.th[q]), w = quad.w[q] / quad.wsum;
+    a.str_ic[ns] = 1.0 / co;
     a.str_w[ns] = (float)w;
-    a.str_wc[ns] = (float)(w / c);
+    a.str_wc[ns] = (float)(w / co);
     ++ns;
   }
   a.n_str = ns;
-  a.OD = OD; a.ODp = OD_plus; a.ODm = OD_minus; a.K = K; a.tau = tau;
-  a.ld = ld; a.ld_tau = ld_tau; a.g = to_dev(grid);
-  a.n_layers = n_layers; a.n_alt = n_alt; a.n_down = n_down; a.return_od = return_od;
+  a.OD = c.OD; a.ODp = c.OD_plus; a.ODm = c.OD_minus; a.K = c.K; a.tau = c.tau;
+  a.ld = c.ld; a.ld_tau = c.ld_tau; a.g = to_dev(c.grid);
+  a.n_layers = n_layers; a.n_alt = n_alt; a.n_down = c.n_down; a.return_od = c.return_od;
   a.with_T = with_T; a.n_spec = n_spec; a.n_lay = n_lay; a.t_pos = t_pos;
-  a.mu = (float)mu; a.mu_d = mu; a.inv_2h = with_T ? (float)(0.5 / fd_step) : 0.f;
+  a.mu = (float)c.mu; a.mu_d = c.mu; a.inv_2h = with_T ? (float)(0.5 / c.fd_step) : 0.f;
+  if (c.dod && c.grid->n > 0 && rtx_tud_zero_rows((size_t)n_layers * (size_t)c.ld, &a.ODm)) return 1;
   return 0;
+}
+
+// workgroups of `per` points over the shard; a count that a launch cannot take is refused
+static inline int tud_blocks(const rtx_grid* grid, int per, unsigned* blocks) {
+  const long long b = (grid->n + per - 1) / per;
+  if (b > 0x7fffffffLL) RTX_FAIL("grid->n=%lld: too many workgroups", (long long)grid->n);
+  *blocks = (unsigned)b;
+  return 0;
+}
+
+// f(TAU, LU, LD) with the three row-group flags as std::bool_constant values: the caller's generic lambda launches its
+// kernel's <TAU, LU, LD> instantiation. At least one flag is set (the entry points refuse the empty selection).
+template <class F>
+static inline void tud_dispatch_rows(bool has_tau, bool has_Lu, bool has_Ld, F&& f) {
+  using Y = std::true_type;
+  using N = std::false_type;
+  switch ((has_tau ? 4 : 0) | (has_Lu ? 2 : 0) | (has_Ld ? 1 : 0)) {
+    case 1: f(N(), N(), Y()); break;
+    case 2: f(N(), Y(), N()); break;
+    case 3: f(N(), Y(), Y()); break;
+    case 4: f(Y(), N(), N()); break;
+    case 5: f(Y(), N(), Y()); break;
+    case 6: f(Y(), Y(), N()); break;
+    default: f(Y(), Y(), Y()); break;
+  }
 }

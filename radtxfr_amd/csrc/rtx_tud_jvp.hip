@@ -20,11 +20,6 @@
 // The vectors of a launch (at most TUDT_NV) share the column reads, D, E and every transcendental; V is read through
 // wave-uniform addresses (scalar loads). A row group that is not requested is compiled out (template flags): no Ld ->
 // no stream sweeps; no L-up and no Ld -> no Planck work; no tau -> tau is not read.
-#include <map>
-#include <mutex>
-#include <vector>
-
-#include "rtx_devmem.h"
 #include "rtx_tud_jac_common.h"
 
 #define TUDT_NV 4  // tangent vectors per launch: [TUDT_NV][TUDJ_QG] fp64 stream tangents stay in registers, no scratch
@@ -223,72 +218,42 @@ __global__ __launch_bounds__(256) void tud_jvp_kernel(TudJvpArgs v) {
   }
 }
 
-// V on the device, per (device, stream), as rtx_xs_od stages its terms: calls on one stream are ordered by it. Grow-only.
-struct JvpStage {
-  std::mutex mu;
-  std::map<std::pair<int, hipStream_t>, DevBuf<double>> buf;
-};
-static JvpStage& jvp_stage() {
-  static JvpStage* const s = new JvpStage();  // never destroyed: no device call from a static destructor
-  return *s;
-}
-
-template <bool TAU, bool LU, bool LD>
-static void jvp_launch(const TudJvpArgs& v, unsigned blocks, hipStream_t st) {
-  hipLaunchKernelGGL((tud_jvp_kernel<TAU, LU, LD>), dim3(blocks), dim3(256), 0, st, v);
-}
+// V on the device, per (device, stream): calls on one stream are ordered by it
+static StreamScratch* const jvp_stage = new StreamScratch();
 
 extern "C" int rtx_tud_jvp_max_vectors(void) { return TUDT_NV; }
 
-// dod: OD_plus is dOD/dT itself (rtx_tud_jvp_dod), OD_minus and fd_step are not the caller's
-static int tud_jvp_run(const float* OD, const float* OD_plus, const float* OD_minus, bool dod, int64_t ld, double fd_step,
-                       const float* K, int n_spec, const float* tau, int64_t ld_tau, const rtx_grid* grid, int n_layers,
-                       const double* T_h, int n_alt, const uint8_t* mask_h, double mu, int n_down, int n_angle,
-                       int return_od, int t_pos, const double* V_h, int n_vec, float* d_tau, float* d_Lu, float* d_Ld,
-                       int64_t ld_out, void* stream) {
-  if (rtx_check_grid(grid)) return 1;
+static int tud_jvp_run(const TudColumnIn& c, const double* V_h, int n_vec, float* d_tau, float* d_Lu, float* d_Ld, int64_t ld_out,
+                       void* stream) {
+  if (tud_column_check(c)) return 1;
   if (!d_tau && !d_Lu && !d_Ld) RTX_FAIL("no output: d_tau, d_Lu and d_Ld are all NULL");
   if (n_vec < 1 || n_vec > TUDT_NV) RTX_FAIL("n_vec=%d outside [1,%d] (rtx_tud_jvp_max_vectors)", n_vec, TUDT_NV);
   if (!V_h) RTX_FAIL("V_h is NULL");
   TudJvpArgs v;
   const int32_t layer0 = 0;  // the request's layer list is not this entry point's: every layer takes part through V
-  if (tud_jac_setup(v.c, OD, OD_plus, OD_minus, ld, fd_step, K, n_spec, tau, ld_tau, d_tau != nullptr, grid, n_layers, T_h, n_alt,
-                    mask_h, mu, n_down, n_angle, return_od, &layer0, 1, t_pos))
-    return 1;
-  if (ld_out < grid->n) RTX_FAIL("ld_out=%lld smaller than the shard", (long long)ld_out);
-  const size_t cnt = (size_t)n_vec * (size_t)(v.c.with_T + n_spec) * (size_t)n_layers;
+  if (tud_jac_setup(v.c, c, d_tau != nullptr, &layer0, 1)) return 1;
+  if (ld_out < c.grid->n) RTX_FAIL("ld_out=%lld smaller than the shard", (long long)ld_out);
+  const size_t cnt = (size_t)n_vec * (size_t)(v.c.with_T + c.n_spec) * (size_t)c.n_layers;
   for (size_t t = 0; t < cnt; ++t)
     if (!isfinite(V_h[t])) RTX_FAIL("V_h[%zu] is not finite", t);
-  if (grid->n == 0) return 0;
-  const long long blocks = (grid->n + 255) / 256;
-  if (blocks > 0x7fffffffLL) RTX_FAIL("grid->n=%lld: too many workgroups", (long long)grid->n);
-  if (dod && rtx_tud_zero_rows((size_t)n_layers * (size_t)ld, &v.c.ODm)) return 1;
+  if (c.grid->n == 0) return 0;
+  unsigned blocks;
+  if (tud_blocks(c.grid, 256, &blocks)) return 1;
   v.prefix = 0;
-  for (int ia = 0; ia < n_alt; ++ia) {
+  for (int ia = 0; ia < c.n_alt; ++ia) {
     bool run = true;
     for (int k = 0; k < v.c.count[ia]; ++k) run = run && ((v.c.lbits[k] >> ia) & 1u);
     if (run) v.prefix |= 1u << ia;
   }
   hipStream_t st = (hipStream_t)stream;
-  int dev = 0;
-  RTX_HIP(hipGetDevice(&dev));
-  JvpStage& stage = jvp_stage();
-  // the lock is held until the kernel is enqueued: a call on another stream may grow ITS buffer meanwhile, never this one
-  std::lock_guard<std::mutex> lock(stage.mu);
-  DevBuf<double>& b = stage.buf[std::make_pair(dev, st)];
-  if (b.reserve(cnt)) return 1;
-  RTX_HIP(hipMemcpyAsync(b.get(), V_h, cnt * sizeof(double), hipMemcpyHostToDevice, st));  // pageable: staged before returning
-  v.V = b.get(); v.d_tau = d_tau; v.d_Lu = d_Lu; v.d_Ld = d_Ld; v.ld_out = ld_out; v.nv = n_vec;
-  const int sel = (d_tau ? 4 : 0) | (d_Lu ? 2 : 0) | (d_Ld ? 1 : 0);
-  switch (sel) {
-    case 1: jvp_launch<false, false, true>(v, (unsigned)blocks, st); break;
-    case 2: jvp_launch<false, true, false>(v, (unsigned)blocks, st); break;
-    case 3: jvp_launch<false, true, true>(v, (unsigned)blocks, st); break;
-    case 4: jvp_launch<true, false, false>(v, (unsigned)blocks, st); break;
-    case 5: jvp_launch<true, false, true>(v, (unsigned)blocks, st); break;
-    case 6: jvp_launch<true, true, false>(v, (unsigned)blocks, st); break;
-    default: jvp_launch<true, true, true>(v, (unsigned)blocks, st); break;
-  }
+  void* V_d = nullptr;
+  if (jvp_stage->get(st, cnt * sizeof(double), &V_d)) return 1;
+  RTX_HIP(hipMemcpyAsync(V_d, V_h, cnt * sizeof(double), hipMemcpyHostToDevice, st));  // pageable: staged before returning
+  v.V = (const double*)V_d; v.d_tau = d_tau; v.d_Lu = d_Lu; v.d_Ld = d_Ld; v.ld_out = ld_out; v.nv = n_vec;
+  tud_dispatch_rows(d_tau, d_Lu, d_Ld, [&](auto tau, auto up, auto down) {
+    hipLaunchKernelGGL((tud_jvp_kernel<decltype(tau)::value, decltype(up)::value, decltype(down)::value>), dim3(blocks), dim3(256),
+                       0, st, v);
+  });
   RTX_LAUNCH_CHECK();
   return 0;
 }
@@ -298,8 +263,9 @@ extern "C" int rtx_tud_jvp(const float* OD, const float* OD_plus, const float* O
                            const double* T_h, int n_alt, const uint8_t* mask_h, double mu, int n_down, int n_angle,
                            int return_od, int t_pos, const double* V_h, int n_vec, float* d_tau, float* d_Lu, float* d_Ld,
                            int64_t ld_out, void* stream) {
-  return tud_jvp_run(OD, OD_plus, OD_minus, false, ld, fd_step, K, n_spec, tau, ld_tau, grid, n_layers, T_h, n_alt, mask_h, mu, n_down,
-                     n_angle, return_od, t_pos, V_h, n_vec, d_tau, d_Lu, d_Ld, ld_out, stream);
+  const TudColumnIn c = {OD, OD_plus, OD_minus, ld, fd_step, K, n_spec, tau, ld_tau, grid, n_layers, T_h, n_alt, mask_h, mu,
+                         n_down, n_angle, return_od, t_pos, false};
+  return tud_jvp_run(c, V_h, n_vec, d_tau, d_Lu, d_Ld, ld_out, stream);
 }
 
 extern "C" int rtx_tud_jvp_dod(const float* OD, const float* dOD_dT, int64_t ld, const float* K, int n_spec, const float* tau,
@@ -307,7 +273,7 @@ extern "C" int rtx_tud_jvp_dod(const float* OD, const float* dOD_dT, int64_t ld,
                                const uint8_t* mask_h, double mu, int n_down, int n_angle, int return_od, int t_pos,
                                const double* V_h, int n_vec, float* d_tau, float* d_Lu, float* d_Ld, int64_t ld_out,
                                void* stream) {
-  if (!dOD_dT) RTX_FAIL("dOD_dT is NULL");
-  return tud_jvp_run(OD, dOD_dT, dOD_dT, true, ld, 0.5, K, n_spec, tau, ld_tau, grid, n_layers, T_h, n_alt, mask_h, mu, n_down, n_angle,
-                     return_od, t_pos, V_h, n_vec, d_tau, d_Lu, d_Ld, ld_out, stream);
+  const TudColumnIn c = {OD, dOD_dT, dOD_dT, ld, 0.5, K, n_spec, tau, ld_tau, grid, n_layers, T_h, n_alt, mask_h, mu,
+                         n_down, n_angle, return_od, t_pos, true};
+  return tud_jvp_run(c, V_h, n_vec, d_tau, d_Lu, d_Ld, ld_out, stream);
 }

@@ -17,10 +17,6 @@
 //   3. tud_vjp_sum_kernel adds the partials of each output element in workgroup order.
 // Which wavenumbers meet in which partial depends on grid->n alone, and a layer's per-lane value on the layer alone:
 // out[v][w][k] is bit-identical for any subset, order or blocking of layers and vectors.
-#include <map>
-#include <mutex>
-
-#include "rtx_devmem.h"
 #include "rtx_tud_jac_common.h"
 
 #define TUDV_NV 4  // cotangent vectors per launch: they share the sweeps; the LDS staging below grows with them
@@ -259,65 +255,37 @@ __global__ __launch_bounds__(64) void tud_vjp_sum_kernel(const double* __restric
   out[e] = s;
 }
 
-// scratch per (device, stream), as rtx_srf_apply's: calls on one stream are ordered by it. Grow-only.
-static int vjp_workspace(size_t bytes, hipStream_t st, void** out) {
-  static std::mutex mu;
-  static auto* const ws = new std::map<std::pair<int, hipStream_t>, DevBuf<char>>();
-  int dev = 0;
-  RTX_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(mu);
-  DevBuf<char>& b = (*ws)[std::make_pair(dev, st)];
-  if (b.reserve(bytes)) return 1;
-  *out = b.get();
-  return 0;
-}
-
-template <bool TAU, bool LU, bool LD>
-static void vjp_launch(const TudVjpArgs& v, unsigned blocks, hipStream_t st) {
-  hipLaunchKernelGGL((tud_vjp_kernel<TAU, LU, LD>), dim3(blocks), dim3(64 * TUDV_WAVES), 0, st, v);
-}
+// the partials, per (device, stream)
+static StreamScratch* const vjp_scratch = new StreamScratch();
 
 extern "C" int rtx_tud_vjp_max_vectors(void) { return TUDV_NV; }
 
-// dod: OD_plus is dOD/dT itself (rtx_tud_vjp_dod), OD_minus and fd_step are not the caller's
-static int tud_vjp_run(const float* OD, const float* OD_plus, const float* OD_minus, bool dod, int64_t ld, double fd_step,
-                       const float* K, int n_spec, const float* tau, int64_t ld_tau, const rtx_grid* grid, int n_layers,
-                       const double* T_h, int n_alt, const uint8_t* mask_h, double mu, int n_down, int n_angle,
-                       int return_od, const int32_t* layers_h, int n_lay, int t_pos, const float* G_tau,
-                       const float* G_Lu, const float* G_Ld, int64_t ld_G, int n_vec, double* out, void* stream) {
-  if (rtx_check_grid(grid)) return 1;
+static int tud_vjp_run(const TudColumnIn& c, const int32_t* layers_h, int n_lay, const float* G_tau, const float* G_Lu,
+                       const float* G_Ld, int64_t ld_G, int n_vec, double* out, void* stream) {
+  if (tud_column_check(c)) return 1;
   if (!out) RTX_FAIL("out is NULL");
   if (!G_tau && !G_Lu && !G_Ld) RTX_FAIL("no cotangent: G_tau, G_Lu and G_Ld are all NULL");
   if (n_vec < 1 || n_vec > TUDV_NV) RTX_FAIL("n_vec=%d outside [1,%d] (rtx_tud_vjp_max_vectors)", n_vec, TUDV_NV);
   TudVjpArgs v;
-  if (tud_jac_setup(v.c, OD, OD_plus, OD_minus, ld, fd_step, K, n_spec, tau, ld_tau, G_tau != nullptr, grid, n_layers, T_h,
-                    n_alt, mask_h, mu, n_down, n_angle, return_od, layers_h, n_lay, t_pos))
-    return 1;
-  if (ld_G < grid->n) RTX_FAIL("ld_G=%lld smaller than the shard", (long long)ld_G);
+  if (tud_jac_setup(v.c, c, G_tau != nullptr, layers_h, n_lay)) return 1;
+  if (ld_G < c.grid->n) RTX_FAIL("ld_G=%lld smaller than the shard", (long long)ld_G);
   hipStream_t st = (hipStream_t)stream;
-  const int n_out = n_vec * (v.c.with_T + n_spec) * n_lay;
-  if (grid->n == 0) {
+  const int n_out = n_vec * (v.c.with_T + c.n_spec) * n_lay;
+  if (c.grid->n == 0) {
     RTX_HIP(hipMemsetAsync(out, 0, (size_t)n_out * sizeof(double), st));
     return 0;
   }
-  const long long blocks = (grid->n + 64 * TUDV_WAVES - 1) / (64 * TUDV_WAVES);
-  if (blocks > 0x7fffffffLL) RTX_FAIL("grid->n=%lld: too many workgroups", (long long)grid->n);
-  if (dod && rtx_tud_zero_rows((size_t)n_layers * (size_t)ld, &v.c.ODm)) return 1;
+  unsigned blocks;
+  if (tud_blocks(c.grid, 64 * TUDV_WAVES, &blocks)) return 1;
   void* ws = nullptr;
-  if (vjp_workspace((size_t)blocks * n_out * sizeof(double), st, &ws)) return 1;
+  if (vjp_scratch->get(st, (size_t)blocks * n_out * sizeof(double), &ws)) return 1;
   v.G_tau = G_tau; v.G_Lu = G_Lu; v.G_Ld = G_Ld; v.ld_G = ld_G; v.part = (double*)ws; v.nv = n_vec;
-  const int sel = (G_tau ? 4 : 0) | (G_Lu ? 2 : 0) | (G_Ld ? 1 : 0);
-  switch (sel) {
-    case 1: vjp_launch<false, false, true>(v, (unsigned)blocks, st); break;
-    case 2: vjp_launch<false, true, false>(v, (unsigned)blocks, st); break;
-    case 3: vjp_launch<false, true, true>(v, (unsigned)blocks, st); break;
-    case 4: vjp_launch<true, false, false>(v, (unsigned)blocks, st); break;
-    case 5: vjp_launch<true, false, true>(v, (unsigned)blocks, st); break;
-    case 6: vjp_launch<true, true, false>(v, (unsigned)blocks, st); break;
-    default: vjp_launch<true, true, true>(v, (unsigned)blocks, st); break;
-  }
+  tud_dispatch_rows(G_tau, G_Lu, G_Ld, [&](auto tau, auto up, auto down) {
+    hipLaunchKernelGGL((tud_vjp_kernel<decltype(tau)::value, decltype(up)::value, decltype(down)::value>), dim3(blocks),
+                       dim3(64 * TUDV_WAVES), 0, st, v);
+  });
   RTX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(tud_vjp_sum_kernel, dim3((unsigned)((n_out + 63) / 64)), dim3(64), 0, st, (const double*)ws, blocks,
+  hipLaunchKernelGGL(tud_vjp_sum_kernel, dim3((unsigned)((n_out + 63) / 64)), dim3(64), 0, st, (const double*)ws, (long long)blocks,
                      n_out, out);
   RTX_LAUNCH_CHECK();
   return 0;
@@ -328,8 +296,9 @@ extern "C" int rtx_tud_vjp(const float* OD, const float* OD_plus, const float* O
                            const double* T_h, int n_alt, const uint8_t* mask_h, double mu, int n_down, int n_angle,
                            int return_od, const int32_t* layers_h, int n_lay, int t_pos, const float* G_tau,
                            const float* G_Lu, const float* G_Ld, int64_t ld_G, int n_vec, double* out, void* stream) {
-  return tud_vjp_run(OD, OD_plus, OD_minus, false, ld, fd_step, K, n_spec, tau, ld_tau, grid, n_layers, T_h, n_alt, mask_h, mu, n_down,
-                     n_angle, return_od, layers_h, n_lay, t_pos, G_tau, G_Lu, G_Ld, ld_G, n_vec, out, stream);
+  const TudColumnIn c = {OD, OD_plus, OD_minus, ld, fd_step, K, n_spec, tau, ld_tau, grid, n_layers, T_h, n_alt, mask_h, mu,
+                         n_down, n_angle, return_od, t_pos, false};
+  return tud_vjp_run(c, layers_h, n_lay, G_tau, G_Lu, G_Ld, ld_G, n_vec, out, stream);
 }
 
 extern "C" int rtx_tud_vjp_dod(const float* OD, const float* dOD_dT, int64_t ld, const float* K, int n_spec, const float* tau,
@@ -337,7 +306,7 @@ extern "C" int rtx_tud_vjp_dod(const float* OD, const float* dOD_dT, int64_t ld,
                                const uint8_t* mask_h, double mu, int n_down, int n_angle, int return_od, const int32_t* layers_h,
                                int n_lay, int t_pos, const float* G_tau, const float* G_Lu, const float* G_Ld, int64_t ld_G,
                                int n_vec, double* out, void* stream) {
-  if (!dOD_dT) RTX_FAIL("dOD_dT is NULL");
-  return tud_vjp_run(OD, dOD_dT, dOD_dT, true, ld, 0.5, K, n_spec, tau, ld_tau, grid, n_layers, T_h, n_alt, mask_h, mu, n_down, n_angle,
-                     return_od, layers_h, n_lay, t_pos, G_tau, G_Lu, G_Ld, ld_G, n_vec, out, stream);
+  const TudColumnIn c = {OD, dOD_dT, dOD_dT, ld, 0.5, K, n_spec, tau, ld_tau, grid, n_layers, T_h, n_alt, mask_h, mu,
+                         n_down, n_angle, return_od, t_pos, true};
+  return tud_vjp_run(c, layers_h, n_lay, G_tau, G_Lu, G_Ld, ld_G, n_vec, out, stream);
 }

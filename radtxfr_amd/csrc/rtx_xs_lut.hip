@@ -2,30 +2,21 @@
 // [row][x] (one row per molecule and (T, p) node, x fastest), and rtx_xs_od forms
 //   OD[l][x] = sum_m sum_{c=0..3} w[l][m][c] * row[rows[l][m][c]][x]
 // from host-made node rows and weights. One kernel, bandwidth-bound: no LDS, a handful of registers.
-#include <mutex>
-#include <vector>
-
 #include "rtx_common.h"
 
 #define XS_BLOCK 256
 #define XS_PER 4                       // points per thread: one 16-byte access
 #define XS_TILE (XS_BLOCK * XS_PER)    // consecutive points owned by a workgroup
 
-// per-stream device copy of the terms of the last rtx_xs_od on that stream (grow-only): two streams may run the same table
-// at once (compute_TUD_batch's two runners), and within a stream the copy is ordered behind the previous kernel
-struct XsTerms {
-  hipStream_t stream;
-  DevBuf<int> rows;
-  DevBuf<float> w;
-};
-
 struct rtx_xs_lut {
   int n_mol;
   long long n_rows, nx, ldx;  // ldx: row stride in floats, a multiple of 4 (every row starts 16-byte aligned)
   DevBuf<float> data;         // [n_rows][ldx]
   int dev;
-  std::mutex mu;
-  std::vector<XsTerms> terms;
+  // per-stream device copy of the terms of the last rtx_xs_od on that stream, rows then weights: two streams may run the
+  // same table at once (compute_TUD_batch's two runners), and within a stream the copy is ordered behind the previous
+  // kernel. It goes with the table (rtx_xs_lut_free: a call of the user's, not a static destructor).
+  StreamScratch terms;
 };
 
 // A workgroup owns XS_TILE consecutive points and walks all layers: a node's segment of the tile comes from HBM about
@@ -152,27 +143,20 @@ extern "C" int rtx_xs_od(rtx_xs_lut* L, int64_t x_offset, int64_t n, int n_layer
     if (!isfinite(weight_h[t])) RTX_FAIL("weight_h[%zu] is not finite", t);
   }
   hipStream_t st = (hipStream_t)stream;
-  // the lock is held until the kernel is enqueued: a larger call on another stream may grow ITS buffer meanwhile, never this one
-  std::lock_guard<std::mutex> lock(L->mu);
-  XsTerms* tb = nullptr;
-  for (XsTerms& t : L->terms)
-    if (t.stream == st) tb = &t;
-  if (!tb) {
-    L->terms.emplace_back();
-    tb = &L->terms.back();
-    tb->stream = st;
-  }
-  if (tb->rows.reserve(cnt) || tb->w.reserve(cnt)) return 1;
-  RTX_HIP(hipMemcpyAsync(tb->rows.get(), rows_h, cnt * sizeof(int), hipMemcpyHostToDevice, st));  // pageable: staged before returning
-  RTX_HIP(hipMemcpyAsync(tb->w.get(), weight_h, cnt * sizeof(float), hipMemcpyHostToDevice, st));
+  void* base = nullptr;
+  if (L->terms.get(st, cnt * (sizeof(int) + sizeof(float)), &base)) return 1;
+  int* const rows_d = (int*)base;
+  float* const w_d = (float*)(rows_d + cnt);
+  RTX_HIP(hipMemcpyAsync(rows_d, rows_h, cnt * sizeof(int), hipMemcpyHostToDevice, st));  // pageable: staged before returning
+  RTX_HIP(hipMemcpyAsync(w_d, weight_h, cnt * sizeof(float), hipMemcpyHostToDevice, st));
   const unsigned tiles = (unsigned)((n + XS_TILE - 1) / XS_TILE);
   const bool vec = (x_offset % 4 == 0) && (ld % 4 == 0) && (((uintptr_t)od_f32 & 15) == 0);
   if (vec)
     hipLaunchKernelGGL(xs_od_kernel<true>, dim3(tiles), dim3(XS_BLOCK), 0, st, L->data.get(), L->ldx, (long long)x_offset, (long long)n, n_layers,
-                       n_terms, tb->rows.get(), tb->w.get(), od_f32, (long long)ld);
+                       n_terms, rows_d, w_d, od_f32, (long long)ld);
   else
     hipLaunchKernelGGL(xs_od_kernel<false>, dim3(tiles), dim3(XS_BLOCK), 0, st, L->data.get(), L->ldx, (long long)x_offset, (long long)n, n_layers,
-                       n_terms, tb->rows.get(), tb->w.get(), od_f32, (long long)ld);
+                       n_terms, rows_d, w_d, od_f32, (long long)ld);
   RTX_LAUNCH_CHECK();
   return 0;
 }

@@ -1,14 +1,16 @@
 // Host-only check of radtxfr_amd/csrc/rtx_devmem.h, built with -fsanitize=address,undefined by tests/test_devmem_host.py.
-// "Device" memory is malloc here: the three rtx_dev_* functions count live allocations and can be told to fail once.
+// "Device" memory is malloc here: the rtx_dev_* functions count live allocations, can be told to fail once, and name the
+// "current device" of the calling thread.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <thread>
 
 #include "../radtxfr_amd/csrc/rtx_devmem.h"
 
-static long g_live = 0;         // allocations not yet freed
+static std::atomic<long> g_live{0};  // allocations not yet freed
 static bool g_fail_alloc = false;  // the next rtx_dev_alloc fails
 static bool g_fail_copy = false;   // the next rtx_dev_h2d fails
 
@@ -28,6 +30,11 @@ void rtx_dev_free(void* p) {
 int rtx_dev_h2d(void* d, const void* h, size_t bytes) {
   if (g_fail_copy) { g_fail_copy = false; return 1; }
   memcpy(d, h, bytes);
+  return 0;
+}
+static thread_local int g_dev = 0;  // the calling thread's current device
+int rtx_dev_current(int* dev) {
+  *dev = g_dev;
   return 0;
 }
 
@@ -156,11 +163,68 @@ static void test_cache() {
   CHECK(g_live == 36);
 }
 
+// as the library holds it: made with new, never destroyed
+static StreamScratch* const scratch = new StreamScratch();
+
+static void test_stream_scratch() {
+  const long live0 = g_live;
+  int s1 = 0, s2 = 0;  // two "streams": any two distinct addresses, and the null stream
+  void *a = nullptr, *b = nullptr, *c = nullptr, *d = nullptr, *p = nullptr;
+  // distinct (device, stream) keys: distinct arrays, each at least as large as asked (the sanitizer checks the size)
+  g_dev = 0;
+  CHECK(scratch->get(&s1, 100, &a) == 0 && a && g_live == live0 + 1);
+  CHECK(scratch->get(&s2, 100, &b) == 0 && b && b != a && g_live == live0 + 2);
+  CHECK(scratch->get(nullptr, 100, &c) == 0 && c && c != a && c != b && g_live == live0 + 3);
+  g_dev = 1;
+  CHECK(scratch->get(&s1, 100, &d) == 0 && d && d != a && d != b && d != c && g_live == live0 + 4);
+  memset(a, 1, 100); memset(b, 2, 100); memset(c, 3, 100); memset(d, 4, 100);
+  CHECK(((char*)a)[99] == 1 && ((char*)b)[0] == 2 && ((char*)c)[50] == 3 && ((char*)d)[99] == 4);
+  // the same key: the same array while the asked size fits, whatever happened on other keys meanwhile
+  g_dev = 0;
+  CHECK(scratch->get(&s1, 100, &p) == 0 && p == a);
+  CHECK(scratch->get(&s1, 1, &p) == 0 && p == a);
+  CHECK(scratch->get(&s1, 0, &p) == 0 && p == a && g_live == live0 + 4);
+  // growth replaces the array (freed first: no more arrays than keys) and leaves the other keys' arrays alone
+  CHECK(scratch->get(&s1, 5000, &p) == 0 && p && g_live == live0 + 4);
+  memset(p, 5, 5000);
+  CHECK(((char*)b)[99] == 2 && ((char*)d)[0] == 4);
+  CHECK(scratch->get(&s1, 100, &a) == 0 && a == p);  // grow-only
+  // a failed allocation: the call fails with a null pointer, the entry is left empty, and the next call works
+  g_fail_alloc = true;
+  CHECK(scratch->get(&s1, 100000, &p) == 1 && p == nullptr && g_live == live0 + 3);
+  CHECK(scratch->get(&s2, 100, &p) == 0 && p == b);  // another key is untouched by it
+  CHECK(scratch->get(&s1, 10, &p) == 0 && p && g_live == live0 + 4);
+  memset(p, 6, 10);
+  // an empty request on a new key: no array, no failure
+  int s3 = 0;
+  CHECK(scratch->get(&s3, 0, &p) == 0 && p == nullptr && g_live == live0 + 4);
+  // two threads on different keys (their own device and stream), growing all the time: each sees only its own bytes
+  bool ok[2] = {true, true};
+  auto work = [&](int t) {
+    g_dev = 2 + t;
+    int st = 0;
+    void* q = nullptr;
+    for (size_t n = 1; n <= 4096 && ok[t]; n += 7) {
+      ok[t] = scratch->get(&st, n, &q) == 0 && q;
+      if (!ok[t]) break;
+      memset(q, 10 + t, n);
+      void* again = nullptr;
+      ok[t] = scratch->get(&st, n / 2, &again) == 0 && again == q && ((char*)q)[n - 1] == 10 + t;
+    }
+  };
+  std::thread t0(work, 0), t1(work, 1);
+  t0.join();
+  t1.join();
+  CHECK(ok[0] && ok[1] && g_live == live0 + 6);
+  g_dev = 0;
+}
+
 int main() {
   test_devbuf();
   test_cache();
+  test_stream_scratch();
   if (g_bad) { fprintf(stderr, "%d checks failed\n", g_bad); return 1; }
   printf("devmem host checks passed\n");
-  // the two caches are left alive on purpose, as in the library: their arrays are still reachable, which is no leak
+  // the caches and the scratch are left alive on purpose, as in the library: their arrays are still reachable, which is no leak
   return 0;
 }

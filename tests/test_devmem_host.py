@@ -1,6 +1,7 @@
-"""Ownership logic of radtxfr_amd/csrc/rtx_devmem.h (DevBuf, DevTableCache) on the host, under AddressSanitizer and
-UndefinedBehaviorSanitizer: tests/devmem_host_main.cpp is a stand-alone program that defines the three rtx_dev_* functions
-over malloc, with a count of live allocations and a switch that makes the next allocation or copy fail. No GPU, no HIP."""
+"""Ownership logic of radtxfr_amd/csrc/rtx_devmem.h (DevBuf, StreamScratch, DevTableCache) on the host, under
+AddressSanitizer and UndefinedBehaviorSanitizer: tests/devmem_host_main.cpp is a stand-alone program that defines the four
+rtx_dev_* functions over malloc, with a count of live allocations, a switch that makes the next allocation or copy fail
+and a per-thread "current device". No GPU, no HIP."""
 import os
 import shutil
 import subprocess

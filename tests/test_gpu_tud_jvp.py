@@ -9,11 +9,14 @@ a. against the fp64 oracle (cpu_ref.jacobian_from_od over all layers, contracted
 b. the two unflagged cases, where the stored J itself misses TOL_L: the same with TOL_L max(1, r_J), r_J the worst ratio of
    the stored Jacobian's own error to its bound on the same inputs (the parent's kernel, not the code under test).
 c. row groups, d. structural zeros, e. N_angle = 1, f. bit identity, g. the adjoint identity <G, J v> = <J^T G, v> against
-   rtx_tud_vjp, h. rt.compute_TUD_jvp end to end.
+   rtx_tud_vjp, h. rt.compute_TUD_jvp end to end, i. the results are, bit for bit, what the parent commit's build
+   gave.
 
 Measured (MI355X; worst ratio of the error to the bound over all elements): a. 0.003, 0.019, 0.017, 0.021,
 0.047 (cases 0-4), 0.021 and 0.047 with unsorted layer altitudes (cases 3, 4); b. r_J = 9.58 and 9.04, the tangent's own ratio at TOL_L 0.094 and 0.073 (0.0098 and 0.0081 of the
 asserted bound); g. 8.5e-5 to 1.6e-3; h. 3.1e-12 (tau, an opaque window), 0.0075 (La), 0.017 (Ld)."""
+import hashlib
+
 import numpy as np
 import pytest
 
@@ -400,3 +403,47 @@ def test_compute_tud_jvp_end_to_end(eng):
     for name in ("tau", "La"):
         assert np.array_equal(d_an[name], direct[name].double().cpu().numpy().transpose(2, 1, 0)), name
     assert np.array_equal(d_an["Ld"], direct["Ld"].double().cpu().numpy().T)
+
+
+# ------------------------------------------------------------------------------- i. the tangent kernel is untouched
+# The seven non-empty selections of the row groups (tau, L-up, Ld): one instantiation of tud_jvp_kernel each.
+SELECTIONS = [(t, u, d) for t in (False, True) for u in (False, True) for d in (False, True)][1:]
+
+# SHA-256 over the concatenated bytes of the results (float32; tau [n_vec][n_alt][n], La the same, Ld [n_vec][n], those
+# requested, in this order) that engine.tud_jvp_from_od gives for the seven SELECTIONS in that order, per case of cases.make
+# with its tangents (cases.tangents); "dod": the same through rtx_tud_jvp_dod on case 1, the derivative given as
+# (ODp - ODm) / (2 H_T). Recorded on an MI355X from a build of the parent commit 14c6c52 (before the entry glue of the
+# three derivative files moved to rtx_tud_jac_common.h and the staged tangents to StreamScratch).
+PARENT_JVP_SHA256 = {
+    1: "9848f72d1d521f01fbe5875415115e2a97668e911756ffef096c5d970f2dcaf5",
+    4: "ec36ec67bc51866443dc4d7d77ba7b5b168714803cea08f53738326aa8b6a7f2",
+    6: "68b83a41b6ef4a9a42f13a01d20c0ca1f4c971f6e0aef27c31f8a70956a07d67",
+    "dod": "9848f72d1d521f01fbe5875415115e2a97668e911756ffef096c5d970f2dcaf5",
+}
+
+
+def jvp_bits(r, dOD_dT=None):
+    """The hash described above for a Run."""
+    h = hashlib.sha256()
+    for sel in SELECTIONS:
+        rows = tuple(name for name, on in zip(("tau", "La", "Ld"), sel) if on)
+        out = r.jvp(r.V, rows=rows, dOD_dT=dOD_dT)
+        assert set(out) == set(rows)
+        for name in rows:
+            a = out[name].contiguous().cpu().numpy()
+            assert a.dtype == np.float32 and a.shape == r.out[name].shape
+            h.update(a.tobytes())
+    return h.hexdigest()
+
+
+@pytest.mark.parametrize("case", [1, 4, 6])
+def test_jvp_bits_are_the_parent_commits(run, case):
+    assert jvp_bits(run(case)) == PARENT_JVP_SHA256[case]
+
+
+def test_jvp_dod_bits_are_the_parent_commits(run):
+    r = run(1)
+    c = r.c
+    d32 = (c["ODp"] - c["ODm"]) / np.float32(2.0 * H_T)  # exact in float32 for these inputs (tud_vjp_cases.make)
+    assert d32.dtype == np.float32
+    assert jvp_bits(r, dOD_dT=_dev(d32, c["pad"])) == PARENT_JVP_SHA256["dod"]

@@ -13,7 +13,8 @@ b. against the fp64 oracle (cpu_ref.jacobian_from_od on the same float32 inputs)
    adjoint a non-zero sum). The term is the stored reference's own error, 1e-38 per unit of |G|; the synthetic cases do
    not need it.
 c. row groups left out, d. structural zeros, e. N_angle = 1, f. bit identity, g. rt.compute_TUD_vjp end to end,
-h. the Jacobian kernel's own results are what they were before its helpers moved to a shared header.
+h. the Jacobian kernel's own results are what they were before its helpers moved to a shared header,
+i. the adjoint's own results are what the parent commit's build gave.
 
 Measured (MI355X; worst ratio of the error to the bound over all elements; DESIGN 4.16): a. 0.12 (the one-point shard;
 0.04-0.07 otherwise), b. 0.017, c. 0.09, g. 0.084."""
@@ -335,3 +336,55 @@ def test_jacobian_bits_are_the_parent_commits(run):
     J = r.jacobian().contiguous().cpu().numpy()
     assert J.dtype == np.float32
     assert hashlib.sha256(J.tobytes()).hexdigest() == PARENT_J_SHA256
+
+
+# ------------------------------------------------------------------------------- i. and so is the adjoint kernel
+# The seven non-empty selections of the row groups (tau, L-up, Ld): one instantiation of tud_vjp_kernel each.
+SELECTIONS = [(t, u, d) for t in (False, True) for u in (False, True) for d in (False, True)][1:]
+
+# SHA-256 over the concatenated bytes of grad (float64, [n_vec][n_wrt][n_lay]) that engine.tud_vjp_from_od gives for the seven
+# SELECTIONS in that order, per case of cases.make; "dod": the same through rtx_tud_vjp_dod on case 1, the derivative given
+# as (ODp - ODm) / (2 H_T). Recorded on an MI355X from a build of the parent commit 14c6c52 (before the entry glue of the
+# three derivative files moved to rtx_tud_jac_common.h and their scratch to StreamScratch; whoever next moves the sweeps or
+# the row factors, which this kernel and tud_jac_kernel each carry, is held to these bits).
+PARENT_VJP_SHA256 = {
+    1: "1dbc5ea54732bfb058af97b5f12f435f8575e8bf24e2f06066cdd2c595094a71",
+    4: "5ee2b63bbc16e287dc8467eaa4c903ee16d92219cd8572c94dd5a658570f33d7",
+    6: "e82281be5766d87799e4e584a8773ae2c00bdb4544580293ee4dac90f490cddb",
+    "dod": "1dbc5ea54732bfb058af97b5f12f435f8575e8bf24e2f06066cdd2c595094a71",
+}
+
+
+def vjp_bits(r, dOD_dT=None):
+    """The hash described above for a Run."""
+    k = r.cols
+    nZ = r.nZ
+    pad = r.c["pad"]
+    G = np.asarray(r.G, dtype=np.float32)
+    fd = (k["ODp"], k["ODm"]) if dOD_dT is None else (None, None)
+    h = hashlib.sha256()
+    for tau, up, down in SELECTIONS:
+        out = r.eng.tud_vjp_from_od(k["OD"], fd[0], fd[1], H_T, k["K"], k["tau"], r.grid, r.c["T"], r.c["Z"],
+                                    G_tau=_dev(G[:, :nZ], pad) if tau else None, G_Lu=_dev(G[:, nZ:2 * nZ], pad) if up else None,
+                                    G_Ld=_dev(G[:, 2 * nZ], pad) if down else None, dOD_dT=dOD_dT, **r.kw())
+        out = out.contiguous().cpu().numpy()
+        assert out.dtype == np.float64 and out.shape == (r.c["n_vec"], len(r.c["wrt"]), len(r.c["layers"]))
+        h.update(out.tobytes())
+    return h.hexdigest()
+
+
+def dod_of(c):
+    """(ODp - ODm) / (2 H_T) in float32: exact for these inputs (tud_vjp_cases.make)."""
+    d32 = (c["ODp"] - c["ODm"]) / np.float32(2.0 * H_T)
+    assert d32.dtype == np.float32
+    return d32
+
+
+@pytest.mark.parametrize("case", [1, 4, 6])
+def test_vjp_bits_are_the_parent_commits(run, case):
+    assert vjp_bits(run(case)) == PARENT_VJP_SHA256[case]
+
+
+def test_vjp_dod_bits_are_the_parent_commits(run):
+    r = run(1)
+    assert vjp_bits(r, dOD_dT=_dev(dod_of(r.c), r.c["pad"])) == PARENT_VJP_SHA256["dod"]
