@@ -521,6 +521,55 @@ int rtx_srf_norms(const rtx_grid* grid, int nB, const int32_t* knot_start, const
                   const float* knot_r, float* N_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Tangent of rtx_srf_moments + rtx_band_mix (forward mode): the change of the band radiances L of
+ * rtx_srf_radiance_vjp's comment along n_vec directions in (tau, La, Ld on the native grid, the surface
+ * temperatures, the emissivity knots), without a Jacobian. Per vector, with w, N, hat_j as at
+ * rtx_srf_moments and tangents d_tau_i, d_La_i, d_Ld_i, dTs_t, dE[j][e]:
+ *   c'_i   = d_tau_i Ld_i + tau_i d_Ld_i + d_La_i
+ *   m'_t,i = d_tau_i (B(nu_i, Ts_t) - Ld_i) + tau_i (dB/dT(nu_i, Ts_t) dTs_t - d_Ld_i)
+ *   C'_b = sum_i w_b,i c'_i,     M'[t][b][j] = sum_i w_b,i m'_t,i hat_j(nu_i)
+ *   dL[vec][t][b][e] = (C'_b + sum_j M'[t][b][j] E[j][e] + sum_j M[t][b][j] dE[j][e]) / N_b,  j over jrange[b].
+ * Nothing of size nX * nE is formed: a second set of moments with tangent integrands, then a contraction.
+ *   grid, tau, Ld, Ts_h, nT, Xk, nk, nB, knot_start, knot_x, knot_r: as rtx_srf_moments (La itself is not
+ *     needed), 1 <= nT <= rtx_srf_radiance_jvp_max_temps();
+ *   d_tau, d_La, d_Ld: [n_vec][ld_d] float32 DEVICE (the rows rtx_tud_jvp writes), ld_d >= grid->n;
+ *   dTs_h: [n_vec][nT] fp64 on the HOST, copied to a library-owned device array per (device, stream)
+ *     before the call returns;  dE: [n_vec][nk][nE] float32 DEVICE;
+ *   N [nB], M [nT][nB][nk], jrange [nB][2]: rtx_srf_moments' outputs for the same grid, bands, Xk and Ts_h;
+ *   E [nk][nE] float32 DEVICE, nE >= 1;  dL [n_vec][nT][nB][nE] float32 DEVICE;
+ *   1 <= n_vec <= rtx_srf_radiance_jvp_max_vectors(): the vectors of a call share the reads of tau and
+ *     Ld, the knot search, the weights and both Planck evaluations per (point, temperature); callers
+ *     loop over groups of vectors and of temperatures.
+ * Any of the five tangent inputs may be NULL, not all: a NULL group is an exact zero tangent (the same
+ * bits as zeros passed) and nothing is evaluated for it: without d_tau and dTs_h no Planck function,
+ * without the three rows and dTs_h no pass over the points (dE alone is a contraction).
+ * A band with N_b = 0 (NaN in the forward) comes out NaN. An all-zero tangent, or one that is non-zero only
+ * at points under no live band, gives exact 0.0 on the live bands.
+ * Refused before anything is launched, nothing written: everything rtx_srf_moments refuses, all five
+ * tangent inputs NULL, n_vec or nT outside its range, ld_d < grid->n, a NULL N, M, jrange, E or dL,
+ * nE < 1, a non-finite dTs_h entry. nB == 0 writes nothing and returns 0.
+ * Arithmetic: c' and m' are formed in fp64 from the fp32 inputs, the fp32 B and the fp32 dB/dT
+ * (rtx_tud_vjp's), left to right as written, nothing fused. w is rtx_srf_moments' fp32 weight to the
+ * letter, the hats its fp32 (1 - f, f); every product with them, (w m') hat, is fp64 and so is every sum,
+ * in a fixed order: the points ascending inside sub-chunks of 64 points cut from the grid's first point (a
+ * point of weight 0 is skipped), the sub-chunks ascending; w c' over the 64 lanes of a wave by a
+ * shuffle-down tree, the 16 waves of a chunk of rtx_srf_chunk_points() points in wave order, the chunks
+ * ascending; the knots of jrange[b] ascending; the three terms of dL in the order written; the division
+ * by the fp64 value of the caller's fp32 N; one rounding to float32, at the store. No atomics.
+ * Determinism: dL[vec][t][b][:] is a pure function of (grid, band b's knots, tau, Ld, Xk, E, N[b],
+ * M[t][b], jrange[b], Ts_t and vector vec's tangents): the same bits run to run, for a vector or a
+ * temperature alone or among others in any order, and for any subset of the bands (order kept).
+ * Calls on one stream share a grow-only workspace; only a call that grows it synchronises. */
+int rtx_srf_radiance_jvp(const rtx_grid* grid, const float* tau, const float* Ld, const float* d_tau,
+                         const float* d_La, const float* d_Ld, int64_t ld_d, const double* Ts_h,
+                         const double* dTs_h, int nT, const double* Xk, int64_t nk, int nB,
+                         const int32_t* knot_start, const double* knot_x, const float* knot_r,
+                         const float* N, const float* M, const int32_t* jrange, const float* E,
+                         const float* dE, int64_t nE, int n_vec, float* dL, void* stream);
+int rtx_srf_radiance_jvp_max_vectors(void); /* tangent vectors one call takes */
+int rtx_srf_radiance_jvp_max_temps(void);   /* temperatures one call takes */
+
+/* ------------------------------------------------------------------------------------------
  * Fused HSI cube (config C5): every pixel has its own emissivity mixture and surface temperature
  * (LWIR_HSI_Generator.py:151-167: em = mixFrac . emis[ix_em], T = Ts + dT*N(0,1),
  * L = tau*(em*B(T) + (1-em)*Ld) + La), evaluated at monochromatic resolution and passed through

@@ -79,6 +79,10 @@ PROTOTYPES = {
     "rtx_srf_radiance_vjp": (_i32, [_gp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
                                      _vp, _vp, _vp]),
     "rtx_srf_norms": (_i32, [_gp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "rtx_srf_radiance_jvp": (_i32, [_gp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "rtx_srf_radiance_jvp_max_vectors": (_i32, []),
+    "rtx_srf_radiance_jvp_max_temps": (_i32, []),
     "rtx_interp_knots": (_i32, [_gp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "rtx_band_moments": (_i32, [_i32, _gp, _vp, _vp, _vp, _dbl, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rtx_band_mix": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp]),

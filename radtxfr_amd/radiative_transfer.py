@@ -800,11 +800,10 @@ def compute_TUD_vjp(Xmin, Xmax, cotangents, opts=options, wrt=("T",), layers=Non
     return X_, tau_, Lu_, Ld_h[0], _grad_dict(grad_h, wrt, n_vec)
 
 
-def _jvp_tangents(tangents, n_lay):
+def _jvp_tangents(tangents, n_lay, fn="compute_TUD_jvp"):
     """compute_TUD_jvp's tangents (a dict whose keys are checked already), checked on the host: (V float64
     [n_vec][n_wrt][n_lay], n_vec or None without a vector axis). Each entry is [n_lay] or [n_lay][n_vec]; the wrt axis
-    follows the dict's order."""
-    fn = "compute_TUD_jvp"
+    follows the dict's order. Errors are raised in the name of the calling function `fn`."""
     cols, n_vecs = [], set()
     for key, v in tangents.items():
         v = np.asarray(v.detach().cpu().numpy() if _is_torch(v) else v, dtype=np.float64)
@@ -961,6 +960,117 @@ def compute_band_radiance_vjp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, co
     out["Ts_surface"] = np.ascontiguousarray(dTs_h) if n_vec is not None else dTs_h[..., 0].copy()
     out["emis"] = np.ascontiguousarray(dE_h) if n_vec is not None else dE_h[..., 0].copy()
     return np.array(sensor.centres), L_h, out
+
+
+_SURFACE_TANGENTS = ("Ts_surface", "emis")
+
+
+def compute_band_radiance_jvp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, tangents, opts=options, layers=None, fd_step_T=0.5,
+                              dT_method="fd", **kwargs):
+    """At-sensor band radiances over a surface and their change along directions in the unknowns of a retrieval, in one
+    call: compute_TUD_jvp's tangent rows of tau / La / Ld (engine.tud_jvp), which stay on the device as float32, fed to the
+    sensor stage's tangent (sensor.band_radiance_srf_jvp), which adds the surface temperature and the emissivity knots. No
+    Jacobian and nothing of size nX x nE is stored. With compute_band_radiance_vjp, J^T (J v) at the bands.
+
+    sensor, Xk, emis_knots, Ts_surface as compute_band_radiance_vjp. tangents: a non-empty dict with keys among
+      "T", a molecule id of MFs_ID   [n_layers] per layer of `layers` (default all), as compute_TUD_jvp takes them;
+      "Ts_surface"                   shaped like Ts_surface [K];
+      "emis"                         [nk][nE];
+    each with an optional trailing axis of n_vec directions (they share everything up to the contraction; all entries must
+    agree on it). A key left out does not move. With only surface keys no rtx_tud_jvp launch and no T -+ fd_step_T or
+    species line-sum is made: the base state alone. kwargs, layers, fd_step_T, dT_method as compute_TUD_jvp, with exactly
+    one sensor altitude and returnOD=False. Returns (X_out, L, dL):
+      X_out  sensor.centres;
+      L      float32 NumPy, bit-identical to compute_band_radiance_vjp's L;
+      dL     float64 NumPy shaped like L, plus a trailing [n_vec] axis when the tangents have one; NaN where L is NaN.
+    Arguments are checked before any device work. NotImplementedError: more than one altitude or theta_r, returnOD=True,
+    broadening=, xs_lut=, reduce=."""
+    name = "compute_band_radiance_jvp"
+    c = _Call(name, Xmin, Xmax, opts, kwargs)
+    if "reduce" in c.o:
+        raise NotImplementedError(name + ": reduce= is not offered: the tangent is defined on the sensor's bands")
+    _no_xs_lut(c)
+    if c.returnOD:
+        raise NotImplementedError(name + ": returnOD=True is not supported (the sensor stage takes transmittances)")
+    if c.Z_s.size != 1:
+        raise NotImplementedError(name + ": exactly one sensor altitude per call (got %d)" % c.Z_s.size)
+    if not isinstance(tangents, dict) or not tangents:
+        raise ValueError(name + ": tangents must be a non-empty dict with keys among \"T\", a molecule id of MFs_ID, %r"
+                         % (_SURFACE_TANGENTS,))
+    atm = {k: v for k, v in tangents.items() if not (isinstance(k, str) and k in _SURFACE_TANGENTS)}
+    bad = [k for k in atm if k != "T" and (isinstance(k, bool) or not isinstance(k, (int, np.integer)))]
+    if bad:
+        raise ValueError(name + ": unknown tangent key %r (expected \"T\", a molecule id of MFs_ID, \"Ts_surface\" or \"emis\")" % (bad[0],))
+    wrt = tuple(atm.keys())
+    # a surface-only call has no wrt entry: the checks that do not concern wrt are run with a stand-in
+    wrt_, lay, nX = _jacobian_args(name, Xmin, Xmax, c.o, wrt if wrt else ("T",), layers, None, fd_step_T if wrt else 1.0,
+                                   host_result=False, dT_method=dT_method)
+    wrt = wrt_ if wrt else ()
+    Xk = np.ascontiguousarray(np.asarray(Xk, dtype=np.float64).ravel())
+    scalar = np.ndim(Ts_surface) == 0
+    Ts_s = np.atleast_1d(np.asarray(Ts_surface, dtype=np.float64))
+    if Ts_s.ndim != 1 or Ts_s.size == 0 or not np.all(Ts_s > 0.0):
+        raise ValueError(name + ": Ts_surface must be a positive scalar or a non-empty 1-D sequence of positive temperatures")
+    if not _is_torch(emis_knots):
+        emis_knots = np.asarray(emis_knots)
+    if tuple(emis_knots.shape[:1]) != (Xk.size,) or len(emis_knots.shape) != 2 or emis_knots.shape[1] < 1:
+        raise ValueError(name + ": emis_knots has shape %r, expected [%d][nE]" % (tuple(emis_knots.shape), Xk.size))
+    nk, nE, nT = Xk.size, int(emis_knots.shape[1]), Ts_s.size
+    n_vecs = set()
+    V = None
+    if atm:
+        V, nv = _jvp_tangents(atm, lay.size, fn=name)
+        n_vecs.add(nv)
+    d_Ts = d_emis = None
+    if "Ts_surface" in tangents:
+        d_Ts = tangents["Ts_surface"]
+        d_Ts = np.asarray(d_Ts.detach().cpu().numpy() if _is_torch(d_Ts) else d_Ts, dtype=np.float64)
+        base = () if scalar else (nT,)
+        got = _vector_axis(d_Ts, base)
+        if got is None:
+            raise ValueError(name + ": tangent \"Ts_surface\" has shape %r, expected %r (Ts_surface's shape) plus an optional "
+                             "trailing vector axis" % (tuple(d_Ts.shape), base))
+        if not np.isfinite(d_Ts).all():
+            raise ValueError(name + ": tangent \"Ts_surface\" has non-finite entries")
+        n_vecs.add(got[1])
+    if "emis" in tangents:
+        d_emis = tangents["emis"]
+        if not _is_torch(d_emis):
+            d_emis = np.asarray(d_emis)
+        got = _vector_axis(d_emis, (nk, nE))
+        if got is None:
+            raise ValueError(name + ": tangent \"emis\" has shape %r, expected %r (emis_knots' shape) plus an optional trailing "
+                             "vector axis" % (tuple(d_emis.shape), (nk, nE)))
+        n_vecs.add(got[1])
+    if len(n_vecs) != 1:
+        raise ValueError(name + ": the tangents disagree on the vector axis: %r" % sorted(n_vecs, key=str))
+    n_vec = n_vecs.pop()
+    from . import sensor as _sensor  # sensor.py imports this module
+    grid = c.grid
+    assert c.X.size == nX
+    tbl = c.table()
+    dev = engine.device()
+    E_d = _dev_f32(emis_knots, dev).contiguous()
+    rows = {}
+    if atm:
+        tau, Lu, Ld, _, d = engine.tud_jvp(tbl, grid, c.Z, c.T, c.P, c.PL, c.MF, c.ID, V, Altitudes=c.Z_s, theta_r=c.theta,
+                                           N_angle=c.N_angle, returnOD=False, wrt=wrt, layers=lay, fd_step_T=float(fd_step_T),
+                                           dT_method=dT_method)
+        # [n_vec][nX] float32 where rtx_tud_jvp wrote them, seen as [nX][n_vec]: no copy, no host round trip
+        rows = dict(d_tau=d["tau"][:, 0, :nX].T, d_La=d["La"][:, 0, :nX].T, d_Ld=d["Ld"][:, :nX].T)
+        if n_vec is None:
+            rows = {k: v[:, 0] for k, v in rows.items()}
+    else:  # the base state alone, exactly what compute_TUD runs
+        T = np.ascontiguousarray(np.atleast_1d(c.T))
+        run = engine.TudRunner(tbl, grid, np.atleast_1d(c.Z), n_layers=T.size, Altitudes=c.Z_s, theta_r=c.theta, N_angle=c.N_angle,
+                               returnOD=False)
+        tau, Lu, Ld = run.run(T, np.atleast_1d(c.P), np.atleast_1d(c.PL), c.MF.reshape(T.size, -1), c.ID)
+    t_, u_, d_ = tau[0, :nX].contiguous(), Lu[0, :nX].contiguous(), Ld[:nX].contiguous()
+    L, dL = _sensor.band_radiance_srf_jvp(grid, t_, u_, d_, Xk, E_d, float(Ts_s[0]) if scalar else Ts_s, sensor, d_Ts=d_Ts,
+                                          d_emis=None if d_emis is None else _dev_f32(d_emis, dev), **rows)
+    L_h = L.cpu().numpy()
+    dL_h = np.ascontiguousarray(dL.to(torch.float64).cpu().numpy())
+    return np.array(sensor.centres), L_h, dL_h
 
 
 def compute_LWIR_apparent_radiance(X, emis, Ts, tau, La, Ld, dT=None, return_Ls=False):

@@ -405,6 +405,114 @@ def band_radiance_srf_vjp(grid, tau, La, Ld, Xk, emis_knots, Ts, sensor, g, outp
     return out
 
 
+def _jvp_tangent(x, base, what, dev=None):
+    """A tangent laid out as `base` plus an optional trailing vector axis: (x with the vector axis FIRST -- a view where it
+    can be --, its length or None where x came without one); None passes through. dev: the device of a float32 tensor to
+    return, or None for float64 NumPy."""
+    if x is None:
+        return None, None
+    if dev is None:
+        x = np.asarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x, dtype=np.float64)
+    else:
+        if not torch.is_tensor(x):
+            x = torch.as_tensor(np.asarray(x, dtype=np.float32))
+        x = x.to(device=dev, dtype=torch.float32)
+    shape = tuple(x.shape)
+    if shape == tuple(base):
+        return x[None], None
+    if len(shape) == len(base) + 1 and shape[:-1] == tuple(base) and shape[-1] >= 1:
+        return (np.moveaxis(x, -1, 0) if dev is None else x.movedim(-1, 0)), shape[-1]
+    raise ValueError("band_radiance_srf_jvp: %s has shape %r, expected %r plus an optional trailing vector axis"
+                     % (what, shape, tuple(base)))
+
+
+def band_radiance_srf_jvp(grid, tau, La, Ld, Xk, emis_knots, Ts, sensor, d_tau=None, d_La=None, d_Ld=None, d_Ts=None, d_emis=None):
+    """band_radiance_srf_fused and its tangent (rtx_srf_radiance_jvp): the change dL of the band radiances L along
+    directions in the inputs, without a Jacobian and without anything of size nX x nE.
+      d_tau, d_La, d_Ld  tangents of tau, La, Ld on the native grid, [nX] (float32; device or NumPy): the rows
+                         engine.tud_jvp returns are taken where they are;
+      d_Ts               tangent of Ts, shaped like Ts (host numbers, taken as float64);
+      d_emis             tangent of emis_knots, [nk][nE] (float32).
+    Each may carry a trailing axis of n_vec directions (all that are given must agree on it: ValueError otherwise); one left
+    None is an exact zero and nothing is evaluated for it; not all five may be None. Same arguments as
+    band_radiance_srf_fused otherwise. Returns (L, dL) on tau's device: L that call's, bit for bit (it comes from the
+    srf_moments + rtx_band_mix run that supplies the tangent's N, M and jrange); dL float32 laid out like L, with a
+    trailing [n_vec] axis when the tangents carry one. A band that is NaN in L is NaN in dL. The temperatures and the
+    vectors go to the library rtx_srf_radiance_jvp_max_temps() / _max_vectors() at a time; the grouping changes no bit."""
+    lib = _lib.load()
+    dev = tau.device
+    scalar = np.ndim(Ts) == 0
+    Ts = np.ascontiguousarray(np.atleast_1d(np.asarray(Ts, dtype=np.float64)))
+    if Ts.ndim != 1 or Ts.size == 0:
+        raise ValueError("Ts: a scalar or a non-empty 1-D sequence")
+    for v in (tau, La, Ld):
+        assert v.dtype == torch.float32 and v.is_cuda and v.is_contiguous() and v.numel() == grid.n
+    plan = _srf_fused_plan(Xk, dev)
+    nB, nk, nE, nT, nX = len(sensor), plan["Xk_d"].numel(), emis_knots.shape[1], Ts.size, grid.n
+    assert emis_knots.dtype == torch.float32 and emis_knots.is_cuda and emis_knots.shape[0] == nk
+    emis_knots = emis_knots.contiguous()
+    rows, n_vecs = {}, set()
+    for key, x in (("d_tau", d_tau), ("d_La", d_La), ("d_Ld", d_Ld)):
+        x, nv = _jvp_tangent(x, (nX,), key, dev)
+        if x is not None:
+            rows[key] = x
+            n_vecs.add(nv)
+    dTs, nv = _jvp_tangent(d_Ts, () if scalar else (nT,), "d_Ts")
+    if dTs is not None:
+        n_vecs.add(nv)
+        dTs = dTs.reshape(-1, nT)
+        if not np.isfinite(dTs).all():
+            raise ValueError("band_radiance_srf_jvp: d_Ts has non-finite entries")
+    dE, nv = _jvp_tangent(d_emis, (nk, nE), "d_emis", dev)
+    if dE is not None:
+        n_vecs.add(nv)
+        dE = dE.contiguous()  # [n_vec][nk][nE]
+    if not n_vecs:
+        raise ValueError("band_radiance_srf_jvp: no tangent (d_tau, d_La, d_Ld, d_Ts and d_emis are all None)")
+    if len(n_vecs) != 1:
+        raise ValueError("band_radiance_srf_jvp: the tangents disagree on the vector axis: %r" % sorted(n_vecs, key=str))
+    n_vec = n_vecs.pop()
+    nV = 1 if n_vec is None else n_vec
+    # the library takes one leading dimension for the three rows: rows that share one go as they are, else they are packed
+    lds = set(x.stride(0) for x in rows.values()) if nV > 1 else {nX}
+    if all(x.stride(1) == 1 for x in rows.values()) and len(lds) == 1 and min(lds) >= nX:
+        ld_d = lds.pop()
+    else:
+        ld_d = nX
+        rows = {k: x.contiguous() for k, x in rows.items()}
+    kx, kr = sensor.on_device(dev)
+    L = torch.empty((nT, nB, nE), dtype=torch.float32, device=dev)
+    dL = torch.empty((nV, nT, nB, nE), dtype=torch.float32, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    step_m, step_t, step_v = lib.rtx_srf_moments_max_temps(), lib.rtx_srf_radiance_jvp_max_temps(), lib.rtx_srf_radiance_jvp_max_vectors()
+    for m0 in range(0, nT, step_m):
+        N, Cb, M, jr = srf_moments(grid, tau, La, Ld, plan["Xk_d"], Ts[m0:m0 + step_m], sensor)
+        for t in range(M.shape[0]):
+            _lib.check(lib.rtx_band_mix(p(N), p(Cb), p(M[t]), p(jr), nB, nk, p(emis_knots), nE, p(L[m0 + t]), st))
+        for t0 in range(m0, m0 + M.shape[0], step_t):
+            t1 = min(t0 + step_t, m0 + M.shape[0])
+            Ts_g = np.ascontiguousarray(Ts[t0:t1])
+            for v0 in range(0, nV, step_v):
+                v1 = min(v0 + step_v, nV)
+                dst = dL[v0:v1, t0:t1]
+                out = dst if dst.is_contiguous() else torch.empty((v1 - v0, t1 - t0, nB, nE), dtype=torch.float32, device=dev)
+                dTs_g = None if dTs is None else np.ascontiguousarray(dTs[v0:v1, t0:t1])
+                row = lambda k: C.c_void_p(rows[k].data_ptr() + 4 * v0 * ld_d) if k in rows else None
+                _lib.check(lib.rtx_srf_radiance_jvp(grid.byref(), p(tau), p(Ld), row("d_tau"), row("d_La"), row("d_Ld"), ld_d,
+                                                    Ts_g.ctypes.data_as(C.c_void_p),
+                                                    None if dTs_g is None else dTs_g.ctypes.data_as(C.c_void_p), t1 - t0,
+                                                    p(plan["Xk_d"]), nk, nB, sensor.knot_start.ctypes.data_as(C.c_void_p), p(kx), p(kr),
+                                                    p(N), p(M[t0 - m0:t1 - m0]), p(jr), p(emis_knots),
+                                                    None if dE is None else p(dE[v0:v1]), nE, v1 - v0, p(out), st))
+                if out is not dst:
+                    dst.copy_(out)
+    if scalar:
+        L, dL = L[0], dL[:, 0]
+    dL = dL.movedim(0, -1) if n_vec is not None else dL[0]
+    return L, dL
+
+
 def chebyshev_lagrange(Q):
     """Chebyshev nodes s_q on (-1,1) and the monomial coefficients coef[q][d] of their Lagrange basis."""
     s = np.cos((2 * np.arange(Q) + 1) * np.pi / (2 * Q))
