@@ -598,6 +598,47 @@ int rtx_pixel_cube(int nB, int Q, const double* centre, const double* sigma, dou
                    const double* Tpix, float* cube, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The HSI cube for ANY sensor: bands are response tables as rtx_srf_moments takes them, of any width.
+ * The definition is this project's own (the reference has the MAKO shapes only). B(nu, T_p) is
+ * interpolated IN TEMPERATURE through Q nodes T_q of the scene's range [T_lo, T_hi] (rtx_pixel_cube
+ * interpolates in wavenumber across a band, which holds for MAKO-narrow bands only):
+ *   N, C, M[q], jrange = rtx_srf_moments at Ts = the Q nodes, unchanged, in one call
+ *   G[e][q][b]  = sum_{j in jrange[b]} M[q][b][j] E[j][e]                          (rtx_srf_cube_tables)
+ *   l_q(T)      = prod_{r != q} (T - T_r) / prod_{r != q} (T_q - T_r)
+ *   cube[b][p]  = ( C_b + sum_m frac[p][m] sum_q l_q(T_p) G[kidx[p][m]][q][b] ) / N_b  (rtx_srf_pixel_cube)
+ * The Ld term inside M rides through exactly (sum_q l_q = 1). No Planck function is evaluated per pixel.
+ *   rtx_srf_cube_max_nodes() = 8 = rtx_srf_moments_max_temps().
+ *   rtx_srf_cube_tables: M [Q][nB][nk], jrange [nB][2], E [nk][nEnd] float32 -> tab [nEnd][Q][nB] (bands
+ *     innermost), all DEVICE; one fp32 fmaf chain per entry over the knots of jrange[b] ascending.
+ *     Refused before the launch: Q outside [1, max_nodes], nk < 1, a negative size, a NULL pointer;
+ *     nB == 0 or nEnd == 0 writes nothing and returns 0.
+ *   rtx_srf_pixel_cube: T_node_h on the HOST, Q + 2 values: the Q nodes, strictly monotonic, then T_lo
+ *     and T_hi, the range the interpolant is admitted on, T_lo <= every node <= T_hi (Chebyshev nodes lie
+ *     inside their range, so the range is not the nodes' hull and travels with them);
+ *     N [nB], C [nB], tab [nEnd][Q][nB] float32; kidx [nPix][nMix] int32, frac [nPix][nMix] float32,
+ *     Tpix [nPix] fp64: DEVICE; cube [nB][nPix] float32 DEVICE.
+ *     A band with N_b = 0 comes out NaN in every pixel (quirk 13). A pixel whose temperature is not
+ *     finite or lies outside [T_lo, T_hi] is NaN down its whole column: no extrapolation, and no
+ *     device-to-host check. An endmember index outside [0, nEnd) is clamped, as rtx_pixel_cube does.
+ *     Refused before the launch, nothing written: a NULL required pointer, Q outside [1, max_nodes], a node
+ *     or range end that is not finite, not positive, outside the range or not distinct from another node,
+ *     nEnd < 1, nMix < 1, a negative size. nB == 0 or nPix == 0 writes nothing and returns 0.
+ * Arithmetic: l_q(T_p) once per pixel: numerator and denominator are fp64 products over r ascending, one
+ * fp64 division, one rounding to fp32 (a pixel exactly at a node gets the weights 1 and 0 exactly). Then
+ * fp32:  s = 0;  for m ascending { t = 0; for q ascending t = fmaf(l_q, G[k_m][q][b], t); s = fmaf(frac_m, t, s); }
+ * cube = (C_b + s) / N_b.
+ * Determinism: cube[b][p] is a pure function of (pixel p's kidx, frac and T; band b's N, C and tab
+ * column; the nodes and the range): the same bits run to run, for any nPix, for any position of the
+ * pixel in the scene, for any subset of the bands (order kept), and whether the kernel holds the table
+ * in LDS (nEnd * Q <= 128) or reads it from global memory. No atomics, no workspace. */
+int rtx_srf_cube_max_nodes(void);
+int rtx_srf_cube_tables(const float* M, const int32_t* jrange, int nB, int Q, int64_t nk,
+                        const float* E, int64_t nEnd, float* tab, void* stream);
+int rtx_srf_pixel_cube(int nB, int Q, const double* T_node_h, const float* N, const float* C,
+                       const float* tab, int nEnd, int64_t nPix, int nMix, const int32_t* kidx,
+                       const float* frac, const double* Tpix, float* cube, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Speed-dependent Voigt line-sum. Replaces the per-line PROFILE_SDVOIGT + scatter-add of
  * absorptionCoefficient_SDVoigt, misc/hapi.py:10897-10900 (PROFILE_SDVOIGT :10117 -> pcqsdhc :9850-10024 with
  * anuVC = eta = 0: PART1 for lines without speed dependence, PART2/3/4 otherwise; CPF = hum1_wei :9833, cpf3 :9645),

@@ -6,13 +6,14 @@ ILS needs an (nS,nX,nB) temporary (1.4 TB at 2000 spectra); here the monochromat
 (560 k wavenumbers x 2000 spectra x 4 B = 4.5 GB) and the order "radiance first, ILS second" is exact.
 """
 import ctypes as C
+import functools
 import threading
 
 import numpy as np
 import torch
 
 from . import _lib, engine
-from .radiative_transfer import _MAKO_UM
+from .radiative_transfer import _MAKO_UM, c1 as _C1, c2 as _C2
 
 
 def interp_knots(grid, Xk, F):
@@ -585,6 +586,114 @@ def hsi_cube(grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, resFactor=2, b
     _lib.check(lib.rtx_band_mix_stacked(p(M), p(jr), nB, Q + 1, nk, p(endmembers), nEnd, p(tab), st))
     _lib.check(lib.rtx_pixel_cube(nB, Q, p(plan["c_d"]), p(plan["s_d"]), 1.0, plan["sn32"].ctypes.data_as(C.c_void_p), p(N), p(Cb), p(tab),
                                   nEnd, nPix, nMix, p(kidx.contiguous()), p(frac.contiguous()), p(Tpix.contiguous()), p(cube), st))
+    return X_out, cube
+
+
+def srf_cube_nodes(T_lo, T_hi, n_nodes):
+    """The n_nodes Chebyshev nodes of [T_lo, T_hi], descending: T_q = (T_lo + T_hi) / 2 + (T_hi - T_lo) / 2 * cos((2 q + 1) pi /
+    (2 n_nodes)): chebyshev_lagrange's nodes mapped to the range."""
+    Q = int(n_nodes)
+    s = np.cos((2 * np.arange(Q) + 1) * np.pi / (2 * Q))  # chebyshev_lagrange(Q)[0], without its basis polynomials
+    return 0.5 * (T_lo + T_hi) + 0.5 * (T_hi - T_lo) * s
+
+
+def _planck_host(x, T):
+    """B(nu, T) [uW/(cm^2 sr cm^-1)] in fp64 NumPy, rtx_planck's constants."""
+    x100 = 100.0 * np.asarray(x, dtype=np.float64)
+    return _C1 * x100 ** 3 * 1e4 / np.expm1(_C2 * x100 / np.asarray(T, dtype=np.float64))
+
+
+@functools.lru_cache(maxsize=64)  # a scene generator asks for one (axis, range, node count) again and again
+def planck_node_error(x_hi, T_lo, T_hi, n_nodes, samples=2001):
+    """What interpolating the Planck function in temperature through srf_cube_nodes(T_lo, T_hi, n_nodes) costs at
+    wavenumber x_hi [cm^-1]: the largest |interpolant - B| over `samples` temperatures evenly spaced over [T_lo, T_hi],
+    relative to the largest B there. Host NumPy, fp64. The error grows with the wavenumber, so a grid's highest is its worst."""
+    Tq = srf_cube_nodes(T_lo, T_hi, n_nodes)
+    T = np.linspace(T_lo, T_hi, int(samples))
+    B = _planck_host(x_hi, T)
+    Bq = _planck_host(x_hi, Tq)
+    interp = np.zeros_like(T)
+    for q in range(Tq.size):
+        others = np.delete(Tq, q)
+        interp += Bq[q] * np.prod((T[:, None] - others[None, :]) / (Tq[q] - others)[None, :], axis=1)
+    return float(np.max(np.abs(interp - B)) / np.max(B))
+
+
+def hsi_cube_srf(grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sensor, n_nodes=8, T_range=None, interp_tol=1e-6):
+    """hsi_cube() for any sensor: band radiances of an HSI cube whose pixels each have an emissivity mixture and a surface
+    temperature of their own, under the sensor's tabulated responses, whatever their width. The Planck function is
+    interpolated in TEMPERATURE through n_nodes Chebyshev nodes of T_range (hsi_cube interpolates in wavenumber across a
+    band, which holds for MAKO-narrow bands only). Arguments as hsi_cube(), with a Sensor in place of resFactor.
+
+    T_range = (T_lo, T_hi) [K]: the range the nodes span. None: the smallest and largest finite Tpix, read from the device
+    -- ONE synchronisation; an explicit range avoids it. A range narrower than 1 K is widened symmetrically to 1 K (the
+    nodes of a one-temperature scene stay distinct). A pixel whose temperature is not finite or lies outside the range is
+    NaN in every band: there is no extrapolation and no check on the device's side.
+    interp_tol: the call raises ValueError, before any device work, when planck_node_error(grid's highest wavenumber,
+    T_lo, T_hi, n_nodes) exceeds it (8 nodes over 230-350 K at 1400 cm^-1: 5.5e-8; 4 nodes: 3.9e-4).
+
+    Returns (X_out [nB] NumPy = sensor.centres, cube [nB][nPix] float32 device); a band with no grid point under it is NaN.
+    Three stages: srf_moments at the node temperatures (the one pass over tau / La / Ld per group of 16 bands),
+    rtx_srf_cube_tables (its n_nodes moment arrays x the endmember knots), rtx_srf_pixel_cube."""
+    lib = _lib.load()
+    Q = int(n_nodes)
+    Q_max = lib.rtx_srf_cube_max_nodes()
+    if Q != n_nodes or Q < 1 or Q > Q_max:
+        raise ValueError(f"n_nodes={n_nodes!r}: an integer from 1 to {Q_max}")
+    Xk = np.asarray(Xk, dtype=np.float64).ravel()
+    if endmembers.dim() != 2 or endmembers.shape[0] != Xk.size or endmembers.shape[1] < 1 or endmembers.dtype != torch.float32:
+        raise ValueError(f"endmembers: float32 [nk = {Xk.size}][nEnd >= 1], got {endmembers.dtype} {tuple(endmembers.shape)}")
+    if kidx.dim() != 2 or kidx.shape[1] < 1 or kidx.dtype != torch.int32:
+        raise ValueError(f"kidx: int32 [nPix][nMix >= 1], got {kidx.dtype} {tuple(kidx.shape)}")
+    if frac.shape != kidx.shape or frac.dtype != torch.float32:
+        raise ValueError(f"frac: float32 {tuple(kidx.shape)} like kidx, got {frac.dtype} {tuple(frac.shape)}")
+    nPix, nMix = kidx.shape
+    if Tpix.dim() != 1 or Tpix.shape[0] != nPix or Tpix.dtype != torch.float64:
+        raise ValueError(f"Tpix: float64 [nPix = {nPix}], got {Tpix.dtype} {tuple(Tpix.shape)}")
+    for name, v in (("tau", tau), ("La", La), ("Ld", Ld)):
+        if v.dtype != torch.float32 or v.numel() != grid.n:
+            raise ValueError(f"{name}: float32 [grid.n = {grid.n}], got {v.dtype} {tuple(v.shape)}")
+    if T_range is None:
+        if not Tpix.is_cuda:
+            raise ValueError("hsi_cube_srf takes device tensors (Tpix is not on a GPU)")
+        fin = torch.isfinite(Tpix)
+        inf = torch.full_like(Tpix, float("inf"))
+        ends = torch.stack([torch.where(fin, Tpix, inf).min(), torch.where(fin, Tpix, -inf).max()]).cpu().numpy() if nPix else None
+        if ends is None or not np.all(np.isfinite(ends)):
+            raise ValueError("T_range=None needs at least one finite Tpix")
+        T_lo, T_hi = float(ends[0]), float(ends[1])
+    else:
+        T_lo, T_hi = (float(v) for v in T_range)
+    if not (np.isfinite(T_lo) and np.isfinite(T_hi) and 0.0 < T_lo <= T_hi):
+        raise ValueError(f"T_range=({T_lo!r}, {T_hi!r}): finite, positive and ascending")
+    if T_hi - T_lo < 1.0:
+        mid = 0.5 * (T_lo + T_hi)
+        T_lo, T_hi = mid - 0.5, mid + 0.5
+    est = planck_node_error(float(grid.x_at(grid.n - 1)), T_lo, T_hi, Q)
+    if not est <= interp_tol:
+        raise ValueError(f"hsi_cube_srf: interpolating Planck through {Q} nodes over [{T_lo:g}, {T_hi:g}] K is off by an estimated "
+                         f"{est:.3g} of the largest B at {grid.x_at(grid.n - 1):g} cm^-1, above interp_tol={interp_tol:g}: narrow "
+                         "T_range, raise n_nodes or split the scene by temperature")
+    for name, v in (("tau", tau), ("endmembers", endmembers), ("kidx", kidx), ("frac", frac), ("Tpix", Tpix)):
+        if not v.is_cuda:
+            raise ValueError(f"hsi_cube_srf takes device tensors ({name} is not on a GPU)")
+    dev = tau.device
+    endmembers, kidx, frac, Tpix = (v.contiguous() for v in (endmembers, kidx, frac, Tpix))
+    nodes = srf_cube_nodes(T_lo, T_hi, Q)
+    X_out = np.array(sensor.centres)
+    nB, nk, nEnd = len(sensor), Xk.size, endmembers.shape[1]
+    cube = torch.empty((nB, nPix), dtype=torch.float32, device=dev)
+    if nB == 0 or nPix == 0:
+        return X_out, cube
+    plan = _srf_fused_plan(Xk, dev)
+    N, Cb, M, jr = srf_moments(grid, tau, La, Ld, plan["Xk_d"], nodes, sensor)
+    tab = torch.empty((nEnd, Q, nB), dtype=torch.float32, device=dev)
+    T_host = np.ascontiguousarray(np.concatenate([nodes, [T_lo, T_hi]]))  # the nodes, then the range
+    p = lambda t: C.c_void_p(t.data_ptr())
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.check(lib.rtx_srf_cube_tables(p(M), p(jr), nB, Q, nk, p(endmembers), nEnd, p(tab), st))
+    _lib.check(lib.rtx_srf_pixel_cube(nB, Q, T_host.ctypes.data_as(C.c_void_p), p(N), p(Cb), p(tab), nEnd, nPix, nMix, p(kidx), p(frac),
+                                      p(Tpix), p(cube), st))
     return X_out, cube
 
 
