@@ -743,7 +743,9 @@ int rtx_ht_params(const rtx_ht* ht, int state, double* params, double* strength,
  *   rtx_fir_reflect: out[r][i] = sum_k taps_h[k] * in[r][R(i + k - centre)], i in [0,n), fp64 accumulation;
  *       R reflects about the first and last sample (j<0 -> -j, j>=n -> 2(n-1)-j), the reference's padding (:1314).
  *       in: [n_rows][ld_in] float32 (in_is_f64 = 0) or float64 (1), device; taps_h: n_taps doubles on the HOST
- *       (n_taps <= 8192, n_taps - 1 <= n); out: [n_rows][ld_out] float64, device.
+ *       (n_taps <= 8192, n_taps - 1 <= n; with n_taps - 1 == n an index can need both reflections, -n -> n -> n - 2 and
+ *       2n - 1 -> -1 -> 1: numpy.pad(mode="reflect"), period 2(n-1); n == 1: every index is sample 0);
+ *       out: [n_rows][ld_out] float64, device.
  *   rtx_cubic_resample: the cubic spline through ALL samples of a uniform axis x0 + i*h, evaluated at x_out
  *       (device, fp64): in the interior scipy's not-a-knot interp1d(kind='cubic') is the cardinal cubic spline,
  *       whose coefficients are the samples filtered by sqrt(3)*(sqrt(3)-2)^|k|; truncated at |k| <= 40 (1e-23).
@@ -763,8 +765,9 @@ int rtx_cubic_resample(const double* Ysm, int64_t ld, int n_rows, int64_t n, dou
  * the not-a-knot end condition acts): the not-a-knot spline on the m local samples Ysm[r][i_first .. i_first+m) with the TRUE
  * knots `knots[m]` (device, fp64; the smoothed axis there), natural at the cut; valid for x_out at least 24 knots inside
  * the cut (2e-14). high_end = 0: local sample 0 is the first sample of the axis; 1: local sample m-1 is the last one.
- * m <= 768. out: [n_rows][ld_out]. */
-int rtx_cubic_end(const double* Ysm, int64_t ld, int n_rows, int64_t i_first, int m, int high_end,
+ * whole_axis = 1: the m samples are the whole (short) axis: not-a-knot at both ends, the reference's spline at every
+ * x_out between the first and the last knot; 0: natural at the cut, as above. 4 <= m <= 768. out: [n_rows][ld_out]. */
+int rtx_cubic_end(const double* Ysm, int64_t ld, int n_rows, int64_t i_first, int m, int high_end, int whole_axis,
                   const double* knots, const double* x_out, int64_t n_out, double* out, int64_t ld_out,
                   void* stream);
 int rtx_cubic_resample_unchecked(const double* Ysm, int64_t ld, int n_rows, int64_t n, double x0, double h,

@@ -95,7 +95,7 @@ PROTOTYPES = {
     "rtx_srf_pixel_cube": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
     "rtx_fir_reflect": (_i32, [_vp, _i32, _i64, _i32, _i64, _vp, _i32, _i32, _vp, _i64, _vp]),
     "rtx_cubic_resample": (_i32, [_vp, _i64, _i32, _i64, _dbl, _dbl, _vp, _i64, _vp, _i64, _vp]),
-    "rtx_cubic_end": (_i32, [_vp, _i64, _i32, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "rtx_cubic_end": (_i32, [_vp, _i64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _vp]),
     "rtx_cubic_resample_unchecked": (_i32, [_vp, _i64, _i32, _i64, _dbl, _dbl, _vp, _i64, _vp, _i64, _vp]),
     "rtx_hapi_spectrum": (_i32, [_i32, _gp, _vp, _vp, _i32, _i32, _i64, _i64, _dbl, _dbl, _vp, _i64, _vp]),
     "rtx_fir_same": (_i32, [_vp, _i32, _i64, _i32, _i64, _vp, _i64, _dbl, _i64, _i64, _vp, _i64, _vp]),

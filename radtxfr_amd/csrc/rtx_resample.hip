@@ -38,7 +38,9 @@ __global__ __launch_bounds__(FIR_BLOCK) void fir_reflect_kernel(const T* __restr
       long long jdx = i0 + k0 - centre + s;
       if (jdx < 0) jdx = -jdx;
       if (jdx >= n) jdx = 2 * (n - 1) - jdx;
-      jdx = jdx < 0 ? 0 : (jdx >= n ? n - 1 : jdx);  // only outputs past the end of the row can get here
+      if (jdx < 0) jdx = -jdx;  // n_taps - 1 == n, centre == 0: the last output's last tap sits at 2n - 1 -> -1 -> 1
+      // what is left: outputs past the end of the row (never stored), and n == 1, where every index is sample 0
+      jdx = jdx < 0 ? 0 : (jdx >= n ? n - 1 : jdx);
       s_x[s] = (double)src[jdx];
     }
     for (int s = threadIdx.x; s < kc; s += FIR_BLOCK) s_t[s] = taps[k0 + s];
@@ -198,9 +200,11 @@ extern "C" int rtx_cubic_resample(const double* Ysm, int64_t ld, int n_rows, int
 // the last output -- is the reference's spline there to 0.268^24 = 2e-14. One workgroup per row: the local tridiagonal
 // system (second-derivative form on the true, non-uniform knots) is solved by one thread in LDS, then every thread
 // evaluates outputs. `high_end`: the window is the LAST m samples; it is mirrored on load so that the true end is index 0.
+// `whole_axis`: the m samples are the whole axis (a short one), so index m-1 is the other true end and not a cut: it gets
+// the reference's not-a-knot condition too, and the spline is the reference's at every abscissa, not only 24 knots inside.
 #define SPL_END_MAX 768
 __global__ __launch_bounds__(256) void cubic_end_kernel(const double* __restrict__ y, long long ld, long long i_first, int m, int high_end,
-                                                        const double* __restrict__ knots, const double* __restrict__ x_out, long long n_out,
+                                                        int whole_axis, const double* __restrict__ knots, const double* __restrict__ x_out, long long n_out,
                                                         double* __restrict__ out, long long ld_out) {
   __shared__ double s_x[SPL_END_MAX], s_y[SPL_END_MAX], s_m[SPL_END_MAX], s_c[SPL_END_MAX], s_d[SPL_END_MAX];
   const int row = blockIdx.x;
@@ -212,8 +216,10 @@ __global__ __launch_bounds__(256) void cubic_end_kernel(const double* __restrict
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    // unknowns M_1 .. M_{m-2}; M_0 from the not-a-knot condition, M_{m-1} = 0 (natural, at the cut)
+    // unknowns M_1 .. M_{m-2}; M_0 from the not-a-knot condition, M_{m-1} = 0 (natural, at the cut) or, on a whole axis,
+    // from the not-a-knot condition at that end
     const double h0 = s_x[1] - s_x[0], h1 = s_x[2] - s_x[1];
+    const double hz = s_x[m - 1] - s_x[m - 2], hy = s_x[m - 2] - s_x[m - 3];
     double dprev = (s_y[1] - s_y[0]) / h0;
     // forward sweep (Thomas): row i: a_i M_{i-1} + b_i M_i + c_i M_{i+1} = r_i
     double cp = 0.0, dp = 0.0;  // modified coefficients of the previous row
@@ -227,7 +233,13 @@ __global__ __launch_bounds__(256) void cubic_end_kernel(const double* __restrict
         c -= h0 * h0 / h1;
         a = 0.0;
       }
-      if (i == m - 2) c = 0.0;  // M_{m-1} = 0
+      if (i == m - 2) {
+        if (whole_axis) {  // M_{m-1} = (1 + hz/hy) M_{m-2} - (hz/hy) M_{m-3} folded in
+          b += hz * (1.0 + hz / hy);
+          a -= hz * hz / hy;
+        }
+        c = 0.0;  // M_{m-1} = 0, or folded
+      }
       const double den = b - a * cp;
       cp = c / den;
       dp = (r - a * dp) / den;
@@ -242,6 +254,7 @@ __global__ __launch_bounds__(256) void cubic_end_kernel(const double* __restrict
       s_m[i] = mn;
     }
     s_m[0] = (1.0 + h0 / h1) * s_m[1] - (h0 / h1) * s_m[2];
+    if (whole_axis) s_m[m - 1] = (1.0 + hz / hy) * s_m[m - 2] - (hz / hy) * s_m[m - 3];
   }
   __syncthreads();
   for (long long q = threadIdx.x; q < n_out; q += blockDim.x) {
@@ -259,8 +272,8 @@ __global__ __launch_bounds__(256) void cubic_end_kernel(const double* __restrict
   }
 }
 
-extern "C" int rtx_cubic_end(const double* Ysm, int64_t ld, int n_rows, int64_t i_first, int m, int high_end, const double* knots,
-                             const double* x_out, int64_t n_out, double* out, int64_t ld_out, void* stream) {
+extern "C" int rtx_cubic_end(const double* Ysm, int64_t ld, int n_rows, int64_t i_first, int m, int high_end, int whole_axis,
+                             const double* knots, const double* x_out, int64_t n_out, double* out, int64_t ld_out, void* stream) {
   if (!Ysm || !knots || !x_out || !out) RTX_FAIL("a required pointer is NULL");
   if (n_rows < 1 || n_rows > 65535) RTX_FAIL("n_rows=%d", n_rows);
   if (m < 4 || m > SPL_END_MAX) RTX_FAIL("m=%d local knots outside [4,%d]", m, SPL_END_MAX);
@@ -268,7 +281,7 @@ extern "C" int rtx_cubic_end(const double* Ysm, int64_t ld, int n_rows, int64_t 
   if (ld_out < n_out) RTX_FAIL("leading dimension smaller than the row");
   if (n_out == 0) return 0;
   hipLaunchKernelGGL(cubic_end_kernel, dim3((unsigned)n_rows), dim3(256), 0, (hipStream_t)stream, Ysm, (long long)ld, (long long)i_first, m,
-                     high_end, knots, x_out, (long long)n_out, out, (long long)ld_out);
+                     high_end, whole_axis, knots, x_out, (long long)n_out, out, (long long)ld_out);
   RTX_LAUNCH_CHECK();
   return 0;
 }

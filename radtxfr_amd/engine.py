@@ -1201,16 +1201,19 @@ SPL_END_MAX = 768    # local knots rtx_cubic_end takes
 
 def _smoothed_axis_ends(x0, h, n, taps, c, m):
     """The first and last m values of the reference's smoothed axis X_ = sm(X) (radiative_transfer.py:1331-1334): the
-    symmetrised window applied to X = x0 + i*h with smooth()'s reflection padding. Host arithmetic on the axis only."""
+    symmetrised window applied to X = x0 + i*h with smooth()'s reflection padding. Host arithmetic on the axis only.
+    Both reflections at both ends: on a short axis (m == n, or a window that reaches from the first m samples past the
+    last one) a knot's window crosses the far end as well."""
     k = np.arange(taps.size)
     i = np.arange(m)
-    j = i[:, None] + k[None, :] - c
-    j = np.where(j < 0, -j, j)
-    lo = (taps[None, :] * (x0 + h * j)).sum(axis=1)
-    j = (n - m + i)[:, None] + k[None, :] - c
-    j = np.where(j >= n, 2 * (n - 1) - j, j)
-    hi = (taps[None, :] * (x0 + h * j)).sum(axis=1)
-    return lo, hi
+
+    def sm(first):
+        j = (first + i)[:, None] + k[None, :] - c
+        j = np.where(j < 0, -j, j)
+        j = np.where(j >= n, 2 * (n - 1) - j, j)
+        return (taps[None, :] * (x0 + h * j)).sum(axis=1)
+
+    return sm(0), sm(n - m)
 
 
 def _reduce_plan(x0, h, n, dX, N, window, x_out, device):
@@ -1236,25 +1239,32 @@ def _reduce_plan(x0, h, n, dX, N, window, x_out, device):
     x_lo, x_hi = x0 + margin * h, x0 + (n - 1 - margin) * h
     n_lo = n_hi = 0
     ends = None
-    if x_out.size and (x_out.min() < x_lo or x_out.max() > x_hi):
-        if np.any(np.diff(x_out) < 0):
-            raise NotImplementedError("reduceResolution: X_out must be ascending when it reaches into the end regions of the axis")
-        n_lo = int(np.searchsorted(x_out, x_lo, side="left"))
-        n_hi = int(x_out.size - np.searchsorted(x_out, x_hi, side="right"))
-        if n_lo + n_hi > x_out.size:  # a short axis: everything is an end region; the low end takes the lower half
-            n_lo = int(np.searchsorted(x_out, x0 + 0.5 * (n - 1) * h, side="left"))
-            n_hi = x_out.size - n_lo
-        m = min(n, margin + SPL_END_GUARD + 2 + (sm_factor + 1) // 2)
+    m = min(n, margin + SPL_END_GUARD + 2 + (sm_factor + 1) // 2)
+    # a short axis (m == n <= 2 margin + 6): the local spline is the spline on all knots; with the not-a-knot condition at
+    # both ends it is the reference's own, so one launch takes every output and nothing is cut
+    whole = m == n
+    if x_out.size and (whole or x_out.min() < x_lo or x_out.max() > x_hi):
         if m > SPL_END_MAX:
             raise NotImplementedError(
                 f"reduceResolution: output points within {margin} samples of an end of the input axis need a local spline of {m} "
                 f"knots (window {sm_factor}); supported up to {SPL_END_MAX}")
+        if whole:
+            n_lo = x_out.size
+        else:  # n > 2 margin + 6: the two end regions do not meet
+            if np.any(np.diff(x_out) < 0):
+                raise NotImplementedError("reduceResolution: X_out must be ascending when it reaches into the end regions of the axis")
+            n_lo = int(np.searchsorted(x_out, x_lo, side="left"))
+            n_hi = int(x_out.size - np.searchsorted(x_out, x_hi, side="right"))
         k_lo, k_hi = _smoothed_axis_ends(x0, h, n, taps, c, m)
-        if (n_lo and x_out[0] < k_lo[0]) or (n_hi and x_out[-1] > k_hi[-1]):
+        # the knots here and the reference's sm(X) differ in the last bit (1e-13 at 900 cm^-1), so an X_out that starts or
+        # ends on the reference's own first or last knot may overshoot ours by that: accepted up to the guard figure of the
+        # point count above, and evaluated by the first or last interval's cubic
+        tol = 1e-9 * h
+        if (n_lo and x_out.min() < k_lo[0] - tol) or ((n_hi or whole) and x_out.max() > k_hi[-1] + tol):
             raise NotImplementedError("reduceResolution: X_out outside the smoothed axis (extrapolation is not supported)")
-        if m < n and ((n_lo and x_out[n_lo - 1] > k_lo[m - 1 - SPL_END_GUARD]) or (n_hi and x_out[x_out.size - n_hi] < k_hi[SPL_END_GUARD])):
+        if not whole and ((n_lo and x_out[n_lo - 1] > k_lo[m - 1 - SPL_END_GUARD]) or (n_hi and x_out[x_out.size - n_hi] < k_hi[SPL_END_GUARD])):
             raise NotImplementedError("reduceResolution: the axis is too short for its end regions to be treated separately")
-        ends = (m, torch.as_tensor(k_lo, device=device), torch.as_tensor(k_hi, device=device))
+        ends = (m, torch.as_tensor(k_lo, device=device), torch.as_tensor(k_hi, device=device), whole)
     return x_out, torch.as_tensor(x_out, device=device), taps, c, n_lo, n_hi, ends
 
 
@@ -1269,14 +1279,14 @@ def _reduce_apply(Y, x0, h, n, plan, checked):
     rows = Ysm.shape[0]
     out = torch.empty((rows, n_out), dtype=torch.float64, device=Y.device)
     ld = Ysm.stride(0) if rows > 1 else n
-    m, k_lo, k_hi = ends
+    m, k_lo, k_hi, whole = ends
     if n_lo:
-        _lib.check(lib.rtx_cubic_end(_ptr(Ysm), ld, rows, 0, m, 0, _ptr(k_lo), C.c_void_p(x_dev.data_ptr()), n_lo,
+        _lib.check(lib.rtx_cubic_end(_ptr(Ysm), ld, rows, 0, m, 0, int(whole), _ptr(k_lo), C.c_void_p(x_dev.data_ptr()), n_lo,
                                      C.c_void_p(out.data_ptr()), out.stride(0), _stream_ptr()))
     if n_mid:
         out[:, n_lo:n_lo + n_mid] = cubic_resample(Ysm, x0, h, x_dev[n_lo:n_lo + n_mid], checked=checked)
     if n_hi:
-        _lib.check(lib.rtx_cubic_end(_ptr(Ysm), ld, rows, n - m, m, 1, _ptr(k_hi), C.c_void_p(x_dev.data_ptr() + 8 * (n_out - n_hi)), n_hi,
+        _lib.check(lib.rtx_cubic_end(_ptr(Ysm), ld, rows, n - m, m, 1, 0, _ptr(k_hi), C.c_void_p(x_dev.data_ptr() + 8 * (n_out - n_hi)), n_hi,
                                      C.c_void_p(out.data_ptr() + 8 * (n_out - n_hi)), out.stride(0), _stream_ptr()))
     return x_out, out
 

@@ -1228,7 +1228,11 @@ def reduceResolution(X, Y, dX, N=4, window="hanning", X_out=None):
     (2) np.int (:1329,1336) is int; (3) X_out must be ascending when it reaches within ceil(window/2) + 20 samples of an
     end of the axis, and must not leave the smoothed axis (interp1d's extrapolation is not reproduced). Output points near
     the ends -- where the reference's knots are the SMOOTHED, no longer uniform axis and its not-a-knot end condition acts --
-    are evaluated by a local not-a-knot spline on those knots (rtx_cubic_end), so short windows work with the default X_out."""
+    are evaluated by a local not-a-knot spline on those knots (rtx_cubic_end), so short windows work with the default X_out.
+    An axis so short that this local spline covers all of it (n <= 2 ceil(window/2) + 46 samples) is one spline with the
+    not-a-knot condition at both ends, the reference's own, for every output point. X_out may overshoot the first or last
+    smoothed knot by 1e-9 of a sample spacing: the knots computed here and the reference's sm(X) differ in the last bit, so
+    an X_out that starts or ends on the reference's own end knots is accepted."""
     Xh, h = _uniform_axis(X, "reduceResolution")
     engine.require_gpu()
     Yt = Y if _is_torch(Y) else torch.as_tensor(np.asarray(Y, dtype=np.float64))
