@@ -814,8 +814,13 @@ int rtx_fir_chunk_taps(void);
  *   rtx_xs_lut_create    n_mol molecules, n_rows rows in all, zero-filled. Allocates device memory and synchronises.
  *   rtx_xs_lut_free      waits for the device, then releases the table and its term buffers.
  *   rtx_xs_lut_bytes     device bytes of the table.
- *   rtx_xs_lut_set_rows  rows [row0, row0 + n_rows) <- rows_h[n_rows][nx] (host, dense; page-locked memory makes the copy
- *                        asynchronous: the caller keeps it unchanged until `stream` has passed the copy).
+ *   rtx_xs_lut_set_rows  rows [row0, row0 + n_rows) <- rows_h[n_rows][nx] (host, dense), one hipMemcpy2DAsync on `stream`. From
+ *                        page-locked memory the copy is asynchronous: the caller keeps rows_h unchanged until `stream` has
+ *                        passed the copy. From pageable memory the call synchronises `stream`: the HIP runtime was
+ *                        observed (ROCm 7.0, a copy of 8 KB) to return only once `stream` had reached the copy and the rows
+ *                        had left rows_h, unlike its 1-D copies. That is the runtime's behaviour as observed, its reason
+ *                        not looked into, and no promise of this library's: a caller who wants rows_h back at once waits
+ *                        for `stream` itself.
  *   rtx_xs_lut_get_rows  the inverse, into rows_h; synchronises `stream`.
  *   rtx_xs_od            od_f32[l][i] = sum_{m < n_mol} sum_{c < 4} weight_h[l][m][c] * row rows_h[l][m][c] at point
  *                        x_offset + i, for l < n_layers, i < n: fp32 [n_layers][ld], the layout rtx_voigt_sum writes, so
