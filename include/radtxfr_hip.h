@@ -255,6 +255,18 @@ int rtx_tud(const float* OD, int64_t ld, const rtx_grid* grid, int n_layers, con
             int n_alt, const uint8_t* mask_h, int n_mu, const double* mu_h, int n_down,
             int n_angle, int return_od, float* tau, float* Lu, float* Ld, float* Ld_angles,
             int64_t ld_out, void* stream);
+/* rtx_tud with promises about its input. flags = 0 is rtx_tud. RTX_TUD_OD_NONNEG: the caller vouches that every OD value is
+ * finite and >= 0. One (altitude, slant) pair with return_od == 0 and a mask that is its first count layers, on a grid fine
+ * enough for the Planck-node kernel (63 steps x (4/nu_min + c2/T_min) <= 7e-3: coarse or low-wavenumber grids never do), may
+ * then pass over the layers an opaque column hides from every output, wave by wave: tau and Ld keep rtx_tud's bits, Lu moves by at
+ * most 2^-35 of the column's coldest Planck radiance before rounding (a few points differ by one ulp). A NaN or negative
+ * depth under this flag gives undefined outputs where rtx_tud would give NaN. Every other call shape ignores the flag;
+ * RADTXFR_TUD_SKIP=0 in the environment (read once) makes every call ignore it. Unknown flag bits are refused. */
+#define RTX_TUD_OD_NONNEG 1u
+int rtx_tud_opts(const float* OD, int64_t ld, const rtx_grid* grid, int n_layers, const double* T_h,
+                 int n_alt, const uint8_t* mask_h, int n_mu, const double* mu_h, int n_down,
+                 int n_angle, int return_od, float* tau, float* Lu, float* Ld, float* Ld_angles,
+                 int64_t ld_out, void* stream, unsigned flags);
 
 /* Jacobian of the rtx_tud outputs with respect to layer temperatures and mixing ratios (one slant factor mu), for the
  * layers layers_h[n_lay] (host, each in [0,n_layers), in output order):
@@ -354,7 +366,10 @@ int rtx_tud_gtable(int n_angle, double* table_h, double* g0_h);
 /* compute_TUD in ONE call: radiative_transfer.py:274-392 with compute_OD (:395-456, the LBLRTM run) replaced by the
  * Voigt line-sum -- rtx_line_prep (profile Voigt, scale 1) + rtx_voigt_sum into OD[n_layers][ld_od] + rtx_tud, enqueued
  * back to back on `stream`. Arguments as for those three entry points; OD is caller-owned (it is also an output: the
- * reference's returnOD / save options expose it). One FFI crossing per atmosphere instead of three. */
+ * reference's returnOD / save options expose it). One FFI crossing per atmosphere instead of three.
+ * Its rtx_tud step runs as rtx_tud_opts(..., RTX_TUD_OD_NONNEG) when every weight_h, qratio_h, T_h and p_atm_h value is
+ * finite and >= 0 (the optical depths are then sums of non-negative terms), as rtx_tud otherwise. The line table's own
+ * strengths are not examined: a table with a negative or NaN intensity must not be combined with an opaque column. */
 int rtx_compute_tud(rtx_prep* prep, const rtx_lines* lines, const rtx_grid* grid, int n_layers,
                     const double* T_h, const double* p_atm_h, const double* qratio_h,
                     const double* weight_h, const double* mass_h, double dil_air, double dil_self,

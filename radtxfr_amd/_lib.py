@@ -49,6 +49,7 @@ PROTOTYPES = {
     "rtx_voigt_tile_points": (_i32, []),
     "rtx_planck": (_i32, [_gp, _vp, _i64, _vp, _i64, _i32, _vp, _vp]),
     "rtx_tud": (_i32, [_vp, _i64, _gp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "rtx_tud_opts": (_i32, [_vp, _i64, _gp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, C.c_uint]),
     "rtx_tud_jacobian": (_i32, [_vp, _vp, _vp, _i64, _dbl, _vp, _i32, _vp, _i64, _gp, _i32, _vp, _i32, _vp, _dbl, _i32, _i32,
                                  _i32, _vp, _i32, _i32, _vp, _i64, _vp]),
     "rtx_tud_vjp": (_i32, [_vp, _vp, _vp, _i64, _dbl, _vp, _i32, _vp, _i64, _gp, _i32, _vp, _i32, _vp, _dbl, _i32, _i32,

@@ -178,6 +178,7 @@ struct TudArgs {
   int count[TUD_MAX_ALT];
   const double* gtab;                  // angle-summed transmission function G (tud_g_kernel): [TUDG_NINT][8] doubles
   double g0;                           // G(0) = sum of the quadrature weights
+  int skip;                            // tud_g_kernel: an opaque wave may pass over the layers no output sees (TUD_SKIP_* there)
 };
 
 #define TUD_OPAQUE_Y 26.0f
@@ -652,6 +653,13 @@ struct TudDown {
     g_floor = a.g0 * (double)__builtin_amdgcn_exp2f(-fminf(opaque_y(a, l), 120.0f));
     live = a.n_down > 0;
   }
+  __device__ __forceinline__ TudDown(const double* s_g, const TudArgs& a, float y_opq) {  // y_opq = opaque_y(a, lane)
+    S = 0.0;
+    g_prev = tudg_eval(s_g, 0.0);
+    acc = 0.f;
+    g_floor = a.g0 * (double)__builtin_amdgcn_exp2f(-fminf(y_opq, 120.0f));
+    live = a.n_down > 0;
+  }
   __device__ __forceinline__ void step(const double* s_g, float od, float B) {
     S += (double)od;
     const double g = tudg_eval(s_g, S);
@@ -664,10 +672,24 @@ struct TudDown {
   }
 };
 
-template <bool PN>
+// The layers an opaque column hides from every output (tud_g_kernel, at the end of its chunk loop)
+// layers below the sensor a wave looks at: the top chunk in registers and two chunks in the 2 * TUD_STAGE LDS slots of a
+// thread -- not a knob, the look is laid out for exactly this (tools/count_tud_layers.py for what other limits would give)
+#define TUD_SKIP_SCAN (3 * TUD_STAGE)
+// a wave looks only if its downwelling has died (or run out of layers) within this many layers: on the C3 column every wave
+// that finds its top opaque is such a wave, and of the waves of the thinned columns that would look in vain (mixing ratios
+// x 1e-1: 73 %) most die later (tools/count_tud_layers.py)
+#define TUD_SKIP_BOTTOM TUD_STAGE
+#define TUD_SKIP_MARGIN 8.0f  // beyond opaque_y: what L-up drops is <= 2^-11 ulp of what it keeps
+#define TUD_SKIP_TAU0 151.0f  // exp2f(-y) is exactly 0 from y = 150 on; one more for fp32 sums taken in another order
+
+// SKIP: the instantiation that may look (launched only with a.skip, and only with PN). Without it every line below that
+// serves the look is compiled out and the kernel is the one it was before the look existed, instruction for instruction.
+template <bool PN, bool SKIP>
 __global__ __launch_bounds__(256) void tud_g_kernel(TudArgs a) {
+  static_assert(PN || !SKIP, "the look at the top is written for the Planck-node instantiation");
   __shared__ double s_g[TUDG_NINT * 8];
-  __shared__ float s_stage[TUD_STAGE][256];  // each thread's own slots
+  __shared__ float s_stage[(SKIP ? 2 : 1) * TUD_STAGE][256];  // each thread's own slots: the first TUD_STAGE hand the chunks over, all of them serve the look at the top
   tudg_load(s_g, a);
   TudLane ln(a);
   const int nL = a.n_layers;
@@ -706,7 +728,10 @@ __global__ __launch_bounds__(256) void tud_g_kernel(TudArgs a) {
   const int nd = a.n_down, cnt0 = a.count[0];
   const float c0 = a.mu_c[0];
   float s0 = 0.f, Lu0 = 0.f;
-  TudDown down(s_g, a, ln);
+  // (SKIP: opaque_y once -- its two Planck values are fp64 work, and the look at the top wants it too)
+  const float y_opq = SKIP ? opaque_y(a, ln) : 0.f;
+  TudDown down = SKIP ? TudDown(s_g, a, y_opq) : TudDown(s_g, a, ln);
+  bool skip_armed = SKIP;  // wave-uniform: the hidden layers (below the chunk loop) have not been looked for yet
   // The layer loop is bound by the CU's one scalar unit, not by HBM or the vector ALUs (round 3: 1.04e8 scalar against
   // 1.19e8 vector instructions per launch, ~45 scalar instructions per layer: 64-bit index products for the prefetch
   // addresses, the 128-bit mask lookup, the up / down flags, the loop control of a run-time inner loop). So: the prefetch
@@ -715,6 +740,9 @@ __global__ __launch_bounds__(256) void tud_g_kernel(TudArgs a) {
   const unsigned long long m_lo = (unsigned long long)mask0.w0 | ((unsigned long long)mask0.w1 << 32);
   const unsigned long long m_hi = (unsigned long long)mask0.w2 | ((unsigned long long)mask0.w3 << 32);
   const size_t bump = (size_t)TUD_STAGE * (size_t)a.ld;
+  const float y_up = y_opq + TUD_SKIP_MARGIN;
+  const int k_top = (cnt0 - 1) & ~(TUD_STAGE - 1);  // the chunk that holds layer cnt0 - 1
+  int k_look = -1;  // >= 0: the chunk loop was left before layer k_look for the look at the top of the column, below it
   const float* pf[TUD_STAGE];
 #pragma unroll
   for (int t = 0; t < TUD_STAGE; ++t) pf[t] = od_col + (size_t)(TUD_STAGE + t) * (size_t)a.ld;
@@ -743,22 +771,164 @@ __global__ __launch_bounds__(256) void tud_g_kernel(TudArgs a) {
         Lu0 = up_step(Lu0, B, od * c0);
         if (down.live) down.step(s_g, od, B);
       }
-      continue;
-    }
-    for (int k = kc; k < k_hi; ++k) {
-      const float od = s_stage[k - kc][threadIdx.x];
-      if (mask0.bit(k)) s0 += od;
-      const bool up = k < cnt0, dn = down.live && k < nd;  // wave-uniform
-      if (!up && !dn) continue;
-      const float B = PN ? planck_nodes_eval(PNd, k) : ln.planck(k);
-      if (up) Lu0 = up_step(Lu0, B, od * c0);
-      if (dn) down.step(s_g, od, B);
+      // (this loop is bound by the scalar unit: where the downwelling lives on, one flag is tested per chunk and no more.
+      //  A downwelling that runs out of layers exactly at the end of the first chunk, n_down == TUD_STAGE < count, alive, is
+      //  therefore not seen here, and the other branch sees it a chunk too late for TUD_SKIP_BOTTOM: such a wave never looks)
+      if (SKIP && !down.live) {
+        if (skip_armed) {
+          skip_armed = false;
+          if (k_hi <= TUD_SKIP_BOTTOM && k_hi + TUD_STAGE <= k_top) { k_look = k_hi; break; }
+        }
+      }
+    } else {
+      for (int k = kc; k < k_hi; ++k) {
+        const float od = s_stage[k - kc][threadIdx.x];
+        if (mask0.bit(k)) s0 += od;
+        const bool up = k < cnt0, dn = down.live && k < nd;  // wave-uniform
+        if (!up && !dn) continue;
+        const float B = PN ? planck_nodes_eval(PNd, k) : ln.planck(k);
+        if (up) Lu0 = up_step(Lu0, B, od * c0);
+        if (dn) down.step(s_g, od, B);
+      }
+      // the downwelling has stopped looking, or has run out of layers, within the first TUD_SKIP_BOTTOM layers, with a chunk to
+      // save below a chunk to look at (a wave is asked once: later chunks see skip_armed false)
+      if (SKIP && skip_armed && !(down.live && k_hi < nd)) {
+        skip_armed = false;
+        if (k_hi <= TUD_SKIP_BOTTOM && k_hi + TUD_STAGE <= k_top) { k_look = k_hi; break; }
+      }
     }
   }
-  if (ln.live) {
-    a.tau[ln.i] = a.return_od ? s0 * a.mu[0] : __builtin_amdgcn_exp2f(s0 * c0);
-    a.Lu[ln.i] = Lu0;
-    a.Ld[ln.i] = down.result(a);
+  // ---- the layers an opaque column hides from every output -----------------------------------------------------------
+  // a.skip: the caller vouches that every OD is finite and >= 0, tau (not the depth) is asked for, and the mask is the
+  // first cnt0 layers. The wave looks at the top TUD_SKIP_SCAN layers of the column, fetched in one go (the loop above is
+  // bound by its chain of dependent fetches, TUD_STAGE loads per lane in flight: a look that took its chunks one round
+  // trip after the other cost what it saved), for the highest chunk boundary k_res above which EVERY lane has an optical
+  // path of opaque_y + TUD_SKIP_MARGIN to the sensor. L-up at the sensor holds nothing of what lies below it: what enters
+  // layer k_res from below lies within the column's Planck range and arrives attenuated by 2^-(26 + 1 + 8) B_cold /
+  // B_hot, i.e. <= 2^-35 B_cold, 2^-11 ulp of anything the top can emit. The chunks in between count for the tau sum
+  // alone -- no Planck value, no up_step -- and not even for that once bottom + top put the sum past TUD_SKIP_TAU0 in
+  // every lane: the layers left out, being >= 0, only add to it. The pass then finishes from k_res out of the registers
+  // and LDS slots the look filled. So s0 is the complete bottom-up sum in its order, or maps to 0 as the complete sum does: tau and
+  // L-down keep their bits, L-up moves by <= 2^-35 B_cold before rounding. Decided once per wave and on whole chunks, and
+  // only by a wave whose downwelling is done within TUD_SKIP_BOTTOM layers (the others rarely find an opaque top). A
+  // wave whose downwelling lives to the top -- every window, every thin column -- tests one flag per chunk and never
+  // comes here; one that finds nothing runs the rest of the column as before, its next chunk having been in flight all
+  // along -- in a copy of the loop without the downwelling, which is done either way (coming back into the loop above
+  // kept that loop's whole state alive across the look: ten registers, a wave per SIMD). A NaN in a layer looked at
+  // fails the comparison: no skip.
+  if (SKIP && k_look >= 0) {
+    int kc = k_look;  // the first layer not yet run
+    // (the column's address is formed again from the thread's index: TudLane's would hold two registers through the loop above)
+    unsigned tid_top = threadIdx.x;
+    asm volatile("" : "+v"(tid_top));  // (kept apart from TudLane's index, or the two are merged again)
+    const long long i_top = (long long)blockIdx.x * blockDim.x + tid_top;
+    const float* __restrict__ od_top = a.OD + (i_top < a.g.n ? i_top : a.g.n - 1);
+    constexpr int NC = TUD_SKIP_SCAN / TUD_STAGE;
+    const float ac0 = -c0;
+    const int k_deep = k_top - (TUD_SKIP_SCAN - TUD_STAGE);
+    const int k_scan = k_deep > kc + TUD_STAGE ? k_deep : kc + TUD_STAGE;  // kc: the first layer not yet run
+    // the top chunk into registers (it may be ragged), the two below it straight into the thread's own LDS slots (LDS-DMA:
+    // no destination registers -- twelve more live values would cost the kernel a wave per SIMD): chunk 1 into the upper
+    // slots, chunk 2 into the hand-over slots, which are free between two chunks of the loop
+    static_assert(NC == 3, "the look at the top is laid out for three chunks");
+    float v0[TUD_STAGE];
+#pragma unroll
+    for (int t = 0; t < TUD_STAGE; ++t) v0[t] = od_top[(size_t)(k_top + t < cnt0 ? k_top + t : cnt0 - 1) * (size_t)a.ld];
+    {
+      // (a rolled loop over one walking pointer: unrolled, the eight addresses were all formed first and took sixteen registers)
+      float* dst = &s_stage[0][threadIdx.x & ~63u];  // wave-uniform base; the DMA adds lane * 4
+      const int n_dma = k_top - 2 * TUD_STAGE >= k_scan ? 2 * TUD_STAGE : k_top - TUD_STAGE >= k_scan ? TUD_STAGE : 0;
+      const float* pc = od_top + (size_t)(k_top - n_dma) * (size_t)a.ld;  // layer k_top - n_dma + j -> slot j (+ TUD_STAGE with one chunk)
+      float* d = dst + (n_dma == TUD_STAGE ? TUD_STAGE * 256 : 0);
+#pragma unroll 1
+      for (int j = 0; j < n_dma; ++j) {
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pc, (__attribute__((address_space(3))) void*)d, 4, 0, 0);
+        pc += a.ld;
+        d += 256;
+      }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the DMA has landed (this wave's own slots)
+    float s_top = 0.f;
+#pragma unroll
+    for (int t = TUD_STAGE - 1; t >= 0; --t)
+      if (k_top + t < cnt0) s_top += v0[t];
+    int k_res = -1;  // the chunk the pass goes on from
+    if (__ballot(s_top * ac0 >= y_up) == ~0ull) k_res = k_top;
+#pragma unroll 1
+    for (int c = 1; c < NC && k_res < 0 && k_top - c * TUD_STAGE >= k_scan; ++c) {
+      const int slot = c == 1 ? TUD_STAGE : 0;
+#pragma unroll
+      for (int t = TUD_STAGE - 1; t >= 0; --t) s_top += s_stage[slot + t][threadIdx.x];
+      if (__ballot(s_top * ac0 >= y_up) == ~0ull) k_res = k_top - c * TUD_STAGE;
+    }
+    if (k_res < 0) {  // nothing found: on with the column at kc, whose chunk has been in flight into nxt all along
+#pragma unroll
+      for (int t = 0; t < TUD_STAGE; ++t) pf[t] = od_top + (size_t)(kc + TUD_STAGE + t) * (size_t)a.ld;
+      for (; kc < cnt0; kc += TUD_STAGE) {
+#pragma unroll
+        for (int t = 0; t < TUD_STAGE; ++t) s_stage[t][threadIdx.x] = nxt[t];
+#pragma unroll
+        for (int t = 0; t < TUD_STAGE; ++t)
+          if (kc + TUD_STAGE + t < cnt0) nxt[t] = *pf[t];
+#pragma unroll
+        for (int t = 0; t < TUD_STAGE; ++t) pf[t] += bump;
+        if (kc + TUD_STAGE <= cnt0) {  // (prefix mask: every layer below cnt0 counts for tau)
+          const bool hi_set = kc >= 64;
+#pragma unroll
+          for (int t = 0; t < TUD_STAGE; ++t) {
+            const float od = s_stage[t][threadIdx.x];
+            s0 += od;
+            Lu0 = up_step(Lu0, planck_nodes_eval(PNd, hi_set, (kc & 63) + t), od * c0);
+          }
+        } else {
+          for (int k = kc; k < cnt0; ++k) {
+            const float od = s_stage[k - kc][threadIdx.x];
+            s0 += od;
+            Lu0 = up_step(Lu0, planck_nodes_eval(PNd, k), od * c0);
+          }
+        }
+      }
+    } else {
+    for (int km = kc; km < k_res; km += TUD_STAGE) {  // kc and k_res are chunk boundaries, every layer here < cnt0
+      if (__ballot((s0 + s_top) * ac0 >= TUD_SKIP_TAU0) == ~0ull) break;
+      float w[TUD_STAGE];
+#pragma unroll
+      for (int t = 0; t < TUD_STAGE; ++t) w[t] = od_top[(size_t)(km + t) * (size_t)a.ld];
+#pragma unroll
+      for (int t = 0; t < TUD_STAGE; ++t) s0 += w[t];
+    }
+#pragma unroll 1
+    for (int kb = k_res; kb < k_top; kb += TUD_STAGE) {  // whole chunks out of the LDS slots
+      const int slot = kb == k_top - TUD_STAGE ? TUD_STAGE : 0;
+#pragma unroll
+      for (int t = 0; t < TUD_STAGE; ++t) {
+        const float od = s_stage[slot + t][threadIdx.x];
+        s0 += od;
+        Lu0 = up_step(Lu0, planck_nodes_eval(PNd, kb + t), od * c0);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < TUD_STAGE; ++t) {  // the top chunk out of its registers
+      if (k_top + t < cnt0) {
+        s0 += v0[t];
+        Lu0 = up_step(Lu0, planck_nodes_eval(PNd, k_top + t), v0[t] * c0);
+      }
+    }
+    }  // (layers from cnt0 on count for nothing here: prefix mask, and the downwelling is done)
+  }
+  // (SKIP: the point's index is formed again here, kept apart from TudLane's: that copy would hold two registers through both loops)
+  long long i_out = ln.i;
+  bool live_out = ln.live;
+  if (SKIP) {
+    unsigned tid_out = threadIdx.x;
+    asm volatile("" : "+v"(tid_out));
+    i_out = (long long)blockIdx.x * blockDim.x + tid_out;
+    live_out = i_out < a.g.n;
+  }
+  if (live_out) {
+    a.tau[i_out] = a.return_od ? s0 * a.mu[0] : __builtin_amdgcn_exp2f(s0 * c0);
+    a.Lu[i_out] = Lu0;
+    a.Ld[i_out] = down.result(a);
   }
 }
 
@@ -1041,10 +1211,11 @@ static int launch_tud(TudArgs& a, int na, hipStream_t st) {
   return tud_launch(tud_kernel<NA, false>, a, (size_t)TUD_STAGE * 256 * sizeof(float), st);
 }
 
-extern "C" int rtx_tud(const float* OD, int64_t ld, const rtx_grid* grid, int n_layers, const double* T_h, int n_alt,
-                       const uint8_t* mask_h, int n_mu, const double* mu_h, int n_down, int n_angle, int return_od,
-                       float* tau, float* Lu, float* Ld, float* Ld_angles, int64_t ld_out, void* stream) {
+extern "C" int rtx_tud_opts(const float* OD, int64_t ld, const rtx_grid* grid, int n_layers, const double* T_h, int n_alt,
+                            const uint8_t* mask_h, int n_mu, const double* mu_h, int n_down, int n_angle, int return_od,
+                            float* tau, float* Lu, float* Ld, float* Ld_angles, int64_t ld_out, void* stream, unsigned flags) {
   if (rtx_check_grid(grid)) return 1;
+  if (flags & ~(unsigned)RTX_TUD_OD_NONNEG) RTX_FAIL("flags=0x%x: unknown bits", flags);
   if (!OD || !T_h || !mask_h || !mu_h || !tau || !Lu || !Ld) RTX_FAIL("a required pointer is NULL");
   if (n_layers < 1 || n_layers > TUD_MAX_LAYERS) RTX_FAIL("n_layers=%d outside [1,%d]", n_layers, TUD_MAX_LAYERS);
   if (n_alt < 1 || n_alt > TUD_MAX_ALT) RTX_FAIL("n_alt=%d outside [1,%d]", n_alt, TUD_MAX_ALT);
@@ -1106,7 +1277,14 @@ extern "C" int rtx_tud(const float* OD, int64_t ld, const rtx_grid* grid, int n_
     const double nu_lo = grid->xmin;
     const bool pn = nu_lo > 0.0 && (4.0 / nu_lo + RT_C2 * 100.0 / t_min) * 63.0 * grid->step <= 7e-3;
     void (*kernel)(TudArgs);
-    if (n_alt * n_mu == 1) kernel = pn ? tud_g_kernel<true> : tud_g_kernel<false>;
+    if (n_alt * n_mu == 1) {
+      kernel = pn ? tud_g_kernel<true, false> : tud_g_kernel<false, false>;
+      // hidden layers of an opaque column (see the kernel): RADTXFR_TUD_SKIP=0 keeps every wave on the full pass
+      static int skip_on = -1;
+      if (skip_on < 0) { const char* e = getenv("RADTXFR_TUD_SKIP"); skip_on = (e && !strcmp(e, "0")) ? 0 : 1; }
+      a.skip = skip_on && (flags & RTX_TUD_OD_NONNEG) && !return_od && prefix && pn;  // (the Planck-node instantiation only)
+      if (a.skip) kernel = tud_g_kernel<true, true>;  // every other call runs the instantiation without the look
+    }
     // one slant path (the reference's main caller: 9 altitudes, nadir): the instantiation without the per-slant guards
     else if (prefix && n_mu == 1) kernel = pn ? tud_g_snap_kernel<1, true> : tud_g_snap_kernel<1, false>;
     else if (prefix) kernel = pn ? tud_g_snap_kernel<TUD_MAX_MU, true> : tud_g_snap_kernel<TUD_MAX_MU, false>;
@@ -1119,6 +1297,13 @@ extern "C" int rtx_tud(const float* OD, int64_t ld, const rtx_grid* grid, int n_
   if (na <= 24) return launch_tud<24>(a, na, st);
   if (na <= 29) return launch_tud<29>(a, na, st);
   return launch_tud<32>(a, na, st);
+}
+
+extern "C" int rtx_tud(const float* OD, int64_t ld, const rtx_grid* grid, int n_layers, const double* T_h, int n_alt,
+                       const uint8_t* mask_h, int n_mu, const double* mu_h, int n_down, int n_angle, int return_od,
+                       float* tau, float* Lu, float* Ld, float* Ld_angles, int64_t ld_out, void* stream) {
+  return rtx_tud_opts(OD, ld, grid, n_layers, T_h, n_alt, mask_h, n_mu, mu_h, n_down, n_angle, return_od, tau, Lu, Ld, Ld_angles,
+                      ld_out, stream, 0u);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1137,6 +1322,17 @@ extern "C" int rtx_compute_tud(rtx_prep* prep, const rtx_lines* lines, const rtx
                             omega_wing_hw, intensity_threshold, 1.0, RTX_PROFILE_VOIGT, stream))
     return 1;
   if (rtx_voigt_sum(prep, grid, n_layers, OD, nullptr, ld_od, stream)) return 1;
-  return rtx_tud(OD, ld_od, grid, n_layers, T_h, n_alt, mask_h, n_mu, mu_h, n_down, n_angle, return_od, tau, Lu, Ld, nullptr,
-                 ld_out, stream);
+  // the optical depths just summed are sums of non-negative terms when every factor the caller gave is finite and >= 0: the
+  // column weights, the partition-sum ratios, T and p (the prologue has accepted lines, n_layers and the arrays by now). Line
+  // strengths are the table's and are not looked at: a table with a negative or NaN S is outside what this vouches for.
+  auto nonneg = [](const double* v, long long n) {
+    for (long long j = 0; j < n; ++j)
+      if (!(v[j] >= 0.0 && v[j] <= 1.7976931348623157e308)) return false;
+    return true;
+  };
+  const long long n_sl = (long long)lines->n_species * n_layers;
+  const unsigned flags = nonneg(weight_h, n_sl) && nonneg(qratio_h, n_sl) && nonneg(T_h, n_layers) && nonneg(p_atm_h, n_layers)
+                             ? RTX_TUD_OD_NONNEG : 0u;
+  return rtx_tud_opts(OD, ld_od, grid, n_layers, T_h, n_alt, mask_h, n_mu, mu_h, n_down, n_angle, return_od, tau, Lu, Ld, nullptr,
+                      ld_out, stream, flags);
 }

@@ -13,6 +13,7 @@ import torch
 from . import _lib, tips
 
 TUD_MAX_MU = 8  # slant paths per rtx_tud launch (include/radtxfr_hip.h)
+TUD_OD_NONNEG = 1  # RTX_TUD_OD_NONNEG
 
 # hapi constants used for per-species / per-layer host factors (misc/hapi.py:84-92, 10163-10164)
 CBOLTS = 1.380648813e-16
@@ -747,10 +748,13 @@ def _check_tud_outputs(tau, Lu, Ld, nrow, n):
     return tau.stride(0) if tau.shape[0] > 1 else max(tau.shape[1], n)  # the stride of a size-1 dimension is arbitrary
 
 
-def tud(OD, grid, T, Z, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=False, per_angle=False, out=None):
+def tud(OD, grid, T, Z, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=False, per_angle=False, out=None,
+        od_nonneg=False):
     """tau[nAlt*nMu][n], Lu[nAlt*nMu][n], Ld[n] float32 device tensors from OD[nL][n] (rtx_tud).
     out=(tau, Lu, Ld): write into caller-owned tensors (tau/Lu [nAlt*nMu][>=n] with a common row stride),
-    e.g. the rows of the packed block a wavenumber shard all-gathers."""
+    e.g. the rows of the packed block a wavenumber shard all-gathers.
+    od_nonneg=True: the caller vouches that every OD value is finite and >= 0 (RTX_TUD_OD_NONNEG, include/radtxfr_hip.h):
+    a single (altitude, slant) pair may then pass over the layers an opaque column hides from every output."""
     lib = _lib.load()
     T = np.atleast_1d(np.asarray(T, dtype=np.float64))
     Z_s, mu_s, mask, n_down = tud_geometry(Z, Altitudes, theta_r)
@@ -770,7 +774,7 @@ def tud(OD, grid, T, Z, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=Fals
             m1 = min(m0 + TUD_MAX_MU, mu_s.size)
             # the per-stream downwelling radiances do not depend on the slant paths: taken from the first block
             res = tud(OD, grid, T, Z, Altitudes=Altitudes, theta_r=th[m0:m1], N_angle=N_angle, returnOD=returnOD,
-                      per_angle=per_angle and m0 == 0)
+                      per_angle=per_angle and m0 == 0, od_nonneg=od_nonneg)
             t_c, l_c, Ld_c = res[:3]
             if m0 == 0:
                 Ld = Ld_c
@@ -792,9 +796,9 @@ def tud(OD, grid, T, Z, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=Fals
     Ld_ang = torch.empty((int(N_angle), ld_out), dtype=torch.float32, device=dev) if per_angle else None
     T_h, T_p = _h(T)
     mu_h, mu_p = _h(mu_s)
-    _lib.check(lib.rtx_tud(_ptr(OD), OD.stride(0), grid.byref(), nL, T_p, Z_s.size, mask.ctypes.data_as(C.c_void_p),
-                           mu_s.size, mu_p, n_down, int(N_angle), int(bool(returnOD)), _ptr(tau), _ptr(Lu), _ptr(Ld),
-                           _ptr(Ld_ang), ld_out, _stream_ptr()))
+    _lib.check(lib.rtx_tud_opts(_ptr(OD), OD.stride(0), grid.byref(), nL, T_p, Z_s.size, mask.ctypes.data_as(C.c_void_p),
+                                mu_s.size, mu_p, n_down, int(N_angle), int(bool(returnOD)), _ptr(tau), _ptr(Lu), _ptr(Ld),
+                                _ptr(Ld_ang), ld_out, _stream_ptr(), TUD_OD_NONNEG if od_nonneg else 0))
     if per_angle:
         return tau, Lu, Ld, (Z_s.size, mu_s.size), Ld_ang[:, :grid.n]
     return tau, Lu, Ld, (Z_s.size, mu_s.size)

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Developer timing of the C3 stages (HIP events on the launch stream), for A/B-testing builds:
-    RADTXFR_LIB=build/libp4.so python tools/time_c3.py [--reps 5] [--n 5500000]"""
+    RADTXFR_LIB=build/libp4.so python tools/time_c3.py [--reps 5] [--n 5500000] [--od-nonneg]
+The TUD is timed through engine.tud, which does not vouch for the optical depths unless --od-nonneg is given; rtx_compute_tud
+(bench.py, TudRunner) does by default. On an opaque column give --od-nonneg to time the path that ships."""
 import argparse, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -14,6 +16,7 @@ ap.add_argument("--layers", type=int, default=32)
 ap.add_argument("--n-alt", type=int, default=1, help="sensor altitudes (the reference's main caller asks for 9)")
 ap.add_argument("--shard", type=str, default="", help="R/N: time rank R's wavenumber shard of N, with the FULL line table")
 ap.add_argument("--mf-scale", type=float, default=1.0, help="scale the mixing ratios (1e-4: an optically thin column, tau ~ 0.5-1 between lines)")
+ap.add_argument("--od-nonneg", action="store_true", help="vouch for the optical depths as rtx_compute_tud does (RTX_TUD_OD_NONNEG: opaque waves pass over hidden layers)")
 ap.add_argument("--table", default="uniform", choices=["uniform", "clustered"], help="clustered: band heads of 3000 lines per 0.5 cm^-1, combs, empty stretches (synthetic.synth_clustered_table)")
 args = ap.parse_args()
 lib = _lib.load()
@@ -38,7 +41,7 @@ for it in range(args.reps + 2):
     ev[0].record()
     engine.voigt_sum(lines, grid, T, p_atm, w, out_f32=OD, qratio=qr, mass=mass)
     ev[1].record()
-    tau, Lu, Ld, _ = engine.tud(OD, grid, T, Z, Altitudes=alts)
+    tau, Lu, Ld, _ = engine.tud(OD, grid, T, Z, Altitudes=alts, **({"od_nonneg": True} if args.od_nonneg else {}))
     ev[2].record()
     torch.cuda.synchronize()
     if it >= 2:
