@@ -861,6 +861,30 @@ int rtx_xs_od(rtx_xs_lut* lut, int64_t x_offset, int64_t n, int n_layers, const 
               float* od_f32, int64_t ld, void* stream);
 int rtx_xs_tile_points(void);
 
+/* ---- tabulated continuum absorption -------------------------------------------------------
+ * LBLRTM, behind the reference's compute_OD, adds the collision-induced continua to its line sum (write_tape5 switches them
+ * on, radiative_transfer.py:591-601). Here the user supplies the coefficient tables (radtxfr_amd/continuum.py) and
+ *   rtx_continuum_add   od_f32[l][i] += R(nu_i, T_h[l]) * sum_{c < n_comp} max(0, sum_{k < 4} L_k(t) * A[c][l][j0 + k])
+ * for l < n_layers and the grid's points i < grid->n, in place on fp32 [n_layers][ld] (the layout rtx_voigt_sum and
+ * rtx_xs_od write, so rtx_tud takes it unchanged). nu_i is the grid value of the GLOBAL index grid->offset + i;
+ * R = nu tanh(c2 nu / (2T)), c2 = 1.43877736830 cm K; component c has the uniform node axis v0_h[c] + j * dv_h[c],
+ * j < n_nodes_h[c] (at least 4 nodes, dv > 0) and contributes where v0 <= nu <= v0 + (n - 1) dv (the sum formed unfused in
+ * fp64), nothing elsewhere; j0 = clamp(floor((nu - v0) / dv) - 1, 0, n - 4), t = (nu - nu_j0) / dv formed in fp64 and then
+ * rounded, L_k the cubic Lagrange basis on the nodes 0, 1, 2, 3. tables_h is a HOST array [n_comp][n_layers][ld_nodes]
+ * of fp32 node values A (column amount, density scaling and coefficients folded in by the caller; every value of a
+ * component's first n nodes must be finite, the columns after them are not read). The value added at a point is a
+ * function of (tables, layer, global index) alone: bit-identical for every offset / n cut of an axis. T_h, the axes and the
+ * tables are copied (hipMemcpyAsync on `stream`, staged before returning) into a grow-only device buffer the library keeps
+ * for each (device, stream) that has called: the first call on a stream, or a larger one, allocates; every other call only
+ * enqueues. 16-byte accesses when ld is a multiple of 4 and od_f32 is 16-byte aligned (point by point for the ragged end
+ * of the last tile); otherwise point by point throughout. flags: none is defined, pass 0 (it follows the stream as in
+ * rtx_tud_opts).
+ *   rtx_continuum_tile_points   consecutive points one workgroup owns (for tests at the edges). */
+int rtx_continuum_add(const rtx_grid* grid, int n_layers, const double* T_h, int n_comp, const double* v0_h,
+                      const double* dv_h, const int32_t* n_nodes_h, const float* tables_h, int64_t ld_nodes, float* od_f32,
+                      int64_t ld, void* stream, unsigned flags);
+int rtx_continuum_tile_points(void);
+
 /* ------------------------------------------------------------------------------------------
  * Single-process collectives over the GPUs of one node. The reference has no multi-GPU code; its scripts are plain
  * Python programs that fan work out with multiprocessing (Generate_LWIR_TUD.py:117-150). These three calls let ONE host

@@ -718,6 +718,30 @@ def xs_od(lut, grid_or_offset, T, P_atm, PL, MF, ID, out_f32=None):
     return out_f32
 
 
+def _continuum_call(lib, tables, axes, grid, T, OD, st):
+    """rtx_continuum_add on host tables [nC][nL][n_max] float32 with axes [(v0, dv, n)]: OD[nL][>= grid.n] += continuum."""
+    v0 = np.array([a[0] for a in axes], dtype=np.float64)
+    dv = np.array([a[1] for a in axes], dtype=np.float64)
+    nn = np.array([a[2] for a in axes], dtype=np.int32)
+    vp = C.c_void_p
+    _lib.check(lib.rtx_continuum_add(grid.byref(), T.size, T.ctypes.data_as(vp), len(axes), v0.ctypes.data_as(vp), dv.ctypes.data_as(vp),
+                                     nn.ctypes.data_as(vp), tables.ctypes.data_as(vp), tables.shape[2], vp(OD.data_ptr()),
+                                     OD.stride(0) if T.size > 1 else max(OD.shape[1], grid.n), st, 0))
+
+
+def continuum_add(cont, grid, T, P_pa, PL_km, MF_VAL, MF_ID, OD):
+    """OD[nL][>= grid.n] float32 on the device += the tabulated continuum `cont` (a continuum.Continuum; DESIGN.md section
+    4.22) of the layers T [K], P_pa [Pa], PL_km [km], MF_VAL[nL][nM] ppmv, MF_ID[nM], in place (rtx_continuum_add); returns
+    OD. The node rows are made on the host in float64 (Continuum.layer_tables; ValueError for a component whose molecule
+    MF_ID lacks). A shard of `grid` gives the bits the whole axis gives."""
+    T = np.ascontiguousarray(np.atleast_1d(T), dtype=np.float64)
+    tables, axes = cont.layer_tables(T, P_pa, PL_km, MF_VAL, MF_ID)
+    assert OD.dtype == torch.float32 and OD.is_cuda and OD.dim() == 2 and OD.shape[0] == T.size
+    assert OD.shape[1] >= grid.n and OD.stride(1) == 1
+    _continuum_call(_lib.load(), tables, axes, grid, T, OD, _stream_ptr())
+    return OD
+
+
 class TudGeometry(NamedTuple):
     """What tud_geometry returns."""
     Z_s: np.ndarray   # sensor altitudes [nAlt]
@@ -814,12 +838,16 @@ class TudRunner:
     broadening: None (the fused rtx_compute_tud), "self" or ("self", gas, ...): each species broadened by its per-layer
     mix (broadening_fractions), run as rtx_line_prep_mix + rtx_voigt_sum + rtx_tud -- the same line-sum and TUD kernels.
     xs_lut: an afit_xs.XsLut instead of `lines` (None then): the optical depths come from the table (rtx_xs_od + rtx_tud);
-    `grid` must coincide with a run of the table's axis. Not with broadening (fixed when the table was made)."""
+    `grid` must coincide with a run of the table's axis. Not with broadening (fixed when the table was made).
+    continuum: a continuum.Continuum added to the optical depths of whichever branch made them,
+    between them and rtx_tud (rtx_continuum_add); the default branch then runs rtx_line_prep + rtx_voigt_sum +
+    rtx_continuum_add + rtx_tud as separate calls. None: every branch is what it is without the option."""
 
     def __init__(self, lines, grid, Z, n_layers=None, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=False, out=None,
-                 OD=None, plan=None, broadening=None, xs_lut=None):
+                 OD=None, plan=None, broadening=None, xs_lut=None, continuum=None):
         self.lib = _lib.load()
         self.lines, self.grid = lines, grid
+        self.continuum = continuum
         self.foreign = broadening_gases(broadening)
         self.xs_lut = xs_lut
         if xs_lut is not None:
@@ -859,6 +887,10 @@ class TudRunner:
         self.tau, self.Lu, self.Ld = tau, Lu, Ld
         self._ptrs = (C.c_void_p(tau.data_ptr()), C.c_void_p(Lu.data_ptr()), C.c_void_p(Ld.data_ptr()))
 
+    def _add_continuum(self, T, P_pa, PL_km, MF_VAL, MF_ID, st):
+        tables, axes = self.continuum.layer_tables(T, P_pa, PL_km, MF_VAL, MF_ID)
+        _continuum_call(self.lib, tables, axes, self.grid, T, self.OD, st)
+
     def run(self, T, P_pa, PL_km, MF_VAL, MF_ID, partitionFunction=None):
         nL, lines = self.nL, self.lines
         T = np.ascontiguousarray(T, dtype=np.float64)
@@ -869,6 +901,8 @@ class TudRunner:
             with trace_range("rtx_xs_od + rtx_tud"):
                 _lib.check(self.lib.rtx_xs_od(self.xs_lut._handle(), self._xs_off, self.grid.n, nL, rows.ctypes.data_as(vp),
                                               wx.ctypes.data_as(vp), vp(self.OD.data_ptr()), self.OD.stride(0), st))
+                if self.continuum is not None:
+                    self._add_continuum(T, P_pa, PL_km, MF_VAL, MF_ID, st)
                 _lib.check(self.lib.rtx_tud(
                     vp(self.OD.data_ptr()), self.OD.stride(0), self.grid.byref(), nL, T.ctypes.data_as(vp), self.shape[0],
                     self.mask.ctypes.data_as(vp), self.shape[1], self.mu.ctypes.data_as(vp), self.n_down, self.N_angle, self.returnOD,
@@ -895,10 +929,28 @@ class TudRunner:
                            lines, nL, dil, None, None, 0.0, 50.0, 0.0, 1.0, 0, st)
                 _lib.check(self.lib.rtx_voigt_sum(self.plan._h, self.grid.byref(), nL, vp(self.OD.data_ptr()), None,
                                                   self.OD.stride(0), st))
+                if self.continuum is not None:
+                    self._add_continuum(T, P_pa, PL_km, MF_VAL, MF_ID, st)
                 _lib.check(self.lib.rtx_tud(
                     vp(self.OD.data_ptr()), self.OD.stride(0), self.grid.byref(), nL, vp(base), self.shape[0],
                     self.mask.ctypes.data_as(vp), self.shape[1], self.mu.ctypes.data_as(vp), self.n_down, self.N_angle, self.returnOD,
                     self._ptrs[0], self._ptrs[1], self._ptrs[2], None, self._ld_out, st))
+            return self.tau, self.Lu, self.Ld
+        if self.continuum is not None:
+            st = _stream_ptr()
+            # what rtx_compute_tud hands its TUD step (include/radtxfr_hip.h): the continuum adds only values >= 0
+            nonneg = TUD_OD_NONNEG if bool(np.all(np.isfinite(env)) and env.min() >= 0.0) else 0
+            with trace_range("rtx_line_prep + rtx_voigt_sum + rtx_continuum_add + rtx_tud"):
+                _lib.check(self.lib.rtx_line_prep(
+                    self.plan._h, lines._h, self.grid.byref(), nL, vp(base), vp(base + 8 * nL), vp(base + 16 * nL),
+                    vp(base + 8 * (2 * nL + nS * nL)), vp(base + 8 * (2 * nL + 2 * nS * nL)), 1.0, 0.0, 0.0, 50.0, 0.0, 1.0, st))
+                _lib.check(self.lib.rtx_voigt_sum(self.plan._h, self.grid.byref(), nL, vp(self.OD.data_ptr()), None,
+                                                  self.OD.stride(0), st))
+                self._add_continuum(T, P_pa, PL_km, MF_VAL, MF_ID, st)
+                _lib.check(self.lib.rtx_tud_opts(
+                    vp(self.OD.data_ptr()), self.OD.stride(0), self.grid.byref(), nL, vp(base), self.shape[0],
+                    self.mask.ctypes.data_as(vp), self.shape[1], self.mu.ctypes.data_as(vp), self.n_down, self.N_angle, self.returnOD,
+                    self._ptrs[0], self._ptrs[1], self._ptrs[2], None, self._ld_out, st, nonneg))
             return self.tau, self.Lu, self.Ld
         with trace_range("rtx_compute_tud"):
             _lib.check(self.lib.rtx_compute_tud(
@@ -917,7 +969,7 @@ class TudPipelines:
     one atmosphere share the chip with the VALU-bound line-sum of the next (C3 on MI355X, bench.py: 1.97 / 1.90 / 1.90 /
     1.91 ms per atmosphere with 1 / 2 / 3 / 4 pipelines; profiles/r3_time_pipeline.txt). Results are the single-runner results bit for bit.
     outs: optional list of P (tau, Lu, Ld) output triples (e.g. rows of packed blocks that are all-gathered).
-    kw: TudRunner's keywords (Altitudes, theta_r, N_angle, returnOD, broadening)."""
+    kw: TudRunner's keywords (Altitudes, theta_r, N_angle, returnOD, broadening, continuum)."""
 
     def __init__(self, lines, grid, Z, n_layers=None, n_pipes=2, outs=None, **kw):
         self.streams = [torch.cuda.Stream() for _ in range(int(n_pipes))]

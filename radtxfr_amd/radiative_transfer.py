@@ -18,7 +18,8 @@ Conscious divergences from the reference:
   * compute_OD: the reference shells out to the LBLRTM Fortran binary with the AER line file; both
     are git-LFS stubs. Here OD(nu) = sum_m k_m(nu; T, p) x_m PL from the Voigt line-sum over the line
     table named by opts["line_table"] (a table in radtxfr_amd.hapi.LOCAL_TABLE_CACHE, or a column
-    dict). No continuum. Chunking / TAPE5 / TAPE12 plumbing does not exist.
+    dict). The continuum LBLRTM adds is added only from tables the caller supplies (continuum=, radtxfr_amd/continuum.py);
+    none is built in. Chunking / TAPE5 / TAPE12 plumbing does not exist.
   * options are copied per call: kwargs no longer leak into the module-level default (quirk 2).
   * make_spectral_axis casts the point count to int (quirk 1: the reference crashes on NumPy>=1.18).
   * spectra are computed in float32 on the device and returned as float64.
@@ -175,9 +176,24 @@ def _xs_lut_option(fn, o):
     return lut
 
 
+def _continuum_option(fn, o, ids):
+    """The per-call continuum= option (a continuum.Continuum, or None): tabulated continuum absorption added to the optical
+    depths. Never stored in `options`. ValueError, before any device work, for a component whose
+    molecule the call's mixing ratios (`ids`) lack: a silent zero would hide a misconfigured call."""
+    cont = o.get("continuum")
+    if cont is not None:
+        have = [int(v) for v in np.asarray(ids).ravel()]
+        lacking = [c.molecule for c in cont.components if c.molecule not in have]
+        if lacking:
+            raise ValueError("%s: continuum component molecule(s) %r are not in the mixing-ratio ids %r" % (fn, lacking, have))
+    return cont
+
+
 def compute_OD(Xmin_in, Xmax_in, opts=options, **kwargs):
     """Monochromatic optical depth of one homogeneous layer, signature of :395-456.
-    kwargs honoured: T [K], P [Pa], PL [km], MF_VAL [ppmv], MF_ID (HITRAN ids), DVOUT, line_table, xs_lut.
+    kwargs honoured: T [K], P [Pa], PL [km], MF_VAL [ppmv], MF_ID (HITRAN ids), DVOUT, line_table, xs_lut, continuum.
+    continuum (per call, a continuum.Continuum): its tabulated continuum absorption is added to the optical depth, whichever
+    way that was made. ValueError: a component whose molecule MF_ID lacks.
     xs_lut (per call, an afit_xs.XsLut): look the optical depth up in a cross-section table (bilinear in T and ln p between
     its nodes) instead of summing lines; line_table is then neither needed nor touched. ValueError: the axis is
     not a run of the table's, (T, P) outside the table, a molecule of MF_ID the table lacks.
@@ -187,14 +203,16 @@ def compute_OD(Xmin_in, Xmax_in, opts=options, **kwargs):
     DVOUT = o.get("DVOUT", 0.025)
     X = make_spectral_axis(Xmin_in, Xmax_in, DVOUT)
     lut = _xs_lut_option("compute_OD", o)
-    if lut is not None:
-        OD = engine.xs_od(lut, engine.Grid(Xmin_in, Xmax_in, X.size), [o["T"]], [o["P"] / 101325.0], [o["PL"]],
-                          np.asarray(o["MF_VAL"], dtype=np.float64)[None, :], o["MF_ID"])
-        return X, OD[0].double().cpu().numpy()
-    tbl = _resolve_table(o.get("line_table"))
+    cont = _continuum_option("compute_OD", o, o["MF_ID"])
     grid = engine.Grid(Xmin_in, Xmax_in, X.size)
-    OD = engine.optical_depths(tbl, grid, [o["T"]], [o["P"]], [o["PL"]], np.asarray(o["MF_VAL"], dtype=np.float64)[None, :],
-                               o["MF_ID"])
+    MF = np.asarray(o["MF_VAL"], dtype=np.float64)[None, :]
+    if lut is not None:
+        OD = engine.xs_od(lut, grid, [o["T"]], [o["P"] / 101325.0], [o["PL"]], MF, o["MF_ID"])
+    else:
+        tbl = _resolve_table(o.get("line_table"))
+        OD = engine.optical_depths(tbl, grid, [o["T"]], [o["P"]], [o["PL"]], MF, o["MF_ID"])
+    if cont is not None:
+        engine.continuum_add(cont, grid, [o["T"]], [o["P"]], [o["PL"]], MF, o["MF_ID"], OD)
     return X, OD[0].double().cpu().numpy()
 
 
@@ -221,8 +239,9 @@ class _Call:
     reference derives from it at the top of compute_TUD (:304-314, :346-349) -- the profile Z, T, P, PL, MF as float64
     arrays and ID, the sensor altitudes Z_s, theta (float64), N_angle, returnOD and the broadening= option. What can
     raise or costs time is made on first use, so that a caller's own argument checks come first: lut (the xs_lut option,
-    _xs_lut_option in `fn`'s name), foreign (broadening's foreign gases), X (the cached axis) and grid; table() looks the
-    line table up (None with an xs_lut), and nothing before it touches a table or a device."""
+    _xs_lut_option in `fn`'s name), continuum (the continuum option, _continuum_option), foreign (broadening's foreign
+    gases), X (the cached axis) and grid; table() looks the line table up (None with an xs_lut), and nothing before it
+    touches a table or a device."""
 
     def __init__(self, fn, Xmin, Xmax, opts, kwargs):
         self.fn, self.Xmin, self.Xmax = fn, Xmin, Xmax
@@ -236,6 +255,7 @@ class _Call:
         self.broadening = o.get("broadening")
 
     lut = functools.cached_property(lambda self: _xs_lut_option(self.fn, self.o))
+    continuum = functools.cached_property(lambda self: _continuum_option(self.fn, self.o, self.ID))
     foreign = functools.cached_property(lambda self: engine.broadening_gases(self.broadening))
     X = functools.cached_property(lambda self: _cached_axis(self.Xmin, self.Xmax, self.o["DVOUT"]))
     grid = functools.cached_property(lambda self: engine.Grid(self.Xmin, self.Xmax, self.X.size))
@@ -280,7 +300,8 @@ def _tud_shapes(tau2, Lu2, nZ, nMu):
 _SIDE_STREAMS = {}
 
 
-def _compute_tud_chunked(tbl, grid, Z, T, P, PL, MF, ID, Z_s, theta, nA, returnOD, n_chunks, broadening=None, xs_lut=None):
+def _compute_tud_chunked(tbl, grid, Z, T, P, PL, MF, ID, Z_s, theta, nA, returnOD, n_chunks, broadening=None, xs_lut=None,
+                         continuum=None):
     """compute_TUD's device work in n_chunks tile-aligned wavenumber chunks, each chunk's widening and device-to-host copy
     (side stream) under the next chunk's kernels: a single call is PCIe-bound (132 MB of float64 at C3 size: 2.7 ms against
     1.9 ms of kernels), and chunks cut on line-sum tile boundaries give the unchunked bits. Returns (tau_h, Lu_h, Ld_h,
@@ -315,7 +336,7 @@ def _compute_tud_chunked(tbl, grid, Z, T, P, PL, MF, ID, Z_s, theta, nA, returnO
         sl = slice(off, off + ln)
         run = engine.TudRunner(tbl, grid.shard(grid.offset + off, ln), Z, n_layers=nL, Altitudes=Z_s, theta_r=theta, N_angle=nA,
                                returnOD=returnOD, out=(tau[:, sl], Lu[:, sl], Ld[sl]), OD=OD[:, :ln], plan=plan,
-                               broadening=broadening, xs_lut=xs_lut)
+                               broadening=broadening, xs_lut=xs_lut, continuum=continuum)
         run.run(T, P, PL, MF, ID)
         ready = torch.cuda.Event()
         ready.record()
@@ -358,10 +379,13 @@ def compute_TUD(Xmin, Xmax, opts=options, **kwargs):
     needed nor touched, and everything after the optical depths is the same code. ValueError: the axis is not a contiguous
     run of the table's, a layer outside the table's (T, p) range, a molecule of MFs_ID the table lacks.
     NotImplementedError: xs_lut together with any broadening= (fixed when the table was made).
+    continuum (keyword only, not in `options`): a continuum.Continuum. Its tabulated continuum absorption (the
+    user's MT_CKD-style tables) is added to the optical depths of whichever branch made them, before the TUD sweep;
+    returnOD=True therefore carries it. ValueError: a component whose molecule MFs_ID lacks.
     """
     trace = [time.perf_counter()] if _TRACE else None
     c = _Call("compute_TUD", Xmin, Xmax, opts, kwargs)
-    o, lut, broadening = c.o, c.lut, c.broadening
+    o, lut, broadening, cont = c.o, c.lut, c.broadening, c.continuum
     Z, T, P, PL, MF, ID, Z_s, nA = c.Z, c.T, c.P, c.PL, c.MF, c.ID, c.Z_s, c.N_angle
     X_, grid = c.X, c.grid
     if trace:
@@ -376,7 +400,7 @@ def compute_TUD(Xmin, Xmax, opts=options, **kwargs):
         chunks = 4 if grid.n >= 2000000 else 2 if grid.n >= 500000 else 1
     if chunks > 1 and c.theta.size <= engine.TUD_MAX_MU and not o["save"]:
         got = _compute_tud_chunked(tbl, grid, Z, T, P, PL, MF, ID, Z_s, c.theta, nA, c.returnOD, int(chunks), broadening=broadening,
-                                   xs_lut=lut)
+                                   xs_lut=lut, continuum=cont)
         if got is not None:
             tau_h, Lu_h, Ld_h, (nZ, nMu) = got
             if trace:
@@ -389,7 +413,7 @@ def compute_TUD(Xmin, Xmax, opts=options, **kwargs):
     if c.theta.size <= engine.TUD_MAX_MU and not o["save"]:
         # the common case: one call into the library (rtx_compute_tud)
         run = engine.TudRunner(tbl, grid, Z, n_layers=T.size, Altitudes=Z_s, theta_r=c.theta, N_angle=nA, returnOD=c.returnOD,
-                               broadening=broadening, xs_lut=lut)
+                               broadening=broadening, xs_lut=lut, continuum=cont)
         tau, Lu, Ld = run.run(T, P, PL, MF, ID)
         nZ, nMu = run.shape
         OD = run.OD
@@ -398,6 +422,8 @@ def compute_TUD(Xmin, Xmax, opts=options, **kwargs):
             OD = engine.xs_od(lut, grid, T, P / 101325.0, PL, MF, ID)
         else:
             OD = engine.optical_depths(tbl, grid, T, P, PL, MF, ID, broadening=broadening)  # [nL][nX] float32 on the device
+        if cont is not None:
+            engine.continuum_add(cont, grid, T, P, PL, MF, ID, OD)
         res = engine.tud(OD, grid, T, Z, Altitudes=Z_s, theta_r=c.theta, N_angle=nA, returnOD=c.returnOD, per_angle=bool(o["save"]))
         tau, Lu, Ld, (nZ, nMu) = res[:4]
     if trace:
@@ -427,7 +453,7 @@ class _TudPipeline:
     outputs: the copy of one is in flight while the other is being computed), each on a compute stream of its own, a
     side stream for the device-to-host copies, a pinned staging ring."""
 
-    def __init__(self, dev, tbl, grid, Z, nL, Z_s, theta_r, N_angle, returnOD, broadening=None, xs_lut=None):
+    def __init__(self, dev, tbl, grid, Z, nL, Z_s, theta_r, N_angle, returnOD, broadening=None, xs_lut=None, continuum=None):
         self.dev = int(dev)
         with torch.cuda.device(self.dev):
             self.lines = tbl.on_device(self.dev) if xs_lut is None else None
@@ -442,7 +468,8 @@ class _TudPipeline:
             for st, pl in zip(self.computes, self.plans):
                 with torch.cuda.stream(st):
                     self.runs.append(engine.TudRunner(self.lines, grid, Z, n_layers=nL, Altitudes=Z_s, theta_r=theta_r, N_angle=N_angle,
-                                                      returnOD=returnOD, plan=pl, broadening=broadening, xs_lut=xs_lut))
+                                                      returnOD=returnOD, plan=pl, broadening=broadening, xs_lut=xs_lut,
+                                                      continuum=continuum))
         self.busy = [None, None]  # copy-done event of each runner's outputs
         self.staging = _hostio.Staging(depth=2)
         self.k = 0
@@ -512,9 +539,14 @@ def compute_TUD_batch(Xmin, Xmax, atmospheres, opts=options, reduce=None, device
     PCIe into a reusable pinned ring, a host thread pool widens: host-memory bound, ~10 ms per 132 MB result).
     xs_lut (keyword only): as for compute_TUD -- every atmosphere's optical depths come from the cross-section table, the line
     table is not touched, results equal per-call compute_TUD(xs_lut=) bit for bit. NotImplementedError: xs_lut with any
-    broadening=, or with devices= naming more than one device (a table lives on one device)."""
+    broadening=, or with devices= naming more than one device (a table lives on one device).
+    continuum (keyword only): as for compute_TUD, the same Continuum for every atmosphere; results equal per-call
+    compute_TUD(continuum=) bit for bit. NotImplementedError: continuum with devices=."""
     c = _Call("compute_TUD_batch", Xmin, Xmax, opts, kwargs)
-    o, lut = c.o, c.lut
+    o, lut, cont = c.o, c.lut, c.continuum
+    if cont is not None and devices is not None:
+        raise NotImplementedError("compute_TUD_batch: continuum with devices=%r is not supported; run on the current device "
+                                  "(devices=None)" % (devices,))
     if lut is not None and devices is not None and len({int(d) for d in devices}) > 1:
         raise NotImplementedError("compute_TUD_batch: xs_lut with devices=%r is not supported: a cross-section table lives on one "
                                   "device" % (devices,))
@@ -534,7 +566,8 @@ def compute_TUD_batch(Xmin, Xmax, atmospheres, opts=options, reduce=None, device
         raise ValueError("compute_TUD_batch: xs_lut lives on device %d, devices=%r" % (lut.device.index, devices))
     with torch.cuda.device(devs[0]):
         tbl = c.table()
-    pipes = [_TudPipeline(d, tbl, grid, c.Z, c.T.size, c.Z_s, c.theta, c.N_angle, c.returnOD, broadening=c.broadening, xs_lut=lut)
+    pipes = [_TudPipeline(d, tbl, grid, c.Z, c.T.size, c.Z_s, c.theta, c.N_angle, c.returnOD, broadening=c.broadening, xs_lut=lut,
+                          continuum=cont)
              for d in devs]
     nZ, nMu = pipes[0].runs[0].shape
     pending = []  # (pipeline, ticket, X of the result) in input order
@@ -625,6 +658,14 @@ def _no_xs_lut(c):
                                   "use line_table=")
 
 
+def _no_continuum(c):
+    """NotImplementedError in the name of the derivative function of call `c` when it carries a continuum: the self term is
+    quadratic in the mixing ratio, and no derivative kernel knows the continuum's dOD/dT or dOD/dMF yet."""
+    if c.o.get("continuum") is not None:
+        raise NotImplementedError(c.fn + ": continuum is not supported (derivatives through the continuum are not implemented; "
+                                  "its self term is quadratic in the mixing ratio); use continuum=None")
+
+
 def _vector_axis(g, base):
     """An array or tensor laid out as `base` plus an optional trailing vector axis: (g with that axis, its length -- None
     where g came without one), or None when g's shape is neither."""
@@ -672,6 +713,7 @@ def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, redu
     NotImplementedError: xs_lut= (the derivatives are built on the line-sum: dOD/dT holds every line's window fixed)."""
     c = _Call("compute_TUD_jacobian", Xmin, Xmax, opts, kwargs)
     _no_xs_lut(c)
+    _no_continuum(c)
     wrt, lay, _ = _jacobian_args(c.fn, Xmin, Xmax, c.o, wrt, layers, reduce, fd_step_T, dT_method=dT_method)
     X_, grid = c.X, c.grid
     tbl = c.table()
@@ -784,6 +826,7 @@ def compute_TUD_vjp(Xmin, Xmax, cotangents, opts=options, wrt=("T",), layers=Non
         raise NotImplementedError("compute_TUD_vjp: reduce= is not offered: map the cotangent to the native grid with the "
                                   "transpose of the reduction and pass that")
     _no_xs_lut(c)
+    _no_continuum(c)
     wrt, lay, nX = _jacobian_args(c.fn, Xmin, Xmax, c.o, wrt, layers, None, fd_step_T, host_result=False, dT_method=dT_method)
     nZ = c.Z_s.size
     G, n_vec = _vjp_cotangents(cotangents, nX, nZ)
@@ -843,6 +886,7 @@ def compute_TUD_jvp(Xmin, Xmax, tangents, opts=options, layers=None, rows=("tau"
     if "reduce" in c.o:
         raise NotImplementedError("compute_TUD_jvp: reduce= is not offered: the results are spectra, pass them to reduceResolution")
     _no_xs_lut(c)
+    _no_continuum(c)
     if isinstance(tangents, dict) and tangents:
         wrt = tuple(tangents.keys())
         bad = [k for k in wrt if k != "T" and (isinstance(k, bool) or not isinstance(k, (int, np.integer)))]
@@ -904,6 +948,7 @@ def compute_band_radiance_vjp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, co
     if "reduce" in c.o:
         raise NotImplementedError(name + ": reduce= is not offered: the cost is defined on the sensor's bands")
     _no_xs_lut(c)
+    _no_continuum(c)
     if c.returnOD:
         raise NotImplementedError(name + ": returnOD=True is not supported (the sensor stage takes transmittances)")
     if c.Z_s.size != 1:
@@ -990,6 +1035,7 @@ def compute_band_radiance_jvp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, ta
     if "reduce" in c.o:
         raise NotImplementedError(name + ": reduce= is not offered: the tangent is defined on the sensor's bands")
     _no_xs_lut(c)
+    _no_continuum(c)
     if c.returnOD:
         raise NotImplementedError(name + ": returnOD=True is not supported (the sensor stage takes transmittances)")
     if c.Z_s.size != 1:
