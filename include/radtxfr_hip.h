@@ -512,7 +512,7 @@ int rtx_srf_moments_max_temps(void); /* temperatures one call takes */
  * anything is launched. nB == 0 writes zeros.
  * Arithmetic: w is rtx_srf_moments' fp32 weight, to the letter; N_b its chunk sums in its order,
  * rounded to fp32 as it stores them (rtx_srf_norms returns them: equal to rtx_srf_moments' N bit for
- * bit); H is an fp64 sum over e ascending, stored fp32; the hats are the forward's fp32 (1 - f, f);
+ * bit); H is an fp64 sum over e ascending, stored fp32; the hats are the forward's fp32 pair (srfm_hats);
  * S and A_t are fp64 sums over the bands in ascending band index; B and dB/dT are fp32 (planck_f32);
  * each row is formed in fp64 and rounded to fp32 once.
  * Determinism: the three rows at point i are a pure function of (grid, the bands that cover i, tau,
@@ -565,7 +565,7 @@ int rtx_srf_norms(const rtx_grid* grid, int nB, const int32_t* knot_start, const
  * nE < 1, a non-finite dTs_h entry. nB == 0 writes nothing and returns 0.
  * Arithmetic: c' and m' are formed in fp64 from the fp32 inputs, the fp32 B and the fp32 dB/dT
  * (rtx_tud_vjp's), left to right as written, nothing fused. w is rtx_srf_moments' fp32 weight to the
- * letter, the hats its fp32 (1 - f, f); every product with them, (w m') hat, is fp64 and so is every sum,
+ * letter, the hats its fp32 pair (srfm_hats); every product with them, (w m') hat, is fp64 and so is every sum,
  * in a fixed order: the points ascending inside sub-chunks of 64 points cut from the grid's first point (a
  * point of weight 0 is skipped), the sub-chunks ascending; w c' over the 64 lanes of a wave by a
  * shuffle-down tree, the 16 waves of a chunk of rtx_srf_chunk_points() points in wave order, the chunks

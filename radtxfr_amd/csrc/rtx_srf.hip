@@ -289,7 +289,7 @@ __global__ __launch_bounds__(256) void srfm_chunk_kernel(SrfmArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   __shared__ float s_g[SRFM_MAXT][SRF_CH];  // tau (B(Ts_t) - Ld)
   __shared__ float s_c[SRF_CH];             // tau Ld + La
-  __shared__ float s_f[SRF_CH];             // the point's weight on knot j0 + 1 (0 outside the knots)
+  __shared__ float2 s_h[SRF_CH];            // the point's weights on knots j0 and j0 + 1 (srfm_hats; (1, 0) outside the knots)
   __shared__ int s_j0[SRF_CH];              // its lower knot; past the grid's end: INT_MAX
   __shared__ float s_w[SRF_CH];             // one band's weights
   __shared__ double s_kx[SRF_MAX_KNOTS];    // one band's knots under the chunk
@@ -335,15 +335,12 @@ __global__ __launch_bounds__(256) void srfm_chunk_kernel(SrfmArgs a) {
     for (int q = 0; q < 4; ++q) {
       const int p = p0 + q;
       int j0 = 0x7fffffff;
-      float f = 0.f, c = 0.f;
+      float h0 = 1.f, h1 = 0.f, c = 0.f;
       if (p < np) {
         const double x = srf_x(a.s, r0 + p);
         while (cnt < a.nk && a.Xk[cnt] <= x) ++cnt;  // the knots ascend with the rows
         j0 = (int)(cnt > 0 ? cnt - 1 : 0);
-        if (cnt > 0 && cnt < a.nk) {
-          const double x0 = a.Xk[cnt - 1], x1 = a.Xk[cnt];
-          f = (float)((x - x0) / (x1 - x0));
-        }
+        if (cnt > 0 && cnt < a.nk) srfm_hats(x, a.Xk[cnt - 1], a.Xk[cnt], h0, h1);
         c = fmaf(tt[q], ld[q], la[q]);
         const bool under = p >= ua && p < ub;
         const double x100 = x * 100.0;
@@ -353,7 +350,7 @@ __global__ __launch_bounds__(256) void srfm_chunk_kernel(SrfmArgs a) {
       } else {
         for (int t = 0; t < a.nT; ++t) s_g[t][p] = 0.f;
       }
-      s_j0[p] = j0; s_f[p] = f; s_c[p] = c;
+      s_j0[p] = j0; s_h[p] = make_float2(h0, h1); s_c[p] = c;
     }
   }
   __syncthreads();
@@ -428,8 +425,9 @@ __global__ __launch_bounds__(256) void srfm_chunk_kernel(SrfmArgs a) {
       float acc = 0.f;
 #pragma unroll 4
       for (int i = u; i < e; ++i) {  // a counted loop: the LDS reads of the rows ahead do not wait for the chain
-        const float w = s_w[i], f = s_f[i];
-        const float hat = s_j0[i] == jk ? 1.0f - f : f;
+        const float w = s_w[i];
+        const float2 h = s_h[i];
+        const float hat = s_j0[i] == jk ? h.x : h.y;
         const float term = fmaf(w * s_g[t][i], hat, acc);
         acc = w != 0.f ? term : acc;  // a row of weight 0 is skipped, not multiplied
       }

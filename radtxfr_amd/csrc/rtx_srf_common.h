@@ -67,6 +67,15 @@ __device__ long long srfm_count(const double* Xk, long long nk, double x) {
   return lo;
 }
 
+// the weights (np.interp's hats) of a point x on the emissivity knots x0 <= x < x1 either side of it: each rounded to fp32
+// once from the fp64 quotient. 1.0f - f from the rounded f is off by up to 2^-25 ABSOLUTELY, which next to the upper knot
+// (f = 0.9963: a hat of 0.0037) is 130 x 2^-24 of the hat itself, and a band of a few such rows carries that into M.
+__device__ __forceinline__ void srfm_hats(double x, double x0, double x1, float& h0, float& h1) {
+  const double f = (x - x0) / (x1 - x0);
+  h0 = (float)(1.0 - f);
+  h1 = (float)f;
+}
+
 // the weight of row i under the band whose knots [0, m) are staged: srf_rows_kernel's, to the letter
 __device__ __forceinline__ float srf_weight(const SrfArgs& a, const double* s_kx, const float* s_kr, int m, int& seg, long long i) {
   const double x = srf_x(a, i);

@@ -22,7 +22,7 @@
 // Workspace row of a (band slot, vector, temperature): rtx_srf_moments' (element j + 2 s for knot j and sub-chunk s), in fp64.
 //
 // Arithmetic: c' and m' are formed in fp64 from the fp32 inputs, fp32 B and fp32 dB/dT (planck_dT), left to right as
-// written above, no fused operation. w is the forward's fp32 weight and the hats its fp32 (1 - f, f); every product with
+// written above, no fused operation. w is the forward's fp32 weight and the hats its fp32 pair (srfm_hats); every product with
 // them is fp64, (w m') hat, and so is every sum: the points of a sub-chunk ascending (a row of weight 0 is skipped, not
 // multiplied), the sub-chunks ascending; w c' over the 64 lanes of a wave by a shuffle-down tree, the 16 waves in wave
 // order, the chunks ascending; the knots of jrange[b] ascending; then ((C' + sum M' E) + sum M dE) / (double)N, N the
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(SRF_CH) void srfj_chunk_kernel(SrfjArgs a) {
   const int nq = a.nv * a.nT;
   __shared__ double s_m[SRF_CH * SRFJ_NQ];  // m' of point i, vector v, temperature t: element (i nv + v) nT + t
   __shared__ double s_c[SRF_CH * SRFJ_NV];  // c' of point i, vector v: element i nv + v
-  __shared__ float s_f[SRF_CH];             // the point's weight on knot j0 + 1 (0 outside the knots)
+  __shared__ float2 s_h[SRF_CH];            // the point's weights on knots j0 and j0 + 1 (srfm_hats; (1, 0) outside the knots)
   __shared__ int s_j0[SRF_CH];              // its lower knot; past the grid's end: INT_MAX
   __shared__ float s_w[SRF_CH];             // one band's weights
   __shared__ double s_kx[SRF_MAX_KNOTS];    // one band's knots under the chunk
@@ -107,16 +107,13 @@ __global__ __launch_bounds__(SRF_CH) void srfj_chunk_kernel(SrfjArgs a) {
   double x = 0.0;
   {
     int j0 = 0x7fffffff;
-    float f = 0.f;
+    float h0 = 1.f, h1 = 0.f;
     if (p < np) {
       const long long i = r0 + p;
       x = srf_x(a.s, i);
       const long long cnt = srfm_count(a.Xk, a.nk, x);
       j0 = (int)(cnt > 0 ? cnt - 1 : 0);
-      if (cnt > 0 && cnt < a.nk) {
-        const double x0 = a.Xk[cnt - 1], x1 = a.Xk[cnt];
-        f = (float)((x - x0) / (x1 - x0));
-      }
+      if (cnt > 0 && cnt < a.nk) srfm_hats(x, a.Xk[cnt - 1], a.Xk[cnt], h0, h1);
       if (p >= ua && p < ub) {  // elsewhere every band's weight is 0 and c', m' are never read
         const double tt = (double)a.tau[i], ld = (double)a.Ld[i];
         double dt[SRFJ_NV], dd[SRFJ_NV];
@@ -148,7 +145,7 @@ __global__ __launch_bounds__(SRF_CH) void srfj_chunk_kernel(SrfjArgs a) {
         }
       }
     }
-    s_j0[p] = j0; s_f[p] = f;
+    s_j0[p] = j0; s_h[p] = make_float2(h0, h1);
   }
   __syncthreads();
   if (threadIdx.x < SRFJ_NSUB) {  // the knots a sub-chunk touches: lower knot of its first point .. upper knot of its last
@@ -228,8 +225,9 @@ __global__ __launch_bounds__(SRF_CH) void srfj_chunk_kernel(SrfjArgs a) {
       }
       double acc = 0.0;
       for (int i = u; i < e; ++i) {
-        const float wi = s_w[i], f = s_f[i];
-        const float hat = s_j0[i] == jk ? 1.0f - f : f;
+        const float wi = s_w[i];
+        const float2 h = s_h[i];
+        const float hat = s_j0[i] == jk ? h.x : h.y;
         if (wi != 0.f) acc += ((double)wi * s_m[i * nq + q]) * (double)hat;  // a row of weight 0 is skipped
       }
       a.P[((size_t)j * nq + q) * (size_t)a.row + (size_t)jk + 2 * (size_t)(chunk * SRFJ_NSUB + s)] = acc;

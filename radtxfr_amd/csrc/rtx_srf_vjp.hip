@@ -184,17 +184,14 @@ __global__ __launch_bounds__(SRF_CH) void srfv_point_kernel(SrfvArgs a) {
   // the point's knot interval and its weight on the upper knot, as srfm_chunk_kernel forms them
   double x = 0.0;
   long long j0 = 0;
-  float f = 0.f;
+  float f0 = 1.f, f = 0.f;
   if (valid) {
     x = srf_x(a.s, i);
     const long long cnt = srfm_count(a.Xk, a.nk, x);
     j0 = cnt > 0 ? cnt - 1 : 0;
-    if (cnt > 0 && cnt < a.nk) {
-      const double x0 = a.Xk[cnt - 1], x1 = a.Xk[cnt];
-      f = (float)((x - x0) / (x1 - x0));
-    }
+    if (cnt > 0 && cnt < a.nk) srfm_hats(x, a.Xk[cnt - 1], a.Xk[cnt], f0, f);
   }
-  const double h0 = (double)(1.0f - f), h1 = (double)f;
+  const double h0 = (double)f0, h1 = (double)f;
   double S = 0.0, A[SRFV_MAXT];
 #pragma unroll
   for (int t = 0; t < SRFV_MAXT; ++t) A[t] = 0.0;

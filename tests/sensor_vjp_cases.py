@@ -76,12 +76,7 @@ def adjoint(X, tables, tau, La, Ld, Xk, E, Ts, g):
                  dTs=np.sum(Aa * np.abs(tau) * dB.T, axis=1))
     # dE through the forward's own moments M (srf_fused_cases.moments), and M's sum of absolute terms for the scale
     _, _, M, _ = FC.moments(X, tables, tau, La, Ld, Xk, Ts)
-    Ma = np.zeros_like(M)
-    for t in range(nT):
-        a = w * np.abs(tau) * (B[:, t] + np.abs(Ld))            # [nB][nX]
-        for b in np.flatnonzero(live):
-            np.add.at(Ma[t, b], j0, a[b] * (1.0 - f))
-            np.add.at(Ma[t, b], j1, a[b] * f)
+    Ma = FC.moments_scale(X, tables, tau, Ld, Xk, Ts)
     invN = np.where(live, 1.0 / np.where(live, N, 1.0), 0.0)
     out["dE"] = np.einsum("tbe,tbj,b->je", g, np.where(live[None, :, None], M, 0.0), invN)
     scale["dE"] = np.einsum("tbe,tbj,b->je", np.abs(g), Ma, invN)

@@ -58,6 +58,39 @@ def moments(X, tables, tau, La, Ld, Xk, Ts):
     return N, Cb, M, jr
 
 
+def moments_scale(X, tables, tau, Ld, Xk, Ts):
+    """fp64 [nT][nB][nk]: the scale of M, its sum with every term's absolute value, w |tau| (B + |Ld|) hat_j; 0 for a band
+    with N = 0. What an error bound of M (and of dE = sum g M / N, sensor_vjp_cases.adjoint) is measured against."""
+    X, Xk = np.asarray(X, dtype=np.float64), np.asarray(Xk, dtype=np.float64)
+    tau, Ld = (np.asarray(v).astype(np.float64) for v in (tau, Ld))
+    Ts = np.atleast_1d(np.asarray(Ts, dtype=np.float64))
+    j0, j1, f = knot_intervals(X, Xk)
+    B = ref.planckian(X, Ts)  # [nX][nT]
+    delta = cells(X)
+    w = np.zeros((len(tables), X.size))
+    for b, (xk, r) in enumerate(tables):
+        xk, r = np.asarray(xk, dtype=np.float64), np.asarray(r, dtype=np.float32).astype(np.float64)
+        w[b] = np.interp(X, xk, r, left=0.0, right=0.0) * delta
+    live = w.sum(axis=1) > 0.0
+    Ma = np.zeros((Ts.size, len(tables), Xk.size))
+    for t in range(Ts.size):
+        a = w * np.abs(tau) * (B[:, t] + np.abs(Ld))            # [nB][nX]
+        for b in np.flatnonzero(live):
+            np.add.at(Ma[t, b], j0, a[b] * (1.0 - f))
+            np.add.at(Ma[t, b], j1, a[b] * f)
+    return Ma
+
+
+def moments_error(got, want, scale):
+    """max over the elements of |got - want| / (2^-24 scale); where the scale is 0 (a knot no point under the band touches)
+    got must be exactly want, which is 0."""
+    got, want, scale = (np.asarray(v, dtype=np.float64) for v in (got, want, scale))
+    assert got.shape == want.shape == scale.shape and np.all(np.isfinite(got))
+    zero = scale == 0.0
+    assert np.array_equal(got[zero], want[zero]) and not want[zero].any()
+    return float(np.max(np.abs(got - want)[~zero] / (2.0 ** -24 * scale[~zero]))) if (~zero).any() else 0.0
+
+
 def moment_form(N, Cb, M, E):
     """[nT][nB][nE] fp64 = (C + M . E) / N; N = 0 gives NaN."""
     with np.errstate(invalid="ignore", divide="ignore"):
@@ -148,8 +181,8 @@ _CACHE = {}
 
 def case(CH, K, knots):
     """Everything of one knot set, made once and frozen: X, the fp32 inputs the kernels receive, the tables, Xk, E [nk][260]
-    and, from those fp32 inputs in fp64, the moments and the direct form's radiances `want` for TS_LIST ([3][nB][260];
-    TS_SCALAR is its middle entry)."""
+    and, from those fp32 inputs in fp64, the moments, M's scale `Ma` (moments_scale) and the direct form's radiances `want`
+    for TS_LIST ([3][nB][260]; TS_SCALAR is its middle entry)."""
     key = (CH, K, knots)
     if key not in _CACHE:
         X = axis(CH)
@@ -159,8 +192,9 @@ def case(CH, K, knots):
         Xk = knot_set(X, knots)
         E = emissivities(Xk.size)
         N, Cb, M, jr = moments(X, tables, d["tau"], d["La"], d["Ld"], Xk, TS_LIST)
+        Ma = moments_scale(X, tables, d["tau"], d["Ld"], Xk, TS_LIST)
         want = direct_form(X, tables, d["tau"], d["La"], d["Ld"], Xk, E, TS_LIST)
-        c = dict(X=X, d64=d64, tables=tables, dead=dead, Xk=Xk, E=E, N=N, C=Cb, M=M, jrange=jr, want=want, **d)
+        c = dict(X=X, d64=d64, tables=tables, dead=dead, Xk=Xk, E=E, N=N, C=Cb, M=M, Ma=Ma, jrange=jr, want=want, **d)
         for v in list(c.values()) + list(d64.values()):
             if isinstance(v, np.ndarray):
                 v.setflags(write=False)

@@ -127,8 +127,8 @@ def test_against_oracle(env, knots, nE, many, vectors):
     the library's maximum of vectors per call, vector v moving SUBSETS[v % 4] (so every vector has its own k). Three
     temperatures are more than one call takes (rtx_srf_radiance_jvp_max_temps() = 2).
     MEASURED on an MI355X, worst over the 18 cases, in units of 2^-24 scale (test_terms_alone has the terms one by one): all
-    groups 1.18 (k = 32), (d_tau, d_La) 0.95 (k = 13), (d_Ld, d_Ts) 0.44 (k = 20), d_E 10.0 (k = 32; coarse knots, nE = 260;
-    2.1 dense, 4.4 on_grid)."""
+    groups 1.09 (k = 32), (d_tau, d_La) 1.05 (k = 13), (d_Ld, d_Ts) 0.37 (k = 20), d_E 3.15 (k = 32; on_grid knots; 2.25 coarse,
+    2.06 dense; 10.0 on the coarse knots before the forward's M took both knot weights from srfm_hats)."""
     c = case(env, knots)
     nv = 1 if vectors == "one" else env["NV"]
     subsets = [SUBSETS[v % len(SUBSETS)] for v in range(nv)]
