@@ -885,6 +885,31 @@ int rtx_continuum_add(const rtx_grid* grid, int n_layers, const double* T_h, int
                       int64_t ld, void* stream, unsigned flags);
 int rtx_continuum_tile_points(void);
 
+/* ---- derivatives through the tabulated continuum -------------------------------------------
+ * The continuum's part of the columns rtx_tud_jacobian, rtx_tud_vjp and rtx_tud_jvp (and their _dod forms) take. With
+ * s_c = sum_{k < 4} L_k(t) * A[c][l][j0 + k] the stencil sum rtx_continuum_add clamps, m_c = [s_c > 0], and s_T,c / s_x,c
+ * the same stencil and weights on the node rows dA/dT (per K) and dA/dMF (per ppmv of the component's own molecule),
+ *   rtx_continuum_add_d   dOD_dT[l][i]        += R_T * sum_c max(0, s_c) + R * sum_c m_c * s_T,c
+ *                         K[slot_h[c]][l][i]  += R * m_c * s_x,c      for every component with slot_h[c] >= 0
+ * for l < n_layers and the grid's points i < grid->n, in place on fp32 dOD_dT[n_layers][ld] and K[n_spec][n_layers][ld];
+ * R as in rtx_continuum_add, R_T = dR/dT = -nu (c2 nu / (2 T^2)) sech^2(c2 nu / (2 T)). The grid, T_h, the axes and
+ * tables_h are those of rtx_continuum_add (the same stencils, weights and fp32 operations: m_c is set exactly where that
+ * call added something; where s_c <= 0, and outside a component's axis, both derivatives are 0: the kink of max(0, .) is
+ * given the value 0). tables_dT_h and tables_dx_h are HOST arrays laid out as tables_h, finite on every component's nodes.
+ * slot_h[n_comp] names the K slot of each component's molecule, -1 for a molecule that is not differentiated; several
+ * components may share a slot, every slot lies in [-1, n_spec). dOD_dT may be NULL (no temperature term; tables_dT_h is
+ * then not read and may be NULL), K may be NULL when every slot is -1 (tables_dx_h is then not read and may be NULL), not
+ * both. Each destination row is read and written once per group of four components, the group's terms summed first: on
+ * a block of zeros the result is the derivative itself, on any block `block + that` rounded once (for up to four
+ * components). The value added at a point is a function of (tables, layer, global index) alone: bit-identical for every
+ * offset / n cut of an axis. Staging (hipMemcpyAsync on `stream`, staged before returning, into a grow-only device buffer
+ * of this entry's own per (device, stream)) and the 16-byte accesses (ld a multiple of 4, dOD_dT and K 16-byte aligned)
+ * as in rtx_continuum_add. flags: none is defined, pass 0. */
+int rtx_continuum_add_d(const rtx_grid* grid, int n_layers, const double* T_h, int n_comp, const double* v0_h,
+                        const double* dv_h, const int32_t* n_nodes_h, const float* tables_h, const float* tables_dT_h,
+                        const float* tables_dx_h, int64_t ld_nodes, const int32_t* slot_h, int n_spec, float* dOD_dT, float* K,
+                        int64_t ld, void* stream, unsigned flags);
+
 /* ------------------------------------------------------------------------------------------
  * Single-process collectives over the GPUs of one node. The reference has no multi-GPU code; its scripts are plain
  * Python programs that fan work out with multiprocessing (Generate_LWIR_TUD.py:117-150). These three calls let ONE host

@@ -122,6 +122,8 @@ PROTOTYPES = {
     "rtx_xs_tile_points": (_i32, []),
     "rtx_continuum_add": (_i32, [_gp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, C.c_uint]),
     "rtx_continuum_tile_points": (_i32, []),
+    "rtx_continuum_add_d": (_i32, [_gp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _vp,
+                                   C.c_uint]),
     "rtx_comm_init_all": (_i32, [_i32, _vp, _i32, C.POINTER(_vp)]),
     "rtx_comm_backend": (_i32, [_vp]),
     "rtx_allgather": (_i32, [_vp, _vp, _vp, _i64, _vp]),

@@ -25,6 +25,15 @@ a misconfigured call.
 
 Continuum.layer_tables makes the float32 rows A the device kernel reads (rtx_continuum_add, engine.continuum_add);
 Continuum.od_host evaluates the definition in NumPy from the float64 A and is what the tests hold the device to.
+
+Derivatives. With S the stencil sum above, g = (p / p_ref) (T_ref / T) and N = n(p, T) PL 1e5:
+    dA_l[j]/dT  = -2 A_l[j] / T + W_l g x Cs(nu_j; T) ln(Cs_b[j] / Cs_a[j]) / (T_b - T_a)     (second term 0 without Cs_b)
+    dA_l[j]/dMF = 1e-6 N g (2 x Cs(nu_j; T) + (1 - 2 x) Cf[j])                                 per ppmv, finite at MF = 0
+    dOD/dT = m (R_T S + R S_T),   dOD/dMF = m R S_x,   m = [S > 0],   R_T = -nu (c2 nu / (2 T^2)) sech^2(c2 nu / (2 T))
+with S_T and S_x the same stencil and weights on dA/dT and dA/dMF. Where S <= 0, and outside the axis, both are exactly 0:
+the kink of max(0, .) at S = 0 is given the value 0. A component differentiates only with respect to its own molecule's
+mixing ratio. Continuum.layer_tables_d makes the three float32 tables rtx_continuum_add_d reads (engine.continuum_add_d);
+Continuum.dod_host is the definition in NumPy float64 and the oracle of the derivative tests.
 """
 import numpy as np
 
@@ -129,6 +138,70 @@ class Component:
             out[l] = np.where(inside, np.maximum(0.0, R * S), 0.0)
         return out
 
+    def self_coefficients_dT(self, T):
+        """d Cs(nu_j; T) / dT float64 [n]: Cs(T) ln(Cs_b / Cs_a) / (T_b - T_a); 0 without Cs_b and where both are 0."""
+        if self.Cs_a is None or self.Cs_b is None:
+            return np.zeros(self.n)
+        pos = self.Cs_a > 0.0
+        ratio = np.where(pos, self.Cs_b, 1.0) / np.where(pos, self.Cs_a, 1.0)
+        return self.self_coefficients(T) * (np.log(ratio) / (self.T_b - self.T_a))
+
+    def layer_rows_d(self, T, P_pa, PL_km, MF_VAL, MF_ID):
+        """(A, A_T, A_x) float64 [nL][n]: layer_rows' A (the same operations: the same bits), dA/dT per K and dA/dMF per ppmv
+        of the component's own molecule. With g = (p / p_ref) (T_ref / T) and N = n(p, T) PL 1e5 (so W = N x, n ~ 1/T):
+            A_T = -2 A / T + W g x dCs/dT,        A_x = 1e-6 N g (2 x Cs(T) + (1 - 2 x) Cf),
+        the second formed without a division by x: MF = 0 gives its finite value N g Cf 1e-6."""
+        T = np.atleast_1d(np.asarray(T, dtype=np.float64))
+        ids = [int(v) for v in np.asarray(MF_ID).ravel()]
+        if self.molecule not in ids:
+            raise ValueError("continuum: component molecule %d is not in MF_ID %r" % (self.molecule, ids))
+        MF = np.asarray(MF_VAL, dtype=np.float64).reshape(T.size, -1)
+        P_pa, PL_km = np.atleast_1d(P_pa), np.atleast_1d(PL_km)
+        W, p_atm = engine.layer_weights_od([(self.molecule, 1)], T, P_pa, PL_km, MF, ids)
+        N = engine.volumeConcentration(p_atm, T) * np.asarray(PL_km, dtype=np.float64) * 1e5
+        x = MF[:, ids.index(self.molecule)] * 1e-6
+        Cf = self.Cf if self.Cf is not None else np.zeros(self.n)
+        A, A_T, A_x = (np.empty((T.size, self.n)) for _ in range(3))
+        for l in range(T.size):
+            g = (p_atm[l] / self.p_ref_atm) * (self.T_ref / T[l])
+            Cs = self.self_coefficients(T[l])
+            A[l] = W[0, l] * (p_atm[l] / self.p_ref_atm) * (self.T_ref / T[l]) * (x[l] * Cs + (1.0 - x[l]) * Cf)
+            A_T[l] = -2.0 / T[l] * A[l] + W[0, l] * g * (x[l] * self.self_coefficients_dT(T[l]))
+            A_x[l] = 1e-6 * N[l] * g * (2.0 * x[l] * Cs + (1.0 - 2.0 * x[l]) * Cf)
+        return A, A_T, A_x
+
+    def stencil(self, X):
+        """(inside [nX] bool, j0 [nX], (L_0 .. L_3) each [nX]) of the definition at the wavenumbers X, float64."""
+        X = np.asarray(X, dtype=np.float64).ravel()
+        inside = (X >= self.v0) & (X <= self.vend)
+        j0 = np.clip(np.floor((X - self.v0) / self.dv).astype(np.int64) - 1, 0, self.n - 4)
+        j0[~inside] = 0
+        t = (X - (self.v0 + j0 * self.dv)) / self.dv
+        Lk = (-(t - 1.0) * (t - 2.0) * (t - 3.0) / 6.0, t * (t - 2.0) * (t - 3.0) / 2.0, -t * (t - 1.0) * (t - 3.0) / 2.0,
+              t * (t - 1.0) * (t - 2.0) / 6.0)
+        return inside, j0, Lk
+
+    def dod_rows(self, X, T, A, A_T, A_x):
+        """(dOD/dT, dOD/dMF) float64 [nL][nX] of the component from its float64 rows (layer_rows_d): with S the stencil sum
+        of od_rows, S_T and S_x the same stencil and weights on A_T and A_x, R_T = dR/dT = -nu (c2 nu / (2 T^2)) sech^2(c2 nu /
+        (2 T)) and m = [S > 0] inside the axis (decided as od_rows decides it, on R S),
+            dOD/dT = m (R_T S + R S_T),        dOD/dMF = m R S_x.
+        Where S <= 0 (max(0, .) cut the cubic's undershoot) and outside the axis both are exactly 0: the kink at S = 0 is
+        given the value 0."""
+        X = np.asarray(X, dtype=np.float64).ravel()
+        T = np.atleast_1d(np.asarray(T, dtype=np.float64))
+        inside, j0, Lk = self.stencil(X)
+        dT, dx = np.zeros((T.size, X.size)), np.zeros((T.size, X.size))
+        for l in range(T.size):
+            S, S_T, S_x = (sum(Lk[k] * a[l, j0 + k] for k in range(4)) for a in (A, A_T, A_x))
+            h = C2_CM_K * X / (2.0 * T[l])
+            R = X * np.tanh(h)
+            R_T = -X * (h / T[l]) / np.cosh(h) ** 2
+            m = inside & (R * S > 0.0)
+            dT[l] = np.where(m, R_T * S + R * S_T, 0.0)
+            dx[l] = np.where(m, R * S_x, 0.0)
+        return dT, dx
+
 
 class Continuum:
     """A list of Components, evaluated in list order. Continuum.from_arrays(...) makes one component; `a + b` joins lists."""
@@ -203,6 +276,42 @@ class Continuum:
         for c, A in zip(self.components, self.layer_rows(T, P_pa, PL_km, MF_VAL, MF_ID)):
             out += c.od_rows(X, T, A)
         return out
+
+    def layer_rows_d(self, T, P_pa, PL_km, MF_VAL, MF_ID):
+        """The float64 (A, A_T, A_x) of every component: a list of triples of [nL][n_c] (Component.layer_rows_d)."""
+        return [c.layer_rows_d(T, P_pa, PL_km, MF_VAL, MF_ID) for c in self.components]
+
+    def layer_tables_d(self, T, P_pa, PL_km, MF_VAL, MF_ID):
+        """(A, A_T, A_x, [(v0, dv, n)]): three float32 [nC][nL][n_max] arrays laid out as layer_tables lays out its one, each
+        formed in float64 and rounded once; A is layer_tables' A bit for bit. What rtx_continuum_add_d reads
+        (engine.continuum_add_d)."""
+        rows = self.layer_rows_d(T, P_pa, PL_km, MF_VAL, MF_ID)
+        shape = (len(rows), rows[0][0].shape[0], max(r[0].shape[1] for r in rows))
+        tabs = tuple(np.zeros(shape, dtype=np.float32) for _ in range(3))
+        for i, r in enumerate(rows):
+            for tab, a in zip(tabs, r):
+                tab[i, :, :a.shape[1]] = a
+        return tabs + (self.axes(),)
+
+    def dod_host(self, X, T, P_pa, PL_km, MF_VAL, MF_ID):
+        """The derivatives of od_host in NumPy, float64: (dOD_dT [nL][nX] per K, {molecule: dOD_dMF [nL][nX] per ppmv}), of
+        each layer's optical depth with respect to that layer's temperature and to its mixing ratio of each molecule that
+        has a component (a component differentiates only with respect to its own molecule; several components of one
+        molecule are summed into that molecule's entry). Components are summed in list order. Piecewise: where a
+        component's stencil sum is <= 0, and outside its axis, its derivatives are exactly 0 (Component.dod_rows: the kink
+        of max(0, .) is given the value 0)."""
+        X = np.asarray(X, dtype=np.float64).ravel()
+        T = np.atleast_1d(np.asarray(T, dtype=np.float64))
+        dT = np.zeros((T.size, X.size))
+        dMF = {}
+        for c, (A, A_T, A_x) in zip(self.components, self.layer_rows_d(T, P_pa, PL_km, MF_VAL, MF_ID)):
+            d_T, d_x = c.dod_rows(X, T, A, A_T, A_x)
+            dT += d_T
+            if c.molecule in dMF:
+                dMF[c.molecule] += d_x
+            else:
+                dMF[c.molecule] = d_x
+        return dT, dMF
 
 
 def synthetic(molecule=1, v0=0.0, dv=10.0, n=701, foreign=True):

@@ -4,36 +4,11 @@
 //   od[l][i] += R(nu_i, T_l) * sum_c max(0, sum_{k<4} L_k(t) * A[c][l][j0 + k]),   R = nu tanh(c2 nu / (2 T))
 // with the four-node Lagrange cubic of the definition. One kernel, bandwidth-bound: it reads and writes the block once per
 // CT_GROUP components; no LDS.
-#include "rtx_common.h"
-
-#define CT_BLOCK 256
-#define CT_PER 4                       // points per thread: one 16-byte access
-#define CT_TILE (CT_BLOCK * CT_PER)    // consecutive points owned by a workgroup
-#define CT_GROUP 4                     // components whose per-point stencils are held in registers at once
-#define CT_C2 1.43877736830            // radiative_transfer.py:72 in cm K
-
-struct __attribute__((aligned(8))) ContComp {
-  double v0, dv, vend;  // vend = v0 + (n - 1) * dv, unfused: the last point that is inside
-  int n, pad;
-};
+#include "rtx_continuum_common.h"
 
 // Scratch of rtx_continuum_add per (device, stream): [ContComp x n_comp][float c2/T x n_layers][tables]. Made with `new`,
 // never destroyed (rtx_devmem.h).
 static StreamScratch* const g_cont_scratch = new StreamScratch();
-
-// nu tanh(c2 nu / (2T)) from x = c2 nu / T: tanh(x/2) = (1 - e) / (1 + e), e = exp(-x), one exponential; below x = 1/8 the
-// difference 1 - e loses bits to cancellation and the odd series in h = x/2 (next term 62 h^9 / 2835 < 1e-12 h) takes over.
-__device__ __forceinline__ float radiation_term(float nu, float x) {
-  float th;
-  if (x < 0.125f) {
-    const float h = 0.5f * x, h2 = h * h;
-    th = h * fmaf(h2, fmaf(h2, fmaf(h2, -17.0f / 315.0f, 2.0f / 15.0f), -1.0f / 3.0f), 1.0f);
-  } else {
-    const float e = __builtin_amdgcn_exp2f(-x * (float)LOG2E);
-    th = (1.0f - e) * __builtin_amdgcn_rcpf(1.0f + e);
-  }
-  return nu * th;
-}
 
 // A workgroup owns CT_TILE consecutive points and walks all layers. Per point and component the stencil start j0 and the
 // four Lagrange weights are made once, from the fp64 wavenumber of the GLOBAL point index (nu - nu_j0 is formed in fp64,
@@ -73,19 +48,7 @@ __global__ __launch_bounds__(CT_BLOCK) void continuum_add_kernel(GridDev g, int 
         const ContComp cc = comps[c0 + c];
         bool same = true;
 #pragma unroll
-        for (int j = 0; j < CT_PER; ++j) {
-          const bool in = nu[j] >= cc.v0 && nu[j] <= cc.vend;
-          int jj = (int)floor((nu[j] - cc.v0) / cc.dv) - 1;
-          jj = !in ? 0 : jj < 0 ? 0 : jj > cc.n - 4 ? cc.n - 4 : jj;
-          const double nj = __dadd_rn(cc.v0, __dmul_rn((double)jj, cc.dv));
-          const float t = (float)((nu[j] - nj) / cc.dv);
-          const float t1 = t - 1.0f, t2 = t - 2.0f, t3 = t - 3.0f;
-          L[c][j][0] = in ? -(1.0f / 6.0f) * (t1 * t2 * t3) : 0.0f;
-          L[c][j][1] = in ? 0.5f * (t * t2 * t3) : 0.0f;
-          L[c][j][2] = in ? -0.5f * (t * t1 * t3) : 0.0f;
-          L[c][j][3] = in ? (1.0f / 6.0f) * (t * t1 * t2) : 0.0f;
-          j0[c][j] = jj;
-        }
+        for (int j = 0; j < CT_PER; ++j) j0[c][j] = cont_stencil(cc, nu[j], L[c][j]);
         jf[c] = __builtin_amdgcn_readfirstlane(j0[c][0]);
 #pragma unroll
         for (int j = 0; j < CT_PER; ++j) same = same && j0[c][j] == jf[c];
@@ -108,14 +71,14 @@ __global__ __launch_bounds__(CT_BLOCK) void continuum_add_kernel(GridDev g, int 
             const float a0 = row[jf[c]], a1 = row[jf[c] + 1], a2 = row[jf[c] + 2], a3 = row[jf[c] + 3];
 #pragma unroll
             for (int j = 0; j < CT_PER; ++j) {
-              const float s = fmaf(L[c][j][3], a3, fmaf(L[c][j][2], a2, fmaf(L[c][j][1], a1, L[c][j][0] * a0)));
+              const float s = cont_stencil_sum(L[c][j], a0, a1, a2, a3);
               acc[j] += fmaxf(s, 0.0f);
             }
           } else {
 #pragma unroll
             for (int j = 0; j < CT_PER; ++j) {
               const float* __restrict__ a = row + j0[c][j];
-              const float s = fmaf(L[c][j][3], a[3], fmaf(L[c][j][2], a[2], fmaf(L[c][j][1], a[1], L[c][j][0] * a[0])));
+              const float s = cont_stencil_sum(L[c][j], a[0], a[1], a[2], a[3]);
               acc[j] += fmaxf(s, 0.0f);
             }
           }

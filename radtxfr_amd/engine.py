@@ -742,6 +742,53 @@ def continuum_add(cont, grid, T, P_pa, PL_km, MF_VAL, MF_ID, OD):
     return OD
 
 
+def continuum_add_d(cont, grid, T, P_pa, PL_km, MF_VAL, MF_ID, dOD_dT=None, K=None, species=()):
+    """The derivatives of the tabulated continuum `cont` added in place to float32 device columns
+    (rtx_continuum_add_d): dOD_dT[nL][>= grid.n] += d(continuum OD)/dT per K, and K[s][nL][>= grid.n] += d(continuum
+    OD)/dMF per ppmv of molecule species[s], for the layers continuum_add takes. species: the molecule ids of K's slots; a
+    component whose molecule is not among them adds nothing to K, several components of one molecule add to its slot.
+    Either output may be None, not both; with both, they share one row stride. The node rows are made on the host in
+    float64 (Continuum.layer_tables_d; ValueError for a component whose molecule MF_ID lacks). Where a component's stencil
+    sum is <= 0 its derivatives are 0 (the kink of max(0, .) is given the value 0). A shard of `grid` gives the bits the
+    whole axis gives. Returns (dOD_dT, K)."""
+    T = np.ascontiguousarray(np.atleast_1d(T), dtype=np.float64)
+    species = [int(m) for m in species]
+    if dOD_dT is None and K is None:
+        raise ValueError("continuum_add_d: dOD_dT and K are both None")
+    if K is not None and (len(set(species)) != len(species) or len(species) != K.shape[0]):
+        raise ValueError("continuum_add_d: species %r must name K's %d slots, each once" % (species, K.shape[0]))
+    A, A_T, A_x, axes = cont.layer_tables_d(T, P_pa, PL_km, MF_VAL, MF_ID)
+    nL, n = T.size, grid.n
+    lds = []  # the row strides the blocks fix; a single row fixes none
+    if dOD_dT is not None:
+        assert dOD_dT.dtype == torch.float32 and dOD_dT.is_cuda and dOD_dT.dim() == 2 and dOD_dT.shape[0] == nL
+        assert dOD_dT.shape[1] >= n and dOD_dT.stride(1) == 1
+        if nL > 1:
+            lds.append(dOD_dT.stride(0))
+    if K is not None:
+        assert K.dtype == torch.float32 and K.is_cuda and K.dim() == 3 and K.shape[1] == nL and K.shape[2] >= n
+        assert K.stride(2) == 1
+        if nL > 1:
+            assert K.shape[0] == 1 or K.stride(0) == nL * K.stride(1)
+            lds.append(K.stride(1))
+        elif K.shape[0] > 1:
+            lds.append(K.stride(0))
+    if len(set(lds)) > 1:
+        raise ValueError("continuum_add_d: dOD_dT and K must share one row stride, got %r" % (lds,))
+    lds = lds or [n]
+    slots = np.array([species.index(c.molecule) if K is not None and c.molecule in species else -1 for c in cont.components],
+                     dtype=np.int32)
+    v0 = np.array([a[0] for a in axes], dtype=np.float64)
+    dv = np.array([a[1] for a in axes], dtype=np.float64)
+    nn = np.array([a[2] for a in axes], dtype=np.int32)
+    vp = C.c_void_p
+    _lib.check(_lib.load().rtx_continuum_add_d(grid.byref(), nL, T.ctypes.data_as(vp), len(axes), v0.ctypes.data_as(vp),
+                                               dv.ctypes.data_as(vp), nn.ctypes.data_as(vp), A.ctypes.data_as(vp),
+                                               A_T.ctypes.data_as(vp), A_x.ctypes.data_as(vp), A.shape[2], slots.ctypes.data_as(vp),
+                                               len(species) if K is not None else 0, _ptr(dOD_dT), _ptr(K), lds[0], _stream_ptr(), 0))
+    return dOD_dT, K
+
+
 class TudGeometry(NamedTuple):
     """What tud_geometry returns."""
     Z_s: np.ndarray   # sensor altitudes [nAlt]
@@ -1489,11 +1536,15 @@ class JacobianStages(NamedTuple):
 
 
 def _jacobian_stages(what, lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt, layers,
-                     fd_step_T, mark, dT_method="fd"):
+                     fd_step_T, mark, dT_method="fd", continuum=None):
     """The stages tud_jacobian and tud_vjp share: argument checks, the base state (exactly what compute_TUD runs), the
     line-sums at T -+ fd_step_T with every line's window at T (skipped without "T" in wrt; dT_method "analytic": one
     voigt_sum_dT instead, fd_step_T ignored) and the line-sum of each species of wrt at 1 ppmv (what the reference's
-    caller gets from perturbed atmospheres, Generate_LWIR_TUD.py:55-71). Returns a JacobianStages."""
+    caller gets from perturbed atmospheres, Generate_LWIR_TUD.py:55-71). Returns a JacobianStages.
+    continuum: a continuum.Continuum in the base state (what compute_TUD(continuum=) runs) and in
+    every column: "fd" adds the continuum at T -+ fd_step_T to the two line-sums (continuum_add: the full definition at
+    that temperature), "analytic" its dOD/dT to the line-sum's, and each species column gets its dOD/dMF at the state
+    (the self term is quadratic in the mixing ratio) -- the last two in one continuum_add_d. None: nothing changes."""
     check_dT_method(dT_method)
     T = np.ascontiguousarray(np.atleast_1d(np.asarray(T, dtype=np.float64)))
     Z = np.atleast_1d(np.asarray(Z, dtype=np.float64))
@@ -1517,7 +1568,8 @@ def _jacobian_stages(what, lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitu
     jacobian_limits(nL, np.array([Altitudes]).size, N_angle, len(spec_cols))
     dev = device()
     # base state: exactly what compute_TUD runs
-    run = TudRunner(lines, grid, Z, n_layers=nL, Altitudes=Altitudes, theta_r=theta_r, N_angle=N_angle, returnOD=returnOD)
+    run = TudRunner(lines, grid, Z, n_layers=nL, Altitudes=Altitudes, theta_r=theta_r, N_angle=N_angle, returnOD=returnOD,
+                    continuum=continuum)
     tau, Lu, Ld = run.run(T, P_pa, PL_km, MF_VAL, MF_ID)
     OD = run.OD
     if mark:
@@ -1535,6 +1587,8 @@ def _jacobian_stages(what, lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitu
             Ts = T + sgn * float(fd_step_T)
             w, p_atm = layer_weights_od(lines.species, Ts, P_pa, PL_km, MF_VAL, MF_ID)
             voigt_sum_window(lines, grid, Ts, T, p_atm, w, out)
+            if continuum is not None:
+                continuum_add(continuum, grid, Ts, P_pa, PL_km, MF_VAL, MF_ID, out)
     if mark:
         mark("T")
     K = None
@@ -1545,6 +1599,9 @@ def _jacobian_stages(what, lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitu
             unit[:, c] = 1.0
             w, p_atm = layer_weights_od(lines.species, T, P_pa, PL_km, unit, MF_ID)
             voigt_sum(lines, grid, T, p_atm, w, out_f32=K[s])
+    if continuum is not None and (dOD is not None or K is not None):
+        continuum_add_d(continuum, grid, T, P_pa, PL_km, MF_VAL, MF_ID, dOD_dT=dOD, K=K,
+                        species=[w_ for w_ in wrt if not isinstance(w_, str)])
     if mark:
         mark("species")
     # the wrt axis of the result follows `wrt`: T at t_pos and the species (K's order = their order in wrt) around it
@@ -1553,7 +1610,8 @@ def _jacobian_stages(what, lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitu
 
 
 def tud_jacobian(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=False,
-                 wrt=("T",), layers=None, fd_step_T=0.5, block_bytes=JAC_BLOCK_BYTES, on_block=None, mark=None, dT_method="fd"):
+                 wrt=("T",), layers=None, fd_step_T=0.5, block_bytes=JAC_BLOCK_BYTES, on_block=None, mark=None, dT_method="fd",
+                 continuum=None):
     """compute_TUD's outputs and their Jacobian with respect to layer temperatures and mixing ratios, on the device.
 
     wrt: "T" and/or molecule ids of MF_ID (T, when present, is computed first whatever its position: J's wrt axis follows
@@ -1566,9 +1624,12 @@ def tud_jacobian(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes=(500,)
     dOD/dT is the central difference of two line-sums at T -+ fd_step_T with every line's window at T (voigt_sum_window),
     or with dT_method="analytic" the closed-form derivative of the line-sum with the same fixed windows (voigt_sum_dT: one
     sum instead of two, fd_step_T ignored); any other dT_method raises ValueError before device work.
-    dOD/dMF of a species is the line-sum of that species alone at 1 ppmv (OD is linear in each mixing ratio)."""
+    dOD/dMF of a species is the line-sum of that species alone at 1 ppmv (OD is linear in each mixing ratio).
+    continuum: a continuum.Continuum carried through the base state and every derivative (_jacobian_stages; DESIGN.md
+    section 4.23). OD is then no longer linear in a mixing ratio: a species entry of J is the local derivative at the
+    state, per ppmv; where a component's stencil sum is <= 0 its derivatives are 0 (the kink of max(0, .) is given 0)."""
     s = _jacobian_stages("tud_jacobian", lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt,
-                         layers, fd_step_T, mark, dT_method)
+                         layers, fd_step_T, mark, dT_method, continuum)
     J = tud_jacobian_from_od(s.OD, s.OD_plus, s.OD_minus, fd_step_T, s.K, s.tau, grid, s.T, s.Z, Altitudes=Altitudes,
                              theta_r=theta_r, N_angle=N_angle, returnOD=returnOD, layers=s.layers, t_pos=s.t_pos,
                              block_bytes=block_bytes, on_block=on_block, mark=mark, dOD_dT=s.dOD_dT)
@@ -1725,7 +1786,8 @@ def tud_vjp_from_od(OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z, G_tau=
 
 
 def tud_vjp(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, G_tau=None, G_Lu=None, G_Ld=None, Altitudes=(500,), theta_r=0.0,
-            N_angle=30, returnOD=False, wrt=("T",), layers=None, fd_step_T=0.5, mark=None, cotangents=None, dT_method="fd"):
+            N_angle=30, returnOD=False, wrt=("T",), layers=None, fd_step_T=0.5, mark=None, cotangents=None, dT_method="fd",
+            continuum=None):
     """compute_TUD's outputs and the gradient of a scalar cost with respect to layer temperatures and mixing ratios, given
     the cost's cotangents on the outputs: tud_jacobian's stages (the same base state, T -+ fd_step_T line-sums and species
     line-sums) followed by rtx_tud_vjp instead of rtx_tud_jacobian. wrt, layers, fd_step_T, dT_method as tud_jacobian; G_* as
@@ -1733,12 +1795,12 @@ def tud_vjp(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, G_tau=None, G_Lu=None
     following `wrt`. mark(name): after each stage ("base", "T", "species", "vjp").
     cotangents: instead of G_tau / G_Lu / G_Ld, a function (tau, Lu, Ld) -> (G_tau, G_Lu, G_Ld) called once the base state
     exists, for a cost whose cotangents depend on the outputs themselves (rt.compute_band_radiance_vjp: the sensor stage's
-    adjoint reads tau, Lu and Ld). The optical depths are computed once either way."""
+    adjoint reads tau, Lu and Ld). The optical depths are computed once either way. continuum: as tud_jacobian."""
     if cotangents is not None and (G_tau is not None or G_Lu is not None or G_Ld is not None):
         raise ValueError("tud_vjp: cotangents= and G_tau / G_Lu / G_Ld exclude each other")
     check_dT_method(dT_method)
     s = _jacobian_stages("tud_vjp", lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt,
-                         layers, fd_step_T, mark, dT_method)
+                         layers, fd_step_T, mark, dT_method, continuum)
     if cotangents is not None:
         G_tau, G_Lu, G_Ld = cotangents(s.tau, s.Lu, s.Ld)
     grad = tud_vjp_from_od(s.OD, s.OD_plus, s.OD_minus, fd_step_T, s.K, s.tau, grid, s.T, s.Z, G_tau=G_tau, G_Lu=G_Lu, G_Ld=G_Ld,
@@ -1805,15 +1867,15 @@ def tud_jvp_from_od(OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z, V, Alt
 
 
 def tud_jvp(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, V, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=False,
-            wrt=("T",), layers=None, fd_step_T=0.5, mark=None, rows=JVP_ROWS, dT_method="fd"):
+            wrt=("T",), layers=None, fd_step_T=0.5, mark=None, rows=JVP_ROWS, dT_method="fd", continuum=None):
     """compute_TUD's outputs and their change along tangent directions in (layer temperatures, mixing ratios):
     tud_jacobian's stages (the same base state, T -+ fd_step_T line-sums and species line-sums) followed by rtx_tud_jvp
     instead of rtx_tud_jacobian. wrt, layers, fd_step_T, dT_method as tud_jacobian; V [n_vec][n_wrt][len(layers)] and rows as
     tud_jvp_from_od, V's wrt axis following `wrt`. Returns (tau, Lu, Ld, OD, d) with d as tud_jvp_from_od returns it.
-    mark(name): after each stage ("base", "T", "species", "jvp")."""
+    mark(name): after each stage ("base", "T", "species", "jvp"). continuum: as tud_jacobian."""
     check_dT_method(dT_method)
     s = _jacobian_stages("tud_jvp", lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt,
-                         layers, fd_step_T, mark, dT_method)
+                         layers, fd_step_T, mark, dT_method, continuum)
     d = tud_jvp_from_od(s.OD, s.OD_plus, s.OD_minus, fd_step_T, s.K, s.tau, grid, s.T, s.Z, V, Altitudes=Altitudes,
                         theta_r=theta_r, N_angle=N_angle, returnOD=returnOD, layers=s.layers, t_pos=s.t_pos, rows=rows,
                         dOD_dT=s.dOD_dT)

@@ -658,12 +658,18 @@ def _no_xs_lut(c):
                                   "use line_table=")
 
 
-def _no_continuum(c):
-    """NotImplementedError in the name of the derivative function of call `c` when it carries a continuum: the self term is
-    quadratic in the mixing ratio, and no derivative kernel knows the continuum's dOD/dT or dOD/dMF yet."""
-    if c.o.get("continuum") is not None:
-        raise NotImplementedError(c.fn + ": continuum is not supported (derivatives through the continuum are not implemented; "
-                                  "its self term is quadratic in the mixing ratio); use continuum=None")
+def _derivative_continuum(c, continuum_derivatives):
+    """The continuum a derivative function differentiates call `c` through: None without continuum=; the call's Continuum
+    with continuum_derivatives=True (checked as _continuum_option checks it: ValueError for a component whose molecule
+    MFs_ID lacks, before any device work); NotImplementedError in the function's name with the default False, which keeps
+    a forward model with a continuum from being paired with a Jacobian that silently lacks it."""
+    if c.o.get("continuum") is None:
+        return None
+    if not continuum_derivatives:
+        raise NotImplementedError(c.fn + ": continuum is not supported by default (its self term is quadratic in the mixing "
+                                  "ratio: a species derivative is then local to the state); pass continuum_derivatives=True "
+                                  "to differentiate through it, or continuum=None")
+    return c.continuum
 
 
 def _vector_axis(g, base):
@@ -684,7 +690,8 @@ def _grad_dict(grad_h, wrt, n_vec):
             for w_i, w in enumerate(wrt)}
 
 
-def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, reduce=None, fd_step_T=0.5, dT_method="fd", **kwargs):
+def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, reduce=None, fd_step_T=0.5, dT_method="fd",
+                         continuum_derivatives=False, **kwargs):
     """compute_TUD and the derivatives of its outputs with respect to layer temperatures and mixing ratios in one call:
     what the reference's caller builds from 1 + 3 x 66 perturbed atmospheres (Generate_LWIR_TUD.py:55-71, JacIn, one
     layer and one quantity at a time, relStep 0.001) -- here closed-form chain rule through the TUD recurrences.
@@ -700,7 +707,8 @@ def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, redu
     sum(OD) mu under returnOD), L-up per sensor altitude and Ld, with every quirk of the reference's TUD body (the
     Z <= zs mask for tau, the first count(mask) layers for L-up, the last altitude's count for Ld, weight 0 at theta = 0).
     With N_angle = 1 that Ld is 0/0 (NaN), and so is every dLd.
-    OD_l is linear in MF_s,l: dOD_l/dMF_s,l is the line-sum of species s alone at 1 ppmv (exact; MF = 0 is fine).
+    OD_l is linear in MF_s,l (without a continuum): dOD_l/dMF_s,l is the line-sum of species s alone at 1 ppmv (exact; MF = 0
+    is fine).
     dOD_l/dT_l is the central difference of line-sums at T -+ fd_step_T [K] with every line's window held at the base T:
     the derivative of the truncated line-sum with each line's support fixed (the reference's cut-off OmegaWingHW x width
     moves with T; a finite difference of it carries those steps). Everything else is analytic.
@@ -710,10 +718,19 @@ def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, redu
     reduce = dict(dX=..., N=4, window="hanning"): reduceResolution of the base outputs and of every J row on the device
     (engine.reduce_resolution_cached). Without it, full-resolution results above 4 GiB are refused (ValueError): pass
     reduce= or fewer layers=. Arguments are checked before any device work.
-    NotImplementedError: xs_lut= (the derivatives are built on the line-sum: dOD/dT holds every line's window fixed)."""
+    NotImplementedError: xs_lut= (the derivatives are built on the line-sum: dOD/dT holds every line's window fixed).
+    continuum= (as compute_TUD takes it) is refused (NotImplementedError) unless continuum_derivatives=True; then the
+    call is differentiated through the continuum: the base outputs are compute_TUD(continuum=)'s bit for
+    bit, "fd" takes the continuum at T -+ fd_step_T with the line-sums, "analytic" its closed-form dOD/dT. With a
+    continuum OD is no longer linear in a mixing ratio (the self term is quadratic in it): J's species entries are the
+    local derivative at the state, per ppmv, and a component differentiates only with respect to its own molecule. The
+    continuum is piecewise, OD_c = max(0, R S_c): where a component's interpolated sum S_c is <= 0 its derivatives are
+    exactly 0 -- the kink at S_c = 0 is given the value 0 (continuum.Continuum.dod_host is the definition).
+    continuum_derivatives=True without a continuum is the plain call, bit for bit. ValueError, before any device work,
+    for a component whose molecule MFs_ID lacks."""
     c = _Call("compute_TUD_jacobian", Xmin, Xmax, opts, kwargs)
     _no_xs_lut(c)
-    _no_continuum(c)
+    cont = _derivative_continuum(c, continuum_derivatives)
     wrt, lay, _ = _jacobian_args(c.fn, Xmin, Xmax, c.o, wrt, layers, reduce, fd_step_T, dT_method=dT_method)
     X_, grid = c.X, c.grid
     tbl = c.table()
@@ -741,7 +758,8 @@ def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, redu
 
     tau, Lu, Ld, _, _ = engine.tud_jacobian(tbl, grid, c.Z, c.T, c.P, c.PL, c.MF, c.ID, Altitudes=c.Z_s, theta_r=c.theta,
                                              N_angle=c.N_angle, returnOD=c.returnOD, wrt=wrt, layers=lay,
-                                             fd_step_T=float(fd_step_T), on_block=on_block, dT_method=dT_method)
+                                             fd_step_T=float(fd_step_T), on_block=on_block, dT_method=dT_method,
+                                             continuum=cont)
     if red is not None:
         rows = torch.cat([tau, Lu, Ld[None, :]])
         X_out, r = engine.reduce_resolution_cached(rows, x0, grid.step, grid.n, red["dX"], N=red["N"], window=red["window"])
@@ -800,7 +818,8 @@ def _vjp_cotangents(cotangents, nX, nZ):
     return out, n_vecs.pop()
 
 
-def compute_TUD_vjp(Xmin, Xmax, cotangents, opts=options, wrt=("T",), layers=None, fd_step_T=0.5, dT_method="fd", **kwargs):
+def compute_TUD_vjp(Xmin, Xmax, cotangents, opts=options, wrt=("T",), layers=None, fd_step_T=0.5, dT_method="fd",
+                    continuum_derivatives=False, **kwargs):
     """compute_TUD and the gradient of a scalar cost of its outputs with respect to layer temperatures and mixing ratios:
     the transpose of compute_TUD_jacobian's J applied to the cost's cotangents, without J ever being stored (reverse mode;
     DESIGN 4.16).
@@ -820,13 +839,16 @@ def compute_TUD_vjp(Xmin, Xmax, cotangents, opts=options, wrt=("T",), layers=Non
     function), has the native-grid cotangent R^T (d cost / d Y), which is passed here. For a cost defined on at-sensor
     band radiances under a sensor's response tables, compute_band_radiance_vjp runs the whole chain, sensor adjoint
     included, and also returns the gradients of the surface temperature and the emissivity knots.
+    continuum=, continuum_derivatives: as compute_TUD_jacobian (refused unless continuum_derivatives=True; then OD is not
+    linear in a mixing ratio, a species entry is the local derivative at the state per ppmv, and where a continuum
+    component's interpolated sum is <= 0 its derivatives are 0: the kink of max(0, .) is given the value 0).
     Arguments are checked before any device work. NotImplementedError: more than one theta_r, broadening=, xs_lut=."""
     c = _Call("compute_TUD_vjp", Xmin, Xmax, opts, kwargs)
     if "reduce" in c.o:
         raise NotImplementedError("compute_TUD_vjp: reduce= is not offered: map the cotangent to the native grid with the "
                                   "transpose of the reduction and pass that")
     _no_xs_lut(c)
-    _no_continuum(c)
+    cont = _derivative_continuum(c, continuum_derivatives)
     wrt, lay, nX = _jacobian_args(c.fn, Xmin, Xmax, c.o, wrt, layers, None, fd_step_T, host_result=False, dT_method=dT_method)
     nZ = c.Z_s.size
     G, n_vec = _vjp_cotangents(cotangents, nX, nZ)
@@ -835,7 +857,8 @@ def compute_TUD_vjp(Xmin, Xmax, cotangents, opts=options, wrt=("T",), layers=Non
     tbl = c.table()
     tau, Lu, Ld, _, grad = engine.tud_vjp(tbl, grid, c.Z, c.T, c.P, c.PL, c.MF, c.ID, G_tau=G.get("tau"), G_Lu=G.get("La"),
                                           G_Ld=G.get("Ld"), Altitudes=c.Z_s, theta_r=c.theta, N_angle=c.N_angle,
-                                          returnOD=c.returnOD, wrt=wrt, layers=lay, fd_step_T=float(fd_step_T), dT_method=dT_method)
+                                          returnOD=c.returnOD, wrt=wrt, layers=lay, fd_step_T=float(fd_step_T), dT_method=dT_method,
+                                          continuum=cont)
     (tau_h, Lu_h, Ld_h), done = _rows_to_host_f64([tau, Lu, Ld[None, :]])
     grad_h = grad.cpu().numpy()  # [n_vec][n_wrt][n_layers]
     done.synchronize()
@@ -865,7 +888,7 @@ def _jvp_tangents(tangents, n_lay, fn="compute_TUD_jvp"):
 
 
 def compute_TUD_jvp(Xmin, Xmax, tangents, opts=options, layers=None, rows=("tau", "La", "Ld"), fd_step_T=0.5, dT_method="fd",
-                    **kwargs):
+                    continuum_derivatives=False, **kwargs):
     """compute_TUD and the change of its outputs along directions in (layer temperatures, mixing ratios): compute_TUD_jacobian's
     J applied to tangent vectors, without J ever being stored (forward mode). The result is spectra, 2 nAlt + 1
     rows per vector: it fits where J does not.
@@ -881,12 +904,15 @@ def compute_TUD_jvp(Xmin, Xmax, tangents, opts=options, layers=None, rows=("tau"
     The tangents are carried through the TUD recurrences in float64 and each result is rounded to float32 once; a point's
     value does not depend on the other vectors of the call. There is no reduce=: the results are spectra, and
     reduceResolution takes them as it takes any spectrum.
+    continuum=, continuum_derivatives: as compute_TUD_jacobian (refused unless continuum_derivatives=True; then OD is not
+    linear in a mixing ratio, a species entry is the local derivative at the state per ppmv, and where a continuum
+    component's interpolated sum is <= 0 its derivatives are 0: the kink of max(0, .) is given the value 0).
     Arguments are checked before any device work. NotImplementedError: more than one theta_r, broadening=, xs_lut=."""
     c = _Call("compute_TUD_jvp", Xmin, Xmax, opts, kwargs)
     if "reduce" in c.o:
         raise NotImplementedError("compute_TUD_jvp: reduce= is not offered: the results are spectra, pass them to reduceResolution")
     _no_xs_lut(c)
-    _no_continuum(c)
+    cont = _derivative_continuum(c, continuum_derivatives)
     if isinstance(tangents, dict) and tangents:
         wrt = tuple(tangents.keys())
         bad = [k for k in wrt if k != "T" and (isinstance(k, bool) or not isinstance(k, (int, np.integer)))]
@@ -907,7 +933,7 @@ def compute_TUD_jvp(Xmin, Xmax, tangents, opts=options, layers=None, rows=("tau"
     tbl = c.table()
     tau, Lu, Ld, _, d = engine.tud_jvp(tbl, grid, c.Z, c.T, c.P, c.PL, c.MF, c.ID, V, Altitudes=c.Z_s, theta_r=c.theta,
                                        N_angle=c.N_angle, returnOD=c.returnOD, wrt=wrt, layers=lay, fd_step_T=float(fd_step_T),
-                                       rows=rows, dT_method=dT_method)
+                                       rows=rows, dT_method=dT_method, continuum=cont)
     (tau_h, Lu_h, Ld_h), done = _rows_to_host_f64([tau, Lu, Ld[None, :]])
     d_h = {name: t.to(torch.float64).cpu().numpy() for name, t in d.items()}  # [n_vec]([nZ])[nX]
     done.synchronize()
@@ -924,7 +950,7 @@ def compute_TUD_jvp(Xmin, Xmax, tangents, opts=options, layers=None, rows=("tau"
 
 
 def compute_band_radiance_vjp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, cotangent, opts=options, wrt=("T",), layers=None,
-                              fd_step_T=0.5, dT_method="fd", **kwargs):
+                              fd_step_T=0.5, dT_method="fd", continuum_derivatives=False, **kwargs):
     """At-sensor band radiances over a surface and the gradient of a scalar cost defined on them, in one call: the
     line-sums (base, T -+ fd_step_T, each species of wrt), compute_TUD's tau / La / Ld, the band radiances of
     sensor.band_radiance_srf_fused under the sensor's response tables, their adjoint (sensor.band_radiance_srf_vjp) and
@@ -941,6 +967,9 @@ def compute_band_radiance_vjp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, co
              grid point under it; such a band contributes nothing to any gradient, whatever its cotangent holds);
       grad   {wrt entry: float64 [n_layers]} as compute_TUD_vjp returns them, plus "Ts_surface" (float64, Ts_surface's
              shape) and "emis" (float64 [nk][nE]); every entry with a trailing [n_vec] axis when the cotangent has one.
+    continuum=, continuum_derivatives: as compute_TUD_jacobian (refused unless continuum_derivatives=True; then OD is not
+    linear in a mixing ratio, a species entry is the local derivative at the state per ppmv, and where a continuum
+    component's interpolated sum is <= 0 its derivatives are 0: the kink of max(0, .) is given the value 0).
     Arguments are checked before any device work. NotImplementedError: more than one altitude or theta_r, returnOD=True,
     broadening=, xs_lut=, reduce=."""
     name = "compute_band_radiance_vjp"
@@ -948,7 +977,7 @@ def compute_band_radiance_vjp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, co
     if "reduce" in c.o:
         raise NotImplementedError(name + ": reduce= is not offered: the cost is defined on the sensor's bands")
     _no_xs_lut(c)
-    _no_continuum(c)
+    cont = _derivative_continuum(c, continuum_derivatives)
     if c.returnOD:
         raise NotImplementedError(name + ": returnOD=True is not supported (the sensor stage takes transmittances)")
     if c.Z_s.size != 1:
@@ -997,7 +1026,7 @@ def compute_band_radiance_vjp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, co
 
     _, _, _, _, grad = engine.tud_vjp(tbl, grid, c.Z, c.T, c.P, c.PL, c.MF, c.ID, Altitudes=c.Z_s, theta_r=c.theta,
                                       N_angle=c.N_angle, returnOD=False, wrt=wrt, layers=lay, fd_step_T=float(fd_step_T),
-                                      cotangents=sensor_stage, dT_method=dT_method)
+                                      cotangents=sensor_stage, dT_method=dT_method, continuum=cont)
     L_h = kept["L"].cpu().numpy()
     dTs_h = torch.stack(kept["Ts"], dim=-1).cpu().numpy()    # Ts_surface's shape + [n_vec]
     dE_h = torch.stack(kept["emis"], dim=-1).cpu().numpy()   # [nk][nE][n_vec]
@@ -1011,7 +1040,7 @@ _SURFACE_TANGENTS = ("Ts_surface", "emis")
 
 
 def compute_band_radiance_jvp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, tangents, opts=options, layers=None, fd_step_T=0.5,
-                              dT_method="fd", **kwargs):
+                              dT_method="fd", continuum_derivatives=False, **kwargs):
     """At-sensor band radiances over a surface and their change along directions in the unknowns of a retrieval, in one
     call: compute_TUD_jvp's tangent rows of tau / La / Ld (engine.tud_jvp), which stay on the device as float32, fed to the
     sensor stage's tangent (sensor.band_radiance_srf_jvp), which adds the surface temperature and the emissivity knots. No
@@ -1028,6 +1057,9 @@ def compute_band_radiance_jvp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, ta
       X_out  sensor.centres;
       L      float32 NumPy, bit-identical to compute_band_radiance_vjp's L;
       dL     float64 NumPy shaped like L, plus a trailing [n_vec] axis when the tangents have one; NaN where L is NaN.
+    continuum=, continuum_derivatives: as compute_TUD_jacobian (refused unless continuum_derivatives=True; then OD is not
+    linear in a mixing ratio, a species entry is the local derivative at the state per ppmv, and where a continuum
+    component's interpolated sum is <= 0 its derivatives are 0: the kink of max(0, .) is given the value 0).
     Arguments are checked before any device work. NotImplementedError: more than one altitude or theta_r, returnOD=True,
     broadening=, xs_lut=, reduce=."""
     name = "compute_band_radiance_jvp"
@@ -1035,7 +1067,7 @@ def compute_band_radiance_jvp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, ta
     if "reduce" in c.o:
         raise NotImplementedError(name + ": reduce= is not offered: the tangent is defined on the sensor's bands")
     _no_xs_lut(c)
-    _no_continuum(c)
+    cont = _derivative_continuum(c, continuum_derivatives)
     if c.returnOD:
         raise NotImplementedError(name + ": returnOD=True is not supported (the sensor stage takes transmittances)")
     if c.Z_s.size != 1:
@@ -1101,7 +1133,7 @@ def compute_band_radiance_jvp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, ta
     if atm:
         tau, Lu, Ld, _, d = engine.tud_jvp(tbl, grid, c.Z, c.T, c.P, c.PL, c.MF, c.ID, V, Altitudes=c.Z_s, theta_r=c.theta,
                                            N_angle=c.N_angle, returnOD=False, wrt=wrt, layers=lay, fd_step_T=float(fd_step_T),
-                                           dT_method=dT_method)
+                                           dT_method=dT_method, continuum=cont)
         # [n_vec][nX] float32 where rtx_tud_jvp wrote them, seen as [nX][n_vec]: no copy, no host round trip
         rows = dict(d_tau=d["tau"][:, 0, :nX].T, d_La=d["La"][:, 0, :nX].T, d_Ld=d["Ld"][:, :nX].T)
         if n_vec is None:
@@ -1109,7 +1141,7 @@ def compute_band_radiance_jvp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, ta
     else:  # the base state alone, exactly what compute_TUD runs
         T = np.ascontiguousarray(np.atleast_1d(c.T))
         run = engine.TudRunner(tbl, grid, np.atleast_1d(c.Z), n_layers=T.size, Altitudes=c.Z_s, theta_r=c.theta, N_angle=c.N_angle,
-                               returnOD=False)
+                               returnOD=False, continuum=cont)
         tau, Lu, Ld = run.run(T, np.atleast_1d(c.P), np.atleast_1d(c.PL), c.MF.reshape(T.size, -1), c.ID)
     t_, u_, d_ = tau[0, :nX].contiguous(), Lu[0, :nX].contiguous(), Ld[:nX].contiguous()
     L, dL = _sensor.band_radiance_srf_jvp(grid, t_, u_, d_, Xk, E_d, float(Ts_s[0]) if scalar else Ts_s, sensor, d_Ts=d_Ts,
