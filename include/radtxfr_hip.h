@@ -850,7 +850,29 @@ int rtx_fir_chunk_taps(void);
  *                        or a larger one, allocates and therefore synchronises; every other call only enqueues.
  *                        16-byte accesses when x_offset and ld are multiples of 4 and od_f32 is 16-byte aligned
  *                        (point by point for the ragged end of the last tile); otherwise point by point throughout.
- *   rtx_xs_tile_points   consecutive points one workgroup owns (for tests at the edges). */
+ *   rtx_xs_tile_points   consecutive points one workgroup owns (for tests at the edges).
+ *   rtx_xs_od_d          the table's part of the columns rtx_tud_jacobian, rtx_tud_vjp and rtx_tud_jvp (and their _dod
+ *                        forms) take, all of them in one pass over the table rows:
+ *                          dOD_dT[l][i]  = sum_{m < n_mol} sum_{c < 4} weight_dT_h[l][m][c] * row rows_h[l][m][c]
+ *                          K[s][l][i]    = sum_{c < 4} weight_K_h[s][l][c] * row rows_h[l][spec_mol_h[s]][c]
+ *                        at point x_offset + i, for l < n_layers, i < n, s < n_spec: fp32 dOD_dT[n_layers][ld] and
+ *                        K[n_spec][n_layers][ld]. The outputs are WRITTEN, as rtx_xs_od writes its own, not added to
+ *                        (rtx_continuum_add_d then adds onto them). rows_h as for rtx_xs_od; weight_dT_h
+ *                        [n_layers][n_mol][4] and weight_K_h [n_spec][n_layers][4] are HOST arrays of derivative weights
+ *                        (radtxfr_amd/afit_xs.py: layer_terms_d); spec_mol_h[n_spec] names the table index of each
+ *                        species' molecule: distinct values in [0, n_mol), n_spec <= 16. Either output may be NULL (with
+ *                        its weights), not both; n_spec = 0 goes with K = NULL. Every row index is checked against the
+ *                        table, every weight must be finite; n = 0 writes nothing. Each output value is one fp32 fmaf
+ *                        chain from 0 in term order (molecule, then corner) over the terms whose weight FOR THAT OUTPUT
+ *                        is not 0; a row both of whose weights are 0 is not read. A value is thus a function of (table,
+ *                        layer, point) alone, bit-identical for every x_offset / n cut, and equal bit for bit to
+ *                        rtx_xs_od run on the same fp32 weights (weight_dT_h; one molecule's weight_K_h, 0 elsewhere).
+ *                        Staging as rtx_xs_od's (hipMemcpyAsync on `stream`, staged before returning) into a grow-only
+ *                        device buffer of this entry's own in the table, one for each stream: the first call on a
+ *                        stream, or a larger one, allocates; every other call only enqueues. 16-byte accesses when
+ *                        x_offset and ld are multiples of 4 and dOD_dT and K are 16-byte aligned (point by point for the
+ *                        ragged end of the last tile); otherwise point by point throughout. flags: none is defined,
+ *                        pass 0. */
 typedef struct rtx_xs_lut rtx_xs_lut;
 int rtx_xs_lut_create(int n_mol, int64_t n_rows, int64_t nx, rtx_xs_lut** out);
 int rtx_xs_lut_free(rtx_xs_lut* lut);
@@ -860,6 +882,9 @@ int rtx_xs_lut_get_rows(const rtx_xs_lut* lut, int64_t row0, int64_t n_rows, flo
 int rtx_xs_od(rtx_xs_lut* lut, int64_t x_offset, int64_t n, int n_layers, const int32_t* rows_h, const float* weight_h,
               float* od_f32, int64_t ld, void* stream);
 int rtx_xs_tile_points(void);
+int rtx_xs_od_d(rtx_xs_lut* lut, int64_t x_offset, int64_t n, int n_layers, const int32_t* rows_h, const float* weight_dT_h,
+                int n_spec, const int32_t* spec_mol_h, const float* weight_K_h, float* dOD_dT, float* K, int64_t ld, void* stream,
+                unsigned flags);
 
 /* ---- tabulated continuum absorption -------------------------------------------------------
  * LBLRTM, behind the reference's compute_OD, adds the collision-induced continua to its line sum (write_tape5 switches them

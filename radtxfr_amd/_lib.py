@@ -120,6 +120,7 @@ PROTOTYPES = {
     "rtx_xs_lut_get_rows": (_i32, [_vp, _i64, _i64, _vp, _vp]),
     "rtx_xs_od": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
     "rtx_xs_tile_points": (_i32, []),
+    "rtx_xs_od_d": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, C.c_uint]),
     "rtx_continuum_add": (_i32, [_gp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, C.c_uint]),
     "rtx_continuum_tile_points": (_i32, []),
     "rtx_continuum_add_d": (_i32, [_gp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _vp,

@@ -13,7 +13,8 @@ launch as "layers" (rtx_line_prep + rtx_voigt_sum), 128 states at a time.
 
 XsLut is the consumer the reference lacks: the files (or cross_section_grid's arrays) as one device-resident table from
 which rt.compute_OD / compute_TUD / compute_TUD_batch(xs_lut=...) look optical depths up per layer instead of summing
-lines."""
+lines, and through which the derivative functions differentiate when asked (layer_terms_d,
+XsLut.dod_host)."""
 import ctypes as C
 import os
 import struct
@@ -275,6 +276,81 @@ def layer_terms(tables, T, P_atm, PL_km, MF_VAL, MF_ID):
     return rows, w
 
 
+def layer_terms_d(tables, T, P_atm, PL_km, MF_VAL, MF_ID, species):
+    """layer_terms' derivative weights at fixed p, host float64. tables, T, P_atm, PL_km, MF_VAL,
+    MF_ID as layer_terms; species: distinct molecule ids of MF_ID whose mixing-ratio derivative is wanted. Returns
+        rows  int32   [L][M][4]   what layer_terms returns
+        w_T   float64 [L][M][4]   dOD_l/dT_l = sum_m sum_c w_T[l][m][c] xs_m[corner c]:  N (-w_c / T + dw_c/dT), with w_c the
+                                  bilinear factor of layer_terms, N ~ 1/T the column amount and
+                                  dw/dT = [-(1-fP), -fP, (1-fP), fP] / (T_{i+1} - T_i), all 0 on an axis with one T node
+        w_K   float64 [S][L][4]   dOD_l/dMF_s,l per ppmv = sum_c w_K[s][l][c] xs_s[corner c]: N(MF = 1) w_c, formed by
+                                  layer_terms' own operations in its order (the weights it gives that molecule alone at
+                                  1 ppmv, bit for bit); exact and finite at MF = 0, OD being linear in MF
+        idx   list [S]            the table index of each species' molecule.
+    OD is piecewise linear-over-T in T, so dOD/dT jumps at a T node: A LAYER EXACTLY ON A NODE TAKES THE SLOPE OF THE CELL
+    bracket() RETURNS FOR IT, the cell to its right, except on the last node, where it is the cell to its left -- the cell
+    whose weights the forward run used. ValueError: what layer_terms raises; a species named twice or not in MF_ID; and a
+    species is range-checked in EVERY layer, also where its MF_VAL is 0 (its derivative is not 0 there), with the forward's
+    text."""
+    T = np.atleast_1d(np.asarray(T, dtype=np.float64))
+    p = np.atleast_1d(np.asarray(P_atm, dtype=np.float64))
+    PL = np.atleast_1d(np.asarray(PL_km, dtype=np.float64))
+    nL = T.size
+    MF = np.asarray(MF_VAL, dtype=np.float64).reshape(nL, -1)
+    ids = [int(v) for v in np.asarray(MF_ID).ravel()]
+    species = [int(s) for s in species]
+    rows, _ = layer_terms(tables, T, p, PL, MF, ids)  # the forward's rows and its checks
+    if len(set(species)) != len(species) or any(s not in ids for s in species):
+        raise ValueError("xs_lut: species %r must be distinct molecule ids of MF_ID %r" % (species, ids))
+    nvol = engine.volumeConcentration(p, T)
+    w_T = np.zeros((nL, len(tables), 4))
+    w_K = np.zeros((len(species), nL, 4))
+    idx = [0] * len(species)
+    for m, (mid, Tn, Pn, row0) in enumerate(tables):
+        if mid not in ids:
+            continue
+        if mid in species:
+            for name, unit, nodes, v in (("T", "K", Tn, T), ("p", "atm", Pn, p)):
+                bad = (v < nodes[0]) | (v > nodes[-1]) if nodes.size > 1 else np.zeros(nL, dtype=bool)
+                if bad.any():
+                    l = int(np.flatnonzero(bad)[0])
+                    raise ValueError("xs_lut: layer %d (%s = %.9g %s) lies outside molecule %d's table range [%.9g, %.9g] %s; there is "
+                                     "no extrapolation" % (l, name, v[l], unit, mid, nodes[0], nodes[-1], unit))
+        N = nvol * (MF[:, ids.index(mid)] * 1e-6) * PL * 1e5
+        iT, fT = bracket(Tn, T)
+        iP, fP = bracket(Pn, p, log=True)
+        corners = np.stack([(1 - fT) * (1 - fP), (1 - fT) * fP, fT * (1 - fP), fT * fP], axis=1)
+        slope = np.zeros((nL, 4))
+        if Tn.size > 1:
+            slope = np.stack([-(1 - fP), -fP, (1 - fP), fP], axis=1) / (Tn[iT + 1] - Tn[iT])[:, None]
+        w_T[:, m, :] = N[:, None] * (-corners / T[:, None] + slope)
+        if mid in species:
+            s = species.index(mid)
+            idx[s] = m
+            N1 = nvol * (np.ones(nL) * 1e-6) * PL * 1e5  # layer_terms' N at 1 ppmv
+            w_K[s] = N1[:, None] * corners
+    return rows, w_T, w_K, idx
+
+
+def dod_from_terms(xs_rows, rows, w_T, w_K, idx):
+    """The derivative columns of layer_terms_d's terms on table rows xs_rows [n_rows][nX], float64 on the host:
+    (dOD_dT [L][nX], dOD_dMF [S][L][nX])."""
+    xs_rows = np.asarray(xs_rows, dtype=np.float64)
+    nL = rows.shape[0]
+    dT = np.zeros((nL, xs_rows.shape[1]))
+    dK = np.zeros((w_K.shape[0], nL, xs_rows.shape[1]))
+    for l in range(nL):
+        for m in range(rows.shape[1]):
+            for c in range(4):
+                if w_T[l, m, c] != 0.0:
+                    dT[l] += w_T[l, m, c] * xs_rows[rows[l, m, c]]
+        for s, m in enumerate(idx):
+            for c in range(4):
+                if w_K[s, l, c] != 0.0:
+                    dK[s, l] += w_K[s, l, c] * xs_rows[rows[l, m, c]]
+    return dT, dK
+
+
 def align_axis(table_grid, grid):
     """Index of grid's first point (of the whole axis, shard offset not counted) on table_grid when `grid` coincides with a
     contiguous run of it -- same spacing, every point within 1e-9 of a step of a table point -- else ValueError naming both
@@ -308,7 +384,9 @@ class XsLut:
 
     Public: molecules (IDs in table order), grid (engine.Grid of the axis), nodes(ID) -> (T, P_atm), exponent(ID),
     rows(ID) (the device rows read back, float32 [nT][nP][nX]), nbytes, device; free() or del releases the device memory.
-    Interpolation rule and summation order: layer_terms, DESIGN.md section 4.11."""
+    Interpolation rule and summation order: layer_terms, DESIGN.md section 4.11. Derivatives with respect to layer
+    temperature and mixing ratios (layer_terms_d, dod_host; xs_derivatives=True of the derivative functions of
+    radiative_transfer): DESIGN.md section 4.24."""
 
     def __init__(self, entries):
         tabs, self.grid = check_xs_entries(entries)
@@ -391,6 +469,31 @@ class XsLut:
         weights times the molecule's 2**-exponent, rounded once)."""
         rows, w = layer_terms(self._tables, T, P_atm, PL_km, MF_VAL, MF_ID)
         return np.ascontiguousarray(rows), np.ascontiguousarray((w * self._scale[None, :, None]).astype(np.float32))
+
+    def layer_terms_d(self, T, P_atm, PL_km, MF_VAL, MF_ID, species):
+        """rtx_xs_od_d's host inputs for one atmosphere: rows int32 [L][M][4], w_T float32 [L][M][4],
+        w_K float32 [S][L][4] (the module's layer_terms_d float64 weights times the molecule's 2**-exponent, rounded once) and
+        the table index of each species, int32 [S]. A layer exactly on a T node takes the slope of the cell bracket() returns
+        for it: the cell to its right, the cell to its left on the last node -- the cell the forward run used."""
+        rows, w_T, w_K, idx = layer_terms_d(self._tables, T, P_atm, PL_km, MF_VAL, MF_ID, species)
+        sK = self._scale[np.asarray(idx, dtype=np.int64)] if len(idx) else np.zeros(0)
+        return (np.ascontiguousarray(rows), np.ascontiguousarray((w_T * self._scale[None, :, None]).astype(np.float32)),
+                np.ascontiguousarray((w_K * sK[:, None, None]).astype(np.float32)), np.asarray(idx, dtype=np.int32))
+
+    def dod_host(self, T, P_atm, PL_km, MF_VAL, MF_ID, species=None):
+        """The definition of the table's derivatives, float64 on the host (the oracle of the device tests): (dOD_dT [nL][nX]
+        per K, {molecule: dOD_dMF [nL][nX] per ppmv}) on the table's whole axis, from the module's layer_terms_d weights in
+        float64 and the float32 rows as stored (rows(ID)) times 2**-exponent. species: the molecules differentiated, default
+        every id of MF_ID once. A layer exactly on a T node takes the slope of the cell bracket() returns for it (the cell to
+        its right; to its left on the last node)."""
+        if species is None:
+            species = list(dict.fromkeys(int(v) for v in np.asarray(MF_ID).ravel()))
+        species = [int(s) for s in species]
+        rows, w_T, w_K, idx = layer_terms_d(self._tables, T, P_atm, PL_km, MF_VAL, MF_ID, species)
+        xs_rows = np.concatenate([np.ldexp(self.rows(m).astype(np.float64), -self._exp[m]).reshape(-1, self.grid.n_total)
+                                  for m in self.molecules])
+        dT, dK = dod_from_terms(xs_rows, rows, w_T, w_K, idx)
+        return dT, {m: dK[s] for s, m in enumerate(species)}
 
     def free(self):
         h, self._h = getattr(self, "_h", None), None

@@ -718,6 +718,51 @@ def xs_od(lut, grid_or_offset, T, P_atm, PL, MF, ID, out_f32=None):
     return out_f32
 
 
+def xs_od_d(lut, grid_or_offset, T, P_atm, PL, MF, ID, dOD_dT=None, K=None, species=()):
+    """The derivative columns of a cross-section table (afit_xs.XsLut; rtx_xs_od_d) WRITTEN to
+    float32 device columns in one pass over the table rows: dOD_dT[nL][>= n] = d(OD)/dT per K at fixed p, and K[s][nL][>= n]
+    = d(OD)/dMF per ppmv of molecule species[s] (distinct ids of ID, at most 16). Either output may be None, not both; with
+    both, they share one row stride. grid_or_offset, T, P_atm, PL, MF, ID as xs_od (n from the outputs with an offset). The
+    weights are made on the host in float64 (afit_xs.layer_terms_d): a layer exactly on a T node takes the slope of the cell
+    afit_xs.bracket returns for it (the cell to its right; to its left on the last node); a species is range-checked in every
+    layer, also where its mixing ratio is 0. Bit-identical for every cut of the axis. Returns (dOD_dT, K)."""
+    T = np.atleast_1d(np.asarray(T, dtype=np.float64))
+    species = [int(m) for m in species]
+    if dOD_dT is None and K is None:
+        raise ValueError("xs_od_d: dOD_dT and K are both None")
+    if K is not None and len(species) != K.shape[0]:
+        raise ValueError("xs_od_d: species %r must name K's %d slots, each once" % (species, K.shape[0]))
+    rows, w_T, w_K, idx = lut.layer_terms_d(T, P_atm, PL, MF, ID, species if K is not None else ())
+    nL = T.size
+    if isinstance(grid_or_offset, Grid):
+        off, n = lut.align(grid_or_offset) + grid_or_offset.offset, grid_or_offset.n
+    else:
+        off, n = int(grid_or_offset), int((dOD_dT if dOD_dT is not None else K).shape[-1])
+    lds = []  # the row strides the blocks fix; a single row fixes none
+    if dOD_dT is not None:
+        assert dOD_dT.dtype == torch.float32 and dOD_dT.is_cuda and dOD_dT.dim() == 2 and dOD_dT.shape[0] == nL
+        assert dOD_dT.shape[1] >= n and dOD_dT.stride(1) == 1
+        if nL > 1:
+            lds.append(dOD_dT.stride(0))
+    if K is not None:
+        assert K.dtype == torch.float32 and K.is_cuda and K.dim() == 3 and K.shape[1] == nL and K.shape[2] >= n
+        assert K.stride(2) == 1
+        if nL > 1:
+            assert K.shape[0] <= 1 or K.stride(0) == nL * K.stride(1)
+            lds.append(K.stride(1))
+        elif K.shape[0] > 1:
+            lds.append(K.stride(0))
+    if len(set(lds)) > 1:
+        raise ValueError("xs_od_d: dOD_dT and K must share one row stride, got %r" % (lds,))
+    ld = lds[0] if lds else n
+    n_spec = len(species) if K is not None else 0
+    vp = C.c_void_p
+    _lib.check(_lib.load().rtx_xs_od_d(lut._handle(), off, n, nL, rows.ctypes.data_as(vp), w_T.ctypes.data_as(vp), n_spec,
+                                       idx.ctypes.data_as(vp), w_K.ctypes.data_as(vp), _ptr(dOD_dT), _ptr(K) if n_spec else None, ld,
+                                       _stream_ptr(), 0))
+    return dOD_dT, K
+
+
 def _continuum_call(lib, tables, axes, grid, T, OD, st):
     """rtx_continuum_add on host tables [nC][nL][n_max] float32 with axes [(v0, dv, n)]: OD[nL][>= grid.n] += continuum."""
     v0 = np.array([a[0] for a in axes], dtype=np.float64)
@@ -1536,7 +1581,7 @@ class JacobianStages(NamedTuple):
 
 
 def _jacobian_stages(what, lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt, layers,
-                     fd_step_T, mark, dT_method="fd", continuum=None):
+                     fd_step_T, mark, dT_method="fd", continuum=None, xs_lut=None):
     """The stages tud_jacobian and tud_vjp share: argument checks, the base state (exactly what compute_TUD runs), the
     line-sums at T -+ fd_step_T with every line's window at T (skipped without "T" in wrt; dT_method "analytic": one
     voigt_sum_dT instead, fd_step_T ignored) and the line-sum of each species of wrt at 1 ppmv (what the reference's
@@ -1544,7 +1589,12 @@ def _jacobian_stages(what, lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitu
     continuum: a continuum.Continuum in the base state (what compute_TUD(continuum=) runs) and in
     every column: "fd" adds the continuum at T -+ fd_step_T to the two line-sums (continuum_add: the full definition at
     that temperature), "analytic" its dOD/dT to the line-sum's, and each species column gets its dOD/dMF at the state
-    (the self term is quadratic in the mixing ratio) -- the last two in one continuum_add_d. None: nothing changes."""
+    (the self term is quadratic in the mixing ratio) -- the last two in one continuum_add_d. None: nothing changes.
+    xs_lut: an afit_xs.XsLut instead of `lines` (None then): the base state is what
+    compute_TUD(xs_lut=) runs, "analytic" takes dOD/dT and every species column from ONE rtx_xs_od_d, "fd" takes the forward
+    rule (xs_od) at T -+ fd_step_T -- a layer the step pushes out of the table raises the forward's ValueError -- and the
+    species columns from rtx_xs_od_d. A layer exactly on a T node takes the slope of the cell afit_xs.bracket returns for it
+    (the cell to its right; to its left on the last node). A continuum composes unchanged after either."""
     check_dT_method(dT_method)
     T = np.ascontiguousarray(np.atleast_1d(np.asarray(T, dtype=np.float64)))
     Z = np.atleast_1d(np.asarray(Z, dtype=np.float64))
@@ -1569,13 +1619,16 @@ def _jacobian_stages(what, lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitu
     dev = device()
     # base state: exactly what compute_TUD runs
     run = TudRunner(lines, grid, Z, n_layers=nL, Altitudes=Altitudes, theta_r=theta_r, N_angle=N_angle, returnOD=returnOD,
-                    continuum=continuum)
+                    continuum=continuum, xs_lut=xs_lut)
     tau, Lu, Ld = run.run(T, P_pa, PL_km, MF_VAL, MF_ID)
     OD = run.OD
     if mark:
         mark("base")
     n = grid.n
     ODp = ODm = dOD = None
+    if xs_lut is not None:
+        return _xs_jacobian_columns(xs_lut, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, wrt, layers, fd_step_T, mark, dT_method, continuum,
+                                    tau, Lu, Ld, OD)
     if with_T and dT_method == "analytic":
         dOD = torch.empty((nL, n), dtype=torch.float32, device=dev)
         w, p_atm = layer_weights_od(lines.species, T, P_pa, PL_km, MF_VAL, MF_ID)
@@ -1609,9 +1662,40 @@ def _jacobian_stages(what, lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitu
     return JacobianStages(T, Z, layers, t_pos, tau, Lu, Ld, OD, ODp, ODm, dOD, K)
 
 
+def _xs_jacobian_columns(lut, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, wrt, layers, fd_step_T, mark, dT_method, continuum, tau, Lu, Ld, OD):
+    """_jacobian_stages' columns from a cross-section table, after its checks and base state: every
+    column has the row stride of the runner's OD (rows 16 bytes apart)."""
+    nL, n, ld, dev = T.size, grid.n, OD.stride(0), OD.device
+    with_T = "T" in wrt
+    species = [w_ for w_ in wrt if not isinstance(w_, str)]
+    P_atm = P_pa / 101325.0
+    column = lambda: torch.empty((nL, ld), dtype=torch.float32, device=dev)[:, :n]
+    ODp = ODm = dOD = K = None
+    if with_T and dT_method == "analytic":
+        dOD = column()
+    elif with_T:
+        ODp, ODm = column(), column()
+        for sgn, out in ((1.0, ODp), (-1.0, ODm)):
+            Ts = T + sgn * float(fd_step_T)
+            xs_od(lut, grid, Ts, P_atm, PL_km, MF_VAL, MF_ID, out_f32=out)  # the forward rule at that temperature
+            if continuum is not None:
+                continuum_add(continuum, grid, Ts, P_pa, PL_km, MF_VAL, MF_ID, out)
+    if species:
+        K = torch.empty((len(species), nL, ld), dtype=torch.float32, device=dev)[:, :, :n]
+    if dOD is not None or K is not None:
+        xs_od_d(lut, grid, T, P_atm, PL_km, MF_VAL, MF_ID, dOD_dT=dOD, K=K, species=species)
+    if mark:
+        mark("T")
+    if continuum is not None and (dOD is not None or K is not None):
+        continuum_add_d(continuum, grid, T, P_pa, PL_km, MF_VAL, MF_ID, dOD_dT=dOD, K=K, species=species)
+    if mark:
+        mark("species")
+    return JacobianStages(T, Z, layers, wrt.index("T") if with_T else 0, tau, Lu, Ld, OD, ODp, ODm, dOD, K)
+
+
 def tud_jacobian(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=False,
                  wrt=("T",), layers=None, fd_step_T=0.5, block_bytes=JAC_BLOCK_BYTES, on_block=None, mark=None, dT_method="fd",
-                 continuum=None):
+                 continuum=None, xs_lut=None):
     """compute_TUD's outputs and their Jacobian with respect to layer temperatures and mixing ratios, on the device.
 
     wrt: "T" and/or molecule ids of MF_ID (T, when present, is computed first whatever its position: J's wrt axis follows
@@ -1627,9 +1711,12 @@ def tud_jacobian(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes=(500,)
     dOD/dMF of a species is the line-sum of that species alone at 1 ppmv (OD is linear in each mixing ratio).
     continuum: a continuum.Continuum carried through the base state and every derivative (_jacobian_stages; DESIGN.md
     section 4.23). OD is then no longer linear in a mixing ratio: a species entry of J is the local derivative at the
-    state, per ppmv; where a component's stencil sum is <= 0 its derivatives are 0 (the kink of max(0, .) is given 0)."""
+    state, per ppmv; where a component's stencil sum is <= 0 its derivatives are 0 (the kink of max(0, .) is given 0).
+    xs_lut: an afit_xs.XsLut instead of `lines` (None then): every column comes from the table (_jacobian_stages; DESIGN.md
+    section 4.24). OD is piecewise in T there: a layer exactly on a T node takes the slope of the cell afit_xs.bracket
+    returns for it, the cell to its right (to its left on the last node)."""
     s = _jacobian_stages("tud_jacobian", lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt,
-                         layers, fd_step_T, mark, dT_method, continuum)
+                         layers, fd_step_T, mark, dT_method, continuum, xs_lut)
     J = tud_jacobian_from_od(s.OD, s.OD_plus, s.OD_minus, fd_step_T, s.K, s.tau, grid, s.T, s.Z, Altitudes=Altitudes,
                              theta_r=theta_r, N_angle=N_angle, returnOD=returnOD, layers=s.layers, t_pos=s.t_pos,
                              block_bytes=block_bytes, on_block=on_block, mark=mark, dOD_dT=s.dOD_dT)
@@ -1787,7 +1874,7 @@ def tud_vjp_from_od(OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z, G_tau=
 
 def tud_vjp(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, G_tau=None, G_Lu=None, G_Ld=None, Altitudes=(500,), theta_r=0.0,
             N_angle=30, returnOD=False, wrt=("T",), layers=None, fd_step_T=0.5, mark=None, cotangents=None, dT_method="fd",
-            continuum=None):
+            continuum=None, xs_lut=None):
     """compute_TUD's outputs and the gradient of a scalar cost with respect to layer temperatures and mixing ratios, given
     the cost's cotangents on the outputs: tud_jacobian's stages (the same base state, T -+ fd_step_T line-sums and species
     line-sums) followed by rtx_tud_vjp instead of rtx_tud_jacobian. wrt, layers, fd_step_T, dT_method as tud_jacobian; G_* as
@@ -1795,12 +1882,12 @@ def tud_vjp(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, G_tau=None, G_Lu=None
     following `wrt`. mark(name): after each stage ("base", "T", "species", "vjp").
     cotangents: instead of G_tau / G_Lu / G_Ld, a function (tau, Lu, Ld) -> (G_tau, G_Lu, G_Ld) called once the base state
     exists, for a cost whose cotangents depend on the outputs themselves (rt.compute_band_radiance_vjp: the sensor stage's
-    adjoint reads tau, Lu and Ld). The optical depths are computed once either way. continuum: as tud_jacobian."""
+    adjoint reads tau, Lu and Ld). The optical depths are computed once either way. continuum, xs_lut: as tud_jacobian."""
     if cotangents is not None and (G_tau is not None or G_Lu is not None or G_Ld is not None):
         raise ValueError("tud_vjp: cotangents= and G_tau / G_Lu / G_Ld exclude each other")
     check_dT_method(dT_method)
     s = _jacobian_stages("tud_vjp", lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt,
-                         layers, fd_step_T, mark, dT_method, continuum)
+                         layers, fd_step_T, mark, dT_method, continuum, xs_lut)
     if cotangents is not None:
         G_tau, G_Lu, G_Ld = cotangents(s.tau, s.Lu, s.Ld)
     grad = tud_vjp_from_od(s.OD, s.OD_plus, s.OD_minus, fd_step_T, s.K, s.tau, grid, s.T, s.Z, G_tau=G_tau, G_Lu=G_Lu, G_Ld=G_Ld,
@@ -1867,15 +1954,16 @@ def tud_jvp_from_od(OD, OD_plus, OD_minus, fd_step_T, K, tau, grid, T, Z, V, Alt
 
 
 def tud_jvp(lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, V, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=False,
-            wrt=("T",), layers=None, fd_step_T=0.5, mark=None, rows=JVP_ROWS, dT_method="fd", continuum=None):
+            wrt=("T",), layers=None, fd_step_T=0.5, mark=None, rows=JVP_ROWS, dT_method="fd", continuum=None,
+            xs_lut=None):
     """compute_TUD's outputs and their change along tangent directions in (layer temperatures, mixing ratios):
     tud_jacobian's stages (the same base state, T -+ fd_step_T line-sums and species line-sums) followed by rtx_tud_jvp
     instead of rtx_tud_jacobian. wrt, layers, fd_step_T, dT_method as tud_jacobian; V [n_vec][n_wrt][len(layers)] and rows as
     tud_jvp_from_od, V's wrt axis following `wrt`. Returns (tau, Lu, Ld, OD, d) with d as tud_jvp_from_od returns it.
-    mark(name): after each stage ("base", "T", "species", "jvp"). continuum: as tud_jacobian."""
+    mark(name): after each stage ("base", "T", "species", "jvp"). continuum, xs_lut: as tud_jacobian."""
     check_dT_method(dT_method)
     s = _jacobian_stages("tud_jvp", lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitudes, theta_r, N_angle, returnOD, wrt,
-                         layers, fd_step_T, mark, dT_method, continuum)
+                         layers, fd_step_T, mark, dT_method, continuum, xs_lut)
     d = tud_jvp_from_od(s.OD, s.OD_plus, s.OD_minus, fd_step_T, s.K, s.tau, grid, s.T, s.Z, V, Altitudes=Altitudes,
                         theta_r=theta_r, N_angle=N_angle, returnOD=returnOD, layers=s.layers, t_pos=s.t_pos, rows=rows,
                         dOD_dT=s.dOD_dT)

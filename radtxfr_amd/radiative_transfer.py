@@ -650,12 +650,24 @@ def _jacobian_args(fn, Xmin, Xmax, o, wrt, layers, reduce, fd_step_T, host_resul
     return wrt, np.ascontiguousarray(lay, dtype=np.int32), nX
 
 
-def _no_xs_lut(c):
-    """NotImplementedError in the name of the derivative function of call `c` when it carries an xs_lut: the derivatives
-    are built on the line-sum."""
-    if c.o.get("xs_lut") is not None:
-        raise NotImplementedError(c.fn + ": xs_lut is not supported (dOD/dT is a difference of line-sums with fixed windows); "
-                                  "use line_table=")
+def _no_xs_lut(c, xs_derivatives=False):
+    """The cross-section table a derivative function differentiates call `c` through: None without xs_lut=; the call's
+    XsLut with xs_derivatives=True (DESIGN.md section 4.24; _xs_lut_option's refusal of broadening= applies);
+    NotImplementedError in the function's name with the default False, before the table is touched: by default the
+    derivatives are built on the line-sum, and OD from a table is piecewise in T (a layer on a T node takes one cell's slope)."""
+    if c.o.get("xs_lut") is None:
+        return None
+    if not xs_derivatives:
+        raise NotImplementedError(c.fn + ": xs_lut is not supported by default (dOD/dT is a difference of line-sums with fixed "
+                                  "windows); use line_table=, or pass xs_derivatives=True to differentiate through the table")
+    return c.lut
+
+
+def _xs_axis(c, lut):
+    """With a table to differentiate through: ValueError, before any device work, unless the call's axis is a run of the
+    table's (XsLut.align; there is no spectral interpolation)."""
+    if lut is not None:
+        lut.align(c.grid)
 
 
 def _derivative_continuum(c, continuum_derivatives):
@@ -691,7 +703,7 @@ def _grad_dict(grad_h, wrt, n_vec):
 
 
 def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, reduce=None, fd_step_T=0.5, dT_method="fd",
-                         continuum_derivatives=False, **kwargs):
+                         continuum_derivatives=False, xs_derivatives=False, **kwargs):
     """compute_TUD and the derivatives of its outputs with respect to layer temperatures and mixing ratios in one call:
     what the reference's caller builds from 1 + 3 x 66 perturbed atmospheres (Generate_LWIR_TUD.py:55-71, JacIn, one
     layer and one quantity at a time, relStep 0.001) -- here closed-form chain rule through the TUD recurrences.
@@ -718,7 +730,13 @@ def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, redu
     reduce = dict(dX=..., N=4, window="hanning"): reduceResolution of the base outputs and of every J row on the device
     (engine.reduce_resolution_cached). Without it, full-resolution results above 4 GiB are refused (ValueError): pass
     reduce= or fewer layers=. Arguments are checked before any device work.
-    NotImplementedError: xs_lut= (the derivatives are built on the line-sum: dOD/dT holds every line's window fixed).
+    xs_lut= (as compute_TUD takes it) is refused (NotImplementedError, before the table is touched) unless
+    xs_derivatives=True; then the call is differentiated through the cross-section table: the base outputs
+    are compute_TUD(xs_lut=)'s bit for bit, "analytic" takes dOD/dT and every species column from the table in one pass
+    (rtx_xs_od_d), "fd" the table's forward rule at T -+ fd_step_T (ValueError where the step leaves the table). The table
+    is piecewise in T: a layer exactly on a T node takes the slope of the cell the forward run used, the cell to its right
+    (to its left on the last node). A species of wrt must lie inside its table in every layer, also where its mixing
+    ratio is 0. xs_derivatives=True without an xs_lut is the plain call, bit for bit.
     continuum= (as compute_TUD takes it) is refused (NotImplementedError) unless continuum_derivatives=True; then the
     call is differentiated through the continuum: the base outputs are compute_TUD(continuum=)'s bit for
     bit, "fd" takes the continuum at T -+ fd_step_T with the line-sums, "analytic" its closed-form dOD/dT. With a
@@ -729,9 +747,10 @@ def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, redu
     continuum_derivatives=True without a continuum is the plain call, bit for bit. ValueError, before any device work,
     for a component whose molecule MFs_ID lacks."""
     c = _Call("compute_TUD_jacobian", Xmin, Xmax, opts, kwargs)
-    _no_xs_lut(c)
+    lut = _no_xs_lut(c, xs_derivatives)
     cont = _derivative_continuum(c, continuum_derivatives)
     wrt, lay, _ = _jacobian_args(c.fn, Xmin, Xmax, c.o, wrt, layers, reduce, fd_step_T, dT_method=dT_method)
+    _xs_axis(c, lut)
     X_, grid = c.X, c.grid
     tbl = c.table()
     nZ = c.Z_s.size
@@ -759,7 +778,7 @@ def compute_TUD_jacobian(Xmin, Xmax, opts=options, wrt=("T",), layers=None, redu
     tau, Lu, Ld, _, _ = engine.tud_jacobian(tbl, grid, c.Z, c.T, c.P, c.PL, c.MF, c.ID, Altitudes=c.Z_s, theta_r=c.theta,
                                              N_angle=c.N_angle, returnOD=c.returnOD, wrt=wrt, layers=lay,
                                              fd_step_T=float(fd_step_T), on_block=on_block, dT_method=dT_method,
-                                             continuum=cont)
+                                             continuum=cont, xs_lut=lut)
     if red is not None:
         rows = torch.cat([tau, Lu, Ld[None, :]])
         X_out, r = engine.reduce_resolution_cached(rows, x0, grid.step, grid.n, red["dX"], N=red["N"], window=red["window"])
@@ -819,7 +838,7 @@ def _vjp_cotangents(cotangents, nX, nZ):
 
 
 def compute_TUD_vjp(Xmin, Xmax, cotangents, opts=options, wrt=("T",), layers=None, fd_step_T=0.5, dT_method="fd",
-                    continuum_derivatives=False, **kwargs):
+                    continuum_derivatives=False, xs_derivatives=False, **kwargs):
     """compute_TUD and the gradient of a scalar cost of its outputs with respect to layer temperatures and mixing ratios:
     the transpose of compute_TUD_jacobian's J applied to the cost's cotangents, without J ever being stored (reverse mode;
     DESIGN 4.16).
@@ -842,14 +861,18 @@ def compute_TUD_vjp(Xmin, Xmax, cotangents, opts=options, wrt=("T",), layers=Non
     continuum=, continuum_derivatives: as compute_TUD_jacobian (refused unless continuum_derivatives=True; then OD is not
     linear in a mixing ratio, a species entry is the local derivative at the state per ppmv, and where a continuum
     component's interpolated sum is <= 0 its derivatives are 0: the kink of max(0, .) is given the value 0).
-    Arguments are checked before any device work. NotImplementedError: more than one theta_r, broadening=, xs_lut=."""
+    xs_lut=, xs_derivatives: as compute_TUD_jacobian (refused unless xs_derivatives=True; then every column comes from the
+    cross-section table, DESIGN 4.24, and a layer exactly on a T node takes the slope of the cell to its right, to its left
+    on the last node).
+    Arguments are checked before any device work. NotImplementedError: more than one theta_r, broadening=, xs_lut= by default."""
     c = _Call("compute_TUD_vjp", Xmin, Xmax, opts, kwargs)
     if "reduce" in c.o:
         raise NotImplementedError("compute_TUD_vjp: reduce= is not offered: map the cotangent to the native grid with the "
                                   "transpose of the reduction and pass that")
-    _no_xs_lut(c)
+    lut = _no_xs_lut(c, xs_derivatives)
     cont = _derivative_continuum(c, continuum_derivatives)
     wrt, lay, nX = _jacobian_args(c.fn, Xmin, Xmax, c.o, wrt, layers, None, fd_step_T, host_result=False, dT_method=dT_method)
+    _xs_axis(c, lut)
     nZ = c.Z_s.size
     G, n_vec = _vjp_cotangents(cotangents, nX, nZ)
     X_, grid = c.X, c.grid
@@ -858,7 +881,7 @@ def compute_TUD_vjp(Xmin, Xmax, cotangents, opts=options, wrt=("T",), layers=Non
     tau, Lu, Ld, _, grad = engine.tud_vjp(tbl, grid, c.Z, c.T, c.P, c.PL, c.MF, c.ID, G_tau=G.get("tau"), G_Lu=G.get("La"),
                                           G_Ld=G.get("Ld"), Altitudes=c.Z_s, theta_r=c.theta, N_angle=c.N_angle,
                                           returnOD=c.returnOD, wrt=wrt, layers=lay, fd_step_T=float(fd_step_T), dT_method=dT_method,
-                                          continuum=cont)
+                                          continuum=cont, xs_lut=lut)
     (tau_h, Lu_h, Ld_h), done = _rows_to_host_f64([tau, Lu, Ld[None, :]])
     grad_h = grad.cpu().numpy()  # [n_vec][n_wrt][n_layers]
     done.synchronize()
@@ -888,7 +911,7 @@ def _jvp_tangents(tangents, n_lay, fn="compute_TUD_jvp"):
 
 
 def compute_TUD_jvp(Xmin, Xmax, tangents, opts=options, layers=None, rows=("tau", "La", "Ld"), fd_step_T=0.5, dT_method="fd",
-                    continuum_derivatives=False, **kwargs):
+                    continuum_derivatives=False, xs_derivatives=False, **kwargs):
     """compute_TUD and the change of its outputs along directions in (layer temperatures, mixing ratios): compute_TUD_jacobian's
     J applied to tangent vectors, without J ever being stored (forward mode). The result is spectra, 2 nAlt + 1
     rows per vector: it fits where J does not.
@@ -907,11 +930,14 @@ def compute_TUD_jvp(Xmin, Xmax, tangents, opts=options, layers=None, rows=("tau"
     continuum=, continuum_derivatives: as compute_TUD_jacobian (refused unless continuum_derivatives=True; then OD is not
     linear in a mixing ratio, a species entry is the local derivative at the state per ppmv, and where a continuum
     component's interpolated sum is <= 0 its derivatives are 0: the kink of max(0, .) is given the value 0).
-    Arguments are checked before any device work. NotImplementedError: more than one theta_r, broadening=, xs_lut=."""
+    xs_lut=, xs_derivatives: as compute_TUD_jacobian (refused unless xs_derivatives=True; then every column comes from the
+    cross-section table, DESIGN 4.24, and a layer exactly on a T node takes the slope of the cell to its right, to its left
+    on the last node).
+    Arguments are checked before any device work. NotImplementedError: more than one theta_r, broadening=, xs_lut= by default."""
     c = _Call("compute_TUD_jvp", Xmin, Xmax, opts, kwargs)
     if "reduce" in c.o:
         raise NotImplementedError("compute_TUD_jvp: reduce= is not offered: the results are spectra, pass them to reduceResolution")
-    _no_xs_lut(c)
+    lut = _no_xs_lut(c, xs_derivatives)
     cont = _derivative_continuum(c, continuum_derivatives)
     if isinstance(tangents, dict) and tangents:
         wrt = tuple(tangents.keys())
@@ -921,6 +947,7 @@ def compute_TUD_jvp(Xmin, Xmax, tangents, opts=options, layers=None, rows=("tau"
     else:
         raise ValueError("compute_TUD_jvp: tangents must be a non-empty dict {\"T\" or a molecule id of MFs_ID: array}")
     wrt, lay, nX = _jacobian_args(c.fn, Xmin, Xmax, c.o, wrt, layers, None, fd_step_T, host_result=False, dT_method=dT_method)
+    _xs_axis(c, lut)
     if isinstance(rows, str):
         rows = (rows,)
     rows = tuple(rows)
@@ -933,7 +960,7 @@ def compute_TUD_jvp(Xmin, Xmax, tangents, opts=options, layers=None, rows=("tau"
     tbl = c.table()
     tau, Lu, Ld, _, d = engine.tud_jvp(tbl, grid, c.Z, c.T, c.P, c.PL, c.MF, c.ID, V, Altitudes=c.Z_s, theta_r=c.theta,
                                        N_angle=c.N_angle, returnOD=c.returnOD, wrt=wrt, layers=lay, fd_step_T=float(fd_step_T),
-                                       rows=rows, dT_method=dT_method, continuum=cont)
+                                       rows=rows, dT_method=dT_method, continuum=cont, xs_lut=lut)
     (tau_h, Lu_h, Ld_h), done = _rows_to_host_f64([tau, Lu, Ld[None, :]])
     d_h = {name: t.to(torch.float64).cpu().numpy() for name, t in d.items()}  # [n_vec]([nZ])[nX]
     done.synchronize()
@@ -950,7 +977,7 @@ def compute_TUD_jvp(Xmin, Xmax, tangents, opts=options, layers=None, rows=("tau"
 
 
 def compute_band_radiance_vjp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, cotangent, opts=options, wrt=("T",), layers=None,
-                              fd_step_T=0.5, dT_method="fd", continuum_derivatives=False, **kwargs):
+                              fd_step_T=0.5, dT_method="fd", continuum_derivatives=False, xs_derivatives=False, **kwargs):
     """At-sensor band radiances over a surface and the gradient of a scalar cost defined on them, in one call: the
     line-sums (base, T -+ fd_step_T, each species of wrt), compute_TUD's tau / La / Ld, the band radiances of
     sensor.band_radiance_srf_fused under the sensor's response tables, their adjoint (sensor.band_radiance_srf_vjp) and
@@ -970,19 +997,23 @@ def compute_band_radiance_vjp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, co
     continuum=, continuum_derivatives: as compute_TUD_jacobian (refused unless continuum_derivatives=True; then OD is not
     linear in a mixing ratio, a species entry is the local derivative at the state per ppmv, and where a continuum
     component's interpolated sum is <= 0 its derivatives are 0: the kink of max(0, .) is given the value 0).
+    xs_lut=, xs_derivatives: as compute_TUD_jacobian (refused unless xs_derivatives=True; then every column comes from the
+    cross-section table, DESIGN 4.24, and a layer exactly on a T node takes the slope of the cell to its right, to its left
+    on the last node).
     Arguments are checked before any device work. NotImplementedError: more than one altitude or theta_r, returnOD=True,
-    broadening=, xs_lut=, reduce=."""
+    broadening=, xs_lut= by default, reduce=."""
     name = "compute_band_radiance_vjp"
     c = _Call(name, Xmin, Xmax, opts, kwargs)
     if "reduce" in c.o:
         raise NotImplementedError(name + ": reduce= is not offered: the cost is defined on the sensor's bands")
-    _no_xs_lut(c)
+    lut = _no_xs_lut(c, xs_derivatives)
     cont = _derivative_continuum(c, continuum_derivatives)
     if c.returnOD:
         raise NotImplementedError(name + ": returnOD=True is not supported (the sensor stage takes transmittances)")
     if c.Z_s.size != 1:
         raise NotImplementedError(name + ": exactly one sensor altitude per call (got %d)" % c.Z_s.size)
     wrt, lay, nX = _jacobian_args(name, Xmin, Xmax, c.o, wrt, layers, None, fd_step_T, host_result=False, dT_method=dT_method)
+    _xs_axis(c, lut)
     Xk = np.ascontiguousarray(np.asarray(Xk, dtype=np.float64).ravel())
     scalar = np.ndim(Ts_surface) == 0
     Ts_s = np.atleast_1d(np.asarray(Ts_surface, dtype=np.float64))
@@ -1026,7 +1057,7 @@ def compute_band_radiance_vjp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, co
 
     _, _, _, _, grad = engine.tud_vjp(tbl, grid, c.Z, c.T, c.P, c.PL, c.MF, c.ID, Altitudes=c.Z_s, theta_r=c.theta,
                                       N_angle=c.N_angle, returnOD=False, wrt=wrt, layers=lay, fd_step_T=float(fd_step_T),
-                                      cotangents=sensor_stage, dT_method=dT_method, continuum=cont)
+                                      cotangents=sensor_stage, dT_method=dT_method, continuum=cont, xs_lut=lut)
     L_h = kept["L"].cpu().numpy()
     dTs_h = torch.stack(kept["Ts"], dim=-1).cpu().numpy()    # Ts_surface's shape + [n_vec]
     dE_h = torch.stack(kept["emis"], dim=-1).cpu().numpy()   # [nk][nE][n_vec]
@@ -1040,7 +1071,7 @@ _SURFACE_TANGENTS = ("Ts_surface", "emis")
 
 
 def compute_band_radiance_jvp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, tangents, opts=options, layers=None, fd_step_T=0.5,
-                              dT_method="fd", continuum_derivatives=False, **kwargs):
+                              dT_method="fd", continuum_derivatives=False, xs_derivatives=False, **kwargs):
     """At-sensor band radiances over a surface and their change along directions in the unknowns of a retrieval, in one
     call: compute_TUD_jvp's tangent rows of tau / La / Ld (engine.tud_jvp), which stay on the device as float32, fed to the
     sensor stage's tangent (sensor.band_radiance_srf_jvp), which adds the surface temperature and the emissivity knots. No
@@ -1060,13 +1091,16 @@ def compute_band_radiance_jvp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, ta
     continuum=, continuum_derivatives: as compute_TUD_jacobian (refused unless continuum_derivatives=True; then OD is not
     linear in a mixing ratio, a species entry is the local derivative at the state per ppmv, and where a continuum
     component's interpolated sum is <= 0 its derivatives are 0: the kink of max(0, .) is given the value 0).
+    xs_lut=, xs_derivatives: as compute_TUD_jacobian (refused unless xs_derivatives=True; then every column comes from the
+    cross-section table, DESIGN 4.24, and a layer exactly on a T node takes the slope of the cell to its right, to its left
+    on the last node).
     Arguments are checked before any device work. NotImplementedError: more than one altitude or theta_r, returnOD=True,
-    broadening=, xs_lut=, reduce=."""
+    broadening=, xs_lut= by default, reduce=."""
     name = "compute_band_radiance_jvp"
     c = _Call(name, Xmin, Xmax, opts, kwargs)
     if "reduce" in c.o:
         raise NotImplementedError(name + ": reduce= is not offered: the tangent is defined on the sensor's bands")
-    _no_xs_lut(c)
+    lut = _no_xs_lut(c, xs_derivatives)
     cont = _derivative_continuum(c, continuum_derivatives)
     if c.returnOD:
         raise NotImplementedError(name + ": returnOD=True is not supported (the sensor stage takes transmittances)")
@@ -1084,6 +1118,7 @@ def compute_band_radiance_jvp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, ta
     wrt_, lay, nX = _jacobian_args(name, Xmin, Xmax, c.o, wrt if wrt else ("T",), layers, None, fd_step_T if wrt else 1.0,
                                    host_result=False, dT_method=dT_method)
     wrt = wrt_ if wrt else ()
+    _xs_axis(c, lut)
     Xk = np.ascontiguousarray(np.asarray(Xk, dtype=np.float64).ravel())
     scalar = np.ndim(Ts_surface) == 0
     Ts_s = np.atleast_1d(np.asarray(Ts_surface, dtype=np.float64))
@@ -1133,7 +1168,7 @@ def compute_band_radiance_jvp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, ta
     if atm:
         tau, Lu, Ld, _, d = engine.tud_jvp(tbl, grid, c.Z, c.T, c.P, c.PL, c.MF, c.ID, V, Altitudes=c.Z_s, theta_r=c.theta,
                                            N_angle=c.N_angle, returnOD=False, wrt=wrt, layers=lay, fd_step_T=float(fd_step_T),
-                                           dT_method=dT_method, continuum=cont)
+                                           dT_method=dT_method, continuum=cont, xs_lut=lut)
         # [n_vec][nX] float32 where rtx_tud_jvp wrote them, seen as [nX][n_vec]: no copy, no host round trip
         rows = dict(d_tau=d["tau"][:, 0, :nX].T, d_La=d["La"][:, 0, :nX].T, d_Ld=d["Ld"][:, :nX].T)
         if n_vec is None:
@@ -1141,7 +1176,7 @@ def compute_band_radiance_jvp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, ta
     else:  # the base state alone, exactly what compute_TUD runs
         T = np.ascontiguousarray(np.atleast_1d(c.T))
         run = engine.TudRunner(tbl, grid, np.atleast_1d(c.Z), n_layers=T.size, Altitudes=c.Z_s, theta_r=c.theta, N_angle=c.N_angle,
-                               returnOD=False, continuum=cont)
+                               returnOD=False, continuum=cont, xs_lut=lut)
         tau, Lu, Ld = run.run(T, np.atleast_1d(c.P), np.atleast_1d(c.PL), c.MF.reshape(T.size, -1), c.ID)
     t_, u_, d_ = tau[0, :nX].contiguous(), Lu[0, :nX].contiguous(), Ld[:nX].contiguous()
     L, dL = _sensor.band_radiance_srf_jvp(grid, t_, u_, d_, Xk, E_d, float(Ts_s[0]) if scalar else Ts_s, sensor, d_Ts=d_Ts,
