@@ -654,6 +654,55 @@ int rtx_srf_pixel_cube(int nB, int Q, const double* T_node_h, const float* N, co
                        const float* frac, const double* Tpix, float* cube, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Adjoint of rtx_srf_pixel_cube: J^T g for the pixels' temperatures and fractions and for the band
+ * radiances of the pure endmembers at the nodes, without a Jacobian and without anything of size
+ * nPix x nX or nPix x nk. With N, tab = G and l_q as above the cube is a linear combination of band
+ * radiances,
+ *   cube[b][p] = sum_m f_pm sum_q l_q(T_p) L[q][b][k_pm] + (1 - sum_m f_pm) L0[b],
+ *   L[q][b][e] = (C_b + G[e][q][b]) / N_b,   L0[b] = C_b / N_b   (emissivity 0; sum_q l_q = 1),
+ * so with u_bp = g[b][p] on a live band (N_b > 0) and an admitted pixel (T_p finite and inside
+ * [T_lo, T_hi]) and u_bp = 0 otherwise -- a select, not a product: a NaN in g under a dead band or a
+ * refused pixel does not spread --
+ *   dfrac[p][m] = sum_b (u_bp / N_b) sum_q l_q(T_p)  G[k_pm][q][b]
+ *   dT[p]       = sum_b (u_bp / N_b) sum_m f_pm sum_q l'_q(T_p) G[k_pm][q][b]
+ *   gL[q][b][e] = sum_p u_bp l_q(T_p) sum_{m: k_pm = e} f_pm                      (e < nEnd)
+ *   gL[0][b][nEnd] = sum_p u_bp (1 - sum_m f_pm),  gL[q > 0][b][nEnd] = 0         (the cotangent of L0)
+ * with l'_q(T) = sum_{s != q} prod_{r != q, s} (T - T_r) / den_q and k_pm clamped to [0, nEnd) as the
+ * forward clamps it. gL [Q][nB][nEnd + 1] is the cotangent rtx_srf_radiance_vjp takes with Ts = the Q
+ * nodes and E' = [E | 0] (one added column of zero emissivity): its rows are G_tau / G_La / G_Ld of the
+ * cube, the first nEnd columns of its dE the gradient of the endmember knots.
+ *   nB, Q, T_node_h, N, tab, nEnd, nPix, nMix, kidx, frac, Tpix: as rtx_srf_pixel_cube (C is not needed);
+ *   g [nB][nPix] float32 DEVICE; dT [nPix] fp64, dfrac [nPix][nMix] fp64, gL [Q][nB][nEnd + 1] float32
+ *   DEVICE, each may be NULL (not computed), not all three.
+ * A pixel that is not admitted gets NaN in its own dT and dfrac (the forward gave it a NaN column) and
+ * adds exact zeros to gL; a dead band adds nothing anywhere.
+ * Refused before anything is launched, nothing written: everything rtx_srf_pixel_cube refuses, a NULL g,
+ * all three outputs NULL, flags != 0. nB == 0 or nPix == 0 writes zeros to the outputs given and returns 0.
+ * Arithmetic: l_q and l'_q in fp64 from the nodes and the host's denominators, products over r
+ * ascending (l'_q: the sum over s ascending of such products), one fp64 division, one rounding to fp32:
+ * l_q has rtx_srf_pixel_cube's bits, so a pixel on a node has the weights 1 and 0. The inner sums over q
+ * are fp32 fmaf chains over the table, q ascending: t = sum_q l_q G, t' = sum_q l'_q G. Everything after
+ * that is fp64: x = (double)u * (1 / (double)N_b); dfrac's term x t; dT's term x sum_m f_m t'_m (m
+ * ascending, each product exact); gL's term u (l_q f_m) (the inner product exact). A mixture of more
+ * than 4 is taken 4 slots at a time and dT adds the passes' band sums in pass order. gL is rounded to
+ * fp32 once, at the store. No atomics.
+ * Determinism: dT[p] and dfrac[p][:] are pure functions of (pixel p's kidx, frac, T and column of g; the
+ * bands; the nodes and the range): the same bits for any nPix, any position of the pixel in the scene,
+ * whatever other outputs are asked for, and whether the table slice is held in LDS (nEnd * Q <= 128) or
+ * read from global memory. The sum over the bands runs over the 64 lanes of a block of 64 bands along the
+ * xor tree of rtx_srf_radiance_vjp's dTs sum (distance 1, 2, 4, .. 32), then over the blocks ascending.
+ * gL has the same bits run to run for a given scene: within a chunk of pixels a table row takes its
+ * pixels ascending (a pixel's slots ascending; a mixture of more than 8 is taken 8 slots at a time per
+ * group of 64 pixels), then the chunks are added ascending; a chunk is 256 pixels, doubled until the
+ * chunk sums ([chunks][nEnd + 1][Q][nB] fp64) fit 64 MiB. Calls on one stream share a grow-only
+ * workspace, owned per (device, stream); a call that has to grow it waits for the device first.
+ * flags: none is defined, pass 0 (anything else is refused). */
+int rtx_srf_pixel_cube_vjp(int nB, int Q, const double* T_node_h, const float* N, const float* tab,
+                           int nEnd, int64_t nPix, int nMix, const int32_t* kidx, const float* frac,
+                           const double* Tpix, const float* g, double* dT, double* dfrac, float* gL,
+                           void* stream, unsigned flags);
+
+/* ------------------------------------------------------------------------------------------
  * Speed-dependent Voigt line-sum. Replaces the per-line PROFILE_SDVOIGT + scatter-add of
  * absorptionCoefficient_SDVoigt, misc/hapi.py:10897-10900 (PROFILE_SDVOIGT :10117 -> pcqsdhc :9850-10024 with
  * anuVC = eta = 0: PART1 for lines without speed dependence, PART2/3/4 otherwise; CPF = hum1_wei :9833, cpf3 :9645),

@@ -1067,6 +1067,83 @@ def compute_band_radiance_vjp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, co
     return np.array(sensor.centres), L_h, out
 
 
+def compute_hsi_cube_vjp(Xmin, Xmax, sensor, Xk, endmembers, kidx, frac, Tpix, cotangent, opts=options, wrt=("T",), layers=None,
+                         fd_step_T=0.5, dT_method="fd", continuum_derivatives=False, xs_derivatives=False, n_nodes=8, T_range=None,
+                         interp_tol=1e-6, **kwargs):
+    """The per-pixel HSI cube of a scene under any sensor and the gradient of a scalar cost defined on it, in one call:
+    the line-sums, compute_TUD's tau / La / Ld, sensor.hsi_cube_srf's cube, its adjoint (sensor.hsi_cube_srf_vjp) and
+    compute_TUD_vjp's adjoint on the native-grid cotangents that gives, which stay on the device. No Jacobian and nothing
+    of size nPix x nX is stored.
+
+    sensor: a sensor.Sensor; Xk [nk] the emissivity knots [cm^-1]; endmembers [nk][nEnd] (float32), kidx [nPix][nMix]
+    (integers), frac [nPix][nMix] (float32), Tpix [nPix] (float64): the scene, NumPy or torch tensors, as hsi_cube_srf takes
+    it; n_nodes, T_range, interp_tol as there (T_range=None: the smallest and largest finite Tpix). cotangent = d cost /
+    d cube, [nB][nPix]: one vector per call. kwargs, wrt, layers, fd_step_T, dT_method as compute_TUD_vjp, with exactly one
+    sensor altitude and returnOD=False. Returns (X_out, cube, grad):
+      X_out  sensor.centres;
+      cube   float32 NumPy [nB][nPix], bit-identical to hsi_cube_srf on compute_TUD's outputs;
+      grad   {wrt entry: float64 [n_layers]} as compute_TUD_vjp returns them, plus "Tpix" [nPix], "frac" [nPix][nMix] and
+             "endmembers" [nk][nEnd], float64.
+    continuum=, continuum_derivatives, xs_lut=, xs_derivatives: as compute_band_radiance_vjp.
+    Arguments are checked before any device work. NotImplementedError: more than one altitude or theta_r, returnOD=True,
+    broadening=, xs_lut= or continuum= without their derivative flags, reduce=. ValueError: a cotangent that is not
+    [nB][nPix] (a trailing vector axis is not offered)."""
+    name = "compute_hsi_cube_vjp"
+    c = _Call(name, Xmin, Xmax, opts, kwargs)
+    if "reduce" in c.o:
+        raise NotImplementedError(name + ": reduce= is not offered: the cost is defined on the sensor's bands")
+    lut = _no_xs_lut(c, xs_derivatives)
+    cont = _derivative_continuum(c, continuum_derivatives)
+    if c.returnOD:
+        raise NotImplementedError(name + ": returnOD=True is not supported (the sensor stage takes transmittances)")
+    if c.Z_s.size != 1:
+        raise NotImplementedError(name + ": exactly one sensor altitude per call (got %d)" % c.Z_s.size)
+    wrt, lay, nX = _jacobian_args(name, Xmin, Xmax, c.o, wrt, layers, None, fd_step_T, host_result=False, dT_method=dT_method)
+    _xs_axis(c, lut)
+    from . import sensor as _sensor  # sensor.py imports this module
+
+    def host(v, what, kinds, dtype):
+        a = v.detach().cpu().numpy() if _is_torch(v) else np.asarray(v)
+        if a.dtype.kind not in kinds:
+            raise ValueError(name + ": %s has dtype %s" % (what, a.dtype))
+        return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype))
+
+    Xk = np.ascontiguousarray(np.asarray(Xk, dtype=np.float64).ravel())
+    E_h, k_h = host(endmembers, "endmembers", "f", np.float32), host(kidx, "kidx", "iu", np.int32)
+    f_h, T_h = host(frac, "frac", "f", np.float32), host(Tpix, "Tpix", "f", np.float64)
+    g_h = host(cotangent, "cotangent", "f", np.float32)
+    if k_h.dim() == 2 and g_h.dim() == 3 and tuple(g_h.shape[:2]) == (len(sensor), k_h.shape[0]):
+        raise ValueError(name + ": one cotangent vector per call: cotangent has shape %r, expected %r"
+                         % (tuple(g_h.shape), (len(sensor), k_h.shape[0])))
+    z = torch.zeros(nX, dtype=torch.float32)  # stands for tau, La, Ld in the checks
+    grid = c.grid
+    assert c.X.size == nX
+    front = _sensor._srf_cube_front(name, grid, z, z, z, Xk, E_h, k_h, f_h, T_h, sensor, n_nodes, T_range, interp_tol, g=g_h,
+                                    need_device=False)
+    T_range = (front["T_lo"], front["T_hi"])  # explicit from here on: no read from the device
+    tbl = c.table()
+    dev = engine.device()
+    E_d, k_d, f_d, T_d, g_d = (v.to(dev) for v in (E_h, k_h, f_h, T_h, g_h))
+    kept = {}
+
+    def sensor_stage(tau, Lu, Ld):
+        t_, u_, d_ = tau[0, :nX].contiguous(), Lu[0, :nX].contiguous(), Ld[:nX].contiguous()
+        _, kept["cube"] = _sensor.hsi_cube_srf(grid, t_, u_, d_, Xk, E_d, k_d, f_d, T_d, sensor, n_nodes=n_nodes, T_range=T_range,
+                                               interp_tol=interp_tol)
+        r = _sensor.hsi_cube_srf_vjp(grid, t_, u_, d_, Xk, E_d, k_d, f_d, T_d, sensor, g_d, n_nodes=n_nodes, T_range=T_range,
+                                     interp_tol=interp_tol)
+        kept.update({k: r[k] for k in ("Tpix", "frac", "endmembers")})
+        return [r["G_tau"].reshape(1, 1, nX), r["G_La"].reshape(1, 1, nX), r["G_Ld"].reshape(1, nX)]
+
+    _, _, _, _, grad = engine.tud_vjp(tbl, grid, c.Z, c.T, c.P, c.PL, c.MF, c.ID, Altitudes=c.Z_s, theta_r=c.theta,
+                                      N_angle=c.N_angle, returnOD=False, wrt=wrt, layers=lay, fd_step_T=float(fd_step_T),
+                                      cotangents=sensor_stage, dT_method=dT_method, continuum=cont, xs_lut=lut)
+    out = _grad_dict(grad.cpu().numpy(), wrt, None)
+    for k in ("Tpix", "frac", "endmembers"):
+        out[k] = kept[k].cpu().numpy()
+    return np.array(sensor.centres), kept["cube"].cpu().numpy(), out
+
+
 _SURFACE_TANGENTS = ("Ts_surface", "emis")
 
 

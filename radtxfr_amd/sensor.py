@@ -619,22 +619,13 @@ def planck_node_error(x_hi, T_lo, T_hi, n_nodes, samples=2001):
     return float(np.max(np.abs(interp - B)) / np.max(B))
 
 
-def hsi_cube_srf(grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sensor, n_nodes=8, T_range=None, interp_tol=1e-6):
-    """hsi_cube() for any sensor: band radiances of an HSI cube whose pixels each have an emissivity mixture and a surface
-    temperature of their own, under the sensor's tabulated responses, whatever their width. The Planck function is
-    interpolated in TEMPERATURE through n_nodes Chebyshev nodes of T_range (hsi_cube interpolates in wavenumber across a
-    band, which holds for MAKO-narrow bands only). Arguments as hsi_cube(), with a Sensor in place of resFactor.
-
-    T_range = (T_lo, T_hi) [K]: the range the nodes span. None: the smallest and largest finite Tpix, read from the device
-    -- ONE synchronisation; an explicit range avoids it. A range narrower than 1 K is widened symmetrically to 1 K (the
-    nodes of a one-temperature scene stay distinct). A pixel whose temperature is not finite or lies outside the range is
-    NaN in every band: there is no extrapolation and no check on the device's side.
-    interp_tol: the call raises ValueError, before any device work, when planck_node_error(grid's highest wavenumber,
-    T_lo, T_hi, n_nodes) exceeds it (8 nodes over 230-350 K at 1400 cm^-1: 5.5e-8; 4 nodes: 3.9e-4).
-
-    Returns (X_out [nB] NumPy = sensor.centres, cube [nB][nPix] float32 device); a band with no grid point under it is NaN.
-    Three stages: srf_moments at the node temperatures (the one pass over tau / La / Ld per group of 16 bands),
-    rtx_srf_cube_tables (its n_nodes moment arrays x the endmember knots), rtx_srf_pixel_cube."""
+def _srf_cube_front(fn, grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sensor, n_nodes, T_range, interp_tol, g=None,
+                    need_device=True):
+    """The front half hsi_cube_srf and hsi_cube_srf_vjp share: the argument checks, the temperature range (T_range=None:
+    one read from the device), the interpolation estimate and the nodes. Everything up to the estimate runs before any
+    device work. g: the cotangent of the adjoint, checked against the cube's shape [nB][nPix]. need_device=False: host
+    tensors pass (a caller that validates before it has device arrays). Returns a dict: Q, Xk, T_lo, T_hi, nodes, and
+    endmembers, kidx, frac, Tpix contiguous."""
     lib = _lib.load()
     Q = int(n_nodes)
     Q_max = lib.rtx_srf_cube_max_nodes()
@@ -653,9 +644,11 @@ def hsi_cube_srf(grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sensor, n_
     for name, v in (("tau", tau), ("La", La), ("Ld", Ld)):
         if v.dtype != torch.float32 or v.numel() != grid.n:
             raise ValueError(f"{name}: float32 [grid.n = {grid.n}], got {v.dtype} {tuple(v.shape)}")
+    if g is not None and (tuple(g.shape) != (len(sensor), nPix) or g.dtype != torch.float32):
+        raise ValueError(f"g: float32 [nB = {len(sensor)}][nPix = {nPix}] like the cube, got {g.dtype} {tuple(g.shape)}")
     if T_range is None:
-        if not Tpix.is_cuda:
-            raise ValueError("hsi_cube_srf takes device tensors (Tpix is not on a GPU)")
+        if need_device and not Tpix.is_cuda:
+            raise ValueError(f"{fn} takes device tensors (Tpix is not on a GPU)")
         fin = torch.isfinite(Tpix)
         inf = torch.full_like(Tpix, float("inf"))
         ends = torch.stack([torch.where(fin, Tpix, inf).min(), torch.where(fin, Tpix, -inf).max()]).cpu().numpy() if nPix else None
@@ -671,30 +664,129 @@ def hsi_cube_srf(grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sensor, n_
         T_lo, T_hi = mid - 0.5, mid + 0.5
     est = planck_node_error(float(grid.x_at(grid.n - 1)), T_lo, T_hi, Q)
     if not est <= interp_tol:
-        raise ValueError(f"hsi_cube_srf: interpolating Planck through {Q} nodes over [{T_lo:g}, {T_hi:g}] K is off by an estimated "
+        raise ValueError(f"{fn}: interpolating Planck through {Q} nodes over [{T_lo:g}, {T_hi:g}] K is off by an estimated "
                          f"{est:.3g} of the largest B at {grid.x_at(grid.n - 1):g} cm^-1, above interp_tol={interp_tol:g}: narrow "
                          "T_range, raise n_nodes or split the scene by temperature")
-    for name, v in (("tau", tau), ("endmembers", endmembers), ("kidx", kidx), ("frac", frac), ("Tpix", Tpix)):
-        if not v.is_cuda:
-            raise ValueError(f"hsi_cube_srf takes device tensors ({name} is not on a GPU)")
-    dev = tau.device
+    if need_device:
+        for name, v in (("tau", tau), ("endmembers", endmembers), ("kidx", kidx), ("frac", frac), ("Tpix", Tpix)):
+            if not v.is_cuda:
+                raise ValueError(f"{fn} takes device tensors ({name} is not on a GPU)")
     endmembers, kidx, frac, Tpix = (v.contiguous() for v in (endmembers, kidx, frac, Tpix))
-    nodes = srf_cube_nodes(T_lo, T_hi, Q)
-    X_out = np.array(sensor.centres)
+    return dict(Q=Q, Xk=Xk, T_lo=T_lo, T_hi=T_hi, nodes=srf_cube_nodes(T_lo, T_hi, Q), endmembers=endmembers, kidx=kidx, frac=frac,
+                Tpix=Tpix)
+
+
+def _srf_cube_tables(grid, tau, La, Ld, f, sensor):
+    """Stages 1 and 2 of hsi_cube_srf on the front half's dict f: (N, C, tab [nEnd][Q][nB], T_host = the nodes, then the range)."""
+    lib = _lib.load()
+    dev = tau.device
+    Q, Xk, endmembers = f["Q"], f["Xk"], f["endmembers"]
     nB, nk, nEnd = len(sensor), Xk.size, endmembers.shape[1]
-    cube = torch.empty((nB, nPix), dtype=torch.float32, device=dev)
-    if nB == 0 or nPix == 0:
-        return X_out, cube
     plan = _srf_fused_plan(Xk, dev)
-    N, Cb, M, jr = srf_moments(grid, tau, La, Ld, plan["Xk_d"], nodes, sensor)
+    N, Cb, M, jr = srf_moments(grid, tau, La, Ld, plan["Xk_d"], f["nodes"], sensor)
     tab = torch.empty((nEnd, Q, nB), dtype=torch.float32, device=dev)
-    T_host = np.ascontiguousarray(np.concatenate([nodes, [T_lo, T_hi]]))  # the nodes, then the range
+    T_host = np.ascontiguousarray(np.concatenate([f["nodes"], [f["T_lo"], f["T_hi"]]]))  # the nodes, then the range
     p = lambda t: C.c_void_p(t.data_ptr())
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     _lib.check(lib.rtx_srf_cube_tables(p(M), p(jr), nB, Q, nk, p(endmembers), nEnd, p(tab), st))
+    return N, Cb, tab, T_host
+
+
+def hsi_cube_srf(grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sensor, n_nodes=8, T_range=None, interp_tol=1e-6):
+    """hsi_cube() for any sensor: band radiances of an HSI cube whose pixels each have an emissivity mixture and a surface
+    temperature of their own, under the sensor's tabulated responses, whatever their width. The Planck function is
+    interpolated in TEMPERATURE through n_nodes Chebyshev nodes of T_range (hsi_cube interpolates in wavenumber across a
+    band, which holds for MAKO-narrow bands only). Arguments as hsi_cube(), with a Sensor in place of resFactor.
+
+    T_range = (T_lo, T_hi) [K]: the range the nodes span. None: the smallest and largest finite Tpix, read from the device
+    -- ONE synchronisation; an explicit range avoids it. A range narrower than 1 K is widened symmetrically to 1 K (the
+    nodes of a one-temperature scene stay distinct). A pixel whose temperature is not finite or lies outside the range is
+    NaN in every band: there is no extrapolation and no check on the device's side.
+    interp_tol: the call raises ValueError, before any device work, when planck_node_error(grid's highest wavenumber,
+    T_lo, T_hi, n_nodes) exceeds it (8 nodes over 230-350 K at 1400 cm^-1: 5.5e-8; 4 nodes: 3.9e-4).
+
+    Returns (X_out [nB] NumPy = sensor.centres, cube [nB][nPix] float32 device); a band with no grid point under it is NaN.
+    Three stages: srf_moments at the node temperatures (the one pass over tau / La / Ld per group of 16 bands),
+    rtx_srf_cube_tables (its n_nodes moment arrays x the endmember knots), rtx_srf_pixel_cube."""
+    lib = _lib.load()
+    f = _srf_cube_front("hsi_cube_srf", grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sensor, n_nodes, T_range, interp_tol)
+    dev = tau.device
+    endmembers, kidx, frac, Tpix, Q = f["endmembers"], f["kidx"], f["frac"], f["Tpix"], f["Q"]
+    nPix, nMix = kidx.shape
+    X_out = np.array(sensor.centres)
+    nB, nEnd = len(sensor), endmembers.shape[1]
+    cube = torch.empty((nB, nPix), dtype=torch.float32, device=dev)
+    if nB == 0 or nPix == 0:
+        return X_out, cube
+    N, Cb, tab, T_host = _srf_cube_tables(grid, tau, La, Ld, f, sensor)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     _lib.check(lib.rtx_srf_pixel_cube(nB, Q, T_host.ctypes.data_as(C.c_void_p), p(N), p(Cb), p(tab), nEnd, nPix, nMix, p(kidx), p(frac),
                                       p(Tpix), p(cube), st))
     return X_out, cube
+
+
+_CUBE_VJP_OUTPUTS = ("G_tau", "G_La", "G_Ld", "Tpix", "frac", "endmembers")
+
+
+def hsi_cube_srf_vjp(grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sensor, g, n_nodes=8, T_range=None, interp_tol=1e-6,
+                     outputs=_CUBE_VJP_OUTPUTS):
+    """The adjoint of hsi_cube_srf: from g = d cost / d cube, [nB][nPix] float32 (device or NumPy), to a dict with
+      "Tpix"                   d cost / d Tpix, float64 [nPix] device;
+      "frac"                   d cost / d frac, float64 [nPix][nMix] device;
+      "endmembers"             d cost / d endmembers, float64 [nk][nEnd] device;
+      "G_tau", "G_La", "G_Ld"  d cost / d tau, La, Ld on the native grid, float32 [nX] on tau's device: the cotangents
+                               engine.tud_vjp_from_od takes.
+    Same arguments, checks and nodes as hsi_cube_srf. No Jacobian is stored and nothing of size nPix x nX or nPix x nk is
+    formed: the cube is a linear combination of the band radiances of the pure endmembers (and of a surface of emissivity
+    0) at the node temperatures, so rtx_srf_pixel_cube_vjp gives the pixels' own gradients and the cotangent gL [Q][nB][nEnd + 1]
+    of those radiances, and band_radiance_srf_vjp at Ts = the nodes, E' = [E | 0] takes gL to the rows and the knots.
+    A band that is NaN in the cube contributes nothing, whatever its g holds; a pixel whose temperature is not finite or
+    lies outside the range is NaN in its own "Tpix" and "frac" entries and contributes nothing elsewhere. The gradient
+    with respect to Tpix is that of the interpolant hsi_cube_srf evaluates. outputs: the keys wanted (default all); one
+    left out is not computed, and with "Tpix" and "frac" alone band_radiance_srf_vjp does not run."""
+    lib = _lib.load()
+    outputs = tuple(outputs)
+    if not outputs or any(k not in _CUBE_VJP_OUTPUTS for k in outputs):
+        raise ValueError("outputs: a non-empty selection of %r (got %r)" % (_CUBE_VJP_OUTPUTS, outputs))
+    if not torch.is_tensor(g):
+        g = np.asarray(g)
+        if g.dtype != np.float32:
+            raise ValueError(f"g: float32 like the cube, got {g.dtype} {tuple(g.shape)}")
+        g = torch.as_tensor(np.ascontiguousarray(g))
+    f = _srf_cube_front("hsi_cube_srf_vjp", grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sensor, n_nodes, T_range, interp_tol, g=g)
+    dev = tau.device
+    endmembers, kidx, frac, Tpix, Q = f["endmembers"], f["kidx"], f["frac"], f["Tpix"], f["Q"]
+    nPix, nMix = kidx.shape
+    nB, nk, nEnd, nX = len(sensor), f["Xk"].size, endmembers.shape[1], grid.n
+    back = {"G_tau": "G_tau", "G_La": "G_La", "G_Ld": "G_Ld", "endmembers": "emis"}
+    want_back = tuple(back[k] for k in outputs if k in back)
+    if nB == 0 or nPix == 0:  # the gradient of nothing
+        zero = {"Tpix": ((nPix,), torch.float64), "frac": ((nPix, nMix), torch.float64), "endmembers": ((nk, nEnd), torch.float64),
+                "G_tau": ((nX,), torch.float32), "G_La": ((nX,), torch.float32), "G_Ld": ((nX,), torch.float32)}
+        return {k: torch.zeros(zero[k][0], dtype=zero[k][1], device=dev) for k in outputs}
+    g = g.to(device=dev).contiguous()
+    N, _, tab, T_host = _srf_cube_tables(grid, tau, La, Ld, f, sensor)
+    dT = torch.empty(nPix, dtype=torch.float64, device=dev) if "Tpix" in outputs else None
+    dfrac = torch.empty((nPix, nMix), dtype=torch.float64, device=dev) if "frac" in outputs else None
+    gL = torch.empty((Q, nB, nEnd + 1), dtype=torch.float32, device=dev) if want_back else None
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.check(lib.rtx_srf_pixel_cube_vjp(nB, Q, T_host.ctypes.data_as(C.c_void_p), p(N), p(tab), nEnd, nPix, nMix, p(kidx), p(frac),
+                                          p(Tpix), p(g), p(dT), p(dfrac), p(gL), st, 0))
+    out = {}
+    if dT is not None:
+        out["Tpix"] = dT
+    if dfrac is not None:
+        out["frac"] = dfrac
+    if want_back:
+        E0 = torch.cat([endmembers, torch.zeros((nk, 1), dtype=torch.float32, device=dev)], dim=1)  # [E | 0]
+        r = band_radiance_srf_vjp(grid, tau.contiguous(), La.contiguous(), Ld.contiguous(), f["Xk"], E0, f["nodes"], sensor, gL,
+                                  outputs=want_back)
+        for k in outputs:
+            if k in back:
+                out[k] = r["emis"][:, :nEnd].contiguous() if k == "endmembers" else r[k]
+    return {k: out[k] for k in outputs}
 
 
 def band_radiance(grid, tau, La, Ld, Xk, emis_knots, Ts, resFactor=None, keep_hires=False):
