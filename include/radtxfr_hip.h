@@ -377,6 +377,29 @@ int rtx_compute_tud(rtx_prep* prep, const rtx_lines* lines, const rtx_grid* grid
                     const uint8_t* mask_h, int n_mu, const double* mu_h, int n_down, int n_angle,
                     int return_od, float* OD, int64_t ld_od, float* tau, float* Lu, float* Ld,
                     int64_t ld_out, void* stream);
+/* rtx_compute_tud with promises about what the caller does with its workspace. flags = 0 is rtx_compute_tud, launch for
+ * launch. Unknown bits are refused.
+ * RTX_CTUD_OD_SCRATCH: the caller will not read OD; entries no output depends on are left unwritten. Where the call is
+ * eligible the layers are then summed in two launches around an early TUD launch: first layers [0, 4) and [k_top - 8,
+ * n_layers), k_top = (count - 1) & ~3 with count the layers below the sensor; the TUD waves (64 consecutive points) that an
+ * opaque column lets finish from those layers alone do so; then the layers in between, without those waves' rows -- a
+ * line-sum tile (16 rows of 64 points) whose rows are all done returns before it loads a record; then the TUD pass of the
+ * remaining waves. tau, Lu and Ld are rtx_compute_tud's bit for bit. UNSPECIFIED afterwards: OD[k][i] for k in
+ * [4, k_top - 8) and i in a block of 64 points (counted from the shard's first) whose wave was done; every other entry
+ * holds rtx_compute_tud's value. Which waves are done depends on the atmosphere: none in a window or a thin column.
+ * Eligible: the TUD step runs the instantiation that looks for hidden layers (RTX_TUD_OD_NONNEG granted, one altitude and
+ * one slant path, return_od == 0, a prefix mask, a grid fine enough for the Planck nodes, RADTXFR_TUD_SKIP not 0, the
+ * default kernels); 8 <= k_top - 8; and the prologue's hot-tile bound is 0 (rtx_prep_split_bound: tables whose tiles are
+ * cut into parts keep the single launch; the parts kernels take no layer subset). Every other call runs rtx_compute_tud's
+ * launches and leaves OD complete. RADTXFR_OD_SKIP=0 in the environment (read once) forces that order for every call. */
+#define RTX_CTUD_OD_SCRATCH 1u
+int rtx_compute_tud_opts(rtx_prep* prep, const rtx_lines* lines, const rtx_grid* grid, int n_layers,
+                         const double* T_h, const double* p_atm_h, const double* qratio_h,
+                         const double* weight_h, const double* mass_h, double dil_air, double dil_self,
+                         double omega_wing, double omega_wing_hw, double intensity_threshold, int n_alt,
+                         const uint8_t* mask_h, int n_mu, const double* mu_h, int n_down, int n_angle,
+                         int return_od, float* OD, int64_t ld_od, float* tau, float* Lu, float* Ld,
+                         int64_t ld_out, void* stream, unsigned flags);
 
 /* ------------------------------------------------------------------------------------------
  * At-sensor radiance. Replaces compute_LWIR_apparent_radiance(), radiative_transfer.py:1017-

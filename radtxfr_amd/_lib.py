@@ -70,6 +70,8 @@ PROTOTYPES = {
     "rtx_tud_gtable": (_i32, [_i32, _vp, _vp]),
     "rtx_compute_tud": (_i32, [_vp, _vp, _gp, _i32, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _i32, _vp, _i32, _vp,
                                 _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "rtx_compute_tud_opts": (_i32, [_vp, _vp, _gp, _i32, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _i32, _vp, _i32, _vp,
+                                     _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, C.c_uint]),
     "rtx_apparent_radiance": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "rtx_ils": (_i32, [_i32, _gp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
     "rtx_srf_apply": (_i32, [_gp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

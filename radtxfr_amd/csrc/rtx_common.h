@@ -219,4 +219,21 @@ struct rtx_prep {
   DevBuf<LineRecDT64> drec64;
   DevBuf<double> dlnsw;
   int dT = 0;
+  // rtx_compute_tud_opts(RTX_CTUD_OD_SCRATCH): one byte per 64 points of the shard (= per row of a line-sum tile), padded to
+  // whole tiles: written by the early TUD launch, read by the line-sum of the middle layers and the late TUD launch
+  DevBuf<unsigned char> done;
 };
+
+// The layers of one line-sum launch (rtx_voigt_sum_layers): blockIdx.y < n_a -> layer k_a + y, else layer k_b + (y - n_a),
+// n_y of them in all. done != nullptr: rows whose byte is set are neither needed nor stored, and a workgroup whose rows
+// are all done returns before it loads a record. ranges: launch tile_ranges_kernel first (all layers; once per prologue).
+struct VoigtLayers {
+  int n_a, k_a, k_b, n_y;
+  const unsigned char* done;
+  bool ranges;
+};
+// rtx_voigt.hip: rtx_voigt_sum's fp32 sum restricted to `sel`; only where rtx_voigt_layers_ok(P) holds (the nodal kernel, no
+// hot-tile parts, a grid prologue with lines)
+__attribute__((visibility("hidden"))) bool rtx_voigt_layers_ok(const rtx_prep* P);
+__attribute__((visibility("hidden"))) int rtx_voigt_sum_layers(const rtx_prep* P, const rtx_grid* grid, int n_layers, float* out_f32,
+                                                                int64_t ld, void* stream, const VoigtLayers& sel);

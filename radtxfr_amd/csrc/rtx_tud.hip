@@ -179,6 +179,8 @@ struct TudArgs {
   const double* gtab;                  // angle-summed transmission function G (tud_g_kernel): [TUDG_NINT][8] doubles
   double g0;                           // G(0) = sum of the quadrature weights
   int skip;                            // tud_g_kernel: an opaque wave may pass over the layers no output sees (TUD_SKIP_* there)
+  unsigned char* done;                 // tud_g_kernel<.., .., 1 | 2>: one byte per wave of the shard (the pass in two launches, see there)
+  float early_smin;                    // tud_g_kernel<.., .., 1>: a depth below which no downwelling has stopped looking (see there)
 };
 
 #define TUD_OPAQUE_Y 26.0f
@@ -685,11 +687,49 @@ struct TudDown {
 
 // SKIP: the instantiation that may look (launched only with a.skip, and only with PN). Without it every line below that
 // serves the look is compiled out and the kernel is the one it was before the look existed, instruction for instruction.
-template <bool PN, bool SKIP>
+//
+// PHASE: the same pass in two launches around the line-sum of the middle layers (rtx_compute_tud_opts, RTX_CTUD_OD_SCRATCH).
+// A wave decides from layers [0, TUD_SKIP_BOTTOM) and [k_top - (TUD_SKIP_SCAN - TUD_STAGE), cnt0) alone whether it skips, and
+// where the tau loop stops before its first load it reads no other layer at all. PHASE 1 (early) runs when only those layers
+// have been summed: such a wave finishes as it always does, stores its outputs and writes done[wave] = 1; every other wave
+// (a downwelling alive after the first chunk, a look that finds nothing, a look that has to sum middle chunks) writes
+// done[wave] = 0 and returns without storing. The line-sum of the middle layers then leaves out the rows of the done waves,
+// and PHASE 2 (late) runs the whole pass for the waves that are not done. Either way a wave executes the instruction sequence
+// of PHASE 0 on the same data, in one launch or the other: tau, L-up and L-down keep their bits. PHASE 0 is the kernel every
+// other call launches; the lines that serve the phases are compiled out of it.
+template <bool PN, bool SKIP, int PHASE = 0>
 __global__ __launch_bounds__(256) void tud_g_kernel(TudArgs a) {
   static_assert(PN || !SKIP, "the look at the top is written for the Planck-node instantiation");
+  static_assert(PHASE == 0 || SKIP, "the two-launch pass belongs to the instantiation that may look");
   __shared__ double s_g[TUDG_NINT * 8];
   __shared__ float s_stage[(SKIP ? 2 : 1) * TUD_STAGE][256];  // each thread's own slots: the first TUD_STAGE hand the chunks over, all of them serve the look at the top
+  // late: the workgroup's four flags in one scalar load (the array is padded to whole workgroups and early wrote every entry)
+  unsigned done4 = 0u;
+  if (PHASE == 2) {
+    done4 = reinterpret_cast<const unsigned*>(a.done)[blockIdx.x];
+    if (done4 == 0x01010101u) return;
+  }
+  // early, on a column that hides nothing: the launch must cost next to nothing there, and a wave's set-up (the G table, eight
+  // fp64 Planck values) and its first chunk are most of what a full pass of a thin column costs per layer. A wave can be done
+  // only if its downwelling has stopped looking after the first chunk, G(S) <= G(0) 2^-opaque_y with opaque_y >= 27 in every
+  // lane, hence only if the depth of that chunk is at least early_smin (the host solves G(S) = G(0) 2^-26.5 and takes a
+  // little off for the fp32 sum; -inf where the downwelling can run out of layers instead). The workgroup whose four waves
+  // all fail that says so and returns before the table is loaded; any other runs on as it is, and its waves decide as always.
+  if (PHASE == 1) {
+    __shared__ int s_may[4];
+    const long long i_pre = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const float* __restrict__ od_pre = a.OD + (i_pre < a.g.n ? i_pre : a.g.n - 1);
+    float s_pre = 0.f;
+#pragma unroll
+    for (int t = 0; t < TUD_STAGE; ++t) s_pre += od_pre[(size_t)(t < a.n_layers ? t : a.n_layers - 1) * a.ld];
+    const bool may = __ballot(s_pre >= a.early_smin) == ~0ull;
+    if ((threadIdx.x & 63) == 0) s_may[threadIdx.x >> 6] = may ? 1 : 0;
+    __syncthreads();
+    if (!(s_may[0] | s_may[1] | s_may[2] | s_may[3])) {
+      if ((threadIdx.x & 63) == 0) a.done[(size_t)blockIdx.x * 4 + (threadIdx.x >> 6)] = 0;
+      return;
+    }
+  }
   tudg_load(s_g, a);
   TudLane ln(a);
   const int nL = a.n_layers;
@@ -705,6 +745,11 @@ __global__ __launch_bounds__(256) void tud_g_kernel(TudArgs a) {
   PlanckNodes PNd;
   if (PN) PNd = planck_nodes_setup(a, ln);
   __syncthreads();  // the table is in LDS
+  // (a done wave of a workgroup that still has work leaves here: the table load above is the whole workgroup's)
+  if (PHASE == 2 && ((done4 >> (8 * (threadIdx.x >> 6))) & 1u)) return;
+  auto not_done = [&]() {
+    if ((threadIdx.x & 63) == 0) a.done[(size_t)blockIdx.x * 4 + (threadIdx.x >> 6)] = 0;
+  };
 
   // ---- every further (altitude, slant factor) pair: transmittance + upwelling bottom-up (:346-356) ----------
   for (int p = 1; p < a.n_alt * a.n_mu; ++p) {
@@ -797,7 +842,9 @@ __global__ __launch_bounds__(256) void tud_g_kernel(TudArgs a) {
         if (k_hi <= TUD_SKIP_BOTTOM && k_hi + TUD_STAGE <= k_top) { k_look = k_hi; break; }
       }
     }
+    if (PHASE == 1) break;  // early: a wave that has not left for the look by now needs layers that are not there yet
   }
+  if (PHASE == 1 && k_look < 0) { not_done(); return; }
   // ---- the layers an opaque column hides from every output -----------------------------------------------------------
   // a.skip: the caller vouches that every OD is finite and >= 0, tau (not the depth) is asked for, and the mask is the
   // first cnt0 layers. The wave looks at the top TUD_SKIP_SCAN layers of the column, fetched in one go (the loop above is
@@ -860,6 +907,10 @@ __global__ __launch_bounds__(256) void tud_g_kernel(TudArgs a) {
 #pragma unroll
       for (int t = TUD_STAGE - 1; t >= 0; --t) s_top += s_stage[slot + t][threadIdx.x];
       if (__ballot(s_top * ac0 >= y_up) == ~0ull) k_res = k_top - c * TUD_STAGE;
+    }
+    if (PHASE == 1) {  // early: done only where the tau loop below stops before its first load
+      if (k_res < 0 || (kc < k_res && __ballot((s0 + s_top) * ac0 >= TUD_SKIP_TAU0) != ~0ull)) { not_done(); return; }
+      if ((threadIdx.x & 63) == 0) a.done[(size_t)blockIdx.x * 4 + (threadIdx.x >> 6)] = 1;
     }
     if (k_res < 0) {  // nothing found: on with the column at kc, whose chunk has been in flight into nxt all along
 #pragma unroll
@@ -1182,6 +1233,31 @@ extern "C" int rtx_tud_gtable(int n_angle, double* table_h, double* g0_h) {
   return 0;
 }
 
+// tud_g_kernel's early launch: a depth S that no downwelling which has stopped looking can lie below. It stops at G(S) <=
+// G(0) 2^-min(opaque_y, 120) with opaque_y >= 27; G falls monotonically, so S exceeds the root of G(S) = G(0) 2^-26.5 (half a
+// binade of margin against the table's 4e-14 G(0)), found by bisection on the direct sum; 1e-4 off for the kernel's fp32
+// sum of the chunk. One value per n_angle, kept.
+static float tudg_early_smin(int n_angle) {
+  static std::mutex mu;
+  static std::map<int, float> memo;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = memo.find(n_angle);
+  if (it != memo.end()) return it->second;
+  const TudQuadrature quad = tud_quadrature(n_angle);
+  float r = -INFINITY;
+  if (n_angle > 1 && quad.wsum > 0.0) {
+    auto G = [&](double S) { double g = 0.0; for (int ii = 1; ii < n_angle; ++ii) g += quad.w[ii] * exp(-S / cos(quad.th[ii])); return g; };
+    const double target = quad.wsum * exp2(-26.5);
+    double lo = 0.0, hi = TUDG_SMAX;
+    if (G(hi) < target) {
+      for (int it2 = 0; it2 < 60; ++it2) { const double mid = 0.5 * (lo + hi); (G(mid) > target ? lo : hi) = mid; }
+      r = (float)(lo * (1.0 - 1e-4));
+    }
+  }
+  memo[n_angle] = r;
+  return r;
+}
+
 // The device copy of the table, one per (device, n_angle), never forgotten.
 static int tudg_table(int n_angle, DevTableCache<double>::Hit* out) {
   static DevTableCache<double>* const cache = new DevTableCache<double>(0);
@@ -1211,9 +1287,34 @@ static int launch_tud(TudArgs& a, int na, hipStream_t st) {
   return tud_launch(tud_kernel<NA, false>, a, (size_t)TUD_STAGE * 256 * sizeof(float), st);
 }
 
-extern "C" int rtx_tud_opts(const float* OD, int64_t ld, const rtx_grid* grid, int n_layers, const double* T_h, int n_alt,
-                            const uint8_t* mask_h, int n_mu, const double* mu_h, int n_down, int n_angle, int return_od,
-                            float* tau, float* Lu, float* Ld, float* Ld_angles, int64_t ld_out, void* stream, unsigned flags) {
+// RADTXFR_TUD_KERNEL=streams forces the stream kernel (cross-checks and timing); RADTXFR_TUD_SKIP=0 keeps every wave of
+// tud_g_kernel on the full pass. Each read once.
+static bool tud_force_streams() {
+  static int v = -1;
+  if (v < 0) { const char* e = getenv("RADTXFR_TUD_KERNEL"); v = (e && !strcmp(e, "streams")) ? 1 : 0; }
+  return v != 0;
+}
+static bool tud_skip_on() {
+  static int v = -1;
+  if (v < 0) { const char* e = getenv("RADTXFR_TUD_SKIP"); v = (e && !strcmp(e, "0")) ? 0 : 1; }
+  return v != 0;
+}
+// B_k across a wave by a parabola through three of its wavenumbers (PlanckNodes) where that is exact to 1e-10:
+// |d ln B / d nu| <= 4/nu + c2/T, and the parabola's error is 0.008 (that x 63 steps)^3
+// decided on the FULL axis (its lowest wavenumber is the worst case), so that every wavenumber shard runs the
+// instantiation the single-rank run does; a shard offset that is a multiple of 64 then has the same waves, hence bits
+static bool tud_planck_nodes(const rtx_grid* grid, double t_min) {
+  const double nu_lo = grid->xmin;
+  return nu_lo > 0.0 && (4.0 / nu_lo + RT_C2 * 100.0 / t_min) * 63.0 * grid->step <= 7e-3;
+}
+
+// phase 0: the whole pass in one launch. 1 / 2: tud_g_kernel<true, true>'s early / late launch with the flags of `done`
+// (one byte per 64 points, padded to whole workgroups); the caller has checked with tud_split_layers() that this call
+// launches that instantiation.
+static int tud_opts_impl(const float* OD, int64_t ld, const rtx_grid* grid, int n_layers, const double* T_h, int n_alt,
+                         const uint8_t* mask_h, int n_mu, const double* mu_h, int n_down, int n_angle, int return_od,
+                         float* tau, float* Lu, float* Ld, float* Ld_angles, int64_t ld_out, void* stream, unsigned flags,
+                         int phase, unsigned char* done) {
   if (rtx_check_grid(grid)) return 1;
   if (flags & ~(unsigned)RTX_TUD_OD_NONNEG) RTX_FAIL("flags=0x%x: unknown bits", flags);
   if (!OD || !T_h || !mask_h || !mu_h || !tau || !Lu || !Ld) RTX_FAIL("a required pointer is NULL");
@@ -1260,8 +1361,8 @@ extern "C" int rtx_tud_opts(const float* OD, int64_t ld, const rtx_grid* grid, i
   hipStream_t st = (hipStream_t)stream;
   // default: the angle-summed form; the stream kernel when the caller wants the per-stream radiances
   // (RADTXFR_TUD_KERNEL=streams forces it, for cross-checks and timing)
-  static int force_streams = -1;
-  if (force_streams < 0) { const char* e = getenv("RADTXFR_TUD_KERNEL"); force_streams = (e && !strcmp(e, "streams")) ? 1 : 0; }
+  const bool force_streams = tud_force_streams();
+  if (phase != 0 && (Ld_angles || force_streams)) RTX_FAIL("internal: a two-launch pass without tud_g_kernel");
   if (!Ld_angles && !force_streams) {
     DevTableCache<double>::Hit gt;  // with the cache's lock, held until the launch below has returned
     if (tudg_table(n_angle, &gt)) return 1;
@@ -1270,20 +1371,20 @@ extern "C" int rtx_tud_opts(const float* OD, int64_t ld, const rtx_grid* grid, i
     for (int ia = 0; ia < n_alt && prefix; ++ia)
       for (int k = 0; k < n_layers; ++k)
         if ((mask_h[(size_t)ia * n_layers + k] != 0) != (k < a.count[ia])) { prefix = false; break; }
-    // B_k across a wave by a parabola through three of its wavenumbers (PlanckNodes) where that is exact to 1e-10:
-    // |d ln B / d nu| <= 4/nu + c2/T, and the parabola's error is 0.008 (that x 63 steps)^3
-    // decided on the FULL axis (its lowest wavenumber is the worst case), so that every wavenumber shard runs the
-    // instantiation the single-rank run does; a shard offset that is a multiple of 64 then has the same waves, hence bits
-    const double nu_lo = grid->xmin;
-    const bool pn = nu_lo > 0.0 && (4.0 / nu_lo + RT_C2 * 100.0 / t_min) * 63.0 * grid->step <= 7e-3;
+    const bool pn = tud_planck_nodes(grid, t_min);  // B_k across a wave by a parabola where that is exact to 1e-10
     void (*kernel)(TudArgs);
+    if (phase != 0 && n_alt * n_mu != 1) RTX_FAIL("internal: a two-launch pass with more than one pair");
     if (n_alt * n_mu == 1) {
       kernel = pn ? tud_g_kernel<true, false> : tud_g_kernel<false, false>;
       // hidden layers of an opaque column (see the kernel): RADTXFR_TUD_SKIP=0 keeps every wave on the full pass
-      static int skip_on = -1;
-      if (skip_on < 0) { const char* e = getenv("RADTXFR_TUD_SKIP"); skip_on = (e && !strcmp(e, "0")) ? 0 : 1; }
-      a.skip = skip_on && (flags & RTX_TUD_OD_NONNEG) && !return_od && prefix && pn;  // (the Planck-node instantiation only)
+      a.skip = tud_skip_on() && (flags & RTX_TUD_OD_NONNEG) && !return_od && prefix && pn;  // (the Planck-node instantiation only)
       if (a.skip) kernel = tud_g_kernel<true, true>;  // every other call runs the instantiation without the look
+      if (phase != 0) {
+        if (!a.skip || !done) RTX_FAIL("internal: a two-launch pass without the look at the top");
+        a.done = done;
+        a.early_smin = n_down >= TUD_STAGE ? tudg_early_smin(n_angle) : -INFINITY;
+        kernel = phase == 1 ? tud_g_kernel<true, true, 1> : tud_g_kernel<true, true, 2>;
+      }
     }
     // one slant path (the reference's main caller: 9 altitudes, nadir): the instantiation without the per-slant guards
     else if (prefix && n_mu == 1) kernel = pn ? tud_g_snap_kernel<1, true> : tud_g_snap_kernel<1, false>;
@@ -1299,6 +1400,13 @@ extern "C" int rtx_tud_opts(const float* OD, int64_t ld, const rtx_grid* grid, i
   return launch_tud<32>(a, na, st);
 }
 
+extern "C" int rtx_tud_opts(const float* OD, int64_t ld, const rtx_grid* grid, int n_layers, const double* T_h, int n_alt,
+                            const uint8_t* mask_h, int n_mu, const double* mu_h, int n_down, int n_angle, int return_od,
+                            float* tau, float* Lu, float* Ld, float* Ld_angles, int64_t ld_out, void* stream, unsigned flags) {
+  return tud_opts_impl(OD, ld, grid, n_layers, T_h, n_alt, mask_h, n_mu, mu_h, n_down, n_angle, return_od, tau, Lu, Ld, Ld_angles,
+                       ld_out, stream, flags, 0, nullptr);
+}
+
 extern "C" int rtx_tud(const float* OD, int64_t ld, const rtx_grid* grid, int n_layers, const double* T_h, int n_alt,
                        const uint8_t* mask_h, int n_mu, const double* mu_h, int n_down, int n_angle, int return_od,
                        float* tau, float* Lu, float* Ld, float* Ld_angles, int64_t ld_out, void* stream) {
@@ -1311,18 +1419,55 @@ extern "C" int rtx_tud(const float* OD, int64_t ld, const rtx_grid* grid, int n_
 // TUD integration enqueued back to back. Same kernels as the three separate entry points; what it saves is host time per
 // atmosphere (one FFI crossing, no per-call Python marshalling between the stages), which is what limits a wavenumber
 // shard small enough to finish in a few hundred microseconds (8-GPU strong scaling, tools/time_overhead.py).
-extern "C" int rtx_compute_tud(rtx_prep* prep, const rtx_lines* lines, const rtx_grid* grid, int n_layers, const double* T_h,
-                               const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
-                               double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
-                               double intensity_threshold, int n_alt, const uint8_t* mask_h, int n_mu, const double* mu_h,
-                               int n_down, int n_angle, int return_od, float* OD, int64_t ld_od, float* tau, float* Lu,
-                               float* Ld, int64_t ld_out, void* stream) {
+// The layers the two-launch pass sums first and last, if this call may take it (rtx_compute_tud_opts): the TUD step would
+// launch tud_g_kernel<true, true> -- exactly tud_opts_impl's conditions, restated on the host arguments before anything is
+// enqueued -- and there is a chunk to leave out between the bottom chunk and the look at the top. k_mid0 / k_mid1: the
+// middle layers [k_mid0, k_mid1). Arguments that tud_opts_impl would refuse give false: the plain order reports them.
+static bool tud_split_layers(const rtx_grid* grid, int n_layers, const double* T_h, int n_alt, const uint8_t* mask_h, int n_mu,
+                             int return_od, unsigned tud_flags, int* k_mid0, int* k_mid1) {
+  if (!tud_skip_on() || tud_force_streams() || !(tud_flags & RTX_TUD_OD_NONNEG) || return_od) return false;
+  if (!grid || !T_h || !mask_h || n_alt != 1 || n_mu != 1 || n_layers < 1 || n_layers > TUD_MAX_LAYERS) return false;
+  int cnt0 = 0;
+  for (int k = 0; k < n_layers; ++k) cnt0 += mask_h[k] != 0;
+  for (int k = 0; k < n_layers; ++k)
+    if ((mask_h[k] != 0) != (k < cnt0)) return false;  // not a prefix mask
+  double t_min = T_h[0];
+  for (int k = 1; k < n_layers; ++k) t_min = T_h[k] < t_min ? T_h[k] : t_min;
+  if (!tud_planck_nodes(grid, t_min)) return false;
+  if (cnt0 < 1) return false;
+  const int k_top = (cnt0 - 1) & ~(TUD_STAGE - 1);
+  const int k_deep = k_top - (TUD_SKIP_SCAN - TUD_STAGE);  // the lowest layer the look at the top can read
+  if (TUD_SKIP_BOTTOM + TUD_STAGE > k_deep) return false;
+  *k_mid0 = TUD_SKIP_BOTTOM; *k_mid1 = k_deep;
+  return true;
+}
+
+// RADTXFR_OD_SKIP=0: rtx_compute_tud_opts keeps the plain order (one line-sum over all layers, one TUD launch) whatever its
+// flags say -- for A/B timing and for support. Read once.
+static bool od_skip_on() {
+  static int v = -1;
+  if (v < 0) { const char* e = getenv("RADTXFR_OD_SKIP"); v = (e && !strcmp(e, "0")) ? 0 : 1; }
+  return v != 0;
+}
+
+// RTX_CTUD_OD_SCRATCH, where the call is eligible (include/radtxfr_hip.h):
+//   prologue -> tile ranges -> line-sum A: layers [0, TUD_SKIP_BOTTOM) and [k_top - (TUD_SKIP_SCAN - TUD_STAGE), n_layers)
+//            -> TUD early: the waves that need nothing else finish and say so (tud_g_kernel, PHASE 1)
+//            -> line-sum B: the layers in between, without the rows of those waves; a tile whose 16 rows are all done returns at once
+//            -> TUD late: every other wave (PHASE 2)
+// On the C3 column the layers of B are the low, wide-winged ones, and a third of the tiles are hidden whole.
+extern "C" int rtx_compute_tud_opts(rtx_prep* prep, const rtx_lines* lines, const rtx_grid* grid, int n_layers, const double* T_h,
+                                    const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
+                                    double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
+                                    double intensity_threshold, int n_alt, const uint8_t* mask_h, int n_mu, const double* mu_h,
+                                    int n_down, int n_angle, int return_od, float* OD, int64_t ld_od, float* tau, float* Lu,
+                                    float* Ld, int64_t ld_out, void* stream, unsigned flags) {
+  if (flags & ~(unsigned)RTX_CTUD_OD_SCRATCH) RTX_FAIL("flags=0x%x: unknown bits", flags);
   if (!OD) RTX_FAIL("OD workspace is NULL");
   if (rtx_line_prep_profile(prep, lines, grid, n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, dil_air, dil_self, omega_wing,
                             omega_wing_hw, intensity_threshold, 1.0, RTX_PROFILE_VOIGT, stream))
     return 1;
-  if (rtx_voigt_sum(prep, grid, n_layers, OD, nullptr, ld_od, stream)) return 1;
-  // the optical depths just summed are sums of non-negative terms when every factor the caller gave is finite and >= 0: the
+  // the optical depths are sums of non-negative terms when every factor the caller gave is finite and >= 0: the
   // column weights, the partition-sum ratios, T and p (the prologue has accepted lines, n_layers and the arrays by now). Line
   // strengths are the table's and are not looked at: a table with a negative or NaN S is outside what this vouches for.
   auto nonneg = [](const double* v, long long n) {
@@ -1331,8 +1476,37 @@ extern "C" int rtx_compute_tud(rtx_prep* prep, const rtx_lines* lines, const rtx
     return true;
   };
   const long long n_sl = (long long)lines->n_species * n_layers;
-  const unsigned flags = nonneg(weight_h, n_sl) && nonneg(qratio_h, n_sl) && nonneg(T_h, n_layers) && nonneg(p_atm_h, n_layers)
-                             ? RTX_TUD_OD_NONNEG : 0u;
+  const unsigned tud_flags = nonneg(weight_h, n_sl) && nonneg(qratio_h, n_sl) && nonneg(T_h, n_layers) && nonneg(p_atm_h, n_layers)
+                                 ? RTX_TUD_OD_NONNEG : 0u;
+  int k_mid0 = 0, k_mid1 = 0;
+  if ((flags & RTX_CTUD_OD_SCRATCH) && od_skip_on() && grid->n > 0 && rtx_voigt_layers_ok(prep) &&
+      tud_split_layers(grid, n_layers, T_h, n_alt, mask_h, n_mu, return_od, tud_flags, &k_mid0, &k_mid1)) {
+    const size_t n_done = (size_t)((grid->n + 1023) / 1024) * 16;  // whole line-sum tiles (hence whole TUD workgroups of 4 waves)
+    if (rtx_voigt_tile_points() != 1024) RTX_FAIL("internal: the done flags are laid out for tiles of 16 rows of 64 points");
+    if (prep->done.reserve(n_done)) return 1;
+    unsigned char* done = prep->done.get();
+    const VoigtLayers la{k_mid0, 0, k_mid1, k_mid0 + (n_layers - k_mid1), nullptr, true};
+    const VoigtLayers lb{k_mid1 - k_mid0, k_mid0, 0, k_mid1 - k_mid0, done, false};
+    if (rtx_voigt_sum_layers(prep, grid, n_layers, OD, ld_od, stream, la)) return 1;
+    if (tud_opts_impl(OD, ld_od, grid, n_layers, T_h, n_alt, mask_h, n_mu, mu_h, n_down, n_angle, return_od, tau, Lu, Ld, nullptr,
+                      ld_out, stream, tud_flags, 1, done))
+      return 1;
+    if (rtx_voigt_sum_layers(prep, grid, n_layers, OD, ld_od, stream, lb)) return 1;
+    return tud_opts_impl(OD, ld_od, grid, n_layers, T_h, n_alt, mask_h, n_mu, mu_h, n_down, n_angle, return_od, tau, Lu, Ld, nullptr,
+                         ld_out, stream, tud_flags, 2, done);
+  }
+  if (rtx_voigt_sum(prep, grid, n_layers, OD, nullptr, ld_od, stream)) return 1;
   return rtx_tud_opts(OD, ld_od, grid, n_layers, T_h, n_alt, mask_h, n_mu, mu_h, n_down, n_angle, return_od, tau, Lu, Ld, nullptr,
-                      ld_out, stream, flags);
+                      ld_out, stream, tud_flags);
+}
+
+extern "C" int rtx_compute_tud(rtx_prep* prep, const rtx_lines* lines, const rtx_grid* grid, int n_layers, const double* T_h,
+                               const double* p_atm_h, const double* qratio_h, const double* weight_h, const double* mass_h,
+                               double dil_air, double dil_self, double omega_wing, double omega_wing_hw,
+                               double intensity_threshold, int n_alt, const uint8_t* mask_h, int n_mu, const double* mu_h,
+                               int n_down, int n_angle, int return_od, float* OD, int64_t ld_od, float* tau, float* Lu,
+                               float* Ld, int64_t ld_out, void* stream) {
+  return rtx_compute_tud_opts(prep, lines, grid, n_layers, T_h, p_atm_h, qratio_h, weight_h, mass_h, dil_air, dil_self, omega_wing,
+                              omega_wing_hw, intensity_threshold, n_alt, mask_h, n_mu, mu_h, n_down, n_angle, return_od, OD, ld_od,
+                              tau, Lu, Ld, ld_out, stream, 0u);
 }

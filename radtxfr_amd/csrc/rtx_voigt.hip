@@ -138,7 +138,7 @@ extern "C" int rtx_voigt_tile_points(void) { return rtx_voigt_scatter_tile_point
 // rtx_voigt_scatter.hip
 int rtx_voigt_sum_scatter(const rtx_prep* P, const rtx_grid* grid, int n_layers, float* out_f32, double* out_f64, int64_t ld,
                           hipStream_t st, void (*launch_ranges)(const rtx_prep*, const rtx_grid*, int, int, int, hipStream_t, int),
-                          int nodal);
+                          int nodal, const VoigtLayers* sel = nullptr);
 
 static void launch_tile_ranges(const rtx_prep* P, const rtx_grid* grid, int n_layers, int n_tiles, int tile, hipStream_t st, int split) {
   RangeArgs ra;
@@ -188,4 +188,23 @@ extern "C" int rtx_voigt_sum(const rtx_prep* P, const rtx_grid* grid, int n_laye
     return 0;
   }
   return rtx_voigt_sum_scatter(P, grid, n_layers, out_f32, out_f64, ld, st, launch_tile_ranges, voigt_kernel_choice() == 0);
+}
+
+// A subset of the layers in one launch of the nodal kernels (struct VoigtLayers, rtx_common.h): what rtx_compute_tud_opts
+// sums before and after the early TUD launch. The values stored are rtx_voigt_sum's, bit for bit.
+bool rtx_voigt_layers_ok(const rtx_prep* P) {
+  return P && !P->axis && P->n_lines > 0 && voigt_kernel_choice() == 0 && !(P->split_bound > 0 && P->items.get());
+}
+int rtx_voigt_sum_layers(const rtx_prep* P, const rtx_grid* grid, int n_layers, float* out_f32, int64_t ld, void* stream,
+                         const VoigtLayers& sel) {
+  if (!rtx_voigt_layers_ok(P)) RTX_FAIL("internal: a layer subset on a prologue that cannot take one");
+  if (rtx_check_grid(grid)) return 1;
+  if (n_layers < 1 || n_layers != P->n_layers) RTX_FAIL("n_layers=%d does not match the last rtx_line_prep (%d)", n_layers, P->n_layers);
+  if (!out_f32) RTX_FAIL("the output is NULL");
+  if (ld < grid->n) RTX_FAIL("ld=%lld < n=%lld", (long long)ld, (long long)grid->n);
+  if (sel.n_a < 0 || sel.n_y < sel.n_a || sel.n_y < 1 || sel.k_a < 0 || sel.k_a + sel.n_a > n_layers || sel.k_b < 0 ||
+      sel.k_b + (sel.n_y - sel.n_a) > n_layers)
+    RTX_FAIL("internal: layer subset outside [0,%d)", n_layers);
+  if (grid->n == 0) return 0;
+  return rtx_voigt_sum_scatter(P, grid, n_layers, out_f32, nullptr, ld, (hipStream_t)stream, launch_tile_ranges, 1, &sel);
 }

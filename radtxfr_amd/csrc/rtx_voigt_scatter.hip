@@ -83,7 +83,26 @@ struct ScArgs {
   const SplitItem* items;
   const int* n_items;
   float* part_ws;
+  // the layers of this launch (struct VoigtLayers, rtx_common.h); rtx_voigt_sum: n_a = n_layers, k_a = 0, done = nullptr
+  int n_a, k_a, k_b;
+  const unsigned char* done;
 };
+// blockIdx.y -> layer
+__device__ __forceinline__ int sc_layer(const ScArgs& a, int y) { return y < a.n_a ? a.k_a + y : a.k_b + (y - a.n_a); }
+// The 16 rows of tile slot b whose optical depths nobody reads: bit r set = done (a.done, one byte per row) or past the end
+// of the grid. All of it wave-uniform: one scalar load of the tile's 16 bytes.
+__device__ __forceinline__ unsigned sc_done_rows(const ScArgs& a, int b) {
+  static_assert(RTX_SC_ROWS == 16, "a tile's done flags are read as four dwords");
+  const int tile = xcd_tile(b);
+  if (!a.done || tile >= a.n_tiles) return 0u;
+  const uint4 d = reinterpret_cast<const uint4*>(a.done)[tile];
+  auto nib = [](unsigned w) -> unsigned { return (((w & 0x01010101u) * 0x01020408u) >> 24) & 0xFu; };  // bytes 0 / 1 -> 4 bits
+  unsigned m = nib(d.x) | (nib(d.y) << 4) | (nib(d.z) << 8) | (nib(d.w) << 12);
+  const long long left = a.g.n - (long long)tile * (64 * RTX_SC_ROWS);  // points from the tile's first to the end of the grid
+  const int rows_in = left >= 64 * RTX_SC_ROWS ? RTX_SC_ROWS : (int)((left + 63) >> 6);
+  m |= (0xFFFFu << rows_in) & 0xFFFFu;
+  return m;
+}
 
 // Row geometry of one line in one tile, in plain integer arithmetic so that the scalar per-line code and the
 // per-lane far-row masks agree exactly. Rows are tile-local, 64 points each.
@@ -439,6 +458,16 @@ __global__ __launch_bounds__(256) void voigt_scatter_kernel(ScArgs a) {
 // the band loops, 1.3982-1.4092 against 1.3848-1.3985 with them -- 63 near-zone rows per tile and layer lie in 29 runs, three quarters
 // of them one or two rows long, and a run costs 13 scalar instructions where the bit-by-bit walk costs 6 per row; one band body with
 // the cut and the series choice as scalar arguments (the compiler makes selects of both: the window compares stay).
+// Layer subsets and done rows (rtx_compute_tud_opts, RTX_CTUD_OD_SCRATCH; profiles/od_skip_time.txt): the layers between the
+// bottom chunk and the TUD pass's look at the top are summed in a launch of their own, after the early TUD launch has said which
+// rows no wave will read. A tile whose 16 rows are all done returns before it loads a record (33.4 % of that launch's
+// workgroups on C3: line-sum 1.419 -> 1.204 ms for both launches together); a done row of any other tile is computed as ever
+// and only not stored -- except in the drain, where the done rows are taken out of a general entry's near-zone and window-edge
+// masks (m_pp, m_ed) once per entry: 63 % of the tiles on C3 are hidden in part, with 53 % of their rows done. Emission, fill
+// levels and drain points are untouched, so a live row's adds keep their order. Step, two sessions of six interleaved runs:
+// 1.4034 -> 1.3793 ms (every run below; 1.8 times the other build's spread, one run of which stood 0.008 apart) and 1.4004 ->
+// 1.3729 ms (4.8 times). Measured and not taken, both for one spilled register in <false> at its 80: the same for the band rows
+// (m_cut after the run is formed, the run's done rows passed over in its loops), and the row test in edge_one.
 #ifndef RTX_SC_WAVES
 #define RTX_SC_WAVES 6
 #endif
@@ -477,9 +506,12 @@ __global__ __launch_bounds__(256) void voigt_scatter_kernel(ScArgs a) {
 // PARTS: the instantiation of the parts kernels. It sends every band row through band_row's full body: with the lighter loops of
 // the drain beside it, voigt_nodal_parts_kernel<false> -- the same 80 registers, and the part's range and output pointer to hold --
 // spills a register. Hot tiles are rare (none on C3), and the values are the same either way.
+// done_rows: rows that are not stored (sc_done_rows; launches with a.done only), and that the drain leaves out of a general
+// entry's near-zone and window-edge rows. The row-level and tile-level passes accumulate all rows at once and stay as they are,
+// and the order of the adds into a live row does not change.
 template <bool SMALLY, bool PARTS = false>
 __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile, const int k, const int2 part_rng = make_int2(0, 0),
-                                           float* __restrict__ part_out = nullptr) {
+                                           float* __restrict__ part_out = nullptr, const unsigned done_rows = 0u) {
   constexpr int ROWS = RTX_SC_ROWS;
   constexpr int TILE = 64 * ROWS;
   __shared__ float s_acc[SC_NW][TILE];              // one private tile per wave (near rows)
@@ -566,6 +598,10 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
       const unsigned w0 = (unsigned)__builtin_amdgcn_readfirstlane(__float_as_int(e3.x));
       const unsigned w1 = (unsigned)__builtin_amdgcn_readfirstlane(__float_as_int(e3.y));
       unsigned m_pp = w0 & 0xffffu, m_ed = w0 >> 16, m_bd = w1 & 0xffffu, m_cut = w1 >> 16;
+      if (!PARTS) {  // done rows (launches with a.done): nobody reads them, and a live row's adds keep their order. The band rows and
+                     // the edge list are left alone: masking either spills a register in <false> (header)
+        m_pp &= ~done_rows; m_ed &= ~done_rows;
+      }
       auto slot = [&]() -> int { return __builtin_amdgcn_readfirstlane(__float_as_int(ent[e][3].z)); };
       STAMP(3);  // entry read
       if (RTX_SC_ABLATE & 4) m_pp = m_ed = 0u;
@@ -942,6 +978,7 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
     for (int jj = 0; jj < CHEB_N; ++jj) wl[jj] = CHEB_W[lane][jj];
 #pragma unroll 4
     for (int r = wave; r < ROWS; r += SC_NW) {
+      if ((done_rows >> r) & 1u) continue;  // wave-uniform
       const int t = r * 64 + lane;
       const long long i = (long long)ia + t;
       float f = 0.f;
@@ -978,15 +1015,19 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
 #endif
 template <bool SMALLY>
 __global__ __launch_bounds__(64 * SC_NW, SMALLY ? RTX_SC_WAVES_SMALLY : RTX_SC_WAVES) void voigt_nodal_kernel(ScArgs a) {
-  const int k = blockIdx.y;
+  const int k = sc_layer(a, blockIdx.y);
   if ((a.smally[k] != 0) != SMALLY) return;
   if (SMALLY) {
     for (int b = blockIdx.x; b < 8 * a.tiles_per_xcd; b += gridDim.x) {
-      nodal_tile<true>(a, b, k);
+      const unsigned done_rows = sc_done_rows(a, b);
+      if (done_rows == 0xFFFFu) continue;  // a hidden tile (uniform over the workgroup)
+      nodal_tile<true>(a, b, k, make_int2(0, 0), nullptr, done_rows);
       __syncthreads();  // the tile copies are reused by the next slot
     }
   } else {
-    nodal_tile<false>(a, blockIdx.x, k);
+    const unsigned done_rows = sc_done_rows(a, blockIdx.x);
+    if (done_rows == 0xFFFFu) return;  // a hidden tile: before a record is loaded
+    nodal_tile<false>(a, blockIdx.x, k, make_int2(0, 0), nullptr, done_rows);
   }
 }
 
@@ -1030,7 +1071,7 @@ __attribute__((visibility("hidden"))) int rtx_voigt_scatter_tile_points(void) { 
 
 int rtx_voigt_sum_scatter(const rtx_prep* P, const rtx_grid* grid, int n_layers, float* out_f32, double* out_f64, int64_t ld,
                           hipStream_t st, void (*launch_ranges)(const rtx_prep*, const rtx_grid*, int, int, int, hipStream_t, int),
-                          int nodal) {
+                          int nodal, const VoigtLayers* sel) {
   constexpr int TILE = 64 * RTX_SC_ROWS;
   const long long n_tiles_ll = (grid->n + TILE - 1) / TILE;
   if (n_tiles_ll > P->max_tiles) RTX_FAIL("grid shard of %lld points exceeds the prep capacity", (long long)grid->n);
@@ -1038,8 +1079,12 @@ int rtx_voigt_sum_scatter(const rtx_prep* P, const rtx_grid* grid, int n_layers,
   // the work list of hot-tile parts is rebuilt by every call (a caller may sum twice after one prologue, e.g. once per
   // output precision): its counter starts from zero each time
   if (nodal && P->split_bound > 0 && P->items.get()) RTX_HIP(hipMemsetAsync(P->n_items, 0, sizeof(int), st));
-  launch_ranges(P, grid, n_layers, n_tiles, TILE, st, nodal);  // the point-by-point cross-check takes every tile whole
-  RTX_LAUNCH_CHECK();
+  if (sel && !nodal) RTX_FAIL("internal: a layer subset with the point-by-point kernel");
+  if (!sel || sel->ranges) {
+    launch_ranges(P, grid, n_layers, n_tiles, TILE, st, nodal);  // the point-by-point cross-check takes every tile whole
+    RTX_LAUNCH_CHECK();
+  }
+  const int n_y = sel ? sel->n_y : n_layers;  // layers of this launch
   ScArgs a;
   a.rec = P->rec.get(); a.rec64 = P->rec64.get(); a.ranges = P->ranges.get(); a.smally = P->smally; a.n_lines = P->n_lines;
   a.n_tiles = n_tiles; a.tiles_per_xcd = xcd_slots(n_tiles);
@@ -1047,6 +1092,7 @@ int rtx_voigt_sum_scatter(const rtx_prep* P, const rtx_grid* grid, int n_layers,
   a.out32 = out_f32; a.out64 = out_f64; a.ld = ld; a.inv_scale = 1.0 / P->scale;
   a.stamp = nullptr;
   a.items = P->items.get(); a.n_items = P->n_items; a.part_ws = P->part_ws.get();
+  a.n_a = sel ? sel->n_a : n_layers; a.k_a = sel ? sel->k_a : 0; a.k_b = sel ? sel->k_b : 0; a.done = sel ? sel->done : nullptr;
 #if RTX_SC_STAMP
   static unsigned long long* d_stamp = nullptr;
   static size_t stamp_cap = 0;
@@ -1063,9 +1109,9 @@ int rtx_voigt_sum_scatter(const rtx_prep* P, const rtx_grid* grid, int n_layers,
   static int lds_pad = -1;
   if (lds_pad < 0) { const char* e = getenv("RADTXFR_DEBUG_LDS_PAD"); lds_pad = e ? atoi(e) : 0; }
   if (nodal) {
-    hipLaunchKernelGGL((voigt_nodal_kernel<false>), dim3(8 * a.tiles_per_xcd, n_layers), dim3(64 * SC_NW), (size_t)lds_pad, st, a);
+    hipLaunchKernelGGL((voigt_nodal_kernel<false>), dim3(8 * a.tiles_per_xcd, n_y), dim3(64 * SC_NW), (size_t)lds_pad, st, a);
     RTX_LAUNCH_CHECK();
-    hipLaunchKernelGGL((voigt_nodal_kernel<true>), dim3(8 * ((a.tiles_per_xcd + 15) / 16), n_layers), dim3(64 * SC_NW), 0, st, a);
+    hipLaunchKernelGGL((voigt_nodal_kernel<true>), dim3(8 * ((a.tiles_per_xcd + 15) / 16), n_y), dim3(64 * SC_NW), 0, st, a);
     if (P->split_bound > 0 && P->items.get()) {  // the table can have hot tiles: their extra parts, then the sums in part order
       RTX_LAUNCH_CHECK();
       const unsigned cap = (unsigned)P->split_bound;

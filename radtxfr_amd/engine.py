@@ -14,6 +14,7 @@ from . import _lib, tips
 
 TUD_MAX_MU = 8  # slant paths per rtx_tud launch (include/radtxfr_hip.h)
 TUD_OD_NONNEG = 1  # RTX_TUD_OD_NONNEG
+CTUD_OD_SCRATCH = 1  # RTX_CTUD_OD_SCRATCH
 
 # hapi constants used for per-species / per-layer host factors (misc/hapi.py:84-92, 10163-10164)
 CBOLTS = 1.380648813e-16
@@ -933,10 +934,17 @@ class TudRunner:
     `grid` must coincide with a run of the table's axis. Not with broadening (fixed when the table was made).
     continuum: a continuum.Continuum added to the optical depths of whichever branch made them,
     between them and rtx_tud (rtx_continuum_add); the default branch then runs rtx_line_prep + rtx_voigt_sum +
-    rtx_continuum_add + rtx_tud as separate calls. None: every branch is what it is without the option."""
+    rtx_continuum_add + rtx_tud as separate calls. None: every branch is what it is without the option.
+    keep_od: whether self.OD must be complete after run(). None, the default: a buffer the runner allocated itself is
+    scratch, a buffer the caller gave (OD=, or assigned to the attribute later) is kept complete; True / False override.
+    Scratch matters only to the fused call (rtx_compute_tud_opts, RTX_CTUD_OD_SCRATCH) on an opaque column with one
+    altitude and one slant path: tau, Lu and Ld are the same bits, but OD[k][i] is then UNSPECIFIED (stale, never
+    written) for the middle layers k in [4, k_top - 8), k_top = (layers below the sensor - 1) & ~3, of every block of 64
+    points, counted from the grid shard's first, that the TUD pass could finish without them. Whoever reads run.OD
+    afterwards passes keep_od=True (the derivative front half does)."""
 
     def __init__(self, lines, grid, Z, n_layers=None, Altitudes=(500,), theta_r=0.0, N_angle=30, returnOD=False, out=None,
-                 OD=None, plan=None, broadening=None, xs_lut=None, continuum=None):
+                 OD=None, plan=None, broadening=None, xs_lut=None, continuum=None, keep_od=None):
         self.lib = _lib.load()
         self.lines, self.grid = lines, grid
         self.continuum = continuum
@@ -956,6 +964,8 @@ class TudRunner:
         dev = device()
         nrow = Z_s.size * self.mu.size
         self.OD = OD if OD is not None else torch.empty((self.nL, grid.n), dtype=torch.float32, device=dev)
+        self.keep_od = keep_od
+        self._own_od = None if OD is not None else self.OD  # the buffer that is scratch unless told otherwise
         if out is None:
             self.tau = torch.empty((nrow, grid.n), dtype=torch.float32, device=dev)
             self.Lu = torch.empty_like(self.tau)
@@ -1044,13 +1054,14 @@ class TudRunner:
                     self.mask.ctypes.data_as(vp), self.shape[1], self.mu.ctypes.data_as(vp), self.n_down, self.N_angle, self.returnOD,
                     self._ptrs[0], self._ptrs[1], self._ptrs[2], None, self._ld_out, st, nonneg))
             return self.tau, self.Lu, self.Ld
+        scratch = (self.OD is self._own_od) if self.keep_od is None else not self.keep_od
         with trace_range("rtx_compute_tud"):
-            _lib.check(self.lib.rtx_compute_tud(
+            _lib.check(self.lib.rtx_compute_tud_opts(
                 self.plan._h, lines._h, self.grid.byref(), nL, vp(base), vp(base + 8 * nL), vp(base + 16 * nL),
                 vp(base + 8 * (2 * nL + nS * nL)), vp(base + 8 * (2 * nL + 2 * nS * nL)), 1.0, 0.0, 0.0, 50.0, 0.0,
                 self.shape[0], self.mask.ctypes.data_as(vp), self.shape[1], self.mu.ctypes.data_as(vp), self.n_down, self.N_angle,
                 self.returnOD, vp(self.OD.data_ptr()), self.OD.stride(0), self._ptrs[0], self._ptrs[1], self._ptrs[2], self._ld_out,
-                _stream_ptr()))
+                _stream_ptr(), CTUD_OD_SCRATCH if scratch else 0))
         return self.tau, self.Lu, self.Ld
 
 
@@ -1061,7 +1072,8 @@ class TudPipelines:
     one atmosphere share the chip with the VALU-bound line-sum of the next (C3 on MI355X, bench.py: 1.97 / 1.90 / 1.90 /
     1.91 ms per atmosphere with 1 / 2 / 3 / 4 pipelines; profiles/r3_time_pipeline.txt). Results are the single-runner results bit for bit.
     outs: optional list of P (tau, Lu, Ld) output triples (e.g. rows of packed blocks that are all-gathered).
-    kw: TudRunner's keywords (Altitudes, theta_r, N_angle, returnOD, broadening, continuum)."""
+    kw: TudRunner's keywords (Altitudes, theta_r, N_angle, returnOD, broadening, continuum, keep_od: each pipeline's
+    optical-depth buffer is the runner's own, hence scratch unless keep_od=True)."""
 
     def __init__(self, lines, grid, Z, n_layers=None, n_pipes=2, outs=None, **kw):
         self.streams = [torch.cuda.Stream() for _ in range(int(n_pipes))]
@@ -1619,7 +1631,7 @@ def _jacobian_stages(what, lines, grid, Z, T, P_pa, PL_km, MF_VAL, MF_ID, Altitu
     dev = device()
     # base state: exactly what compute_TUD runs
     run = TudRunner(lines, grid, Z, n_layers=nL, Altitudes=Altitudes, theta_r=theta_r, N_angle=N_angle, returnOD=returnOD,
-                    continuum=continuum, xs_lut=xs_lut)
+                    continuum=continuum, xs_lut=xs_lut, keep_od=True)  # the derivatives read every layer of OD
     tau, Lu, Ld = run.run(T, P_pa, PL_km, MF_VAL, MF_ID)
     OD = run.OD
     if mark:

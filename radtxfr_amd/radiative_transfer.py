@@ -336,7 +336,7 @@ def _compute_tud_chunked(tbl, grid, Z, T, P, PL, MF, ID, Z_s, theta, nA, returnO
         sl = slice(off, off + ln)
         run = engine.TudRunner(tbl, grid.shard(grid.offset + off, ln), Z, n_layers=nL, Altitudes=Z_s, theta_r=theta, N_angle=nA,
                                returnOD=returnOD, out=(tau[:, sl], Lu[:, sl], Ld[sl]), OD=OD[:, :ln], plan=plan,
-                               broadening=broadening, xs_lut=xs_lut, continuum=continuum)
+                               broadening=broadening, xs_lut=xs_lut, continuum=continuum, keep_od=False)  # OD: this function's scratch
         run.run(T, P, PL, MF, ID)
         ready = torch.cuda.Event()
         ready.record()

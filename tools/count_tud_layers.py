@@ -121,6 +121,16 @@ def main():
                   scale, 100.0 * sk.mean(), c["full"].mean(), c["summed"].mean(), c["scanned"].mean(),
                   100.0 * ((c["scanned"] > 0) & ~sk).mean(), c["full"][sk].mean() if sk.any() else float("nan"),
                   100.0 * c["fine_skip"].mean(), c["fine"][c["fine_skip"]].mean() if c["fine_skip"].any() else float("nan")))
+        # what rtx_compute_tud_opts leaves out of the line-sum (RTX_CTUD_OD_SCRATCH): a wave that skips and loads no middle chunk is
+        # done; a line-sum tile is 16 consecutive waves (counted from each window's start, which is a wave but not a tile boundary
+        # of the bench grid: the same statistics, not the same tiles)
+        done = sk & (c["summed"] == 0)
+        if args.points % 1024 == 0:
+            t = done.reshape(-1, 16)
+            print("    done waves (skip, no middle chunk loaded) %5.1f %%; tiles with every wave done %5.1f %%, with some %5.1f %%"
+                  % (100.0 * done.mean(), 100.0 * t.all(1).mean(), 100.0 * (t.any(1) & ~t.all(1)).mean()))
+        else:
+            print("    done waves (skip, no middle chunk loaded) %5.1f %%" % (100.0 * done.mean()))
 
 
 if __name__ == "__main__":
