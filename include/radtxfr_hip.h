@@ -195,6 +195,19 @@ int rtx_line_prep_axis_mix(rtx_prep* prep, const rtx_lines* lines, const double*
 int rtx_voigt_tile_points(void);
 int rtx_voigt_sum(const rtx_prep* prep, const rtx_grid* grid, int n_layers, float* out_f32,
                   double* out_f64, int64_t ld, void* stream);
+/* rtx_voigt_sum's fp32 sum for a part of the column: layers [k_lo, k_hi) (an empty range enqueues nothing), and of those
+ * layers only the rows nobody has said to skip. A row is 64 consecutive points counted from the shard's first, 16 rows make
+ * a line-sum tile (rtx_voigt_tile_points()).
+ *   skip_rows  device, one byte per row, padded to whole tiles (16 bytes per tile, ceil(n / tile points) tiles), 16-byte
+ *              aligned, read by the kernels on `stream`; NULL: nothing is skipped. A row whose byte is not 0 is neither
+ *              summed nor written: out_f32 keeps what it held there. A tile whose 16 rows are skipped loads no line record.
+ * Every value written is rtx_voigt_sum's, bit for bit; layers outside [k_lo, k_hi) are not touched. This is the launch that
+ * rtx_compute_tud_opts(RTX_CTUD_OD_SCRATCH) makes for its middle layers, with the caller's rows in place of the TUD pass's.
+ * flags must be 0. Refused, with a message: the last prologue was an axis one; the table has a hot-tile bound
+ * (rtx_prep_split_bound(prep) > 0: the parts kernels take no subset); RADTXFR_VOIGT_KERNEL=scatter (the point-by-point kernel
+ * takes none either); a layer range outside [0, n_layers); skip_rows misaligned, or given for a table without lines. */
+int rtx_voigt_sum_rows(const rtx_prep* prep, const rtx_grid* grid, int n_layers, float* out_f32, int64_t ld, int k_lo,
+                       int k_hi, const unsigned char* skip_rows, void* stream, unsigned flags);
 /* The line-sum on the axis of the last rtx_line_prep_axis (an error if the last prologue was a grid one, and
  * rtx_voigt_sum after an axis prologue is one too): out_*[n_layers][ld], ld >= nx, as for rtx_voigt_sum. Point by point
  * (no Chebyshev-node far wings), deterministic: repeated calls give identical bits. */

@@ -38,6 +38,7 @@ PROTOTYPES = {
     "rtx_line_prep_window": (_i32, [_vp, _vp, _gp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _i32, _vp]),
     "rtx_line_prep_axis": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _i32, _vp]),
     "rtx_voigt_sum": (_i32, [_vp, _gp, _i32, _vp, _vp, _i64, _vp]),
+    "rtx_voigt_sum_rows": (_i32, [_vp, _gp, _i32, _vp, _i64, _i32, _i32, _vp, _vp, C.c_uint]),
     "rtx_voigt_sum_axis": (_i32, [_vp, _i32, _vp, _vp, _i64, _vp]),
     "rtx_sdvoigt_sum": (_i32, [_vp, _gp, _i32, _vp, _vp, _i64, _vp]),
     "rtx_lines_set_sd": (_i32, [_vp, _vp, _vp]),

@@ -208,3 +208,28 @@ int rtx_voigt_sum_layers(const rtx_prep* P, const rtx_grid* grid, int n_layers, 
   if (grid->n == 0) return 0;
   return rtx_voigt_sum_scatter(P, grid, n_layers, out_f32, nullptr, ld, (hipStream_t)stream, launch_tile_ranges, 1, &sel);
 }
+
+// The public form of the subset: layers [k_lo, k_hi), and of those every 64-point row whose byte in skip_rows is not set.
+extern "C" int rtx_voigt_sum_rows(const rtx_prep* P, const rtx_grid* grid, int n_layers, float* out_f32, int64_t ld, int k_lo,
+                                  int k_hi, const unsigned char* skip_rows, void* stream, unsigned flags) {
+  if (flags != 0) RTX_FAIL("rtx_voigt_sum_rows: flags=%u, none is defined", flags);
+  if (!P) RTX_FAIL("prep is NULL");
+  if (P->axis) RTX_FAIL("rtx_voigt_sum_rows: the last prologue was rtx_line_prep_axis, whose sum takes no subset");
+  if (voigt_kernel_choice() != 0) RTX_FAIL("rtx_voigt_sum_rows: RADTXFR_VOIGT_KERNEL=scatter, the point-by-point kernel takes no subset");
+  if (P->split_bound > 0 && P->items.get())
+    RTX_FAIL("rtx_voigt_sum_rows: the table has a hot-tile bound (%lld extra parts), whose tiles take no subset", (long long)P->split_bound);
+  if (n_layers < 1 || n_layers != P->n_layers) RTX_FAIL("n_layers=%d does not match the last rtx_line_prep (%d)", n_layers, P->n_layers);
+  if (k_lo < 0 || k_hi < k_lo || k_hi > n_layers) RTX_FAIL("rtx_voigt_sum_rows: layers [%d,%d) outside [0,%d)", k_lo, k_hi, n_layers);
+  if ((uintptr_t)skip_rows & 15u) RTX_FAIL("rtx_voigt_sum_rows: skip_rows is not 16-byte aligned");
+  if (rtx_check_grid(grid)) return 1;
+  if (!out_f32) RTX_FAIL("the output is NULL");
+  if (ld < grid->n) RTX_FAIL("ld=%lld < n=%lld", (long long)ld, (long long)grid->n);
+  if (k_lo == k_hi || grid->n == 0) return 0;
+  if (P->n_lines == 0) {
+    if (skip_rows) RTX_FAIL("rtx_voigt_sum_rows: skip_rows on a table without lines");
+    RTX_HIP(hipMemset2DAsync(out_f32 + (size_t)k_lo * (size_t)ld, ld * sizeof(float), 0, grid->n * sizeof(float), k_hi - k_lo, (hipStream_t)stream));
+    return 0;
+  }
+  const VoigtLayers sel{k_hi - k_lo, k_lo, 0, k_hi - k_lo, skip_rows, true};
+  return rtx_voigt_sum_layers(P, grid, n_layers, out_f32, ld, stream, sel);
+}

@@ -461,13 +461,29 @@ __global__ __launch_bounds__(256) void voigt_scatter_kernel(ScArgs a) {
 // Layer subsets and done rows (rtx_compute_tud_opts, RTX_CTUD_OD_SCRATCH; profiles/od_skip_time.txt): the layers between the
 // bottom chunk and the TUD pass's look at the top are summed in a launch of their own, after the early TUD launch has said which
 // rows no wave will read. A tile whose 16 rows are all done returns before it loads a record (33.4 % of that launch's
-// workgroups on C3: line-sum 1.419 -> 1.204 ms for both launches together); a done row of any other tile is computed as ever
-// and only not stored -- except in the drain, where the done rows are taken out of a general entry's near-zone and window-edge
-// masks (m_pp, m_ed) once per entry: 63 % of the tiles on C3 are hidden in part, with 53 % of their rows done. Emission, fill
-// levels and drain points are untouched, so a live row's adds keep their order. Step, two sessions of six interleaved runs:
-// 1.4034 -> 1.3793 ms (every run below; 1.8 times the other build's spread, one run of which stood 0.008 apart) and 1.4004 ->
-// 1.3729 ms (4.8 times). Measured and not taken, both for one spilled register in <false> at its 80: the same for the band rows
-// (m_cut after the run is formed, the run's done rows passed over in its loops), and the row test in edge_one.
+// workgroups on C3: line-sum 1.419 -> 1.204 ms for both launches together). 63 % of the tiles on C3 are hidden in part, with
+// 53 % of their rows done, and those tiles are 94 % of the workgroups that still run in that launch. For them the launch has an
+// instantiation of its own, voigt_nodal_kernel<false, true> (HIDE; profiles/od_hide_time.txt, tools/count_hidden_rows.py is the
+// census); the plain <false> one, which every other launch runs, knows of no done rows at all, and the fp64 one only does not
+// store them and masks m_pp and m_ed in the drain, as before. HIDE, every stored value unchanged bit for bit:
+//  - row level: a block of four rows that are all done is passed over in both passes behind one wave-uniform test (30 % of the
+//    row evaluations of a partly hidden tile by the census; a test per pair or per row would remove 41 % and 47 %). Members,
+//    groups, pulls and the adds into every other nod[r] are what they were; final stage 1 skips a done row's sum;
+//  - entry lists: the live-row mask is applied where the masks are formed (lane = candidate). An edge-only entry whose row is
+//    done and a general entry with no live row are not stored (48 % and 36 % of them); a stored entry's m_pp and m_ed hold live
+//    rows only, its band run m_bd is trimmed to its first and last live row (55 % of the band rows go; a done row inside the run
+//    is evaluated into the tile copy and never stored). m_bd & ~m_cut stays one run. The fill level of each list is counted as
+//    before, over every emitted candidate dead or alive, and the list is drained when THAT count reaches the capacity; a second
+//    wave-uniform counter and a ballot of the live lanes give the write position. So the dead entries drop out of the sequence
+//    of adds into a live point and nothing else moves.
+// Launch B 458.7 -> 348.2 us (rocprofv3, 50 launches each; launch A 720.9 -> 720.6), per launch B 2.683e8 -> 1.890e8 VALU,
+// 1.124e8 -> 0.894e8 SALU and 3.637e7 -> 2.806e7 LDS wave-instructions; step, six interleaved runs each: 1.3819-1.3888 (median
+// 1.3839) -> 1.2773-1.2896 (1.2810) ms, 15 times the parent's spread. Each part on its own against the parent: the row level
+// 1.3574-1.3664 (1.3625, 3.1 times), the lists 1.3025-1.3145 (1.3041, 11.6 times). Registers: 80 VGPRs, none spilled, 6 waves
+// per SIMD, two SGPRs spilled to lanes; the shared instantiation had spilled VGPRs with a test per row or per pair.
+// Measured and not taken: the row-level test per pair and per row with the lists as above (7 and 13 spilled SGPRs, no VGPR):
+// 1.2797 / 1.2768 and 1.2847 / 1.2753 ms against 1.2799 / 1.2763 for the block of four, two interleaved runs each -- the finer
+// tests remove more evaluations and pay for it in branches and lane spills.
 #ifndef RTX_SC_WAVES
 #define RTX_SC_WAVES 6
 #endif
@@ -496,6 +512,12 @@ __global__ __launch_bounds__(256) void voigt_scatter_kernel(ScArgs a) {
 #ifndef RTX_SC_BAND_SPLIT
 #define RTX_SC_BAND_SPLIT 1  // band rows wholly inside the window (y >= 1) in loops of their own, without the window mask (drain)
 #endif
+#ifndef RTX_SC_HIDE_ROWS
+#define RTX_SC_HIDE_ROWS 4  // row level of the instantiation for launches with done rows: rows passed over per wave-uniform test (1, 2, 4; 0: none)
+#endif
+#ifndef RTX_SC_HIDE_LISTS
+#define RTX_SC_HIDE_LISTS 1  // the same instantiation: dead entries are not stored, the stored ones carry live rows only
+#endif
 #ifndef SC_ENT_CAP
 #define SC_ENT_CAP (SC_EDGE_LIST ? 16 : 32)  // point-by-point entries per wave (64 B each). Without the edge list, two waves per workgroup: 16 -> 2.02 ms, 24 -> 1.99, 32 -> 1.96, 48 -> 2.03
 #endif
@@ -506,13 +528,22 @@ __global__ __launch_bounds__(256) void voigt_scatter_kernel(ScArgs a) {
 // PARTS: the instantiation of the parts kernels. It sends every band row through band_row's full body: with the lighter loops of
 // the drain beside it, voigt_nodal_parts_kernel<false> -- the same 80 registers, and the part's range and output pointer to hold --
 // spills a register. Hot tiles are rare (none on C3), and the values are the same either way.
-// done_rows: rows that are not stored (sc_done_rows; launches with a.done only), and that the drain leaves out of a general
-// entry's near-zone and window-edge rows. The row-level and tile-level passes accumulate all rows at once and stay as they are,
-// and the order of the adds into a live row does not change.
-template <bool SMALLY, bool PARTS = false>
+// done_rows: rows that are not stored (sc_done_rows; launches with a.done only). HIDE = false (the fp64 instantiation in such a
+// launch; 0 everywhere else): the drain leaves them out of a general entry's near-zone and window-edge rows. HIDE: the
+// instantiation for launches with a.done (header: row level, stage 1, entry lists). The tile-level pass stays as it is, and the
+// order of the adds into a live row does not change.
+template <bool SMALLY, bool PARTS = false, bool HIDE = false>
 __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile, const int k, const int2 part_rng = make_int2(0, 0),
                                            float* __restrict__ part_out = nullptr, const unsigned done_rows = 0u) {
+  static_assert(!HIDE || (!SMALLY && !PARTS), "done rows are left out by the fp32 tile kernel alone");
   constexpr int ROWS = RTX_SC_ROWS;
+  constexpr int HIDE_G = HIDE ? RTX_SC_HIDE_ROWS : 0;        // row level: rows per test
+  constexpr bool HIDE_L = HIDE && RTX_SC_HIDE_LISTS != 0;    // entry lists without dead entries
+  // rows [r0, r0 + HIDE_G) all done (wave-uniform; r0 a multiple of HIDE_G)
+  auto grp_done = [&](int r0) -> bool {
+    constexpr unsigned G = (1u << (HIDE_G > 0 ? HIDE_G : 1)) - 1u;
+    return HIDE_G > 0 && ((done_rows >> r0) & G) == G;
+  };
   constexpr int TILE = 64 * ROWS;
   __shared__ float s_acc[SC_NW][TILE];              // one private tile per wave (near rows)
   __shared__ float4 s_ent[SC_NW][SC_ENT_CAP][4];
@@ -566,7 +597,8 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
   }
   float tnod_a = 0.f, tnod_b = 0.f;
   int n_tile_members = 0;  // wave-uniform
-  int n_ent = 0;  // wave-uniform
+  int n_ent = 0;  // wave-uniform: the list's fill level, counted over every emitted candidate; a drain when it reaches the capacity
+  int n_ent_w = 0;  // HIDE_L: entries stored (the emitted candidates with a live row); wave-uniform
   float4(*__restrict__ ent)[4] = s_ent[wave];
   // number of set bits of a wave mask below this lane: v_mbcnt_lo/hi on the (scalar) mask -- no per-lane mask registers
   auto below = [](unsigned long long m) -> int {
@@ -589,7 +621,8 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
   // prologue's clamp of zw, and then |u| > 2^24), so stepping u from row to row would round differently there.
   static_assert(ROWS <= 16, "an entry packs its row masks as 16-bit halves");
   auto drain = [&]() {
-    for (int e = 0; e < n_ent; ++e) {
+    const int n_stored = HIDE_L ? n_ent_w : n_ent;
+    for (int e = 0; e < n_stored; ++e) {
       const float4 e0 = ent[e][0], e1 = ent[e][1], e2 = ent[e][2], e3 = ent[e][3];
       LineRec q;
       q.a = e0.x; q.c = e0.y; q.b1 = e0.z; q.b0 = e0.w;
@@ -598,8 +631,8 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
       const unsigned w0 = (unsigned)__builtin_amdgcn_readfirstlane(__float_as_int(e3.x));
       const unsigned w1 = (unsigned)__builtin_amdgcn_readfirstlane(__float_as_int(e3.y));
       unsigned m_pp = w0 & 0xffffu, m_ed = w0 >> 16, m_bd = w1 & 0xffffu, m_cut = w1 >> 16;
-      if (!PARTS) {  // done rows (launches with a.done): nobody reads them, and a live row's adds keep their order. The band rows and
-                     // the edge list are left alone: masking either spills a register in <false> (header)
+      if (!PARTS && !HIDE_L) {  // done rows (the fp64 instantiation in a launch with a.done): nobody reads them, and a live row's adds
+                                // keep their order. HIDE_L: the masks lost their done rows at emission
         m_pp &= ~done_rows; m_ed &= ~done_rows;
       }
       auto slot = [&]() -> int { return __builtin_amdgcn_readfirstlane(__float_as_int(ent[e][3].z)); };
@@ -665,13 +698,15 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
       STAMP(5);  // band rows
     }
     n_ent = 0;
+    n_ent_w = 0;
   };
 
   // Window-edge entries: [a c b1 b0] [Ay Ay0 u(lane 0 of the row) packed], packed = first inside lane (left edge) or first
   // outside lane (right edge) | row << 7 | right << 12. SC_EDGE_UNROLL entries per iteration: their reads and evaluations are
   // independent, only the two read-add-writes of the tile copy are ordered (a wave's LDS operations complete in order, so
   // two entries of the same row add up correctly); the list order, hence the summation order, is fixed.
-  int n_edge = 0;  // wave-uniform
+  int n_edge = 0;  // wave-uniform: fill level over every emitted candidate, as n_ent
+  int n_edge_w = 0;  // HIDE_L: entries stored
   float4(*__restrict__ edg)[2] = s_edge[wave];
   auto edge_one = [&](const float4& E0, const float4& E1, int pk) {
     const int r = (pk >> 7) & 31, t = pk & 127;
@@ -687,12 +722,13 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
     p[0] = fmaf(num, rden, p[0]);
   };
   auto drain_edges = [&]() {
-    for (int e = 0; e < n_edge; e += SC_EDGE_UNROLL) {
+    const int n_stored = HIDE_L ? n_edge_w : n_edge;
+    for (int e = 0; e < n_stored; e += SC_EDGE_UNROLL) {
       float4 E0[SC_EDGE_UNROLL], E1[SC_EDGE_UNROLL];
       int pk[SC_EDGE_UNROLL];
 #pragma unroll
       for (int q = 0; q < SC_EDGE_UNROLL; ++q) {
-        const int eq = e + q < n_edge ? e + q : e;
+        const int eq = e + q < n_stored ? e + q : e;
         E0[q] = edg[eq][0];
         E1[q] = edg[eq][1];
       }
@@ -700,9 +736,10 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
       for (int q = 0; q < SC_EDGE_UNROLL; ++q) pk[q] = __builtin_amdgcn_readfirstlane(__float_as_int(E1[q].w));
 #pragma unroll
       for (int q = 0; q < SC_EDGE_UNROLL; ++q)
-        if (e + q < n_edge) edge_one(E0[q], E1[q], pk[q]);
+        if (e + q < n_stored) edge_one(E0[q], E1[q], pk[q]);
     }
     n_edge = 0;
+    n_edge_w = 0;
   };
 
   // 64 SC_NW candidates per round: wave w, lane i takes candidate rng.x + w + SC_NW i (+ 64 SC_NW per round)
@@ -744,18 +781,24 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
       const int t = left ? dlo - 64 * re : dhi - 64 * re;  // in [1, 63] for a cut row
       const int pk = (t & 127) | (re << 7) | (left ? 0 : 1 << 12);
       bool emit = edge_only;
+      // HIDE_L: an entry whose row is done takes its place in the count and is not stored -- the drain points, and with them the
+      // order of the adds into a live point, are those of the full list
+      const bool live = !HIDE_L || !((done_rows >> re) & 1u);
       unsigned long long eb = __ballot(emit);
       while (eb) {
         const int room = SC_EDGE_CAP - n_edge;
         const int r = below(eb);
-        if (emit && r < room) {
-          float4* d = edg[n_edge + r];
+        const bool take = emit && r < room;
+        const unsigned long long lb = HIDE_L ? __ballot(take && live) : 0ull;
+        if (take && live) {
+          float4* d = edg[HIDE_L ? n_edge_w + below(lb) : n_edge + r];
           d[0] = f0;
           d[1] = make_float4(f1.x, f1.y, ub + (float)(64 * re), __int_as_float(pk));
-          emit = false;
         }
+        emit = emit && !take;
         const int cnt = __popcll(eb);
         n_edge += cnt < room ? cnt : room;
+        if (HIDE_L) n_edge_w += __popcll(lb);
         if (n_edge == SC_EDGE_CAP) drain_edges();
         eb = __ballot(emit);
       }
@@ -764,23 +807,36 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
       // the packed row masks (drain): formed here, so that the emission loop holds two registers, not the masks they come from
       // band rows that take band_row's full body: cut by a window edge, or of a y < 1 line (fp64 on its inner rows, or its
       // band lanes left to the other pass: nothing for a lighter body to save)
-      const unsigned m_cut = f1.z < 1.0f ? m_bd : m_bd & ~m_in;
-      const unsigned w0 = m_pp | (m_ed << 16), w1 = m_bd | (m_cut << 16);
-      bool emit = !(RTX_SC_ABLATE & 8) && !edge_only && (w0 | w1) != 0u;
+      // HIDE_L: the stored masks hold live rows only -- m_pp and m_ed without their done rows, the band run m_bd trimmed to its
+      // first and last live row (still one run, and so is m_bd & ~m_cut: the drain's band loops rely on that; a done row inside
+      // the run is evaluated and never stored). A candidate with no live row takes its place in the count and is not stored.
+      unsigned l_bd = m_bd;
+      if (HIDE_L) {
+        const unsigned lv = m_bd & ~done_rows;
+        l_bd = lv ? bits(__builtin_ctz(lv), 32 - __builtin_clz(lv)) : 0u;
+      }
+      const unsigned l_pp = HIDE_L ? m_pp & ~done_rows : m_pp, l_ed = HIDE_L ? m_ed & ~done_rows : m_ed;
+      const unsigned m_cut = f1.z < 1.0f ? l_bd : l_bd & ~m_in;
+      const unsigned w0 = l_pp | (l_ed << 16), w1 = l_bd | (m_cut << 16);
+      bool emit = !(RTX_SC_ABLATE & 8) && !edge_only && (m_pp | m_ed | m_bd) != 0u;
+      const bool live = !HIDE_L || (w0 | w1) != 0u;
       unsigned long long eb = __ballot(emit);
       while (eb) {
         const int room = SC_ENT_CAP - n_ent;
         const int r = below(eb);
-        if (emit && r < room) {
-          float4* d = ent[n_ent + r];
+        const bool take = emit && r < room;
+        const unsigned long long lb = HIDE_L ? __ballot(take && live) : 0ull;
+        if (take && live) {
+          float4* d = ent[HIDE_L ? n_ent_w + below(lb) : n_ent + r];
           d[0] = f0;
           d[1] = f1;
           d[2] = make_float4(ub, (float)(qlo - qi0), (float)(qhi - qi0), qzw > 0 ? (float)qzw : -1.0f);
           d[3] = make_float4(__int_as_float((int)w0), __int_as_float((int)w1), __int_as_float(slot), __int_as_float((f1.z < 1.0f ? 1 : 0) | (f1.z >= 6.0f ? 2 : 0)));
-          emit = false;
         }
+        emit = emit && !take;
         const int cnt = __popcll(eb);
         n_ent += cnt < room ? cnt : room;
+        if (HIDE_L) n_ent_w += __popcll(lb);
         if (n_ent == SC_ENT_CAP) drain();
         eb = __ballot(emit);
       }
@@ -846,13 +902,21 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
         const float dx = 64.0f * qa;
         if (pass == 0) {
           if (e >= nR) { qAy = 0.f; qAy0 = 0.f; }  // empty slot of the last group: numerator 0 on every row
+          // HIDE: a group of rows that are all done is passed over (wave-uniform). Its nod[] are never read (final stage 1), and
+          // the members, the pulls and the adds into every other row stay what they are.
+          constexpr int RG = HIDE_G > 0 ? HIDE_G : ROWS;
+          static_assert(ROWS % RG == 0, "row groups tile the rows");
 #pragma unroll
-          for (int r = 0; r < ROWS; ++r) {
-            const float x = fmaf((float)r, dx, x0);
-            const float xx = x * x;
-            const float num = fmaf(xx, qAy, qAy0);
-            const float rden = __builtin_amdgcn_rcpf(fmaf(xx + qb1, xx, qb0));
-            nod[r] = fmaf(num, rden, nod[r]);
+          for (int r0 = 0; r0 < ROWS; r0 += RG) {
+            if (grp_done(r0)) continue;
+#pragma unroll
+            for (int r = r0; r < r0 + RG; ++r) {
+              const float x = fmaf((float)r, dx, x0);
+              const float xx = x * x;
+              const float num = fmaf(xx, qAy, qAy0);
+              const float rden = __builtin_amdgcn_rcpf(fmaf(xx + qb1, xx, qb0));
+              nod[r] = fmaf(num, rden, nod[r]);
+            }
           }
         } else {
           int mf = __builtin_amdgcn_ds_bpermute(sl << 2, (int)m_far);
@@ -876,8 +940,15 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
           // groups save)
           // (skipping the blocks of four rows that no member of the group has set -- a partial member has ~9 of its 16 rows set --
           // behind a ballot each: 1.815 against 1.823 ms, not worth the branches)
-          SC_PART_ROW(0) SC_PART_ROW(1) SC_PART_ROW(2) SC_PART_ROW(3) SC_PART_ROW(4) SC_PART_ROW(5) SC_PART_ROW(6) SC_PART_ROW(7)
-          SC_PART_ROW(8) SC_PART_ROW(9) SC_PART_ROW(10) SC_PART_ROW(11) SC_PART_ROW(12) SC_PART_ROW(13) SC_PART_ROW(14) SC_PART_ROW(15)
+          // HIDE: as in the full pass, one wave-uniform test per group of HIDE_G rows (1, 2 or 4)
+          static_assert(HIDE_G == 0 || HIDE_G == 1 || HIDE_G == 2 || HIDE_G == 4, "rows per done-row test");
+#define SC_PART_ONE(r_) if (HIDE_G != 1 || !grp_done(r_)) { SC_PART_ROW(r_) }
+#define SC_PART_TWO(r_) if (HIDE_G != 2 || !grp_done(r_)) { SC_PART_ONE(r_) SC_PART_ONE(r_ + 1) }
+#define SC_PART_FOUR(r_) if (HIDE_G != 4 || !grp_done(r_)) { SC_PART_TWO(r_) SC_PART_TWO(r_ + 2) }
+          SC_PART_FOUR(0) SC_PART_FOUR(4) SC_PART_FOUR(8) SC_PART_FOUR(12)
+#undef SC_PART_FOUR
+#undef SC_PART_TWO
+#undef SC_PART_ONE
           SC_PART_ROW(16) SC_PART_ROW(17) SC_PART_ROW(18) SC_PART_ROW(19) SC_PART_ROW(20) SC_PART_ROW(21) SC_PART_ROW(22) SC_PART_ROW(23)
           SC_PART_ROW(24) SC_PART_ROW(25) SC_PART_ROW(26) SC_PART_ROW(27) SC_PART_ROW(28) SC_PART_ROW(29) SC_PART_ROW(30)
 #undef SC_PART_ROW
@@ -948,6 +1019,7 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
   // stage 1: thread (r, jj) adds the waves' row-level sums in a fixed order
   static_assert(SC_NW == 1 || SC_NW == 2 || SC_NW == 4, "one, two or four waves per workgroup");
   for (int o = wave * 64 + ln; o < ROWS * CHEB_N; o += 64 * SC_NW) {  // o = r * CHEB_N + jj
+    if (HIDE && ((done_rows >> (o >> 3)) & 1u)) continue;  // a done row: stage 2 does not read its sums
     float v = reinterpret_cast<const float*>(&s_ent[0][0][0])[o];
     if constexpr (SC_NW >= 2) v += reinterpret_cast<const float*>(&s_ent[1][0][0])[o];
     if constexpr (SC_NW == 4) v += reinterpret_cast<const float*>(&s_ent[2][0][0])[o] + reinterpret_cast<const float*>(&s_ent[3][0][0])[o];
@@ -1013,8 +1085,10 @@ __device__ __forceinline__ void nodal_tile(const ScArgs& a, const int b_or_tile,
 #ifndef RTX_SC_WAVES_SMALLY
 #define RTX_SC_WAVES_SMALLY 4
 #endif
-template <bool SMALLY>
+// HIDE (fp32 only): the instantiation for launches that carry done rows (a.done); the plain one knows of none.
+template <bool SMALLY, bool HIDE = false>
 __global__ __launch_bounds__(64 * SC_NW, SMALLY ? RTX_SC_WAVES_SMALLY : RTX_SC_WAVES) void voigt_nodal_kernel(ScArgs a) {
+  static_assert(!(SMALLY && HIDE), "the fp64 instantiation treats done rows as before");
   const int k = sc_layer(a, blockIdx.y);
   if ((a.smally[k] != 0) != SMALLY) return;
   if (SMALLY) {
@@ -1024,10 +1098,12 @@ __global__ __launch_bounds__(64 * SC_NW, SMALLY ? RTX_SC_WAVES_SMALLY : RTX_SC_W
       nodal_tile<true>(a, b, k, make_int2(0, 0), nullptr, done_rows);
       __syncthreads();  // the tile copies are reused by the next slot
     }
-  } else {
+  } else if (HIDE) {
     const unsigned done_rows = sc_done_rows(a, blockIdx.x);
     if (done_rows == 0xFFFFu) return;  // a hidden tile: before a record is loaded
-    nodal_tile<false>(a, blockIdx.x, k, make_int2(0, 0), nullptr, done_rows);
+    nodal_tile<false, false, true>(a, blockIdx.x, k, make_int2(0, 0), nullptr, done_rows);
+  } else {
+    nodal_tile<false>(a, blockIdx.x, k);
   }
 }
 
@@ -1109,7 +1185,8 @@ int rtx_voigt_sum_scatter(const rtx_prep* P, const rtx_grid* grid, int n_layers,
   static int lds_pad = -1;
   if (lds_pad < 0) { const char* e = getenv("RADTXFR_DEBUG_LDS_PAD"); lds_pad = e ? atoi(e) : 0; }
   if (nodal) {
-    hipLaunchKernelGGL((voigt_nodal_kernel<false>), dim3(8 * a.tiles_per_xcd, n_y), dim3(64 * SC_NW), (size_t)lds_pad, st, a);
+    if (a.done) hipLaunchKernelGGL((voigt_nodal_kernel<false, true>), dim3(8 * a.tiles_per_xcd, n_y), dim3(64 * SC_NW), (size_t)lds_pad, st, a);
+    else hipLaunchKernelGGL((voigt_nodal_kernel<false>), dim3(8 * a.tiles_per_xcd, n_y), dim3(64 * SC_NW), (size_t)lds_pad, st, a);
     RTX_LAUNCH_CHECK();
     hipLaunchKernelGGL((voigt_nodal_kernel<true>), dim3(8 * ((a.tiles_per_xcd + 15) / 16), n_y), dim3(64 * SC_NW), 0, st, a);
     if (P->split_bound > 0 && P->items.get()) {  // the table can have hot tiles: their extra parts, then the sums in part order

@@ -509,6 +509,26 @@ def voigt_sum(lines, grid, T, p_atm, weight, out_f32=None, out_f64=None, dil_air
     return out_f32, out_f64
 
 
+def voigt_sum_rows(lines, grid, n_layers, out_f32, k_lo=0, k_hi=None, skip_rows=None):
+    """The sum alone, for a part of the column (rtx_voigt_sum_rows), on the records of the last grid prologue that ran on
+    lines.plan(n_layers, grid.n) -- voigt_sum's, say: layers [k_lo, k_hi) into out_f32 [n_layers][grid.n], without the
+    64-point rows whose byte in skip_rows is set (a uint8 device tensor, 16 rows per tile of rtx_voigt_tile_points() points,
+    padded to whole tiles; None: nothing is skipped). What is written is voigt_sum's, bit for bit; everything else in
+    out_f32 keeps its value."""
+    lib = _lib.load()
+    nL = int(n_layers)
+    k_hi = nL if k_hi is None else int(k_hi)
+    _check_outputs(nL, grid.n, out_f32, None)
+    if skip_rows is not None:
+        tile = lib.rtx_voigt_tile_points()
+        need = -(-grid.n // tile) * (tile // 64)
+        assert skip_rows.dtype == torch.uint8 and skip_rows.is_cuda and skip_rows.is_contiguous() and skip_rows.numel() >= need, \
+            (skip_rows.dtype, skip_rows.shape, need)
+    _lib.check(lib.rtx_voigt_sum_rows(lines.plan(nL, grid.n)._h, grid.byref(), nL, _ptr(out_f32), grid.n, int(k_lo), k_hi,
+                                      _ptr(skip_rows), _stream_ptr(), 0))
+    return out_f32
+
+
 def voigt_sum_axis(lines, X, T, p_atm, weight, out_f32=None, out_f64=None, dil_air=1.0, dil_self=0.0, omega_wing=0.0,
                    omega_wing_hw=50.0, intensity_threshold=0.0, scale=1.0, partitionFunction=None, qratio=None, mass=None,
                    profile=0, diluent=None):
