@@ -739,6 +739,48 @@ int rtx_srf_pixel_cube_vjp(int nB, int Q, const double* T_node_h, const float* N
                            void* stream, unsigned flags);
 
 /* ------------------------------------------------------------------------------------------
+ * Tangent of rtx_srf_pixel_cube: J v along directions in the pixels' fractions and temperatures and in
+ * the band radiances of the pure endmembers at the nodes, without a Jacobian; the exact transpose of
+ * rtx_srf_pixel_cube_vjp. With N, tab = G, l_q, l'_q, L and the clamped k_pm as there, per vector v
+ *   t_m  = sum_q l_q(T_p)  G[k_pm][q][b]
+ *   t'_m = sum_q l'_q(T_p) G[k_pm][q][b]
+ *   s_m  = sum_q l_q(T_p)  dL[v][q][b][k_pm]
+ *   d_cube[v][b][p] = sum_m ( d_frac[v][p][m] t_m + d_Tpix[v][p] frac[p][m] t'_m ) / N_b
+ *                   + sum_m frac[p][m] s_m + (1 - sum_m frac[p][m]) dL[v][0][b][nEnd]
+ * dL [n_vec][Q][nB][nEnd + 1] is the tangent of L: what rtx_srf_radiance_jvp writes at Ts = the Q nodes,
+ * E' = [E | 0], dE' = [dE | 0], no dTs (its column nEnd holds the same bits at every node; node 0's is
+ * taken, where the adjoint places the cotangent). The d_Tpix term is the derivative of the interpolant
+ * rtx_srf_pixel_cube evaluates, not of Planck's function.
+ *   nB, Q, T_node_h, N, tab, nEnd, nPix, nMix, kidx, frac, Tpix: as rtx_srf_pixel_cube_vjp;
+ *   d_frac [n_vec][nPix][nMix] float32, d_Tpix [n_vec][nPix] fp64, dL float32: DEVICE, each may be NULL
+ *   (an exact zero tangent: nothing is read or evaluated for it, and the result has the bits of zeros
+ *   passed), not all three; 1 <= n_vec <= rtx_srf_pixel_cube_jvp_max_vectors() = 2;
+ *   d_cube [n_vec][nB][nPix] float32 DEVICE.
+ * A band with N_b = 0 is NaN in every pixel and a pixel whose temperature is not finite or lies outside
+ * [T_lo, T_hi] is NaN down its column, in every vector: selects at the store, whatever the tangents hold.
+ * Refused before anything is launched, nothing written: everything rtx_srf_pixel_cube refuses, all three
+ * tangents NULL, a NULL d_cube, n_vec outside [1, max_vectors], flags != 0. nB == 0 or nPix == 0 writes
+ * nothing and returns 0.
+ * Arithmetic: l_q and l'_q as rtx_srf_pixel_cube_vjp forms them (the same code). t, t' and s are fp32
+ * fmaf chains, q ascending: t and t' have the adjoint's bits. Then fp64, m ascending:
+ *   A = fma(d_frac, t, A);  A = fma(d_Tpix * frac, t', A);  B = fma(frac, s, B);  F = F + frac
+ *   d_cube = fma(1 - F, dL[v][0][b][nEnd], A / (double)N_b + B), rounded to float32 once, at the store.
+ * Determinism: d_cube[v][b][p] is a pure function of (pixel p's kidx, frac, T, d_frac[v] and d_Tpix[v];
+ * band b's N and tab column; vector v's dL column; the nodes and the range): the same bits run to run,
+ * for any nPix, any position of the pixel in the scene, any subset of the bands (order kept), for a
+ * vector alone or beside another, and whether the table slice is held in LDS (nEnd * Q <= 128) or read
+ * from global memory. No atomics. The vectors of a call share the pixel's weights, its mixture and t,
+ * t'; each has one 16 KiB output tile in LDS beside at most 32 KiB of table, which is what bounds
+ * max_vectors. dL is re-laid with the bands innermost into a grow-only workspace, owned per (device,
+ * stream), that also holds the weights; a call that has to grow it waits for the device first.
+ * flags: none is defined, pass 0 (anything else is refused). */
+int rtx_srf_pixel_cube_jvp(int nB, int Q, const double* T_node_h, const float* N, const float* tab,
+                           int nEnd, int64_t nPix, int nMix, const int32_t* kidx, const float* frac,
+                           const double* Tpix, const float* d_frac, const double* d_Tpix,
+                           const float* dL, int n_vec, float* d_cube, void* stream, unsigned flags);
+int rtx_srf_pixel_cube_jvp_max_vectors(void);
+
+/* ------------------------------------------------------------------------------------------
  * Speed-dependent Voigt line-sum. Replaces the per-line PROFILE_SDVOIGT + scatter-add of
  * absorptionCoefficient_SDVoigt, misc/hapi.py:10897-10900 (PROFILE_SDVOIGT :10117 -> pcqsdhc :9850-10024 with
  * anuVC = eta = 0: PART1 for lines without speed dependence, PART2/3/4 otherwise; CPF = hum1_wei :9833, cpf3 :9645),

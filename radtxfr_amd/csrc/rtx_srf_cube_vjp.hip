@@ -23,6 +23,7 @@
 //                      slice 0. Writes the chunk's sums to the workspace, [chunk][nEnd + 1][Q][nB].
 //   scv_sum_kernel     gL[q][b][e]: the chunks ascending in fp64, rounded to fp32 at the store.
 #include "rtx_common.h"
+#include "rtx_srf_cube_common.h"
 
 #define SCV_QMAX 8       // rtx_srf_cube_max_nodes()
 #define SCV_PB 256       // pixels per workgroup of the pixel kernel
@@ -62,21 +63,7 @@ __device__ __forceinline__ float scv_uniform(float v) { return __int_as_float(__
 // l_q(T) and l'_q(T) in fp64, the products over r ascending as rtx_srf_pixel_cube forms them, one division each
 template <int Q>
 __device__ __forceinline__ void scv_weight(const ScvArgs& a, double T, int q, double& l, double& dl) {
-  double num = 1.0, dnum = 0.0;
-#pragma unroll
-  for (int r = 0; r < Q; ++r)
-    if (r != q) num *= T - a.Tn[r];
-#pragma unroll
-  for (int s = 0; s < Q; ++s) {
-    if (s == q) continue;
-    double prod = 1.0;
-#pragma unroll
-    for (int r = 0; r < Q; ++r)
-      if (r != q && r != s) prod *= T - a.Tn[r];
-    dnum += prod;
-  }
-  l = num / a.den[q];
-  dl = dnum / a.den[q];
+  srf_cube_weight<Q>(a, T, q, l, dl);  // shared with the tangent (rtx_srf_cube_jvp.hip)
 }
 
 // Row k of the table for this lane's band: sc_row of rtx_srf_cube.hip, the same LDS layout.

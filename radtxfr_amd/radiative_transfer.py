@@ -1263,6 +1263,115 @@ def compute_band_radiance_jvp(Xmin, Xmax, sensor, Xk, emis_knots, Ts_surface, ta
     return np.array(sensor.centres), L_h, dL_h
 
 
+_CUBE_TANGENTS = ("Tpix", "frac", "endmembers")
+
+
+def compute_hsi_cube_jvp(Xmin, Xmax, sensor, Xk, endmembers, kidx, frac, Tpix, tangents, opts=options, layers=None, fd_step_T=0.5,
+                         dT_method="fd", continuum_derivatives=False, xs_derivatives=False, n_nodes=8, T_range=None, interp_tol=1e-6,
+                         **kwargs):
+    """The per-pixel HSI cube of a scene under any sensor and its change along directions in the unknowns of a retrieval,
+    in one call: compute_TUD_jvp's tangent rows of tau / La / Ld (engine.tud_jvp), which stay on the device as float32, fed
+    to the cube's tangent (sensor.hsi_cube_srf_jvp), which adds the pixels' temperatures and fractions and the endmember
+    knots. No Jacobian and nothing of size nPix x nX is stored. With compute_hsi_cube_vjp, J^T (J v) on the cube.
+
+    sensor, Xk, endmembers, kidx, frac, Tpix, n_nodes, T_range, interp_tol as compute_hsi_cube_vjp. tangents: a non-empty
+    dict with keys among
+      "T", a molecule id of MFs_ID   [n_layers] per layer of `layers` (default all), as compute_TUD_jvp takes them;
+      "Tpix"                         [nPix] [K];
+      "frac"                         [nPix][nMix];
+      "endmembers"                   [nk][nEnd];
+    each with an optional trailing axis of n_vec directions (all entries must agree on it). A key left out does not move.
+    With only "Tpix" / "frac" / "endmembers" no rtx_tud_jvp launch and no T -+ fd_step_T or species line-sum is made: the
+    base state alone. kwargs, layers, fd_step_T, dT_method as compute_TUD_jvp, with exactly one sensor altitude and
+    returnOD=False. Returns (X_out, cube, d_cube):
+      X_out   sensor.centres;
+      cube    float32 NumPy [nB][nPix], bit-identical to compute_hsi_cube_vjp's cube;
+      d_cube  float32 NumPy shaped like cube, plus a trailing [n_vec] axis when the tangents have one; NaN where cube is NaN.
+    continuum=, continuum_derivatives, xs_lut=, xs_derivatives: as compute_band_radiance_vjp.
+    Arguments are checked before any device work. NotImplementedError: more than one altitude or theta_r, returnOD=True,
+    broadening=, xs_lut= or continuum= without their derivative flags, reduce=."""
+    name = "compute_hsi_cube_jvp"
+    c = _Call(name, Xmin, Xmax, opts, kwargs)
+    if "reduce" in c.o:
+        raise NotImplementedError(name + ": reduce= is not offered: the tangent is defined on the sensor's bands")
+    lut = _no_xs_lut(c, xs_derivatives)
+    cont = _derivative_continuum(c, continuum_derivatives)
+    if c.returnOD:
+        raise NotImplementedError(name + ": returnOD=True is not supported (the sensor stage takes transmittances)")
+    if c.Z_s.size != 1:
+        raise NotImplementedError(name + ": exactly one sensor altitude per call (got %d)" % c.Z_s.size)
+    if not isinstance(tangents, dict) or not tangents:
+        raise ValueError(name + ": tangents must be a non-empty dict with keys among \"T\", a molecule id of MFs_ID, %r" % (_CUBE_TANGENTS,))
+    atm = {k: v for k, v in tangents.items() if not (isinstance(k, str) and k in _CUBE_TANGENTS)}
+    bad = [k for k in atm if k != "T" and (isinstance(k, bool) or not isinstance(k, (int, np.integer)))]
+    if bad:
+        raise ValueError(name + ": unknown tangent key %r (expected \"T\", a molecule id of MFs_ID, \"Tpix\", \"frac\" or \"endmembers\")"
+                         % (bad[0],))
+    wrt = tuple(atm.keys())
+    # a call without an atmospheric key has no wrt entry: the checks that do not concern wrt are run with a stand-in
+    wrt_, lay, nX = _jacobian_args(name, Xmin, Xmax, c.o, wrt if wrt else ("T",), layers, None, fd_step_T if wrt else 1.0,
+                                   host_result=False, dT_method=dT_method)
+    wrt = wrt_ if wrt else ()
+    _xs_axis(c, lut)
+    from . import sensor as _sensor  # sensor.py imports this module
+
+    def host(v, what, kinds, dtype):
+        a = v.detach().cpu().numpy() if _is_torch(v) else np.asarray(v)
+        if a.dtype.kind not in kinds:
+            raise ValueError(name + ": %s has dtype %s" % (what, a.dtype))
+        return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype))
+
+    Xk = np.ascontiguousarray(np.asarray(Xk, dtype=np.float64).ravel())
+    E_h, k_h = host(endmembers, "endmembers", "f", np.float32), host(kidx, "kidx", "iu", np.int32)
+    f_h, T_h = host(frac, "frac", "f", np.float32), host(Tpix, "Tpix", "f", np.float64)
+    z = torch.zeros(nX, dtype=torch.float32)  # stands for tau, La, Ld in the checks
+    grid = c.grid
+    assert c.X.size == nX
+    front = _sensor._srf_cube_front(name, grid, z, z, z, Xk, E_h, k_h, f_h, T_h, sensor, n_nodes, T_range, interp_tol, need_device=False)
+    T_range = (front["T_lo"], front["T_hi"])  # explicit from here on: no read from the device
+    n_vecs = set()
+    V = None
+    if atm:
+        V, nv = _jvp_tangents(atm, lay.size, fn=name)
+        n_vecs.add(nv)
+    own = {"Tpix": ("d_Tpix", T_h, np.float64), "frac": ("d_frac", f_h, np.float32), "endmembers": ("d_endmembers", E_h, np.float32)}
+    d_own = {}
+    for key, (arg, like, dtype) in own.items():
+        if key not in tangents:
+            continue
+        d = host(tangents[key], "tangent \"%s\"" % key, "fiu", dtype)
+        if _vector_axis(d, tuple(like.shape)) is None:
+            raise ValueError(name + ": tangent \"%s\" has shape %r, expected %r plus an optional trailing vector axis"
+                             % (key, tuple(d.shape), tuple(like.shape)))
+        n_vecs.add(_vector_axis(d, tuple(like.shape))[1])
+        d_own[arg] = d
+    if len(n_vecs) != 1:
+        raise ValueError(name + ": the tangents disagree on the vector axis: %r" % sorted(n_vecs, key=str))
+    n_vec = n_vecs.pop()
+    tbl = c.table()
+    dev = engine.device()
+    E_d, k_d, f_d, T_d = (v.to(dev) for v in (E_h, k_h, f_h, T_h))
+    d_own = {k: v.to(dev) for k, v in d_own.items()}
+    rows = {}
+    if atm:
+        tau, Lu, Ld, _, d = engine.tud_jvp(tbl, grid, c.Z, c.T, c.P, c.PL, c.MF, c.ID, V, Altitudes=c.Z_s, theta_r=c.theta,
+                                           N_angle=c.N_angle, returnOD=False, wrt=wrt, layers=lay, fd_step_T=float(fd_step_T),
+                                           dT_method=dT_method, continuum=cont, xs_lut=lut)
+        # [n_vec][nX] float32 where rtx_tud_jvp wrote them, seen as [nX][n_vec]: no copy, no host round trip
+        rows = dict(d_tau=d["tau"][:, 0, :nX].T, d_La=d["La"][:, 0, :nX].T, d_Ld=d["Ld"][:, :nX].T)
+        if n_vec is None:
+            rows = {k: v[:, 0] for k, v in rows.items()}
+    else:  # the base state alone, exactly what compute_TUD runs
+        T = np.ascontiguousarray(np.atleast_1d(c.T))
+        run = engine.TudRunner(tbl, grid, np.atleast_1d(c.Z), n_layers=T.size, Altitudes=c.Z_s, theta_r=c.theta, N_angle=c.N_angle,
+                               returnOD=False, continuum=cont, xs_lut=lut)
+        tau, Lu, Ld = run.run(T, np.atleast_1d(c.P), np.atleast_1d(c.PL), c.MF.reshape(T.size, -1), c.ID)
+    t_, u_, d_ = tau[0, :nX].contiguous(), Lu[0, :nX].contiguous(), Ld[:nX].contiguous()
+    _, cube, d_cube = _sensor.hsi_cube_srf_jvp(grid, t_, u_, d_, Xk, E_d, k_d, f_d, T_d, sensor, n_nodes=n_nodes, T_range=T_range,
+                                               interp_tol=interp_tol, **rows, **d_own)
+    return np.array(sensor.centres), cube.cpu().numpy(), np.ascontiguousarray(d_cube.cpu().numpy())
+
+
 def compute_LWIR_apparent_radiance(X, emis, Ts, tau, La, Ld, dT=None, return_Ls=False):
     r"""L = tau [emis B(Ts + dT) + (1 - emis) Ld] + La for every combination, signature of :1017-1069.
 

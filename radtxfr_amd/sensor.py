@@ -406,10 +406,10 @@ def band_radiance_srf_vjp(grid, tau, La, Ld, Xk, emis_knots, Ts, sensor, g, outp
     return out
 
 
-def _jvp_tangent(x, base, what, dev=None):
+def _jvp_tangent(x, base, what, dev=None, fn="band_radiance_srf_jvp"):
     """A tangent laid out as `base` plus an optional trailing vector axis: (x with the vector axis FIRST -- a view where it
     can be --, its length or None where x came without one); None passes through. dev: the device of a float32 tensor to
-    return, or None for float64 NumPy."""
+    return, or None for float64 NumPy. fn: the caller named in the error."""
     if x is None:
         return None, None
     if dev is None:
@@ -423,8 +423,46 @@ def _jvp_tangent(x, base, what, dev=None):
         return x[None], None
     if len(shape) == len(base) + 1 and shape[:-1] == tuple(base) and shape[-1] >= 1:
         return (np.moveaxis(x, -1, 0) if dev is None else x.movedim(-1, 0)), shape[-1]
-    raise ValueError("band_radiance_srf_jvp: %s has shape %r, expected %r plus an optional trailing vector axis"
-                     % (what, shape, tuple(base)))
+    raise ValueError("%s: %s has shape %r, expected %r plus an optional trailing vector axis" % (fn, what, shape, tuple(base)))
+
+
+def _jvp_pack_rows(rows, nV, nX):
+    """The tangent rows {name: [n_vec][nX] float32 device} as rtx_srf_radiance_jvp takes them, and their leading dimension:
+    the library takes one leading dimension for the three rows: rows that share one go as they are, else they are packed."""
+    lds = set(x.stride(0) for x in rows.values()) if nV > 1 else {nX}
+    if all(x.stride(1) == 1 for x in rows.values()) and len(lds) == 1 and min(lds) >= nX:
+        return rows, lds.pop()
+    return {k: x.contiguous() for k, x in rows.items()}, nX
+
+
+def _srf_radiance_jvp_groups(grid, tau, Ld, plan, sensor, emis_knots, N, M, jr, Ts, m0, rows, ld_d, dTs, dE, dL):
+    """rtx_srf_radiance_jvp on the moments N, M [nM][nB][nk], jr that srf_moments gave at Ts[m0:m0 + nM], into
+    dL[:, m0:m0 + nM] ([n_vec][nT][nB][nE]): the temperatures and the vectors rtx_srf_radiance_jvp_max_temps() /
+    _max_vectors() at a time. rows, ld_d from _jvp_pack_rows; dTs [n_vec][nT] host or None; dE [n_vec][nk][nE] or None."""
+    lib = _lib.load()
+    dev = tau.device
+    nV, nB, nE, nk = dL.shape[0], dL.shape[2], dL.shape[3], plan["Xk_d"].numel()
+    kx, kr = sensor.on_device(dev)
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    step_t, step_v = lib.rtx_srf_radiance_jvp_max_temps(), lib.rtx_srf_radiance_jvp_max_vectors()
+    for t0 in range(m0, m0 + M.shape[0], step_t):
+        t1 = min(t0 + step_t, m0 + M.shape[0])
+        Ts_g = np.ascontiguousarray(Ts[t0:t1])
+        for v0 in range(0, nV, step_v):
+            v1 = min(v0 + step_v, nV)
+            dst = dL[v0:v1, t0:t1]
+            out = dst if dst.is_contiguous() else torch.empty((v1 - v0, t1 - t0, nB, nE), dtype=torch.float32, device=dev)
+            dTs_g = None if dTs is None else np.ascontiguousarray(dTs[v0:v1, t0:t1])
+            row = lambda k: C.c_void_p(rows[k].data_ptr() + 4 * v0 * ld_d) if k in rows else None
+            _lib.check(lib.rtx_srf_radiance_jvp(grid.byref(), p(tau), p(Ld), row("d_tau"), row("d_La"), row("d_Ld"), ld_d,
+                                                Ts_g.ctypes.data_as(C.c_void_p),
+                                                None if dTs_g is None else dTs_g.ctypes.data_as(C.c_void_p), t1 - t0,
+                                                p(plan["Xk_d"]), nk, nB, sensor.knot_start.ctypes.data_as(C.c_void_p), p(kx), p(kr),
+                                                p(N), p(M[t0 - m0:t1 - m0]), p(jr), p(emis_knots),
+                                                None if dE is None else p(dE[v0:v1]), nE, v1 - v0, p(out), st))
+            if out is not dst:
+                dst.copy_(out)
 
 
 def band_radiance_srf_jvp(grid, tau, La, Ld, Xk, emis_knots, Ts, sensor, d_tau=None, d_La=None, d_Ld=None, d_Ts=None, d_emis=None):
@@ -474,40 +512,17 @@ def band_radiance_srf_jvp(grid, tau, La, Ld, Xk, emis_knots, Ts, sensor, d_tau=N
         raise ValueError("band_radiance_srf_jvp: the tangents disagree on the vector axis: %r" % sorted(n_vecs, key=str))
     n_vec = n_vecs.pop()
     nV = 1 if n_vec is None else n_vec
-    # the library takes one leading dimension for the three rows: rows that share one go as they are, else they are packed
-    lds = set(x.stride(0) for x in rows.values()) if nV > 1 else {nX}
-    if all(x.stride(1) == 1 for x in rows.values()) and len(lds) == 1 and min(lds) >= nX:
-        ld_d = lds.pop()
-    else:
-        ld_d = nX
-        rows = {k: x.contiguous() for k, x in rows.items()}
-    kx, kr = sensor.on_device(dev)
+    rows, ld_d = _jvp_pack_rows(rows, nV, nX)
     L = torch.empty((nT, nB, nE), dtype=torch.float32, device=dev)
     dL = torch.empty((nV, nT, nB, nE), dtype=torch.float32, device=dev)
     p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    step_m, step_t, step_v = lib.rtx_srf_moments_max_temps(), lib.rtx_srf_radiance_jvp_max_temps(), lib.rtx_srf_radiance_jvp_max_vectors()
+    step_m = lib.rtx_srf_moments_max_temps()
     for m0 in range(0, nT, step_m):
         N, Cb, M, jr = srf_moments(grid, tau, La, Ld, plan["Xk_d"], Ts[m0:m0 + step_m], sensor)
         for t in range(M.shape[0]):
             _lib.check(lib.rtx_band_mix(p(N), p(Cb), p(M[t]), p(jr), nB, nk, p(emis_knots), nE, p(L[m0 + t]), st))
-        for t0 in range(m0, m0 + M.shape[0], step_t):
-            t1 = min(t0 + step_t, m0 + M.shape[0])
-            Ts_g = np.ascontiguousarray(Ts[t0:t1])
-            for v0 in range(0, nV, step_v):
-                v1 = min(v0 + step_v, nV)
-                dst = dL[v0:v1, t0:t1]
-                out = dst if dst.is_contiguous() else torch.empty((v1 - v0, t1 - t0, nB, nE), dtype=torch.float32, device=dev)
-                dTs_g = None if dTs is None else np.ascontiguousarray(dTs[v0:v1, t0:t1])
-                row = lambda k: C.c_void_p(rows[k].data_ptr() + 4 * v0 * ld_d) if k in rows else None
-                _lib.check(lib.rtx_srf_radiance_jvp(grid.byref(), p(tau), p(Ld), row("d_tau"), row("d_La"), row("d_Ld"), ld_d,
-                                                    Ts_g.ctypes.data_as(C.c_void_p),
-                                                    None if dTs_g is None else dTs_g.ctypes.data_as(C.c_void_p), t1 - t0,
-                                                    p(plan["Xk_d"]), nk, nB, sensor.knot_start.ctypes.data_as(C.c_void_p), p(kx), p(kr),
-                                                    p(N), p(M[t0 - m0:t1 - m0]), p(jr), p(emis_knots),
-                                                    None if dE is None else p(dE[v0:v1]), nE, v1 - v0, p(out), st))
-                if out is not dst:
-                    dst.copy_(out)
+        _srf_radiance_jvp_groups(grid, tau, Ld, plan, sensor, emis_knots, N, M, jr, Ts, m0, rows, ld_d, dTs, dE, dL)
     if scalar:
         L, dL = L[0], dL[:, 0]
     dL = dL.movedim(0, -1) if n_vec is not None else dL[0]
@@ -676,8 +691,9 @@ def _srf_cube_front(fn, grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sen
                 Tpix=Tpix)
 
 
-def _srf_cube_tables(grid, tau, La, Ld, f, sensor):
-    """Stages 1 and 2 of hsi_cube_srf on the front half's dict f: (N, C, tab [nEnd][Q][nB], T_host = the nodes, then the range)."""
+def _srf_cube_tables(grid, tau, La, Ld, f, sensor, keep_moments=False):
+    """Stages 1 and 2 of hsi_cube_srf on the front half's dict f: (N, C, tab [nEnd][Q][nB], T_host = the nodes, then the range);
+    keep_moments: followed by srf_moments' M [Q][nB][nk] and jrange at the nodes, which the cube's tangent uses again."""
     lib = _lib.load()
     dev = tau.device
     Q, Xk, endmembers = f["Q"], f["Xk"], f["endmembers"]
@@ -689,7 +705,7 @@ def _srf_cube_tables(grid, tau, La, Ld, f, sensor):
     p = lambda t: C.c_void_p(t.data_ptr())
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     _lib.check(lib.rtx_srf_cube_tables(p(M), p(jr), nB, Q, nk, p(endmembers), nEnd, p(tab), st))
-    return N, Cb, tab, T_host
+    return (N, Cb, tab, T_host, M, jr) if keep_moments else (N, Cb, tab, T_host)
 
 
 def hsi_cube_srf(grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sensor, n_nodes=8, T_range=None, interp_tol=1e-6):
@@ -787,6 +803,104 @@ def hsi_cube_srf_vjp(grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sensor
             if k in back:
                 out[k] = r["emis"][:, :nEnd].contiguous() if k == "endmembers" else r[k]
     return {k: out[k] for k in outputs}
+
+
+def _cube_jvp_axis(fn, tangents, bases):
+    """The vector axis of a cube tangent's groups, from their shapes alone (nothing is moved or converted): tangents
+    {name: array, tensor or None}, bases {name: the shape of the input it moves}. Returns n_vec, or None where the tangents
+    come without a trailing axis. ValueError: a shape that is neither, all None, or groups that disagree."""
+    n_vecs = set()
+    for key, x in tangents.items():
+        if x is None:
+            continue
+        shape, base = tuple(np.shape(x) if not torch.is_tensor(x) else x.shape), tuple(bases[key])
+        if shape == base:
+            n_vecs.add(None)
+        elif len(shape) == len(base) + 1 and shape[:-1] == base and shape[-1] >= 1:
+            n_vecs.add(shape[-1])
+        else:
+            raise ValueError("%s: %s has shape %r, expected %r plus an optional trailing vector axis" % (fn, key, shape, base))
+    if not n_vecs:
+        raise ValueError("%s: no tangent (%s are all None)" % (fn, ", ".join(tangents)))
+    if len(n_vecs) != 1:
+        raise ValueError("%s: the tangents disagree on the vector axis: %r" % (fn, sorted(n_vecs, key=str)))
+    return n_vecs.pop()
+
+
+def hsi_cube_srf_jvp(grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sensor, d_tau=None, d_La=None, d_Ld=None,
+                     d_endmembers=None, d_frac=None, d_Tpix=None, n_nodes=8, T_range=None, interp_tol=1e-6):
+    """hsi_cube_srf and its tangent: the change d_cube of the cube along directions in its inputs, without a
+    Jacobian and without anything of size nPix x nX or nPix x nk.
+      d_tau, d_La, d_Ld  tangents of tau, La, Ld on the native grid, [nX] (float32; device or NumPy): the rows
+                         engine.tud_jvp returns are taken where they are;
+      d_endmembers       tangent of endmembers, [nk][nEnd] (float32);
+      d_frac             tangent of frac, [nPix][nMix] (float32);
+      d_Tpix             tangent of Tpix, [nPix] (float64).
+    Each may carry a trailing axis of n_vec directions (all that are given must agree on it: ValueError otherwise); one left
+    None is an exact zero and nothing is evaluated for it; not all six may be None. Same arguments, checks and nodes as
+    hsi_cube_srf otherwise. Returns (X_out, cube, d_cube) on tau's device: cube that call's, bit for bit; d_cube float32 laid
+    out like cube, with a trailing [n_vec] axis when the tangents carry one. The cube is a linear combination of the band
+    radiances of the pure endmembers (and of a surface of emissivity 0) at the node temperatures: when any of the first four
+    tangents is given, rtx_srf_radiance_jvp at Ts = the nodes, E' = [E | 0] supplies their tangent dL, on the node moments
+    the cube itself is made from (one srf_moments pass for both), and rtx_srf_pixel_cube_jvp takes dL, d_frac and d_Tpix to
+    d_cube; with d_frac / d_Tpix alone the band tangent does not run. A band that is NaN in the cube is NaN in d_cube, and so
+    is the column of a pixel whose temperature is not finite or lies outside the range. The tangent along d_Tpix is that of
+    the interpolant hsi_cube_srf evaluates. The vectors go to the library rtx_srf_pixel_cube_jvp_max_vectors() at a time;
+    the grouping changes no bit."""
+    lib = _lib.load()
+    fn = "hsi_cube_srf_jvp"
+    f = _srf_cube_front(fn, grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sensor, n_nodes, T_range, interp_tol,
+                        need_device=False)
+    endmembers, kidx, frac, Tpix, Q = f["endmembers"], f["kidx"], f["frac"], f["Tpix"], f["Q"]
+    nPix, nMix = kidx.shape
+    nB, nk, nEnd, nX = len(sensor), f["Xk"].size, endmembers.shape[1], grid.n
+    given = dict(d_tau=d_tau, d_La=d_La, d_Ld=d_Ld, d_endmembers=d_endmembers, d_frac=d_frac, d_Tpix=d_Tpix)
+    bases = dict(d_tau=(nX,), d_La=(nX,), d_Ld=(nX,), d_endmembers=(nk, nEnd), d_frac=(nPix, nMix), d_Tpix=(nPix,))
+    n_vec = _cube_jvp_axis(fn, given, bases)
+    nV = 1 if n_vec is None else n_vec
+    for name, v in (("tau", tau), ("endmembers", endmembers), ("kidx", kidx), ("frac", frac), ("Tpix", Tpix)):
+        if not v.is_cuda:
+            raise ValueError(f"{fn} takes device tensors ({name} is not on a GPU)")
+    dev = tau.device
+    X_out = np.array(sensor.centres)
+    cube = torch.empty((nB, nPix), dtype=torch.float32, device=dev)
+    d_cube = torch.empty((nV, nB, nPix), dtype=torch.float32, device=dev)
+    shaped = lambda d: d.movedim(0, -1) if n_vec is not None else d[0]
+    if nB == 0 or nPix == 0:
+        return X_out, cube, shaped(d_cube)
+    rows = {}
+    for key in ("d_tau", "d_La", "d_Ld"):
+        x, _ = _jvp_tangent(given[key], (nX,), key, dev, fn=fn)
+        if x is not None:
+            rows[key] = x
+    dE, _ = _jvp_tangent(d_endmembers, (nk, nEnd), "d_endmembers", dev, fn=fn)
+    dF, _ = _jvp_tangent(d_frac, (nPix, nMix), "d_frac", dev, fn=fn)
+    dF = None if dF is None else dF.contiguous()  # [n_vec][nPix][nMix]
+    dT = None
+    if d_Tpix is not None:
+        dT = d_Tpix if torch.is_tensor(d_Tpix) else torch.as_tensor(np.asarray(d_Tpix, dtype=np.float64))
+        dT = dT.to(device=dev, dtype=torch.float64)
+        dT = (dT.movedim(-1, 0) if n_vec is not None else dT[None]).contiguous()  # [n_vec][nPix]
+    tau, La, Ld = tau.contiguous(), La.contiguous(), Ld.contiguous()
+    N, Cb, tab, T_host, M, jr = _srf_cube_tables(grid, tau, La, Ld, f, sensor, keep_moments=True)
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    T_p = T_host.ctypes.data_as(C.c_void_p)
+    _lib.check(lib.rtx_srf_pixel_cube(nB, Q, T_p, p(N), p(Cb), p(tab), nEnd, nPix, nMix, p(kidx), p(frac), p(Tpix), p(cube), st))
+    dL = None
+    if rows or dE is not None:  # the tangent of the pure endmembers' band radiances at the nodes, column nEnd: emissivity 0
+        pad = lambda x: torch.cat([x, torch.zeros(tuple(x.shape[:-1]) + (1,), dtype=torch.float32, device=dev)], dim=-1)
+        dL = torch.empty((nV, Q, nB, nEnd + 1), dtype=torch.float32, device=dev)
+        rows, ld_d = _jvp_pack_rows(rows, nV, nX)
+        _srf_radiance_jvp_groups(grid, tau, Ld, _srf_fused_plan(f["Xk"], dev), sensor, pad(endmembers), N, M, jr, f["nodes"], 0, rows, ld_d,
+                                 None, None if dE is None else pad(dE.contiguous()), dL)
+    step = lib.rtx_srf_pixel_cube_jvp_max_vectors()
+    for v0 in range(0, nV, step):
+        v1 = min(v0 + step, nV)
+        part = lambda t: p(t[v0:v1]) if t is not None else None
+        _lib.check(lib.rtx_srf_pixel_cube_jvp(nB, Q, T_p, p(N), p(tab), nEnd, nPix, nMix, p(kidx), p(frac), p(Tpix), part(dF), part(dT),
+                                              part(dL), v1 - v0, p(d_cube[v0:v1]), st, 0))
+    return X_out, cube, shaped(d_cube)
 
 
 def band_radiance(grid, tau, La, Ld, Xk, emis_knots, Ts, resFactor=None, keep_hires=False):
