@@ -781,6 +781,77 @@ int rtx_srf_pixel_cube_jvp(int nB, int Q, const double* T_node_h, const float* N
 int rtx_srf_pixel_cube_jvp_max_vectors(void);
 
 /* ------------------------------------------------------------------------------------------
+ * Per-pixel least-squares fit of temperature and fractions to a measured cube. The
+ * atmosphere (N, C, tab) and every pixel's endmember indices are fixed, so each pixel is its own
+ * problem in the 1 + nMix unknowns u = (T, f_1 .. f_nMix), in that order, under rtx_srf_pixel_cube's
+ * model y_b(u). N, C, tab = G, the nodes, the range, l_q, l'_q, the clamped k_pm, "live band" (N_b > 0)
+ * and "admitted pixel" (T finite and inside [T_lo, T_hi]) are as in rtx_srf_pixel_cube / _vjp.
+ *   meas [nB][nPix] float32 DEVICE: the measured cube, in the forward's layout;
+ *   wgt  [nB] float32 DEVICE or NULL (every weight 1). A band COUNTS when it is live and w_b > 0: a select,
+ *   so whatever meas holds under a band that does not count (NaN included) is never read.
+ * One evaluation at u (T fp64, f float32 as the forward takes them), per counting band:
+ *   w_q = (float)l_q, w'_q = (float)l'_q, by the adjoint's code (l_q has the forward's bits);
+ *   t_m = fmaf(w_q, G[k_m][q][b], t_m), t'_m = fmaf(w'_q, G[k_m][q][b], t'_m), q ascending (fp32);
+ *   s = fmaf(f_m, t_m, s), m ascending;  y = (C_b + s) / N_b in fp32: rtx_srf_pixel_cube's bits;
+ *   then fp64: r = (double)y - (double)meas, invN = 1 / (double)N_b,
+ *   j_0 = invN * S with S = fma((double)f_m, (double)t'_m, S), m ascending;  j_m = invN * (double)t_m;
+ *   wr = w r;  cost = fma(wr, r, cost);  grad_i = fma(j_i, wr, grad_i);  H_ij = fma(w j_i, j_j, H_ij), i >= j.
+ * THE BAND SUM RUNS OVER THE BANDS ASCENDING, in the pixel's own lane, wherever the table lies.
+ *   cost = sum w r^2 (no 1/2), grad = J^T W r, H = J^T W J packed as the lower triangle by rows
+ *   (H_00, H_10, H_11, H_20, ..): (1 + nMix)(2 + nMix) / 2 values.
+ * Damped step: (H + lambda diag H) step = -grad by Cholesky in fp64, A_ii = fma(lambda, H_ii, H_ii), the
+ * columns ascending, every inner sum by fma(-L_ik, L_jk, .) with k ascending, forward then back
+ * substitution. A pivot that is not finite or not positive: the step is NaN ("singular").
+ *
+ * rtx_srf_pixel_cube_normal: one evaluation at (Tpix, frac) and one step per pixel.
+ *   lambda [nPix] fp64 DEVICE or NULL (0); cost [nPix] fp64; grad [nPix][1 + nMix], hess
+ *   [nPix][(1 + nMix)(2 + nMix) / 2], step [nPix][1 + nMix] fp64 DEVICE, each may be NULL (not written).
+ *   A pixel that is not admitted gets NaN in all its outputs. flags: none is defined, pass 0.
+ * rtx_srf_pixel_cube_fit: Levenberg-Marquardt per pixel; pixels never interact.
+ *   1 start: under RTX_FIT_START_GIVEN the (Tpix, frac) passed in. Otherwise the node scan: for q ascending,
+ *     T = T_q (the weights are exactly 1 and 0); evaluate at f = 0; f_q = (float)(-H_ff^-1 grad_f), the
+ *     fraction block alone with lambda = 0 (a singular block skips the node); evaluate at (T_q, f_q); the
+ *     strictly smallest cost is kept, the first node wins a tie. No node with a finite cost, or a given
+ *     start whose cost is not finite: status 3.
+ *   2 lambda = lambda0.
+ *   3 a trial: the step; T' = min(max(T + step_0, T_lo), T_hi); f'_m = (float)((double)f_m + step_m);
+ *     evaluate at u'; accepted iff cost' < cost (a NaN cost rejects). Accepted: lambda = max(0.1 lambda,
+ *     1e-12), the trial's H and grad become current. Rejected: lambda = min(10 lambda, 1e12). n_iter counts
+ *     trials.
+ *   4 stops, tested in this order before a trial: cost == 0 (status 0); n_iter == max_iter (status 1); a
+ *     singular step (status 3). After an accepted trial: cost - cost' < ftol cost (status 0; ftol = 0:
+ *     never). After a rejected one: lambda at its cap (status 0).
+ *   5 status [nPix] int32: 0 stopped by cost, ftol or the cap of lambda; 1 iteration cap; 2 the given start
+ *     is not admitted or a fraction of it is not finite; 3 singular. Under 2 and 3 Tpix, frac, cost and
+ *     hess of the pixel are NaN.
+ *   frac [nPix][nMix] float32 and Tpix [nPix] fp64 DEVICE: read under RTX_FIT_START_GIVEN, always written;
+ *   0 <= max_iter <= rtx_srf_pixel_cube_fit_max_iter() = 1000, so every launch terminates; lambda0 and
+ *   ftol finite and >= 0; cost [nPix] fp64, n_iter [nPix] int32; hess as above, the final point's, or NULL.
+ * Both: 1 <= nMix <= rtx_srf_pixel_cube_fit_max_mix() = 4 (what every instantiation holds in registers
+ * without scratch). Refused before anything is launched, nothing written: everything rtx_srf_pixel_cube
+ * refuses, a NULL meas or required output, nMix above max_mix, max_iter outside its range, lambda0 or
+ * ftol not finite or negative, unknown flag bits. nB == 0 or nPix == 0 writes nothing and returns 0.
+ * Determinism: every output of pixel p is a pure function of (pixel p's kidx, start and column of meas;
+ * the counting bands and wgt; the nodes and the range): the same bits run to run, for any nPix, any
+ * position of the pixel in the scene, for the table slice in LDS (nEnd * Q <= 128) or read from global
+ * memory, and in _normal whichever optional outputs are asked for. _fit under RTX_FIT_START_GIVEN equals,
+ * bit for bit, a host loop over _normal that applies rule 3 in fp64. Lane = pixel: no atomics, no
+ * cross-lane sum, no workspace. */
+#define RTX_FIT_START_GIVEN 1u
+int rtx_srf_pixel_cube_fit_max_mix(void);
+int rtx_srf_pixel_cube_fit_max_iter(void);
+int rtx_srf_pixel_cube_normal(int nB, int Q, const double* T_node_h, const float* N, const float* C,
+                              const float* tab, int nEnd, int64_t nPix, int nMix, const int32_t* kidx,
+                              const float* frac, const double* Tpix, const float* meas, const float* wgt,
+                              const double* lambda, double* cost, double* grad, double* hess, double* step,
+                              void* stream, unsigned flags);
+int rtx_srf_pixel_cube_fit(int nB, int Q, const double* T_node_h, const float* N, const float* C,
+                           const float* tab, int nEnd, int64_t nPix, int nMix, const int32_t* kidx,
+                           const float* meas, const float* wgt, float* frac, double* Tpix, int max_iter,
+                           double lambda0, double ftol, double* cost, int32_t* n_iter, int32_t* status,
+                           double* hess, void* stream, unsigned flags);
+
+/* ------------------------------------------------------------------------------------------
  * Speed-dependent Voigt line-sum. Replaces the per-line PROFILE_SDVOIGT + scatter-add of
  * absorptionCoefficient_SDVoigt, misc/hapi.py:10897-10900 (PROFILE_SDVOIGT :10117 -> pcqsdhc :9850-10024 with
  * anuVC = eta = 0: PART1 for lines without speed dependence, PART2/3/4 otherwise; CPF = hum1_wei :9833, cpf3 :9645),

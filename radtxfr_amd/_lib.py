@@ -101,6 +101,12 @@ PROTOTYPES = {
     "rtx_srf_pixel_cube_jvp": (_i32, [_i32, _i32, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp,
                                        C.c_uint]),
     "rtx_srf_pixel_cube_jvp_max_vectors": (_i32, []),
+    "rtx_srf_pixel_cube_fit_max_mix": (_i32, []),
+    "rtx_srf_pixel_cube_fit_max_iter": (_i32, []),
+    "rtx_srf_pixel_cube_normal": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, C.c_uint]),
+    "rtx_srf_pixel_cube_fit": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _dbl, _vp, _vp,
+                                       _vp, _vp, _vp, C.c_uint]),
     "rtx_fir_reflect": (_i32, [_vp, _i32, _i64, _i32, _i64, _vp, _i32, _i32, _vp, _i64, _vp]),
     "rtx_cubic_resample": (_i32, [_vp, _i64, _i32, _i64, _dbl, _dbl, _vp, _i64, _vp, _i64, _vp]),
     "rtx_cubic_end": (_i32, [_vp, _i64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _vp]),

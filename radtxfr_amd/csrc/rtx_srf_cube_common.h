@@ -1,4 +1,5 @@
-// What the derivatives of the per-pixel cube share (rtx_srf_cube_vjp.hip, rtx_srf_cube_jvp.hip): the node weights of a pixel.
+// What the derivatives of the per-pixel cube and the fit built on them share (rtx_srf_cube_vjp.hip, rtx_srf_cube_jvp.hip,
+// rtx_srf_cube_fit.hip): the node weights of a pixel.
 #pragma once
 
 // l_q(T) and l'_q(T) in fp64, the products over r ascending as rtx_srf_pixel_cube forms them, one division each.

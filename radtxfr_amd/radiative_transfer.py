@@ -1144,6 +1144,67 @@ def compute_hsi_cube_vjp(Xmin, Xmax, sensor, Xk, endmembers, kidx, frac, Tpix, c
     return np.array(sensor.centres), kept["cube"].cpu().numpy(), out
 
 
+def compute_hsi_cube_fit(Xmin, Xmax, sensor, Xk, endmembers, kidx, meas, T_range, frac0=None, T0=None, weights=None, max_iter=50,
+                         lambda0=1e-3, ftol=0.0, opts=options, n_nodes=8, interp_tol=1e-6, **kwargs):
+    """Fit every pixel's surface temperature and fractions to a measured HSI cube under a known atmosphere, in one call: the
+    line-sums and compute_TUD's tau / La / Ld, which stay on the device, then sensor.hsi_cube_srf_fit.
+
+    sensor, Xk, endmembers [nk][nEnd] (float32), kidx [nPix][nMix] (integers): as compute_hsi_cube_vjp; meas [nB][nPix]
+    (float32): the measured cube, laid out as hsi_cube_srf returns it; T_range = (T_lo, T_hi), required. frac0 [nPix][nMix]
+    and T0 [nPix] (both or neither), weights [nB], max_iter, lambda0, ftol, n_nodes, interp_tol: as hsi_cube_srf_fit. NumPy
+    arrays or torch tensors. kwargs as compute_TUD, with exactly one sensor altitude and one theta_r and returnOD=False.
+    Returns (X_out, fit): sensor.centres and hsi_cube_srf_fit's dict as NumPy arrays ("Tpix", "frac", "cost", "n_iter",
+    "status", "hess"). Arguments are checked before any device work. NotImplementedError: more than one altitude or theta_r,
+    returnOD=True, save=True."""
+    name = "compute_hsi_cube_fit"
+    c = _Call(name, Xmin, Xmax, opts, kwargs)
+    if c.returnOD:
+        raise NotImplementedError(name + ": returnOD=True is not supported (the sensor stage takes transmittances)")
+    if c.Z_s.size != 1 or c.theta.size != 1:
+        raise NotImplementedError(name + ": exactly one sensor altitude and one theta_r per call (got %d, %d)" % (c.Z_s.size, c.theta.size))
+    if c.o["save"]:
+        raise NotImplementedError(name + ": save=True is not supported")
+    from . import _lib, sensor as _sensor  # sensor.py imports this module
+
+    def host(v, what, kinds, dtype):
+        a = v.detach().cpu().numpy() if _is_torch(v) else np.asarray(v)
+        if a.dtype.kind not in kinds:
+            raise ValueError(name + ": %s has dtype %s" % (what, a.dtype))
+        return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype))
+
+    if T_range is None:
+        raise ValueError(name + ": T_range=(T_lo, T_hi) is required (there is no Tpix to read it from)")
+    if (frac0 is None) != (T0 is None):
+        raise ValueError(name + ": frac0 and T0 come together (a start) or not at all (the node scan)")
+    it_max = _lib.load().rtx_srf_pixel_cube_fit_max_iter()
+    if int(max_iter) != max_iter or not 0 <= max_iter <= it_max:
+        raise ValueError(name + ": max_iter=%r: an integer from 0 to %d" % (max_iter, it_max))
+    for what, v in (("lambda0", lambda0), ("ftol", ftol)):
+        if not (np.isfinite(v) and v >= 0.0):
+            raise ValueError(name + ": %s=%r: finite and not negative" % (what, v))
+    Xk = np.ascontiguousarray(np.asarray(Xk, dtype=np.float64).ravel())
+    E_h, k_h, m_h = host(endmembers, "endmembers", "f", np.float32), host(kidx, "kidx", "iu", np.int32), host(meas, "meas", "f", np.float32)
+    if k_h.dim() != 2:
+        raise ValueError(name + ": kidx: integers [nPix][nMix >= 1], got shape %r" % (tuple(k_h.shape),))
+    given = frac0 is not None
+    f_h = host(frac0, "frac0", "f", np.float32) if given else torch.empty(tuple(k_h.shape), dtype=torch.float32)
+    T_h = host(T0, "T0", "f", np.float64) if given else torch.empty((k_h.shape[0],), dtype=torch.float64)
+    grid, nX = c.grid, c.X.size
+    z = torch.zeros(nX, dtype=torch.float32)  # stands for tau, La, Ld in the checks
+    _sensor._srf_cube_front(name, grid, z, z, z, Xk, E_h, k_h, f_h, T_h, sensor, n_nodes, T_range, interp_tol, need_device=False)
+    w_h = _sensor._cube_fit_args(name, sensor, k_h, m_h, weights)
+    tbl = c.table()
+    dev = engine.device()
+    run = engine.TudRunner(tbl, grid, c.Z, n_layers=c.T.size, Altitudes=c.Z_s, theta_r=c.theta, N_angle=c.N_angle, returnOD=False,
+                           broadening=c.broadening, xs_lut=c.lut, continuum=c.continuum)
+    tau, Lu, Ld = run.run(c.T, c.P, c.PL, c.MF, c.ID)
+    t_, u_, d_ = tau[0, :nX].contiguous(), Lu[0, :nX].contiguous(), Ld[:nX].contiguous()
+    r = _sensor.hsi_cube_srf_fit(grid, t_, u_, d_, Xk, E_h.to(dev), k_h.to(dev), m_h.to(dev), sensor, T_range,
+                                 frac0=f_h.to(dev) if given else None, T0=T_h.to(dev) if given else None, weights=w_h, max_iter=int(max_iter),
+                                 lambda0=float(lambda0), ftol=float(ftol), n_nodes=n_nodes, interp_tol=interp_tol)
+    return np.array(sensor.centres), {k: v.cpu().numpy() for k, v in r.items()}
+
+
 _SURFACE_TANGENTS = ("Ts_surface", "emis")
 
 

@@ -903,6 +903,139 @@ def hsi_cube_srf_jvp(grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sensor
     return X_out, cube, shaped(d_cube)
 
 
+RTX_FIT_START_GIVEN = 1  # include/radtxfr_hip.h
+_CUBE_NORMAL_OUTPUTS = ("cost", "grad", "hess", "step")
+
+
+def _cube_fit_args(fn, sensor, kidx, meas, weights):
+    """What hsi_cube_srf_normal and hsi_cube_srf_fit check beside _srf_cube_front, before any device work: the mixture
+    length against the library's, meas [nB][nPix] float32, weights [nB] (anything np.asarray takes, or a tensor) or None.
+    Returns weights as a float32 host or device tensor, or None."""
+    nMix_max = _lib.load().rtx_srf_pixel_cube_fit_max_mix()
+    if kidx.dim() == 2 and kidx.shape[1] > nMix_max:
+        raise ValueError(f"{fn}: nMix={kidx.shape[1]} above the {nMix_max} unknown fractions a pixel's fit holds")
+    nB, nPix = len(sensor), kidx.shape[0]
+    if not torch.is_tensor(meas) or tuple(meas.shape) != (nB, nPix) or meas.dtype != torch.float32:
+        raise ValueError(f"{fn}: meas: a float32 tensor [nB = {nB}][nPix = {nPix}] like the cube, got "
+                         f"{getattr(meas, 'dtype', type(meas))} {tuple(getattr(meas, 'shape', ()))}")
+    if weights is None:
+        return None
+    w = weights if torch.is_tensor(weights) else torch.as_tensor(np.ascontiguousarray(np.asarray(weights, dtype=np.float32)))
+    if tuple(w.shape) != (nB,) or not w.dtype.is_floating_point:
+        raise ValueError(f"{fn}: weights: [nB = {nB}] floating point, got {w.dtype} {tuple(w.shape)}")
+    return w.to(torch.float32)
+
+
+def hsi_cube_srf_normal(grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sensor, meas, weights=None, damping=None,
+                        outputs=_CUBE_NORMAL_OUTPUTS, n_nodes=8, T_range=None, interp_tol=1e-6):
+    """The per-pixel normal equations of fitting (Tpix, frac) to a measured cube under hsi_cube_srf's model, the atmosphere
+    and kidx fixed: with r = cube(Tpix, frac) - meas on the bands that count (live, weight > 0),
+      "cost"  sum_b w_b r_b^2, float64 [nPix] device;
+      "grad"  J^T W r, float64 [nPix][1 + nMix], the unknowns in the order T, then the fractions;
+      "hess"  J^T W J, float64 [nPix][(1 + nMix)(2 + nMix) / 2], the lower triangle by rows;
+      "step"  the solution of (H + damping diag H) step = -grad, NaN where that matrix is not positive definite.
+    meas: float32 [nB][nPix] device tensor; weights: [nB] or None (all 1); damping: float64 [nPix] device tensor, a number, or
+    None (0). outputs: the keys wanted ("cost" is always computed). Other arguments, checks and nodes as hsi_cube_srf. A pixel
+    whose temperature is not finite or lies outside the range is NaN in all its outputs. One kernel: rtx_srf_pixel_cube_normal."""
+    lib = _lib.load()
+    fn = "hsi_cube_srf_normal"
+    outputs = tuple(outputs)
+    if not outputs or any(k not in _CUBE_NORMAL_OUTPUTS for k in outputs):
+        raise ValueError("outputs: a non-empty selection of %r (got %r)" % (_CUBE_NORMAL_OUTPUTS, outputs))
+    f = _srf_cube_front(fn, grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sensor, n_nodes, T_range, interp_tol)
+    w = _cube_fit_args(fn, sensor, f["kidx"], meas, weights)
+    endmembers, kidx, frac, Tpix, Q = f["endmembers"], f["kidx"], f["frac"], f["Tpix"], f["Q"]
+    nPix, nMix = kidx.shape
+    nU, nB, nEnd = 1 + nMix, len(sensor), endmembers.shape[1]
+    if damping is not None and torch.is_tensor(damping) and (tuple(damping.shape) != (nPix,) or damping.dtype != torch.float64):
+        raise ValueError(f"{fn}: damping: float64 [nPix = {nPix}] or a number, got {damping.dtype} {tuple(damping.shape)}")
+    if not meas.is_cuda:
+        raise ValueError(f"{fn} takes device tensors (meas is not on a GPU)")
+    dev = tau.device
+    shapes = dict(cost=(nPix,), grad=(nPix, nU), hess=(nPix, nU * (nU + 1) // 2), step=(nPix, nU))
+    out = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) for k in set(outputs) | {"cost"}}
+    if nPix == 0:
+        return {k: out[k] for k in outputs}
+    if nB == 0:
+        return {k: out[k].zero_() if k != "step" else out[k].fill_(float("nan")) for k in outputs}
+    lam = None
+    if damping is not None:
+        lam = damping.to(dev).contiguous() if torch.is_tensor(damping) else torch.full((nPix,), float(damping), dtype=torch.float64, device=dev)
+    w = None if w is None else w.to(dev).contiguous()
+    N, Cb, tab, T_host = _srf_cube_tables(grid, tau, La, Ld, f, sensor)
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.check(lib.rtx_srf_pixel_cube_normal(nB, Q, T_host.ctypes.data_as(C.c_void_p), p(N), p(Cb), p(tab), nEnd, nPix, nMix, p(kidx), p(frac),
+                                             p(Tpix), p(meas.contiguous()), p(w), p(lam), p(out["cost"]), p(out.get("grad")), p(out.get("hess")),
+                                             p(out.get("step")), st, 0))
+    return {k: out[k] for k in outputs}
+
+
+def hsi_cube_srf_fit(grid, tau, La, Ld, Xk, endmembers, kidx, meas, sensor, T_range, frac0=None, T0=None, weights=None, max_iter=50,
+                     lambda0=1e-3, ftol=0.0, n_nodes=8, interp_tol=1e-6):
+    """Fit every pixel's surface temperature and fractions to a measured cube under hsi_cube_srf's model, the atmosphere
+    (tau, La, Ld) and the pixel's endmember indices kidx fixed: an unconstrained Levenberg-Marquardt loop per
+    pixel in 1 + nMix unknowns, the whole loop in one kernel (rtx_srf_pixel_cube_fit; include/radtxfr_hip.h has the
+    algorithm step by step). meas: float32 [nB][nPix] device tensor; weights [nB] or None (all 1): a band counts when it is
+    live and its weight is > 0, and what meas holds under any other band is never read.
+    T_range = (T_lo, T_hi) is required: the nodes span it and T never leaves it. frac0 [nPix][nMix] float32 and T0 [nPix]
+    float64 (both or neither): the start; without them every pixel starts from the best of the n_nodes node temperatures
+    with the fractions that minimise the cost there. max_iter trials at most (0 .. the library's 1000), lambda0 the first
+    damping, ftol the relative decrease of the cost below which an accepted step is the last (0: never).
+    Returns a dict of device tensors: "Tpix" float64 [nPix], "frac" float32 [nPix][nMix], "cost" float64 [nPix] (sum of
+    w r^2), "n_iter" int32 [nPix] trials, "status" int32 [nPix] (0 converged or stalled, 1 iteration cap, 2 the start is
+    outside T_range or not finite, 3 singular; under 2 and 3 the pixel's results are NaN), "hess" float64
+    [nPix][(1 + nMix)(2 + nMix) / 2] = J^T W J at the result, lower triangle by rows: with nU = 1 + nMix unknowns and n
+    counting bands, inv(hess) cost / (n - nU) estimates the covariance of (T, frac). All checks run before any device work."""
+    lib = _lib.load()
+    fn = "hsi_cube_srf_fit"
+    if T_range is None:
+        raise ValueError(f"{fn}: T_range=(T_lo, T_hi) is required (there is no Tpix to read it from)")
+    if (frac0 is None) != (T0 is None):
+        raise ValueError(f"{fn}: frac0 and T0 come together (a start) or not at all (the node scan)")
+    it_max = lib.rtx_srf_pixel_cube_fit_max_iter()
+    if int(max_iter) != max_iter or not 0 <= max_iter <= it_max:
+        raise ValueError(f"{fn}: max_iter={max_iter!r}: an integer from 0 to {it_max}")
+    for name, v in (("lambda0", lambda0), ("ftol", ftol)):
+        if not (np.isfinite(v) and v >= 0.0):
+            raise ValueError(f"{fn}: {name}={v!r}: finite and not negative")
+    given = frac0 is not None
+    if not torch.is_tensor(kidx) or kidx.dim() != 2:
+        raise ValueError(f"{fn}: kidx: int32 [nPix][nMix >= 1] tensor")
+    # the start stands in for frac / Tpix in the shared checks; without one, host placeholders of the right shape do
+    fr = frac0 if given else torch.empty(tuple(kidx.shape), dtype=torch.float32)
+    Tp = T0 if given else torch.empty((kidx.shape[0],), dtype=torch.float64)
+    f = _srf_cube_front(fn, grid, tau, La, Ld, Xk, endmembers, kidx, fr, Tp, sensor, n_nodes, T_range, interp_tol, need_device=False)
+    w = _cube_fit_args(fn, sensor, f["kidx"], meas, weights)
+    for name, v in (("tau", tau), ("endmembers", endmembers), ("kidx", kidx), ("meas", meas)) + ((("frac0", frac0), ("T0", T0)) if given else ()):
+        if not v.is_cuda:
+            raise ValueError(f"{fn} takes device tensors ({name} is not on a GPU)")
+    endmembers, kidx, Q = f["endmembers"], f["kidx"], f["Q"]
+    nPix, nMix = kidx.shape
+    nU, nB, nEnd = 1 + nMix, len(sensor), endmembers.shape[1]
+    dev = tau.device
+    frac = f["frac"].clone() if given else torch.empty((nPix, nMix), dtype=torch.float32, device=dev)
+    Tpix = f["Tpix"].clone() if given else torch.empty(nPix, dtype=torch.float64, device=dev)
+    out = dict(Tpix=Tpix, frac=frac, cost=torch.empty(nPix, dtype=torch.float64, device=dev),
+               n_iter=torch.zeros(nPix, dtype=torch.int32, device=dev), status=torch.zeros(nPix, dtype=torch.int32, device=dev),
+               hess=torch.empty((nPix, nU * (nU + 1) // 2), dtype=torch.float64, device=dev))
+    if nPix == 0:
+        return out
+    if nB == 0:  # nothing to fit to
+        for k in ("Tpix", "frac", "cost", "hess"):
+            out[k].fill_(float("nan"))
+        out["status"].fill_(3)
+        return out
+    w = None if w is None else w.to(dev).contiguous()
+    N, Cb, tab, T_host = _srf_cube_tables(grid, tau, La, Ld, f, sensor)
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.check(lib.rtx_srf_pixel_cube_fit(nB, Q, T_host.ctypes.data_as(C.c_void_p), p(N), p(Cb), p(tab), nEnd, nPix, nMix, p(kidx),
+                                          p(meas.contiguous()), p(w), p(frac), p(Tpix), int(max_iter), float(lambda0), float(ftol), p(out["cost"]),
+                                          p(out["n_iter"]), p(out["status"]), p(out["hess"]), st, RTX_FIT_START_GIVEN if given else 0))
+    return out
+
+
 def band_radiance(grid, tau, La, Ld, Xk, emis_knots, Ts, resFactor=None, keep_hires=False):
     """C4: L_b,k = ILS_MAKO( tau*(eps_k*B(Ts) + (1-eps_k)*Ld) + La ) for every emissivity column k.
 
