@@ -77,8 +77,11 @@ def adjoint(N, G, sc, Tq, T_range, g):
         s_dT += np.abs(f[:, m]) * np.sum(np.abs(x) * np.einsum("pq,qbp->bp", np.abs(wp), np.abs(Gm)), axis=0)
         np.add.at(F, (np.arange(nPix), k[:, m]), f[:, m])
         np.add.at(Fa, (np.arange(nPix), k[:, m]), np.abs(f[:, m]))
-    gL = np.einsum("bp,pq,pe->qbe", u, w, F)
-    s_gL = np.einsum("bp,pq,pe->qbe", np.abs(u), np.abs(w), Fa)
+    # sum_p u_bp l_q(T_p) F_pe as one matrix product [Q nB][nPix] x [nPix][nEnd + 1], fp64 all the same: the three-operand einsum
+    # it replaces took 7 s for each of the two on a scene of 8000 pixels
+    rows = lambda a, b: (a[None] * b.T[:, None, :]).reshape(Q * nB, nPix)
+    gL = (rows(u, w) @ F).reshape(Q, nB, nEnd + 1)
+    s_gL = (rows(np.abs(u), np.abs(w)) @ Fa).reshape(Q, nB, nEnd + 1)
     rest = 1.0 - f.sum(axis=1)
     gL[:, :, nEnd], s_gL[:, :, nEnd] = 0.0, 0.0
     gL[0, :, nEnd] = u @ rest

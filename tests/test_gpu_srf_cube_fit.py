@@ -16,6 +16,7 @@ import pytest
 
 import srf_cube_cases as CC
 import srf_cube_fit_cases as FT
+import srf_cube_vjp_cases as VC
 import srf_fused_cases as FC
 from test_gpu_sensor_vjp import within
 
@@ -50,26 +51,31 @@ def dev(env, a):
 _TABLES = {}
 
 
-def device_tables(env, knots, nEnd, tname, times=1):
+def device_tables(env, knots, nEnd, tname, times=1, nB=None):
     """The device's own N, C [nB] and table [nEnd][Q][nB] (float32, device) at the nodes, with fp64 host copies N_h, C_h and
-    G_h [Q][nB][nEnd], what the oracle is evaluated on. times: the case's 20 bands repeated that often."""
-    key = (knots, nEnd, tname, times)
+    G_h [Q][nB][nEnd], what the oracle is evaluated on. tname: a name of CC.T_CONFIGS, or (T_range, Q) itself. The bands are
+    the case's 20 repeated `times` over, or repeated and cut to nB (the 3 dead bands recur every 20)."""
+    nB = 20 * times if nB is None else nB
+    key = (knots, nEnd, tname, nB)
     if key not in _TABLES:
         torch, sensor, lib = env["torch"], env["sensor"], env["lib"]
         c = FC.case(env["CH"], env["K"], knots)
-        T_range, Q = CC.T_CONFIGS[tname]
+        T_range, Q = CC.T_CONFIGS[tname] if isinstance(tname, str) else tname
         End = CC.endmembers(c["Xk"].size, nEnd)
-        s = sensor.Sensor.from_tables(list(c["tables"]) * times)
+        assert len(c["tables"]) == 20
+        reps = -(-nB // 20)
+        s = sensor.Sensor.from_tables((list(c["tables"]) * reps)[:nB])
         nodes = sensor.srf_cube_nodes(T_range[0], T_range[1], Q)
         grid = env["engine"].Grid(*FC.grid_tuple(env["CH"]))
         N, Cb, M, jr = sensor.srf_moments(grid, dev(env, c["tau"]), dev(env, c["La"]), dev(env, c["Ld"]), dev(env, c["Xk"]), nodes, s)
-        nB, nk = len(s), c["Xk"].size
+        assert len(s) == nB
+        nk = c["Xk"].size
         tab = torch.empty((nEnd, Q, nB), dtype=torch.float32, device="cuda")
         p = lambda t: C.c_void_p(t.data_ptr())
         env["_lib"].check(lib.rtx_srf_cube_tables(p(M), p(jr), nB, Q, nk, p(dev(env, End)), nEnd, p(tab), None))
         torch.cuda.synchronize()
         _TABLES[key] = dict(N=N, C=Cb, tab=tab, T_host=np.ascontiguousarray(np.concatenate([nodes, list(T_range)])), nodes=nodes, T_range=T_range,
-                            Q=Q, End=End, dead=np.tile(c["dead"], times), case=c, N_h=N.cpu().numpy().astype(np.float64),
+                            Q=Q, End=End, dead=np.tile(c["dead"], reps)[:nB], case=c, N_h=N.cpu().numpy().astype(np.float64),
                             C_h=Cb.cpu().numpy().astype(np.float64), G_h=tab.cpu().numpy().astype(np.float64).transpose(1, 2, 0))
     return _TABLES[key]
 
@@ -185,6 +191,71 @@ def first_case(env):
         lam = np.random.default_rng(29).uniform(0.0, 0.5, FT.NPIX)
         _FIRST["v"] = (t, sc, meas, st, lam, normal(env, t, st, meas, lam=lam))
     return _FIRST["v"]
+
+
+def host_loop(env, t, kidx, meas, start, k, lambda0, ftol, w=None):
+    """k host-driven trials built from rtx_srf_pixel_cube_normal, with the trial point and the accept rule in torch fp64: what
+    rtx_srf_pixel_cube_fit(max_iter = k) computes, as NumPy under fit()'s keys. start: (T, frac) of RTX_FIT_START_GIVEN, or
+    None: the start is the device's own scan (the fit with max_iter = 0), and a pixel the scan gives up (status 3) stays given
+    up. Returns (the dict, the number of trial temperatures that were clamped at an end of the range, the number of lanes
+    that stopped because lambda reached its cap)."""
+    torch = env["torch"]
+    nPix, nMix = kidx.shape
+    T_lo, T_hi = t["T_range"]
+    tt = lambda a: torch.as_tensor(np.array(a), device="cuda")
+    status = torch.full((nPix,), -1, dtype=torch.int32, device="cuda")
+    if start is None:
+        s0 = fit(env, t, kidx, meas, w=w, max_iter=0)
+        assert np.all((s0["status"] == 1) | (s0["status"] == 3)) and np.all(s0["n_iter"] == 0)
+        lost = s0["status"] == 3
+        status[tt(lost)] = 3
+        T0, f0 = np.where(lost, 0.5 * (T_lo + T_hi), s0["T"]), np.where(lost[:, None], np.float32(0.0), s0["frac"])
+    else:
+        T0, f0 = np.array(start[0], dtype=np.float64), np.array(start[1], dtype=np.float32)
+        bad = ~(VC.admitted(T0, t["T_range"]) & np.all(np.isfinite(f0), axis=1))
+        status[tt(bad)] = 2
+        T0[bad], f0[bad] = T_lo, 0.0
+    T, f = tt(T0), tt(f0)
+    call = lambda T_, f_, lam_, outs: {key: tt(v) for key, v in normal(env, t, dict(kidx=kidx, frac=f_.cpu().numpy(), T=T_.cpu().numpy()), meas, w=w,
+                                                                         lam=lam_.cpu().numpy(), outs=outs).items()}
+    lam = torch.full((nPix,), lambda0, dtype=torch.float64, device="cuda")
+    cur = call(T, f, lam, ("cost", "hess"))
+    status[(status < 0) & ~torch.isfinite(cur["cost"])] = 3  # no finite cost to start from
+    n_iter = torch.zeros(nPix, dtype=torch.int32, device="cuda")
+    clamped, capped = 0, 0
+    for _ in range(k + 1):
+        status[(status < 0) & (cur["cost"] == 0.0)] = 0
+        status[(status < 0) & (n_iter >= k)] = 1
+        run = status < 0
+        if not bool(run.any()):
+            break
+        step = call(T, f, lam, ("step",))["step"]
+        sing = run & torch.isnan(step).any(dim=1)
+        status[sing] = 3
+        run = status < 0
+        step = torch.where(run[:, None], step, torch.zeros_like(step))
+        raw_T = T + step[:, 0]
+        Tt = torch.clamp(raw_T, min=T_lo, max=T_hi)
+        clamped += int((run & (Tt != raw_T)).sum())
+        ft = (f.double() + step[:, 1:]).float()
+        tr = call(Tt, ft, lam, ("cost", "hess"))
+        n_iter[run] += 1
+        acc = run & (tr["cost"] < cur["cost"])
+        rej = run & ~acc
+        small = acc & (cur["cost"] - tr["cost"] < ftol * cur["cost"])
+        T, f = torch.where(acc, Tt, T), torch.where(acc[:, None], ft, f)
+        cur = {key: torch.where(acc.reshape((-1,) + (1,) * (cur[key].dim() - 1)), tr[key], cur[key]) for key in cur}
+        lam = torch.where(acc, torch.clamp(0.1 * lam, min=FT.LAM_MIN), torch.where(rej, torch.clamp(10.0 * lam, max=FT.LAM_MAX), lam))
+        status[small] = 0
+        cap = rej & (lam >= FT.LAM_MAX)
+        capped += int(cap.sum())
+        status[cap] = 0
+    gone = (status >= 2).cpu().numpy()  # a pixel that is refused or given up: NaN in every floating output
+    out = dict(T=T, frac=f, cost=cur["cost"], hess=cur["hess"], n_iter=n_iter, status=status)
+    out = {key: v.cpu().numpy() for key, v in out.items()}
+    for key in ("T", "frac", "cost", "hess"):
+        out[key][gone] = np.nan
+    return out, clamped, capped
 
 
 def check_normal(env, t, st, meas, what, w=None):
@@ -315,50 +386,17 @@ def test_fit_equals_a_host_loop_over_normal(env, k):
     trial point and the accept rule in torch fp64: T, frac, cost, hess, n_iter and status. One pixel starts on the truth
     (cost 0: it stops before any trial). An ftol of 0.3 stops pixels early: with k = 8, 121 of the 257 end with status 0 after
     1 to 8 trials, the rest at the cap."""
-    torch = env["torch"]
     t, sc, meas, st, _, _ = first_case(env)
-    T_lo, T_hi = t["T_range"]
     lambda0, ftol = 1e-3, 0.3
     T0, f0 = np.array(st["T"]), np.array(st["frac"])
     T0[9], f0[9] = sc["T"][9], sc["frac"][9]
     got = fit(env, t, sc["kidx"], meas, start=(T0, f0), max_iter=k, lambda0=lambda0, ftol=ftol)
-    tt = lambda a: torch.as_tensor(a, device="cuda")
-    T, f = tt(T0), tt(f0)
-    call = lambda T_, f_, lam_, outs: {key: tt(v) for key, v in normal(env, t, dict(kidx=sc["kidx"], frac=f_.cpu().numpy(), T=T_.cpu().numpy()), meas,
-                                                                         lam=lam_.cpu().numpy(), outs=outs).items()}
-    lam = torch.full((FT.NPIX,), lambda0, dtype=torch.float64, device="cuda")
-    cur = call(T, f, lam, ("cost", "hess"))
-    status = torch.full((FT.NPIX,), -1, dtype=torch.int32, device="cuda")
-    n_iter = torch.zeros(FT.NPIX, dtype=torch.int32, device="cuda")
-    for _ in range(k + 1):
-        status[(status < 0) & (cur["cost"] == 0.0)] = 0
-        status[(status < 0) & (n_iter >= k)] = 1
-        run = status < 0
-        if not bool(run.any()):
-            break
-        step = call(T, f, lam, ("step",))["step"]
-        sing = run & torch.isnan(step).any(dim=1)
-        status[sing] = 3
-        run = status < 0
-        step = torch.where(run[:, None], step, torch.zeros_like(step))
-        Tt = torch.clamp(T + step[:, 0], min=T_lo, max=T_hi)
-        ft = (f.double() + step[:, 1:]).float()
-        tr = call(Tt, ft, lam, ("cost", "hess"))
-        n_iter[run] += 1
-        acc = run & (tr["cost"] < cur["cost"])
-        rej = run & ~acc
-        small = acc & (cur["cost"] - tr["cost"] < ftol * cur["cost"])
-        T, f = torch.where(acc, Tt, T), torch.where(acc[:, None], ft, f)
-        cur = {key: torch.where(acc.reshape((-1,) + (1,) * (cur[key].dim() - 1)), tr[key], cur[key]) for key in cur}
-        lam = torch.where(acc, torch.clamp(0.1 * lam, min=FT.LAM_MIN), torch.where(rej, torch.clamp(10.0 * lam, max=FT.LAM_MAX), lam))
-        status[small] = 0
-        status[rej & (lam >= FT.LAM_MAX)] = 0
-    want = dict(T=T, frac=f, cost=cur["cost"], hess=cur["hess"], n_iter=n_iter, status=status)
+    want, _, _ = host_loop(env, t, sc["kidx"], meas, (T0, f0), k, lambda0, ftol)
     assert int(got["n_iter"][9]) == 0 and int(got["status"][9]) == 0
     print("srf cube fit vs host loop k=%d: trials %s, statuses %s" % (k, np.bincount(got["n_iter"]).tolist(), np.bincount(got["status"]).tolist()))
     assert got["n_iter"].max() == k and (got["status"] == 1).any()
     for key, v in want.items():
-        assert np.array_equal(got[key], v.cpu().numpy()), key
+        assert np.array_equal(got[key], v), key
 
 
 def test_purity(env):
