@@ -852,6 +852,67 @@ int rtx_srf_pixel_cube_fit(int nB, int Q, const double* T_node_h, const float* N
                            double* hess, void* stream, unsigned flags);
 
 /* ------------------------------------------------------------------------------------------
+ * The same fit inside a box: T_lo <= T <= T_hi, f_m >= 0, and an optional soft sum-to-one.
+ * Unknowns, model, meas, wgt, counting bands, one evaluation and the packing of H are those above; what
+ * rtx_srf_pixel_cube_normal and rtx_srf_pixel_cube_fit compute does not change.
+ * The pseudo-band: with sum_weight = delta > 0 (fp64; delta == 0 skips it entirely) one more term follows
+ * the band loop, accumulated exactly as a band:
+ *   r_s = (sum_m (double)f_m, m ascending, plain fp64 adds) - 1,  j_0 = 0,  j_m = 1;
+ *   cost = fma(delta r_s, r_s, cost);  grad_m = fma(1, delta r_s, grad_m);  H_mm' = fma(delta, 1, H_mm'), m, m' >= 1.
+ * delta weighs (sum f - 1)^2 against squared radiance residuals: its unit is radiance^2, and delta =
+ * (sigma_L / sigma_sum)^2 asks the sum to stay within sigma_sum of 1 beside a band noise of sigma_L.
+ * The box step from u = (T, (double)f_1 ..) with grad g, H, lambda, lo = (T_lo, 0, ..), hi = (T_hi, +inf, ..):
+ *   1 B = { i : (u_i <= lo_i and g_i > 0) or (u_i >= hi_i and g_i < 0) }, with prescribed steps s_i = 0.
+ *   2 a pass: the Cholesky solve above, same order and fma pattern, over all 1 + nMix unknowns of the matrix
+ *     whose rows and columns of B are the identity's (A_ii = 1, undamped, off-diagonals 0; the L entries there
+ *     are exact zeros, so the free block has the bits of its own Cholesky), A_jj = fma(lambda, H_jj, H_jj) on
+ *     the free diagonal. Right-hand side: s_i on B; for a free j, -(g_j + sum_{i in B} H_ji s_i), the sum by
+ *     fma(H_ji, s_i, .) onto g_j with i ascending. d_i = s_i on B. Every free i with u_i + d_i < lo_i joins B
+ *     with s_i = lo_i - u_i, with u_i + d_i > hi_i with s_i = hi_i - u_i. None joined: the step is d.
+ *     Otherwise another pass, 1 + nMix passes at most; what joins in the last one was the only free unknown
+ *     left and takes d_i = s_i. A pivot that is not finite or not positive in any pass: the step is NaN.
+ *   3 the trial point: T' = min(max(T + d_0, T_lo), T_hi); f'_m = max(0f, (float)((double)f_m + d_m)), where
+ *     max(0f, x) = x > 0 ? x : 0f.
+ * rtx_srf_pixel_cube_normal_box: rtx_srf_pixel_cube_normal's arguments, then sum_weight and
+ *   active [nPix] int32 DEVICE or NULL: bit i set where unknown i ended in B (step 1's set included); 0 for a
+ *   pixel that is not admitted. step is the box step d; cost, grad and hess include the pseudo-band. With
+ *   sum_weight == 0, at a point strictly inside the box whose step stays inside, every output has
+ *   rtx_srf_pixel_cube_normal's bits.
+ * rtx_srf_pixel_cube_fit_box: rtx_srf_pixel_cube_fit's arguments, then sum_weight,
+ *   grad [nPix][1 + nMix] fp64 DEVICE or NULL: the final point's gradient (NaN under status 2 and 3), and
+ *   active [nPix] int32 DEVICE or NULL: step 1's set at the final point, the KKT active set (0 under status 2
+ *   and 3). The covariance of the free unknowns is the inverse of hess with those rows and columns removed.
+ *   Rules 1 - 5 of rtx_srf_pixel_cube_fit with these changes: a given start's fractions are projected by
+ *   max(0f, .) first (status 2 is decided on the values passed in); the node scan's second evaluation is at
+ *   the trial point of the box step with T held in B (s_0 = 0), lambda = 0, from (T_q, f = 0), and a NaN step
+ *   skips the node; a trial is the box step and its trial point; and one more stop, tested after the singular
+ *   step and before the evaluation: a trial point equal bit for bit to the current point gives status 0 and
+ *   is not counted in n_iter. The accept rule, the lambda schedule, caps, statuses and NaN rules are unchanged.
+ * Both: 1 <= nMix <= rtx_srf_pixel_cube_fit_box_max_mix() = 4 (every instantiation without scratch). Refused
+ * before anything is launched, nothing written: everything the unconstrained entries refuse, and a
+ * sum_weight that is not finite or negative. nB == 0 or nPix == 0 writes nothing and returns 0 (with no band
+ * the pseudo-band is not evaluated either).
+ * Determinism: every output of pixel p is a pure function of (pixel p's kidx, start and column of meas;
+ * the counting bands and wgt; the nodes and the range; sum_weight): the same bits run to run, for any nPix,
+ * any position of the pixel in the scene, for the table slice in LDS (nEnd * Q <= 128) or read from global
+ * memory, and in _normal_box whichever optional outputs are asked for. _fit_box under RTX_FIT_START_GIVEN
+ * equals, bit for bit, a host loop over _normal_box that applies rule 3 and the new stop in fp64. Lane =
+ * pixel: no atomics, no cross-lane sum, no workspace. */
+int rtx_srf_pixel_cube_fit_box_max_mix(void);
+int rtx_srf_pixel_cube_normal_box(int nB, int Q, const double* T_node_h, const float* N, const float* C,
+                                  const float* tab, int nEnd, int64_t nPix, int nMix, const int32_t* kidx,
+                                  const float* frac, const double* Tpix, const float* meas, const float* wgt,
+                                  const double* lambda, double* cost, double* grad, double* hess,
+                                  double* step, void* stream, unsigned flags, double sum_weight,
+                                  int32_t* active);
+int rtx_srf_pixel_cube_fit_box(int nB, int Q, const double* T_node_h, const float* N, const float* C,
+                               const float* tab, int nEnd, int64_t nPix, int nMix, const int32_t* kidx,
+                               const float* meas, const float* wgt, float* frac, double* Tpix, int max_iter,
+                               double lambda0, double ftol, double* cost, int32_t* n_iter, int32_t* status,
+                               double* hess, void* stream, unsigned flags, double sum_weight, double* grad,
+                               int32_t* active);
+
+/* ------------------------------------------------------------------------------------------
  * Speed-dependent Voigt line-sum. Replaces the per-line PROFILE_SDVOIGT + scatter-add of
  * absorptionCoefficient_SDVoigt, misc/hapi.py:10897-10900 (PROFILE_SDVOIGT :10117 -> pcqsdhc :9850-10024 with
  * anuVC = eta = 0: PART1 for lines without speed dependence, PART2/3/4 otherwise; CPF = hum1_wei :9833, cpf3 :9645),

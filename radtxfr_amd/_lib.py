@@ -107,6 +107,11 @@ PROTOTYPES = {
                                           _vp, C.c_uint]),
     "rtx_srf_pixel_cube_fit": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _dbl, _vp, _vp,
                                        _vp, _vp, _vp, C.c_uint]),
+    "rtx_srf_pixel_cube_fit_box_max_mix": (_i32, []),
+    "rtx_srf_pixel_cube_normal_box": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              _vp, _vp, C.c_uint, _dbl, _vp]),
+    "rtx_srf_pixel_cube_fit_box": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _dbl, _vp,
+                                           _vp, _vp, _vp, _vp, C.c_uint, _dbl, _vp, _vp]),
     "rtx_fir_reflect": (_i32, [_vp, _i32, _i64, _i32, _i64, _vp, _i32, _i32, _vp, _i64, _vp]),
     "rtx_cubic_resample": (_i32, [_vp, _i64, _i32, _i64, _dbl, _dbl, _vp, _i64, _vp, _i64, _vp]),
     "rtx_cubic_end": (_i32, [_vp, _i64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _vp]),

@@ -1145,7 +1145,7 @@ def compute_hsi_cube_vjp(Xmin, Xmax, sensor, Xk, endmembers, kidx, frac, Tpix, c
 
 
 def compute_hsi_cube_fit(Xmin, Xmax, sensor, Xk, endmembers, kidx, meas, T_range, frac0=None, T0=None, weights=None, max_iter=50,
-                         lambda0=1e-3, ftol=0.0, opts=options, n_nodes=8, interp_tol=1e-6, **kwargs):
+                         lambda0=1e-3, ftol=0.0, opts=options, n_nodes=8, interp_tol=1e-6, nonneg=False, sum_weight=0.0, **kwargs):
     """Fit every pixel's surface temperature and fractions to a measured HSI cube under a known atmosphere, in one call: the
     line-sums and compute_TUD's tau / La / Ld, which stay on the device, then sensor.hsi_cube_srf_fit.
 
@@ -1155,7 +1155,9 @@ def compute_hsi_cube_fit(Xmin, Xmax, sensor, Xk, endmembers, kidx, meas, T_range
     arrays or torch tensors. kwargs as compute_TUD, with exactly one sensor altitude and one theta_r and returnOD=False.
     Returns (X_out, fit): sensor.centres and hsi_cube_srf_fit's dict as NumPy arrays ("Tpix", "frac", "cost", "n_iter",
     "status", "hess"). Arguments are checked before any device work. NotImplementedError: more than one altitude or theta_r,
-    returnOD=True, save=True."""
+    returnOD=True, save=True.
+    nonneg=True, sum_weight: the fit inside the box T_range x frac >= 0 with an optional soft sum-to-one, as hsi_cube_srf_fit
+    (DESIGN 4.28); the dict gains "grad" and "active". sum_weight > 0 without nonneg is a ValueError."""
     name = "compute_hsi_cube_fit"
     c = _Call(name, Xmin, Xmax, opts, kwargs)
     if c.returnOD:
@@ -1193,6 +1195,7 @@ def compute_hsi_cube_fit(Xmin, Xmax, sensor, Xk, endmembers, kidx, meas, T_range
     z = torch.zeros(nX, dtype=torch.float32)  # stands for tau, La, Ld in the checks
     _sensor._srf_cube_front(name, grid, z, z, z, Xk, E_h, k_h, f_h, T_h, sensor, n_nodes, T_range, interp_tol, need_device=False)
     w_h = _sensor._cube_fit_args(name, sensor, k_h, m_h, weights)
+    nonneg, sum_weight = _sensor._cube_box_args(name, nonneg, sum_weight, k_h)
     tbl = c.table()
     dev = engine.device()
     run = engine.TudRunner(tbl, grid, c.Z, n_layers=c.T.size, Altitudes=c.Z_s, theta_r=c.theta, N_angle=c.N_angle, returnOD=False,
@@ -1201,7 +1204,8 @@ def compute_hsi_cube_fit(Xmin, Xmax, sensor, Xk, endmembers, kidx, meas, T_range
     t_, u_, d_ = tau[0, :nX].contiguous(), Lu[0, :nX].contiguous(), Ld[:nX].contiguous()
     r = _sensor.hsi_cube_srf_fit(grid, t_, u_, d_, Xk, E_h.to(dev), k_h.to(dev), m_h.to(dev), sensor, T_range,
                                  frac0=f_h.to(dev) if given else None, T0=T_h.to(dev) if given else None, weights=w_h, max_iter=int(max_iter),
-                                 lambda0=float(lambda0), ftol=float(ftol), n_nodes=n_nodes, interp_tol=interp_tol)
+                                 lambda0=float(lambda0), ftol=float(ftol), n_nodes=n_nodes, interp_tol=interp_tol, nonneg=nonneg,
+                                 sum_weight=sum_weight)
     return np.array(sensor.centres), {k: v.cpu().numpy() for k, v in r.items()}
 
 

@@ -926,8 +926,26 @@ def _cube_fit_args(fn, sensor, kidx, meas, weights):
     return w.to(torch.float32)
 
 
+def _cube_box_args(fn, nonneg, sum_weight, kidx):
+    """The checks of the bound-constrained variants, before any device work. Returns (nonneg, sum_weight)."""
+    nonneg = bool(nonneg)
+    try:
+        sw = float(sum_weight)
+    except (TypeError, ValueError):
+        raise ValueError(f"{fn}: sum_weight={sum_weight!r}: a finite number that is not negative") from None
+    if not (np.isfinite(sw) and sw >= 0.0):
+        raise ValueError(f"{fn}: sum_weight={sum_weight!r}: a finite number that is not negative")
+    if sw > 0.0 and not nonneg:
+        raise ValueError(f"{fn}: sum_weight={sw!r} needs nonneg=True (the soft sum-to-one belongs to the constrained fit)")
+    if nonneg and torch.is_tensor(kidx) and kidx.dim() == 2:
+        nMix_max = _lib.load().rtx_srf_pixel_cube_fit_box_max_mix()
+        if kidx.shape[1] > nMix_max:
+            raise ValueError(f"{fn}: nMix={kidx.shape[1]} above the {nMix_max} unknown fractions a pixel's constrained fit holds")
+    return nonneg, sw
+
+
 def hsi_cube_srf_normal(grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sensor, meas, weights=None, damping=None,
-                        outputs=_CUBE_NORMAL_OUTPUTS, n_nodes=8, T_range=None, interp_tol=1e-6):
+                        outputs=_CUBE_NORMAL_OUTPUTS, n_nodes=8, T_range=None, interp_tol=1e-6, nonneg=False, sum_weight=0.0):
     """The per-pixel normal equations of fitting (Tpix, frac) to a measured cube under hsi_cube_srf's model, the atmosphere
     and kidx fixed: with r = cube(Tpix, frac) - meas on the bands that count (live, weight > 0),
       "cost"  sum_b w_b r_b^2, float64 [nPix] device;
@@ -936,12 +954,20 @@ def hsi_cube_srf_normal(grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sen
       "step"  the solution of (H + damping diag H) step = -grad, NaN where that matrix is not positive definite.
     meas: float32 [nB][nPix] device tensor; weights: [nB] or None (all 1); damping: float64 [nPix] device tensor, a number, or
     None (0). outputs: the keys wanted ("cost" is always computed). Other arguments, checks and nodes as hsi_cube_srf. A pixel
-    whose temperature is not finite or lies outside the range is NaN in all its outputs. One kernel: rtx_srf_pixel_cube_normal."""
+    whose temperature is not finite or lies outside the range is NaN in all its outputs. One kernel: rtx_srf_pixel_cube_normal.
+    nonneg=True (rtx_srf_pixel_cube_normal_box): "step" is the box step of the fit inside T_range and frac >= 0
+    (unknowns on a bound whose gradient points outward stay, a step that would leave the box is cut there and the rest
+    re-solved), and the dict gains "active", int32 [nPix]: bit i set where unknown i (0: T, m: fraction m) ended on a bound.
+    sum_weight > 0 (needs nonneg=True) adds the soft sum-to-one term sum_weight (sum_m frac_m - 1)^2 to cost, grad and hess;
+    its unit is radiance^2: (band noise / tolerated deviation of the sum)^2. The term rides on the band loop: a sensor with no
+    band (nB == 0) evaluates nothing, the term included, as the library entry does (cost, grad, hess 0, step NaN, active 0).
+    With the defaults nothing changes."""
     lib = _lib.load()
     fn = "hsi_cube_srf_normal"
     outputs = tuple(outputs)
     if not outputs or any(k not in _CUBE_NORMAL_OUTPUTS for k in outputs):
         raise ValueError("outputs: a non-empty selection of %r (got %r)" % (_CUBE_NORMAL_OUTPUTS, outputs))
+    nonneg, sum_weight = _cube_box_args(fn, nonneg, sum_weight, kidx)
     f = _srf_cube_front(fn, grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sensor, n_nodes, T_range, interp_tol)
     w = _cube_fit_args(fn, sensor, f["kidx"], meas, weights)
     endmembers, kidx, frac, Tpix, Q = f["endmembers"], f["kidx"], f["frac"], f["Tpix"], f["Q"]
@@ -954,6 +980,8 @@ def hsi_cube_srf_normal(grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sen
     dev = tau.device
     shapes = dict(cost=(nPix,), grad=(nPix, nU), hess=(nPix, nU * (nU + 1) // 2), step=(nPix, nU))
     out = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) for k in set(outputs) | {"cost"}}
+    if nonneg:
+        return _cube_normal_box(lib, f, sensor, grid, tau, La, Ld, meas, w, damping, outputs, out, sum_weight)
     if nPix == 0:
         return {k: out[k] for k in outputs}
     if nB == 0:
@@ -971,8 +999,34 @@ def hsi_cube_srf_normal(grid, tau, La, Ld, Xk, endmembers, kidx, frac, Tpix, sen
     return {k: out[k] for k in outputs}
 
 
+def _cube_normal_box(lib, f, sensor, grid, tau, La, Ld, meas, w, damping, outputs, out, sum_weight):
+    """hsi_cube_srf_normal's device part under nonneg=True: rtx_srf_pixel_cube_normal_box on the same tables."""
+    kidx, frac, Tpix, Q = f["kidx"], f["frac"], f["Tpix"], f["Q"]
+    nPix, nMix = kidx.shape
+    nB, nEnd, dev = len(sensor), f["endmembers"].shape[1], tau.device
+    active = torch.zeros(nPix, dtype=torch.int32, device=dev)
+    res = lambda: dict({k: out[k] for k in outputs}, active=active)
+    if nPix == 0:
+        return res()
+    if nB == 0:  # no band: the library entry evaluates nothing, the pseudo-band included (documented above)
+        for k in outputs:
+            out[k].zero_() if k != "step" else out[k].fill_(float("nan"))
+        return res()
+    lam = None
+    if damping is not None:
+        lam = damping.to(dev).contiguous() if torch.is_tensor(damping) else torch.full((nPix,), float(damping), dtype=torch.float64, device=dev)
+    w = None if w is None else w.to(dev).contiguous()
+    N, Cb, tab, T_host = _srf_cube_tables(grid, tau, La, Ld, f, sensor)
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.check(lib.rtx_srf_pixel_cube_normal_box(nB, Q, T_host.ctypes.data_as(C.c_void_p), p(N), p(Cb), p(tab), nEnd, nPix, nMix, p(kidx),
+                                                 p(frac), p(Tpix), p(meas.contiguous()), p(w), p(lam), p(out["cost"]), p(out.get("grad")),
+                                                 p(out.get("hess")), p(out.get("step")), st, 0, sum_weight, p(active)))
+    return res()
+
+
 def hsi_cube_srf_fit(grid, tau, La, Ld, Xk, endmembers, kidx, meas, sensor, T_range, frac0=None, T0=None, weights=None, max_iter=50,
-                     lambda0=1e-3, ftol=0.0, n_nodes=8, interp_tol=1e-6):
+                     lambda0=1e-3, ftol=0.0, n_nodes=8, interp_tol=1e-6, nonneg=False, sum_weight=0.0):
     """Fit every pixel's surface temperature and fractions to a measured cube under hsi_cube_srf's model, the atmosphere
     (tau, La, Ld) and the pixel's endmember indices kidx fixed: an unconstrained Levenberg-Marquardt loop per
     pixel in 1 + nMix unknowns, the whole loop in one kernel (rtx_srf_pixel_cube_fit; include/radtxfr_hip.h has the
@@ -986,9 +1040,19 @@ def hsi_cube_srf_fit(grid, tau, La, Ld, Xk, endmembers, kidx, meas, sensor, T_ra
     w r^2), "n_iter" int32 [nPix] trials, "status" int32 [nPix] (0 converged or stalled, 1 iteration cap, 2 the start is
     outside T_range or not finite, 3 singular; under 2 and 3 the pixel's results are NaN), "hess" float64
     [nPix][(1 + nMix)(2 + nMix) / 2] = J^T W J at the result, lower triangle by rows: with nU = 1 + nMix unknowns and n
-    counting bands, inv(hess) cost / (n - nU) estimates the covariance of (T, frac). All checks run before any device work."""
+    counting bands, inv(hess) cost / (n - nU) estimates the covariance of (T, frac). All checks run before any device work.
+    nonneg=True (rtx_srf_pixel_cube_fit_box) fits inside the box T_range x frac >= 0: every trial is the box step
+    (see hsi_cube_srf_normal), a given start's fractions are raised to 0 first, and a pixel whose step no longer moves it
+    stops with status 0. sum_weight > 0 (needs nonneg=True) adds sum_weight (sum_m frac_m - 1)^2 to the cost, a soft
+    sum-to-one; its unit is radiance^2, so a sensible value is (band noise / tolerated deviation of the sum)^2, times the
+    band weights' scale when weights are given. The dict gains "grad" float64 [nPix][1 + nMix], the gradient at the result,
+    and "active" int32 [nPix]: bit i set where unknown i (0: T, m: fraction m) sits on a bound with the gradient pointing
+    out of the box (the KKT active set). The covariance estimate then holds for the free unknowns only: invert hess with
+    the rows and columns of the active unknowns removed, and count nU as the number of free ones. With the defaults the
+    unconstrained entry is called and nothing changes."""
     lib = _lib.load()
     fn = "hsi_cube_srf_fit"
+    nonneg, sum_weight = _cube_box_args(fn, nonneg, sum_weight, kidx)
     if T_range is None:
         raise ValueError(f"{fn}: T_range=(T_lo, T_hi) is required (there is no Tpix to read it from)")
     if (frac0 is None) != (T0 is None):
@@ -1019,10 +1083,13 @@ def hsi_cube_srf_fit(grid, tau, La, Ld, Xk, endmembers, kidx, meas, sensor, T_ra
     out = dict(Tpix=Tpix, frac=frac, cost=torch.empty(nPix, dtype=torch.float64, device=dev),
                n_iter=torch.zeros(nPix, dtype=torch.int32, device=dev), status=torch.zeros(nPix, dtype=torch.int32, device=dev),
                hess=torch.empty((nPix, nU * (nU + 1) // 2), dtype=torch.float64, device=dev))
+    if nonneg:
+        out["grad"] = torch.empty((nPix, nU), dtype=torch.float64, device=dev)
+        out["active"] = torch.zeros(nPix, dtype=torch.int32, device=dev)
     if nPix == 0:
         return out
     if nB == 0:  # nothing to fit to
-        for k in ("Tpix", "frac", "cost", "hess"):
+        for k in ("Tpix", "frac", "cost", "hess") + (("grad",) if nonneg else ()):
             out[k].fill_(float("nan"))
         out["status"].fill_(3)
         return out
@@ -1030,6 +1097,12 @@ def hsi_cube_srf_fit(grid, tau, La, Ld, Xk, endmembers, kidx, meas, sensor, T_ra
     N, Cb, tab, T_host = _srf_cube_tables(grid, tau, La, Ld, f, sensor)
     p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    if nonneg:
+        _lib.check(lib.rtx_srf_pixel_cube_fit_box(nB, Q, T_host.ctypes.data_as(C.c_void_p), p(N), p(Cb), p(tab), nEnd, nPix, nMix, p(kidx),
+                                                  p(meas.contiguous()), p(w), p(frac), p(Tpix), int(max_iter), float(lambda0), float(ftol),
+                                                  p(out["cost"]), p(out["n_iter"]), p(out["status"]), p(out["hess"]), st,
+                                                  RTX_FIT_START_GIVEN if given else 0, sum_weight, p(out["grad"]), p(out["active"])))
+        return out
     _lib.check(lib.rtx_srf_pixel_cube_fit(nB, Q, T_host.ctypes.data_as(C.c_void_p), p(N), p(Cb), p(tab), nEnd, nPix, nMix, p(kidx),
                                           p(meas.contiguous()), p(w), p(frac), p(Tpix), int(max_iter), float(lambda0), float(ftol), p(out["cost"]),
                                           p(out["n_iter"]), p(out["status"]), p(out["hess"]), st, RTX_FIT_START_GIVEN if given else 0))
